@@ -7,9 +7,13 @@ BiGRU(192), T=30, batch 256 per GPU, fp32 -- on synthetic clips resident in HBM.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --config 5        # BASELINE config 5: 100 words, 96x96 ROI, CNN 16/32/64/96, BiGRU(512), bf16 MFMA
+    python bench.py --full            # the headline plus everything below
 
-The default (config 2, one GPU) line also carries ``config4`` (BASELINE config 4: 4 096 x T=60 windows, forward-only,
-hipGraph replay, softmax + top-3 on device, with its own roofline) and ``cpu_baseline`` for config 2 at the bench batch
+A plain run sets up, warms up, times the K steps and prints the line (``--dump-outputs DIR``: and writes as
+DIR/<name>.npy what one more, untimed step of the timed path computes from the seeded start state -- train_block says
+why).  ``--full`` adds the per-kernel timing pass with the dominant kernel's ``roofline``, four more timed windows (``extra``) and, on the default (config 2, one GPU) line, ``config5``, ``shipped``,
+``config4`` (BASELINE config 4: 4 096 x T=60 windows, forward-only, hipGraph replay, softmax + top-3 on device, with its
+own roofline), ``padded_batches``, ``sliding_window_serving`` and ``cpu_baseline`` for config 2 at the bench batch
 (``also``: config 2 at batch 32 and config 1, landmark-only at batch 8 -- SURVEY.md 8d's three CPU rows).
 
 One JSON line on rank 0.  ``value`` = clips of all ranks / max-over-ranks wall time of exactly K steps.
@@ -301,9 +305,12 @@ def spec_for(config, B, T, K, roi, C):
                           "train step = fwd + CE(ls .05) + bwd + grad all-reduce + clip(1.0) + Adam, dropout on"))
 
 
-def train_block(ss, L, dev, world, rank, spec, X, lengths, R, y, steps, warmup, kernel_times, micro_batches, dist_on, extra_windows=0):
-    """W warm-up steps, then exactly K timed steps of the fused training step between barriers (max over ranks); then K more
-    steps on one stream with a HIP-event pair around every launch for the per-kernel table and the dominant kernel's roofline."""
+def train_block(ss, L, dev, world, rank, spec, X, lengths, R, y, steps, warmup, kernel_times, micro_batches, dist_on, extra_windows=0,
+                outputs=None):
+    """W warm-up steps, then exactly K timed steps of the fused training step between barriers (max over ranks); with
+    ``kernel_times``, K more steps on one stream with a HIP-event pair around every launch for the per-kernel table and the
+    dominant kernel's roofline.  ``outputs`` (a dict) receives what one step of the timed path computes from the seeded start
+    state: loss and correct count, and the parameters and gradients it leaves in the model (see below)."""
     import torch.distributed as dist
 
     B, T, D, C, E, H = spec["B"], spec["T"], spec["D"], spec["C"], spec["E"], spec["H"]
@@ -319,6 +326,8 @@ def train_block(ss, L, dev, world, rank, spec, X, lengths, R, y, steps, warmup, 
         torch.cuda.synchronize()
 
     gb = B * world
+    if outputs is not None:
+        start = [t.clone() for t in (model.flat_params, trainer.m, trainer.v)]
     for _ in range(warmup):
         trainer.step(X, lengths, R, y, global_batch=gb)
     barrier()
@@ -327,6 +336,17 @@ def train_block(ss, L, dev, world, rank, spec, X, lengths, R, y, steps, warmup, 
         loss, _ = trainer.step(X, lengths, R, y, global_batch=gb)
     barrier()
     elapsed = time.perf_counter() - t0
+    if outputs is not None:
+        # The step's reductions are float atomics, summed in whatever order the workgroups finish: one step's results differ
+        # from run to run in the last bits (~3e-7 relative), and the chained Adam steps of the warm-up and timed window grow
+        # that to ~1e-4 by step 25, so the state they leave is not a function of the inputs.  What is dumped is one more step
+        # of the same path on the same inputs, untimed, from the seeded start state (parameters, Adam moments, step count).
+        for dst, src in zip((model.flat_params, trainer.m, trainer.v), start):
+            dst.copy_(src)
+        trainer.step_count = 0
+        loss0, correct0 = trainer.step(X, lengths, R, y, global_batch=gb)
+        outputs.update(loss=loss0.clone(), correct=correct0.clone(), params=model.flat_params.clone(), grads=model.flat_grads.clone())
+        barrier()
     if dist_on:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -549,17 +569,20 @@ def padded_block(ss, L, dev, B, T, K, roi, C, X, R, y, steps=20, warmup=5):
     return res
 
 
-def shipped_blocks(ss, L, dev, world, rank, args, dist_on):
+def shipped_blocks(ss, L, dev, world, rank, args, dist_on, outputs=None):
     """The configuration the reference actually runs: BATCH_SIZE 16 (as shipped) and 256 clips of MAX_T = 90 frames, 88 landmarks
-    (D = 180), ROI 96 wide x 48 high, 10 words."""
+    (D = 180), ROI 96 wide x 48 high, 10 words.  ``outputs`` receives each batch's train_block outputs as ``b<B>_<name>``."""
     out = {}
     for B in [int(v) for v in args.shipped_batches.split(",")]:
         name = "b%d" % B
         sp = spec_for("shipped", B, SHIPPED["T"], SHIPPED["K"], SHIPPED["roi_hw"], SHIPPED["C"])
         X, l, R, y = synth_inputs(L, dev, rank, B, sp["T"], sp["K"], sp["roi_hw"], sp["C"])
         l = ragged(l, sp["T"], args.min_len_frac, sp)
+        got = None if outputs is None else {}
         out[name] = train_block(ss, L, dev, world, rank, sp, X, l, R, y, args.steps, max(2, args.warmup // 2),
-                                not args.no_kernel_times, 1, dist_on)
+                                args.kernel_times, 1, dist_on, outputs=got)
+        if got:
+            outputs.update({"%s_%s" % (name, k): v for k, v in got.items()})
         del X, R
         torch.cuda.empty_cache()
     return out
@@ -598,6 +621,28 @@ def cpu_baseline_shipped(seconds):
             "ms_per_step": round(1000 * el / n, 1)}
 
 
+DUMP_MAX_ELEMENTS = 4 << 20  # per array (16 MB in float32)
+DUMP_MAX_BYTES = 64 << 20  # all arrays of one dump
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as ``path/<name>.npy``, float64 kept, anything else as float32.  An array of more than
+    DUMP_MAX_ELEMENTS elements is written as the same seeded sample of its flattened elements (ascending indices) in every run."""
+    import numpy as np
+
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        out[name] = a
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES, {k: a.nbytes for k, a in out.items()}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -613,6 +658,13 @@ def main():
     ap.add_argument("--classes", type=int, default=5)
     ap.add_argument("--cpu-batch", type=int, default=32)
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps also run the per-kernel timing pass (roofline), the extra timed windows and, on "
+                         "the default line, the config-5, shipped, config-4, padded-batches and sliding-window blocks and the CPU "
+                         "baselines; a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write as DIR/<name>.npy (float32 / float64) what one more step of the timed path "
+                         "computes from the seeded start state: the same arrays every run, to rounding")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-times", action="store_true")
     ap.add_argument("--mode", choices=["train", "infer", "assemble", "stream", "crop", "live"], default="train",
@@ -621,20 +673,23 @@ def main():
     ap.add_argument("--config", type=int, choices=[2, 5], default=2,
                     help="2 = the headline (f32, 64x64 ROI, H=192, 5 words); 5 = BASELINE config 5 (bf16 MFMA, 96x96 ROI, CNN "
                          "16/32/64/96, H=512, 100 words)")
-    ap.add_argument("--no-padded", action="store_true", help="skip the padded-batches block of the default run")
-    ap.add_argument("--no-config4", action="store_true", help="skip the config-4 (hipGraph serving) block of the default run")
-    ap.add_argument("--no-config5", action="store_true", help="skip the config-5 (bf16, 96x96 ROI, H=512) block of the default run")
-    ap.add_argument("--no-shipped", action="store_true", help="skip the block at the reference's shipped configuration")
+    ap.add_argument("--no-padded", action="store_true", help="skip the padded-batches block of a --full run")
+    ap.add_argument("--no-config4", action="store_true", help="skip the config-4 (hipGraph serving) block of a --full run")
+    ap.add_argument("--no-config5", action="store_true", help="skip the config-5 (bf16, 96x96 ROI, H=512) block of a --full run")
+    ap.add_argument("--no-shipped", action="store_true", help="skip the block at the reference's shipped configuration of a --full run")
     ap.add_argument("--shipped", dest="shipped_only", action="store_true",
                     help="only the reference's shipped configuration (48x96 ROI, 88 landmarks -> D=180, 10 words, T=90; batch 16 as "
-                         "shipped and batch 256), one JSON line with its CPU row")
+                         "shipped and batch 256), one JSON line (with --full: its CPU row)")
     ap.add_argument("--extra-windows", type=int, default=4,
-                    help="further timed windows of --steps steps behind the contract's one: median / min under 'extra'")
+                    help="--full: further timed windows of --steps steps behind the contract's one, median / min under 'extra'")
     ap.add_argument("--shipped-batches", default="16,256", help="batches of the shipped-configuration block (a profile takes 256 only)")
     ap.add_argument("--force-dist", action="store_true",
                     help="join an 'nccl' (= RCCL) process group and run the data-parallel leg -- broadcast of the parameters, the flat "
                          "gradient all-reduce every step, barriers, max-over-ranks timing -- even with one rank")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode not in ("train", "infer"):
+        ap.error("--dump-outputs covers --mode train and --mode infer")
+    args.kernel_times = args.full and not args.no_kernel_times
     if args.config == 5:
         args.roi, args.classes = C5["roi"], C5["classes"]
 
@@ -656,9 +711,12 @@ def main():
     import silent_speech_amd as ss
     from silent_speech_amd import _lib as L
 
+    outputs = {} if args.dump_outputs else None
     if args.shipped_only:
-        out = shipped_blocks(ss, L, dev, world, rank, args, dist_on)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out = shipped_blocks(ss, L, dev, world, rank, args, dist_on, outputs=outputs)
+        if rank == 0 and outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_shipped(seconds=args.cpu_seconds)
         if dist_on:
             dist.destroy_process_group()
@@ -688,9 +746,11 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            g_inf()
+            logits = g_inf()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, {"logits": logits})
         print(json.dumps({"metric": "windows/sec (60-frame, forward-only, hipGraph)", "value": round(B * args.steps / el, 1),
                           "unit": "windows/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(1000 * el / args.steps, 3), "higher_is_better": True, "dtype": "f32",
@@ -832,31 +892,34 @@ def main():
         return
     spec = spec_for(args.config, B, T, K, roi, C)
     lengths = ragged(lengths, T, args.min_len_frac, spec)
-    out = train_block(ss, L, dev, world, rank, spec, X, lengths, R, y, args.steps, args.warmup, not args.no_kernel_times,
-                      args.micro_batches, dist_on, extra_windows=args.extra_windows)
+    out = train_block(ss, L, dev, world, rank, spec, X, lengths, R, y, args.steps, args.warmup, args.kernel_times,
+                      args.micro_batches, dist_on, extra_windows=args.extra_windows if args.full else 0, outputs=outputs)
+    if rank == 0 and outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     solo = rank == 0 and world == 1
-    # ---- the other BASELINE configs ride along in the default run, so that the driver's one command measures them too
-    if args.config == 2 and not args.no_config5:
+    full = args.full and args.config == 2
+    # ---- --full: the other BASELINE configs ride along with the headline, so that one command measures them too
+    if full and not args.no_config5:
         # BASELINE config 5 is a data-parallel training config like the headline: every rank runs it (one all-reduce per step)
         torch.cuda.empty_cache()
         s5 = spec_for(5, 256, 30, K, C5["roi"], C5["classes"])
         X5, l5, R5, y5 = synth_inputs(L, dev, rank, 256, 30, K, s5["roi_hw"], s5["C"])
         out["config5"] = train_block(ss, L, dev, world, rank, s5, X5, l5, R5, y5, args.steps, max(2, args.warmup // 2),
-                                     not args.no_kernel_times, 1, dist_on)
+                                     args.kernel_times, 1, dist_on)
         del X5, R5
-    if args.config == 2 and not args.no_shipped and not args.shipped_only:
+    if full and not args.no_shipped:
         out["shipped"] = shipped_blocks(ss, L, dev, world, rank, args, dist_on)
-    if solo and args.config == 2 and not args.no_config4:
+    if solo and full and not args.no_config4:
         torch.cuda.empty_cache()
         out["config4"] = config4_block(ss, dev, D, C, roi, 20, 3)
-    if solo and args.config == 2 and args.min_len_frac >= 1.0 and not args.no_padded:
+    if solo and full and args.min_len_frac >= 1.0 and not args.no_padded:
         out["padded_batches"] = padded_block(ss, L, dev, B, T, K, roi, C, X, R, y)
-    if solo and args.config == 2 and not args.no_config4:
+    if solo and full and not args.no_config4:
         # beside config 4 (4 096 INDEPENDENT windows through the whole model): the same count of camera streams served as what they
         # are, windows that slide by two frames -- not config 4's number, which recomputes every frame of every window
         torch.cuda.empty_cache()
         out["sliding_window_serving"] = stream_block(ss, dev, D, C, roi, 4096, 60, 10)
-    if solo and not args.no_cpu_baseline:
+    if solo and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, D, C, args.config)
         if "config5" in out:
             out["config5"]["cpu_baseline"] = cpu_baseline_c5(args, D, 30, seconds=6.0)

@@ -133,6 +133,8 @@ def gen_model_case(tmo, live, name, cls, x_dim, C, roi_hw, B, T, lengths, layers
         out["loss2"] = float(loss2)
         out["logits_after2"] = m(X, L, R).detach().numpy()
         _check_against_the_loop_statements(tmo, sd, x_dim, C, use_roi, X, L, R, y, m, float(loss2))
+    if use_roi and out["R"].nbytes > 512 * 1024:  # no committed file over 1 MiB: big ROI frames go beside (weights.load_model_case)
+        np.savez_compressed(os.path.join(HERE, name + "_roi.npz"), R=out.pop("R"))
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
     print("wrote", name, "logits", out["logits"][0][:3])
 

@@ -7,6 +7,7 @@ generated weights so a generator drift would be caught rather than silently mis-
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -96,3 +97,13 @@ def reduce_tensor(t: torch.Tensor, full_below: int = 4096, stride: int = 53) -> 
     if f.numel() <= full_below:
         return f.numpy().copy()
     return np.concatenate([[float(f.sum()), float(f.norm())], f[::stride].numpy()])
+
+
+def load_model_case(golden_dir: str, name: str) -> dict:
+    """Arrays of the model case ``<name>.npz``.  A case whose ROI frames would push its file past 1 MiB keeps them in
+    ``<name>_roi.npz`` beside it (``make_golden.py`` writes both); they are merged here."""
+    d = dict(np.load(os.path.join(golden_dir, name + ".npz"), allow_pickle=False))
+    roi = os.path.join(golden_dir, name + "_roi.npz")
+    if os.path.exists(roi):
+        d.update(np.load(roi, allow_pickle=False))
+    return d

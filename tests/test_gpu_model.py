@@ -29,7 +29,7 @@ def ss():
 
 
 def load_case(golden_dir, name):
-    d = np.load(os.path.join(golden_dir, name + ".npz"), allow_pickle=False)
+    d = W.load_model_case(golden_dir, name)
     use_roi = bool(int(d["use_roi"]))
     sd = W.make_state_dict(int(d["seed"]), int(d["x_dim"]), int(d["num_classes"]), use_roi, gru_layers=int(d["layers"]))
     X, Lh, y = torch.from_numpy(d["X"]), torch.from_numpy(d["lengths"]), torch.from_numpy(d["y"])
@@ -279,7 +279,8 @@ def test_bench_multi_rank_branch_runs_under_torchrun(ss):
     """bench.py's OWN data-parallel branch -- init_process_group("nccl", device_id=), broadcast of the flat parameters, the
     gradient all-reduce in every step, dist.barrier, all_reduce(MAX) of the wall time -- exactly as the driver starts it for
     N > 1 (python -m torch.distributed.run ... bench.py --gpus N), here with the one rank this box has (--force-dist), in a
-    fresh child that has not touched the GPU before it joins the group.  The line must carry the all-reduce time."""
+    fresh child that has not touched the GPU before it joins the group.  The line must carry the all-reduce time (timed by the
+    per-kernel pass of --full)."""
     import json
     import socket
     import subprocess
@@ -293,7 +294,7 @@ def test_bench_multi_rank_branch_runs_under_torchrun(ss):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1",
-           "--batch", "32", "--no-cpu-baseline", "--no-config4", "--no-config5", "--no-shipped"]
+           "--batch", "32", "--full", "--no-cpu-baseline", "--no-config4", "--no-config5", "--no-shipped"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -302,6 +303,46 @@ def test_bench_multi_rank_branch_runs_under_torchrun(ss):
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["value"] > 0 and d["config"]["parallelism"] == "dp1"
     assert d["allreduce_ms"] > 0 and d["allreduce_bytes"] == 4 * 1079588
     assert d["final_loss"] == d["final_loss"]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_a_reproducible_step(ss, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps of the headline and carries nothing else.  With
+    --dump-outputs it writes one more step of the timed path from the seeded start state; a second run with the same arguments
+    writes the same arrays to rounding (the float atomics that sum a step's reductions over workgroups)."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert abs(d["value"] - 32 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in d
+        for k in ("roofline", "kernels_ms_per_step", "extra", "config5", "shipped", "config4", "padded_batches",
+                  "sliding_window_serving", "cpu_baseline"):
+            assert k not in d, k
+        arrays = {p.stem: np.load(p) for p in out.glob("*.npy")}
+        assert sorted(arrays) == ["correct", "grads", "loss", "params"]
+        assert arrays["params"].shape == arrays["grads"].shape == (1079588,)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        got.append(arrays)
+    a, b = got
+    assert float(a["correct"]) == float(b["correct"])
+    assert abs(float(a["loss"]) - float(b["loss"])) <= 1e-6 * abs(float(a["loss"]))
+    assert np.abs(a["grads"] - b["grads"]).max() <= 1e-5 * np.abs(a["grads"]).max()
+    # one Adam step moves a parameter whose gradient is rounding noise far below eps = 1e-8 (pool.score.bias: softmax is shift
+    # invariant) by lr * noise / eps, a few 1e-6 at most; every other one agrees to ~1e-8
+    assert np.abs(a["params"] - b["params"]).max() <= 1e-5
 
 
 @pytest.mark.parametrize("layers", [1, 2])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Diagnostic: the numbers of one bench.py JSON line that DESIGN.md quotes.   python tools/bench_digest.py gpurun_out/r4_b2.log"""
+"""Diagnostic: the numbers of one ``bench.py --full`` JSON line that DESIGN.md quotes.   python tools/bench_digest.py bench.log"""
 import json
 import sys
 
