@@ -63,13 +63,35 @@ MODEL_CASES = [
     # the reference's shipped shape at its shipped length: MAX_T = 90 frames, 88 landmarks -> D = 180, ROI 48 x 96, 10 words
     # (train_model_official.py:29-38); one full-length clip and one ragged one
     ("model_shipped_t90", "train", 180, 10, (48, 96), 2, 90, [90, 53], 2),
+    # batches padded past their longest clip, as the reference trains: the clips go through its own NPZWordDataset(augment=False)
+    # + collate_fn (train_model_official.py:93-117, 174-204), so T = MAX_T = 90 while the GRU output has max(lengths) columns
+    # (:301-305).  The trailing element marks a collated case (gen_collated_batch)
+    ("model_shipped_pad90", "train", 180, 10, (48, 96), 4, 90, [53, 17, 1, 34], 2, True),
+    ("model_lm_pad90", "train", 84, 5, None, 12, 90, [29, 1, 89, 8, 41, 3, 17, 60, 5, 33, 12, 22], 2, True),
 ]
 
 
-def gen_model_case(tmo, live, name, cls, x_dim, C, roi_hw, B, T, lengths, layers, seed):
+def gen_collated_batch(tmo, X, L, R, y, C, T):
+    """Writes clip b as the recorder does (X: (L[b], D) float32, roi: (L[b], H, W) uint8, a word label) into a temp dir, as
+    gen_dataset does, and returns the batch the reference's NPZWordDataset(max_t=T, augment=False) + collate_fn make of them."""
+    label_to_id = {f"w{c}": c for c in range(C)}
+    with tempfile.TemporaryDirectory() as tmp:
+        files = []
+        for b, n in enumerate(L.tolist()):
+            save = dict(X=X[b, :n].numpy(), ts=np.arange(n), label=f"w{int(y[b])}", speaker="me", idxs=np.arange(4))
+            if R is not None:
+                save["roi"] = R[b, :n].numpy()
+            f = os.path.join(tmp, f"c{b}.npz")
+            np.savez_compressed(f, **save)
+            files.append(f)
+        ds = tmo.NPZWordDataset(files, label_to_id, max_t=T, augment=False, use_roi=R is not None)
+        return tmo.collate_fn([ds[b] for b in range(len(files))])
+
+
+def gen_model_case(tmo, live, name, cls, x_dim, C, roi_hw, B, T, lengths, layers, collated=False, *, seed):
     use_roi = roi_hw is not None
     sd = W.make_state_dict(seed, x_dim, C, use_roi, gru_layers=layers)
-    X, L, R, y = W.make_inputs(seed, B, T, x_dim, C, roi_hw, lengths)
+    X, L, R, y = W.make_inputs(seed, B, T, x_dim, C, roi_hw, lengths, zero_padding=collated)
     if use_roi:
         # exercise the std clamp (train_model_official.py:290): constant and near-constant frames
         R[0, 0] = 0
@@ -78,6 +100,13 @@ def gen_model_case(tmo, live, name, cls, x_dim, C, roi_hw, B, T, lengths, layers
         if T > 2:
             R[0, 2] = 17
             R[0, 2, 3, 5] = 18
+    if collated:
+        assert max(lengths) < T
+        Xc, Lc, Rc, yc = gen_collated_batch(tmo, X, L, R, y, C, T)
+        # what the reference's loop feeds its model is what make_inputs(..., zero_padding=True) rebuilds in the tests
+        assert torch.equal(Xc, X) and torch.equal(Lc, L) and torch.equal(yc, y), name
+        assert (Rc is None) == (R is None) and (R is None or torch.equal(Rc, R)), name
+        X, L, R, y = Xc, Lc, Rc, yc
     if cls == "train":
         m = tmo.BiGRUClassifier(x_dim, C, use_roi=use_roi, roi_emb=32, hidden=192)
     else:
@@ -133,8 +162,17 @@ def gen_model_case(tmo, live, name, cls, x_dim, C, roi_hw, B, T, lengths, layers
         out["loss2"] = float(loss2)
         out["logits_after2"] = m(X, L, R).detach().numpy()
         _check_against_the_loop_statements(tmo, sd, x_dim, C, use_roi, X, L, R, y, m, float(loss2))
-    if use_roi and out["R"].nbytes > 512 * 1024:  # no committed file over 1 MiB: big ROI frames go beside (weights.load_model_case)
-        np.savez_compressed(os.path.join(HERE, name + "_roi.npz"), R=out.pop("R"))
+    if collated:  # only the rows inside the clips (1 MiB per file); weights.load_model_case rebuilds the zero padding
+        out["T"] = T
+        for k in ("X", "R", "gru_out"):
+            if k in out:
+                full = out.pop(k)
+                out[k + "_valid"] = np.concatenate([full[b, :n] for b, n in enumerate(L.tolist())])
+                assert np.array_equal(W.pad_frames(out[k + "_valid"], L, full.shape[1]), full), (name, k)
+        assert out["gru_out_valid"].shape[0] == int(L.sum()) and hooks["gru_out"].shape[1] == max(lengths)
+    rk = "R_valid" if collated else "R"
+    if use_roi and (collated or out[rk].nbytes > 512 * 1024):  # no committed file over 1 MiB: big ROI frames go beside (weights.load_model_case)
+        np.savez_compressed(os.path.join(HERE, name + "_roi.npz"), **{rk: out.pop(rk)})
     np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
     print("wrote", name, "logits", out["logits"][0][:3])
 

@@ -73,7 +73,9 @@ def checksum(sd) -> float:
     return float(sum(float(v.double().abs().sum()) for v in sd.values()))
 
 
-def make_inputs(seed: int, B: int, T: int, x_dim: int, num_classes: int, roi_hw=None, lengths=None):
+def make_inputs(seed: int, B: int, T: int, x_dim: int, num_classes: int, roi_hw=None, lengths=None, zero_padding: bool = False):
+    """``zero_padding=True`` zeroes every frame at or behind a clip's length, as the reference's clip_pad_trim / roi_pad_trim
+    (train_model_official.py:93-117) pad a clip to MAX_T; the random stream, and so every other number, is the same."""
     g = torch.Generator().manual_seed(seed + 7919)
     X = torch.randn(B, T, x_dim, generator=g) * 0.7
     y = torch.randint(0, num_classes, (B,), generator=g)
@@ -88,7 +90,24 @@ def make_inputs(seed: int, B: int, T: int, x_dim: int, num_classes: int, roi_hw=
         # smooth-ish structure so conv responses are not pure noise: blend with a ramp
         ramp = (torch.arange(W).view(1, 1, 1, W) * 255 // max(1, W - 1)).to(torch.int32)
         R = ((R.to(torch.int32) + ramp) // 2).to(torch.uint8)
+    if zero_padding:
+        pad = torch.arange(T).unsqueeze(0) >= lengths.unsqueeze(1)
+        X[pad] = 0
+        if R is not None:
+            R[pad] = 0
     return X, lengths, R, y
+
+
+def pad_frames(valid: np.ndarray, lengths, T: int) -> np.ndarray:
+    """(sum(lengths), ...) frames of the clips one after the other -> (B, T, ...) with zero frames behind each clip."""
+    lengths = [int(n) for n in lengths]
+    out = np.zeros((len(lengths), T) + valid.shape[1:], valid.dtype)
+    o = 0
+    for b, n in enumerate(lengths):
+        out[b, :n] = valid[o:o + n]
+        o += n
+    assert o == valid.shape[0]
+    return out
 
 
 def reduce_tensor(t: torch.Tensor, full_below: int = 4096, stride: int = 53) -> np.ndarray:
@@ -106,4 +125,9 @@ def load_model_case(golden_dir: str, name: str) -> dict:
     roi = os.path.join(golden_dir, name + "_roi.npz")
     if os.path.exists(roi):
         d.update(np.load(roi, allow_pickle=False))
+    # a case collated as the reference trains keeps only the rows inside its clips: the padding is zeros, of T = MAX_T frames
+    # in the inputs (clip_pad_trim, roi_pad_trim) and of max(lengths) columns in the GRU output (pad_packed_sequence)
+    for k in ("X", "R", "gru_out"):
+        if k + "_valid" in d:
+            d[k] = pad_frames(d.pop(k + "_valid"), d["lengths"], int(d["T"]) if k != "gru_out" else int(d["lengths"].max()))
     return d

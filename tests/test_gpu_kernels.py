@@ -262,6 +262,12 @@ def _gru_case(H, In, B, T, seed, lengths=None):
 def test_gru_fwd_bwd(L, H, B, T, split):
     """split=True hands the kernels a sync workspace: the (slice, direction) recurrences then run on several CUs each
     and exchange their state through `out` / `d_g`; three launches share the workspace (generation counter)."""
+    _check_gru_fwd_bwd(L, H, B, T, split)
+
+
+def _check_gru_fwd_bwd(L, H, B, T, split, lengths=None, gen0=0):
+    """Body of test_gru_fwd_bwd.  ``lengths`` replaces the random ones of _gru_case; ``gen0`` is the launch generation the sync
+    header holds before the first launch (int32 bits).  Returns the kernels' outputs and the sync workspace."""
     In = 20
     sync_ws = None
     if split:
@@ -269,8 +275,9 @@ def test_gru_fwd_bwd(L, H, B, T, split):
         if nb == 0:
             pytest.skip("shape always takes the one-CU-per-slice kernels")
         sync_ws = torch.zeros(nb // 4, device="cuda", dtype=torch.int32)
+        sync_ws[0] = gen0
     sw = L.ptr(sync_ws)
-    sd, x, lengths = _gru_case(H, In, B, T, seed=H + B + T)
+    sd, x, lengths = _gru_case(H, In, B, T, seed=H + B + T, lengths=lengths)
     N = B * T
     # reference: explicit masked GRU on CPU with autograd
     leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
@@ -340,7 +347,8 @@ def test_gru_fwd_bwd(L, H, B, T, split):
                      (torch.cat([colsum[0], colsum[1], colsum[3]]) + 0.5).float(), atol=2e-4, rtol=1e-4)
     if split:
         assert int(sync_ws[2]) == 0, "a wait on a partner workgroup timed out"
-        assert int(sync_ws[0]) == 4 and int(sync_ws[1]) == 0  # four launches (three forward, one backward), each closed its generation
+        # four launches (three forward, one backward), each closed its generation
+        assert (int(sync_ws[0]) - gen0) % 2**32 == 4 and int(sync_ws[1]) == 0
     # inter-layer dropout fused into the read of d_out == ss_dropout on d_out first, bit for bit
     p_drop, seed, off = 0.25, 1234567, 3 << 40
     dmask = torch.empty_like(dout_d)
@@ -364,14 +372,81 @@ def test_gru_fwd_bwd(L, H, B, T, split):
         db_hh = leaves["gru.bias_hh_l0" + suf].grad
         assert_close(f"d b_hh n dir{d}", dg_d[d, :, 3].sum(0), db_hh[2 * H:], atol=2e-4, rtol=1e-4)
         assert_close(f"d b_hh rz dir{d}", dg_d[d, :, :2].reshape(N, 2 * H).sum(0), db_hh[: 2 * H], atol=2e-4, rtol=1e-4)
+    if split:
+        assert int(sync_ws[2]) == 0 and (int(sync_ws[0]) - gen0) % 2**32 == 6  # and the two backward launches with dropout
+    return dict(out=out_d, out2=out2, out3=out3, od3=od3, dg=dg_d, gb=gb_d, dg_a=dg_a, dg_b=dg_b), sync_ws
+
+
+# Batches padded past their longest clip, as the reference trains (MAX_T = 90, train_model_official.py:93-117): the first
+# T - max(len) steps of the reverse recurrence run with no valid clip in the batch -- in the multi-CU form whole sweeps that
+# publish zero state -- and the last T - max(len) forward steps emit nothing.
+GRU_PADDED = [
+    (192, 5, 7, [3, 1, 6, 2, 5]),
+    (192, 16, 6, [1] * 16),                                              # every clip one frame long
+    (192, 37, 12, [1 + (5 * b) % 9 for b in range(37)]),                 # max 9 of 12, three slices
+    (64, 250, 9, [1 + (3 * b) % 7 for b in range(250)]),
+    (192, 16, 90, [53, 17, 1, 34] + [2 + (11 * b) % 87 for b in range(12)]),   # the shipped MAX_T, max(len) = 88
+    (192, 130, 90, [1 + (7 * b) % 80 for b in range(130)]),
+]
+
+
+@pytest.mark.parametrize("split", [False, True], ids=["one_cu", "multi_cu"])
+@pytest.mark.parametrize("H,B,T,lengths", GRU_PADDED, ids=[f"H{h}-B{b}-T{t}-max{max(n)}" for h, b, t, n in GRU_PADDED])
+def test_gru_fwd_bwd_padded_past_the_longest_clip(L, H, B, T, lengths, split):
+    assert max(lengths) < T and len(lengths) == B
+    _check_gru_fwd_bwd(L, H, B, T, split, lengths=lengths)
+
+
+@pytest.mark.parametrize("T", [1022, 1023])
+def test_gru_fwd_bwd_at_the_step_tag_limit(L, T):
+    """Step tags are 10 bits (gru_split.h, SPLIT_MAX_T = 1022): T = 1022 is the longest clip the multi-CU recurrence takes, at
+    T = 1023 gru_sync_bytes says 0 and the one-CU kernels run.  Both sides against the reference, ragged, max(len) < T on one side."""
+    H, B = 192, 3
+    nb = L.gru_sync_bytes(B, T, H)
+    assert (nb > 0) == (T <= 1022), nb
+    lengths = [T, 1, 700] if T == 1022 else [1022, 5, 700]
+    _check_gru_fwd_bwd(L, H, B, T, nb > 0, lengths=lengths)
+
+
+@pytest.mark.parametrize("gen0", [2**22 - 2, -2], ids=["gen_2^22-2", "gen_2^32-2"])
+def test_gru_split_generation_wrap(L, gen0):
+    """The launch generation is masked to 22 bits in the step tags ((gen & 0x3FFFFF) << 10, gru_split.h) and is a 32-bit
+    counter in the header: a graph replayed for every served window reaches both wraps.  The six launches of test_gru_fwd_bwd
+    across each wrap give the bits a fresh workspace gives, and no bounded wait gives up (a wrong tag shows as NaN plus a
+    time-out count in sync[2], not as a hang)."""
+    H, B, T = 192, 37, 12
+    lengths = [T] + [1 + (5 * b) % 9 for b in range(B - 1)]
+    fresh, ws0 = _check_gru_fwd_bwd(L, H, B, T, True, lengths=lengths)
+    wrapped, ws1 = _check_gru_fwd_bwd(L, H, B, T, True, lengths=lengths, gen0=gen0)
+    assert int(ws0[0]) == 6 and int(ws1[0]) == gen0 + 6  # (int32: -2 + 6 launches = 4 past the 32-bit wrap)
+    assert int(ws1[2]) == 0 and int(ws1[1]) == 0
+    for k, v in fresh.items():
+        if k == "gb":  # the bias-gradient column sums are float atomics over the 16-clip slices: their order is the scheduler's
+            assert float((wrapped[k] - v).abs().max()) <= 1e-6 * max(1.0, float(v.abs().max())), k
+        else:
+            assert torch.equal(wrapped[k], v), k
 
 
 # ------------------------------------------------------------------------------------- AttnPool / LayerNorm / CE
 def test_attn_pool(L):
-    B, T, D = 7, 11, 384
+    _check_attn_pool(L, 7, 11, [11, 1, 5, 11, 2, 7, 3])
+
+
+# every column >= max(len) is masked for every clip: the softmax of each row runs over its clip alone
+ATTN_PADDED = [(7, 11, [4, 1, 5, 9, 2, 7, 3]), (5, 90, [1] * 5), (16, 90, [53, 17, 1, 34] + [2 + (11 * b) % 87 for b in range(12)])]
+
+
+@pytest.mark.parametrize("B,T,lengths", ATTN_PADDED, ids=[f"B{b}-T{t}-max{max(n)}" for b, t, n in ATTN_PADDED])
+def test_attn_pool_padded_past_the_longest_clip(L, B, T, lengths):
+    assert max(lengths) < T
+    _check_attn_pool(L, B, T, lengths)
+
+
+def _check_attn_pool(L, B, T, lengths):
+    D = 384
     g = torch.Generator().manual_seed(3)
     h = torch.randn(B, T, D, generator=g)
-    lengths = torch.tensor([11, 1, 5, 11, 2, 7, 3])
+    lengths = torch.tensor(lengths)
     for b in range(B):
         h[b, lengths[b]:] = 0
     sd = {"pool.score.weight": torch.randn(1, D, generator=g) * 0.2, "pool.score.bias": torch.randn(1, generator=g)}
@@ -428,14 +503,31 @@ def test_fused_tail_fwd_bwd(L, B, T, C, Hd):
     """ss_tail_fwd / ss_tail_bwd (AttnPool + head + CE in one launch per direction) against the oracle's autograd.
     Hd = 512 is config 5's width (2H = 1024: the columns beyond the forward kernel's register prefetch), 250 a width that is
     no multiple of the 64-lane column groups."""
+    _check_fused_tail(L, B, T, C, Hd)
+
+
+TAIL_PADDED = [(7, 11, 5, 192, [4, 1, 5, 9, 2, 7, 3]), (4, 90, 10, 192, [53, 17, 1, 34]), (3, 9, 7, 250, [1, 1, 1]),
+               (5, 90, 100, 512, [89, 1, 40, 7, 66])]
+
+
+@pytest.mark.parametrize("B,T,C,Hd,lengths", TAIL_PADDED, ids=[f"B{b}-T{t}-C{c}-Hd{h}-max{max(n)}" for b, t, c, h, n in TAIL_PADDED])
+def test_fused_tail_fwd_bwd_padded_past_the_longest_clip(L, B, T, C, Hd, lengths):
+    assert max(lengths) < T
+    _check_fused_tail(L, B, T, C, Hd, lengths)
+
+
+def _check_fused_tail(L, B, T, C, Hd, lengths=None):
     D, MID = 2 * Hd, 128
     import weights as W
 
     g = torch.Generator().manual_seed(B * 7 + T)
     sd = {k: v for k, v in W.make_state_dict(31 + B, 84, C, False, hidden=Hd).items() if k.startswith(("pool.", "head."))}
     h = torch.randn(B, T, D, generator=g)
-    lengths = torch.randint(1, T + 1, (B,), generator=g)
-    lengths[0] = T
+    drawn = torch.randint(1, T + 1, (B,), generator=g)
+    if lengths is None:
+        lengths = drawn
+        lengths[0] = T
+    lengths = torch.as_tensor(lengths, dtype=torch.int64)
     for b in range(B):
         h[b, lengths[b]:] = 0
     y = torch.randint(0, C, (B,), generator=g)
@@ -639,6 +731,21 @@ def test_active_frames_list_and_cleared_rows(L, B, T):
     g = torch.Generator().manual_seed(B * 31 + T)
     lengths = torch.randint(-1, T + 3, (B,), generator=g, dtype=torch.int32)  # incl. 0, negative and longer than T
     lengths[0] = T
+    _check_active_frames(L, B, T, lengths)
+
+
+# the trailing T - max(len) time columns are dropped for every clip
+FRAMES_PADDED = [(7, 12, [4, 1, 5, 9, 2, 7, 11]), (300, 5, [1] * 300), (4, 90, [53, 17, 1, 34]),
+                 (256, 90, [1 + (7 * b) % 89 for b in range(256)])]
+
+
+@pytest.mark.parametrize("B,T,lengths", FRAMES_PADDED, ids=[f"B{b}-T{t}-max{max(n)}" for b, t, n in FRAMES_PADDED])
+def test_active_frames_padded_past_the_longest_clip(L, B, T, lengths):
+    assert max(lengths) < T
+    _check_active_frames(L, B, T, torch.tensor(lengths, dtype=torch.int32))
+
+
+def _check_active_frames(L, B, T, lengths):
     want = [b * T + t for b in range(B) for t in range(min(max(int(lengths[b]), 0), T))]
     ld, x_dim, E = 13, 5, 6
     Z = torch.full((B * T, ld), 7.0, device="cuda")

@@ -44,7 +44,8 @@ def build(ss, d, sd, standardize=True):
     return m.cuda().eval()
 
 
-@pytest.mark.parametrize("name", ["model_lm_only", "model_roi64", "model_shipped", "model_live_l1", "model_live_l2", "model_shipped_t90"])
+@pytest.mark.parametrize("name", ["model_lm_only", "model_roi64", "model_shipped", "model_live_l1", "model_live_l2", "model_shipped_t90",
+                                  "model_shipped_pad90", "model_lm_pad90"])
 def test_logits_match_reference_golden(ss, golden_dir, name):
     d, sd, X, Lh, R, y = load_case(golden_dir, name)
     m = build(ss, d, sd, standardize=(str(d["cls"]) == "train"))
@@ -110,7 +111,8 @@ def test_state_dict_surface(ss):
         m2(torch.zeros(1, 3, 84), torch.tensor([3]))  # CPU tensors: no CPU path, must fail loudly
 
 
-@pytest.mark.parametrize("name", ["model_lm_only", "model_roi64", "model_shipped", "model_shipped_t90"])
+@pytest.mark.parametrize("name", ["model_lm_only", "model_roi64", "model_shipped", "model_shipped_t90", "model_shipped_pad90",
+                                  "model_lm_pad90"])
 def test_autograd_grads_match_oracle_and_golden(ss, golden_dir, name):
     d, sd, X, Lh, R, y = load_case(golden_dir, name)
     m = build(ss, d, sd)
@@ -135,7 +137,7 @@ def test_autograd_grads_match_oracle_and_golden(ss, golden_dir, name):
                                    rtol=5e-3, err_msg=k)
 
 
-@pytest.mark.parametrize("name", ["model_lm_only", "model_roi64", "model_shipped_t90"])
+@pytest.mark.parametrize("name", ["model_lm_only", "model_roi64", "model_shipped_t90", "model_shipped_pad90", "model_lm_pad90"])
 def test_fused_trainer_two_steps_match_reference(ss, golden_dir, name):
     d, sd, X, Lh, R, y = load_case(golden_dir, name)
     m = build(ss, d, sd)
@@ -155,6 +157,51 @@ def test_fused_trainer_two_steps_match_reference(ss, golden_dir, name):
         after = m(Xd, Ld, Rd)
     err = float((after.cpu() - torch.from_numpy(d["logits_after2"])).abs().max())
     assert err < LOGIT_TOL and err < 2e-4, err
+
+
+def test_padded_batch_trainers_match_the_reference_step(ss, golden_dir):
+    """model_shipped_pad90: four clips collated by the reference to MAX_T = 90, none of them full.  The fused trainer walks the
+    frame list (the default: only the 105 frames inside the clips) and reproduces the reference's first step; so does
+    Trainer(micro_batches=2) on the batch repeated eight times (32 clips: two slices of 16 -- the mean loss, its gradients, their
+    norm and so the Adam step of eight copies are the reference's)."""
+    d, sd, X, Lh, R, y = load_case(golden_dir, "model_shipped_pad90")
+    assert X.shape[1] == 90 and int(Lh.max()) < 90
+    for reps, mb in ((1, 1), (8, 2)):
+        m = build(ss, d, sd)
+        tr = ss.Trainer(m, dropout=False, micro_batches=mb)
+        Xd, Ld, Rd, yd = X.repeat(reps, 1, 1).cuda(), Lh.repeat(reps).cuda(), R.repeat(reps, 1, 1, 1).cuda(), y.repeat(reps).cuda()
+        loss, _ = tr.step(Xd, Ld, Rd, yd)
+        assert abs(float(loss) - float(d["loss"])) < 2e-5, (reps, float(loss))
+        assert abs(float(tr.grad_norm()) - float(d["total_norm"])) < 1e-3 * float(d["total_norm"]), reps
+        if mb == 1:
+            ws = m._workspace(Xd, Rd, train=True, slot=0)
+            assert ws.frames is not None and int(ws.frames[0]) == int(Lh.sum()), "the trainer did not walk the frame list"
+        for k, v in m.state_dict().items():
+            atol = 6.1e-4 if k == "pool.score.bias" else 3e-6  # see tests/test_oracle_golden.py
+            np.testing.assert_allclose(W.reduce_tensor(v.detach().cpu()), d["step1::" + k], atol=atol, rtol=2e-5, err_msg=f"{reps} {k}")
+
+
+def test_padded_batch_graph_replay_and_live_calls(ss, golden_dir):
+    """model_shipped_pad90 through GraphedInference(B, 90): the replay is bit-equal to the eager forward and within TIGHT of the
+    reference's logits.  And the live script's call (live_infer_official.py:344-359): one clip, unpadded, T = len, at the shortest
+    clip it predicts on (5 frames) and at MAX_T = 90, against the oracle."""
+    d, sd, X, Lh, R, y = load_case(golden_dir, "model_shipped_pad90")
+    m = build(ss, d, sd)
+    B, T = X.shape[:2]
+    Xd, Rd = X.cuda(), R.cuda()
+    with torch.no_grad():
+        eager = m(Xd, Lh, Rd)
+    g = ss.GraphedInference(m, B, T, tuple(R.shape[2:]))
+    out = g(Xd, Lh, Rd).clone()
+    assert torch.equal(out, eager)
+    err = float((out.cpu() - torch.from_numpy(d["logits"])).abs().max())
+    assert err < TIGHT, f"graph replay vs reference: {err:.3e}"
+    for n in (5, 90):
+        X1, L1, R1, _ = W.make_inputs(60 + n, 1, n, int(d["x_dim"]), int(d["num_classes"]), tuple(R.shape[2:]), lengths=[n])
+        with torch.no_grad():
+            got = m(X1.cuda(), L1, R1.cuda()).cpu()
+        e = float((got - MR.forward(sd, X1, L1, R1)).abs().max())
+        assert e < TIGHT, f"live call T = {n}: {e:.3e}"
 
 
 def test_minimal_change_loop_matches_reference_step(ss, golden_dir):

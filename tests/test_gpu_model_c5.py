@@ -35,8 +35,17 @@ def build(ss, sd, C=100):
 
 @pytest.mark.parametrize("seed,B,T", [(1, 5, 9), (2, 70, 4)])
 def test_c5_logits(ss, seed, B, T):
+    _check_c5_logits(ss, seed, B, T)
+
+
+def test_c5_logits_padded_past_the_longest_clip(ss):
+    """The reference's MAX_T = 90 with every clip shorter (a batch as its collate_fn pads it)."""
+    _check_c5_logits(ss, 4, 3, 90, lengths=[53, 1, 88])
+
+
+def _check_c5_logits(ss, seed, B, T, lengths=None):
     sd = W.make_state_dict(seed, 84, 100, True, **C5)
-    X, Lh, R, y = W.make_inputs(seed, B, T, 84, 100, (96, 96))
+    X, Lh, R, y = W.make_inputs(seed, B, T, 84, 100, (96, 96), lengths=lengths, zero_padding=lengths is not None)
     m = build(ss, sd)
     with torch.no_grad():
         logits = m(X.cuda(), Lh, R.cuda()).cpu()
@@ -57,9 +66,17 @@ def test_c5_logits(ss, seed, B, T):
 
 
 def test_c5_autograd_gradients(ss):
-    sd = W.make_state_dict(3, 84, 100, True, **C5)
-    B, T = 6, 7
-    X, Lh, R, y = W.make_inputs(3, B, T, 84, 100, (96, 96))
+    _check_c5_autograd_gradients(ss, 3, 6, 7)
+
+
+def test_c5_autograd_gradients_padded_past_the_longest_clip(ss):
+    """The same bounds at the reference's MAX_T = 90, every clip shorter."""
+    _check_c5_autograd_gradients(ss, 5, 4, 90, lengths=[61, 17, 1, 89])
+
+
+def _check_c5_autograd_gradients(ss, seed, B, T, lengths=None):
+    sd = W.make_state_dict(seed, 84, 100, True, **C5)
+    X, Lh, R, y = W.make_inputs(seed, B, T, 84, 100, (96, 96), lengths=lengths, zero_padding=lengths is not None)
     m = build(ss, sd)
     logits = m(X.cuda(), Lh.cuda(), R.cuda())
     loss = torch.nn.functional.cross_entropy(logits, y.cuda(), label_smoothing=0.05)
