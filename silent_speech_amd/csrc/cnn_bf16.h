@@ -51,11 +51,9 @@ template <> struct ImgLayout<64, 24> { static constexpr int PS = 80, RS = 2176; 
 template <> struct ImgLayout<96, 12> { static constexpr int PS = 112, RS = 1600; };  // conv4 data gradient: dy4
 
 // TR = true: the image is read by the transposing reads of a weight-gradient kernel (ds_read_b64_tr_b16, two groups of 32 lanes):
-// those keep the round-2 strides (measured: conv3's weight gradient 0.25 -> 0.30 ms on the ds_read_b128 layout of its input).
-#ifndef SS_TR_PAD
-#define SS_TR_PAD 8
-#endif
-constexpr int TR_PAD = SS_TR_PAD;  // elements added to a pixel of an image (C >= 32) that the transposing reads walk
+// those keep the round-2 strides (measured: conv3's weight gradient 0.25 -> 0.30 ms on the ds_read_b128 layout of its input;
+// a pad of 16 instead of 8 measured no gain).
+constexpr int TR_PAD = 8;  // elements added to a pixel of an image (C >= 32) that the transposing reads walk
 template <int C_, int H_, int W_, bool TR = false>
 struct Img {
   static constexpr int C = C_, H = H_, W = W_;

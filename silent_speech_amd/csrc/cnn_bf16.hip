@@ -383,9 +383,6 @@ __global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(ConvFwdParams p) {
 // channel group = 2 x 18 fragments (144 registers) for the whole walk and multiplies them with some of the frame's nine pixel
 // tiles (16 consecutive pixels each: conv_fwd's A-fragment read as the B operand), 36 MFMAs and 18 fragment reads per tile.  Waves 6 and 7 are PRODUCERS: they write the next frame (loaded a whole frame time earlier) into the other
 // image, copy the previous frame's sign mask out and finish its average; one workgroup barrier per frame.
-#ifndef SS_L4_NRD
-#define SS_L4_NRD 9
-#endif
 struct ConvLastWsParams {
   const bf16_t* in;   // (N, 12, 12, 64)
   int N;
@@ -448,7 +445,7 @@ __global__ __launch_bounds__(NT, 2) void conv_last_fwd_ws_kernel(ConvLastWsParam
 
   // producers: a frame is 144 pixels x 8 pieces of 16 bytes = 1152 pieces, 9 per producer thread
   // (in rounds of NRD pieces: nine quads of staging registers live across a pass beside the consumers' 144 weight registers spilled)
-  constexpr int NLD = (NPIX * (C3 / 8) + NPT - 1) / NPT, NRD = SS_L4_NRD;
+  constexpr int NLD = (NPIX * (C3 / 8) + NPT - 1) / NPT, NRD = 9;
   static_assert(NLD % NRD == 0, "load rounds");
   const int pt = tid - NCONS * 64;
   auto copy_frame = [&](int n, bf16_t* img) {
@@ -797,20 +794,12 @@ extern "C" int ss_c5_conv12_fwd(const uint8_t* R, int N, int standardize, const 
   return ss_c5_conv12_fwd_i1(R, N, standardize, w1, b1, w2, b2, a2, i2, st, nullptr, stream);
 }
 
-static const bool ss_c5_last_ws = !(getenv("SS_C5_LAST_WS") && getenv("SS_C5_LAST_WS")[0] == '0');
-
 // layer 4 without the Linear: feat (N, 96) f32 = global average of ReLU(conv4), mask (N,144,96) u8 or null
 extern "C" int ss_c5_conv_last_fwd_feat(const uint16_t* in, int N, const float* w, const float* b, uint8_t* mask, float* feat,
                                         ss_stream_t stream) {
   SS_REQUIRE(in && w && b && feat && N > 0, SS_ERR_ARG);
-  if (ss_c5_last_ws) {  // weight-stationary form (SS_C5_LAST_WS=0: the LDS-resident weights of conv_fwd_kernel)
-    ConvLastWsParams q{in, N, w, b, mask, feat};
-    return launch_persistent(conv_last_fwd_ws_kernel, q, CONV_LAST_WS_LDS, N, static_cast<hipStream_t>(stream));
-  }
-  ConvFwdParams p{};
-  p.in = in; p.N = N; p.w = w; p.b = b; p.mask = mask; p.feat = feat;
-  return launch_persistent(conv_fwd_kernel<C3, C4, 12, 12, true, 3, 3>, p, conv_fwd_lds<C3, C4, 12, 12, true>(), N,
-                           static_cast<hipStream_t>(stream));
+  ConvLastWsParams q{in, N, w, b, mask, feat};  // weight-stationary form
+  return launch_persistent(conv_last_fwd_ws_kernel, q, CONV_LAST_WS_LDS, N, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ss_c5_conv1_fwd(const uint8_t* R, int N, int standardize, const float* w1, const float* b1, uint16_t* a1,

@@ -1234,8 +1234,6 @@ extern "C" int ss_c5_conv_last_wgrad(const uint16_t* a_in, const float* dz, int 
                            static_cast<hipStream_t>(stream));
 }
 
-static const bool ss_c5_last_ws = !(getenv("SS_C5_LAST_WS") && getenv("SS_C5_LAST_WS")[0] == '0');
-
 // The same two with d feat * 144 = d z . W_fc of every frame ready-made (dfeat (N, 96) f32: one small GEMM in front of them); the fc
 // gradients (g_wfc = d z^T . feat, g_bfc = column sums of d z) are then the caller's GEMMs as well.
 extern "C" int ss_c5_conv_last_wgrad_df(const uint16_t* a_in, const float* dfeat, const uint8_t* mask, int N, float* g_w, float* g_b,
@@ -1250,14 +1248,8 @@ extern "C" int ss_c5_conv_last_wgrad_df(const uint16_t* a_in, const float* dfeat
 extern "C" int ss_c5_conv_last_dgrad_df(const float* dfeat, const uint8_t* mask, int N, const float* w, uint16_t* da_in,
                                         ss_stream_t stream) {
   SS_REQUIRE(dfeat && mask && w && da_in && N > 0, SS_ERR_ARG);
-  if (ss_c5_last_ws) {  // weight-stationary form (SS_C5_LAST_WS=0: the LDS-resident weights of conv_dgrad_kernel)
-    ConvLastDgradWsParams q{N, dfeat, mask, w, da_in};
-    return launch_persistent(conv_last_dgrad_ws_kernel, q, CONV_LAST_DGRAD_WS_LDS, N, static_cast<hipStream_t>(stream));
-  }
-  ConvBwdParams p{};
-  p.N = N; p.dfeat = dfeat; p.mask = mask; p.w = w; p.da_in = da_in;
-  return launch_persistent(conv_dgrad_kernel<C3, C4, 12, 12, true, 12, 3, false>, p, dgrad_lds<C3, C4, 12, 12, false>(), N,
-                           static_cast<hipStream_t>(stream));
+  ConvLastDgradWsParams q{N, dfeat, mask, w, da_in};  // weight-stationary form
+  return launch_persistent(conv_last_dgrad_ws_kernel, q, CONV_LAST_DGRAD_WS_LDS, N, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int ss_c5_conv_last_dgrad(const float* dz, int ld_dz, int E, const float* wfc, const uint8_t* mask, int N, const float* w,

@@ -1025,8 +1025,6 @@ extern "C" int ss_gemm_splitk_reduce(const float* ws, int M, int N, int K, int s
   return ss_launch_status();
 }
 
-static const bool ss_gemm_no_dma = getenv("SS_GEMM_NO_DMA") != nullptr;  // diagnostic: force the register-staged kernel
-
 // Argument checks and kernel parameters shared by the plain and the grouped entry points.
 struct GemmLaunch {
   GemmParams p;
@@ -1061,7 +1059,7 @@ static int gemm_prepare(int a_kcontig, int b_kcontig, int M, int N, int K, const
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   out->dma_ok = !a_colsum && al16(A) && al16(B) && (lda & 3) == 0 && (ldb & 3) == 0 && (stride_a & 3) == 0 &&
                 (stride_b & 3) == 0 && (a_kcontig || (M >= 4 && (M & 3) == 0)) && (b_kcontig || (N >= 4 && (N & 3) == 0)) &&
-                p.ksplit >= 4 * BK && !ss_gemm_no_dma;
+                p.ksplit >= 4 * BK;
   return SS_OK;
 }
 
@@ -1095,9 +1093,8 @@ extern "C" int ss_gemm_f32_batched(int a_kcontig, int b_kcontig, int M, int N, i
     grid.z = p.nz;
   }
   // [row][k] x [row][k] with enough 192 x 192 output tiles to fill most of the chip in one round, plain store (+ bias): the
-  // wide-tile kernel (the GRU input projections; SS_GEMM_WIDE_KC=0: diagnostic)
-  static const bool wide_kc_on = getenv("SS_GEMM_WIDE_KC") == nullptr || atoi(getenv("SS_GEMM_WIDE_KC")) != 0;
-  if (dma_ok && wide_kc_on && a_kcontig && b_kcontig && !(flags & 31) && splits == 1 && p.ra.G == 0x7fffffff && p.ra.off == 0 &&
+  // wide-tile kernel (the GRU input projections)
+  if (dma_ok && a_kcontig && b_kcontig && !(flags & 31) && splits == 1 && p.ra.G == 0x7fffffff && p.ra.off == 0 &&
       p.rb.G == 0x7fffffff && p.rb.off == 0 && (K & 3) == 0) {
     const long tiles = (long)ceil_div(M, wide::WT) * ceil_div(N, wide::WT) * batch;
     const int cus = ss_device_cus();
@@ -1146,7 +1143,6 @@ static long group_ws_offset(const ss_gemm_problem* pr, int j) {  // floats in fr
 
 // The wide-tile form (namespace wide) of a group: K slices chosen here, from the shapes and the chip's CU count alone, so that the
 // workgroups of all problems together fill the chip once (one 512-thread workgroup per CU); `splits` of the records is ignored.
-static const bool ss_gemm_dw_wide = getenv("SS_GEMM_DW_WIDE") == nullptr || atoi(getenv("SS_GEMM_DW_WIDE")) != 0;
 static bool wide_plan(const ss_gemm_problem* pr, int n, wide::WideGroup* out, long* floats) {
   using namespace wide;
   long work = 0;
@@ -1198,7 +1194,7 @@ static bool wide_plan(const ss_gemm_problem* pr, int n, wide::WideGroup* out, lo
   if (floats) *floats = off;
   // what the DMA ring and the row clamps need: k-major operands, 16-byte aligned, row counts that are multiples of 4
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  bool ok = ss_gemm_dw_wide && !ss_gemm_no_dma;
+  bool ok = true;
   for (int j = 0; j < n; ++j) {
     const ss_gemm_problem& q = pr[j];
     ok = ok && !q.a_kcontig && !q.b_kcontig && al16(q.A) && al16(q.B) && (q.lda & 3) == 0 && (q.ldb & 3) == 0 &&

@@ -794,7 +794,6 @@ int launch_gemm_bf16(int a_kcontig, int b_kcontig, const GemmBfParams& p, dim3 g
 }  // namespace
 
 // ---- grouped weight-gradient GEMMs (ring kernel, stream-K over the group; see gemm_bf16_ring_group_kernel)
-static const bool ss_gemm_bf16_group_split = getenv("SS_GEMM_BF16_GROUP_SPLIT") != nullptr;  // diagnostic: always the stream-K form
 static int ring_group_cus() { return ss_device_cus(); }
 static int ring_group_prepare(const ss_gemm_problem* pr, int n, float* ws, ring::RingGroup* out, int* wgs, long* floats) {
   SS_REQUIRE(pr && n >= 1 && n <= ring::GROUP_MAX, SS_ERR_ARG);
@@ -829,7 +828,7 @@ static int ring_group_prepare(const ss_gemm_problem* pr, int n, float* ws, ring:
   *wgs = ceil_div(units, gg.U);
   *floats = (long)gg.tbase[n] * gg.maxc * ring::SLAB_FLOATS;
   // at least half a chip of output tiles (and no more than a chip): one workgroup per tile, no K split
-  gg.whole = (2 * gg.tbase[n] >= ring_group_cus() && gg.tbase[n] <= ring_group_cus() && !ss_gemm_bf16_group_split) ? 1 : 0;
+  gg.whole = (2 * gg.tbase[n] >= ring_group_cus() && gg.tbase[n] <= ring_group_cus()) ? 1 : 0;
   if (gg.whole) *wgs = gg.tbase[n];
   return SS_OK;
 }
@@ -864,8 +863,6 @@ extern "C" int ss_gemm_bf16_splitk_group(const ss_gemm_problem* problems, int n,
   return ss_launch_status();
 }
 
-static const bool ss_gemm_bf16_no_ring = getenv("SS_GEMM_BF16_NO_RING") != nullptr;
-
 extern "C" int ss_gemm_bf16_batched(int a_kcontig, int b_kcontig, int M, int N, int K, const void* A, int lda, int a_group,
                                     int a_gstride, int a_off, const void* B, int ldb, int b_group, int b_gstride, int b_off,
                                     float* C, int ldc, const float* bias, int flags, int splits, int batch, long stride_a,
@@ -897,8 +894,8 @@ extern "C" int ss_gemm_bf16_batched(int a_kcontig, int b_kcontig, int M, int N, 
   p.sa = stride_a; p.sb = stride_b; p.sc = stride_c; p.sbias = stride_bias;
   dim3 grid(ceil_div(N, BN), ceil_div(M, BM), batch * p.splits);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // bf16 operands, whole 64-deep k tiles, an output worth a 256 x 128 tile: the ring kernel (SS_GEMM_BF16_NO_RING: diagnostic)
-  if (src16 && K % 64 == 0 && (M >= 128 || (flags & 16)) && !ss_gemm_bf16_no_ring) {
+  // bf16 operands, whole 64-deep k tiles, an output worth a 256 x 128 tile: the ring kernel
+  if (src16 && K % 64 == 0 && (M >= 128 || (flags & 16))) {
     const int kcat = (flags & 16) ? batch : 1;
     if (a_kcontig && b_kcontig) return ring::launch_ring<1, 1>(p, batch, kcat, s);
     if (a_kcontig) return ring::launch_ring<1, 0>(p, batch, kcat, s);

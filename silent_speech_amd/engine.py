@@ -25,18 +25,12 @@ import torch
 from . import _lib as L
 
 INT_MAX = 2**31 - 1
-# bench.py turns this off for its per-kernel timing pass: HIP-event pairs only bracket a kernel's own run time when
-# every launch sits on one stream
-JOIN_BEFORE_CNN_BWD = True
-# weight-gradient GEMMs of layer l > 0 are queued behind its d layer_in GEMM, so they run beside the recurrence of layer l - 1
-# (latency-bound) rather than beside that GEMM (MFMA-bound like them): 2.30 vs 2.32 ms/step
-SIDE_AFTER_DX = os.environ.get("SS_SIDE_AFTER_DX", "1") == "1"
-USE_SPLIT_GRU = True
-FUSE_GRU_DROPOUT = os.environ.get("SS_FUSE_GRU_DROPOUT", "1") != "0"  # 0: the inter-layer dropout as its own launch (ss_dropout)
 # K slices of the d W_hh GEMMs (18 / 12 output tiles): fewer, longer slices than for d W_ih halve the scratch traffic of
 # their reduce passes (measured 512: -0.3 % on the step against 768; 384 and 256: +0.4 %)
-_HH_TARGET = int(os.environ.get("SS_SPLITK_TARGET_HH", "512"))
-USE_SIDE_STREAM = os.environ.get("SS_NO_SIDE_STREAM", "0") != "1"
+_HH_TARGET = 512
+# bench.py turns this off for its per-kernel timing pass: HIP-event pairs only bracket a kernel's own run time when
+# every launch sits on one stream
+USE_SIDE_STREAM = True
 
 
 @dataclass
@@ -81,17 +75,16 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, Cm, ldc, bias=None, accumulate=Fal
            b_map[0], b_map[1], b_map[2], Cm, ldc, bias, a_colsum, flags, splits, batch, *strides, L.stream(), tag=tag)
 
 
-_SPLITK_TARGET = int(os.environ.get("SS_SPLITK_TARGET", "768"))
+_SPLITK_TARGET = 768
 # Layer 0's weight-gradient group runs when no recurrence is left to share the chip with: wide 192 x 192 tiles, one workgroup per
 # CU (ss_gemm_f32_splitk_group flags bit 0).  The upper layers' groups run beside the BPTT kernel of the layer below and keep the
 # 128 x 64 form: measured in the step, the wide form there made the launch 12 % shorter and the step 1 % longer.
-DW_WIDE_ALONE = int(os.environ.get("SS_DW_WIDE_ALONE", "1"))
+DW_WIDE_ALONE = 1
 # The fused ROI-CNN kernels walk only the frames inside their clips (rows t >= lengths[b] of a padded batch never reach the packed
 # recurrence and carry no gradient): a batch that is 40 % padding costs 40 % less CNN time.  0 = every frame, as the reference does.
 SKIP_PADDED_FRAMES = os.environ.get("SS_CNN_SKIP_PADDING", "1") != "0"
 
-
-_DX_SPLIT_CAP = int(os.environ.get("SS_DX_SPLITS", "2"))  # K slices of a d layer_in GEMM with few output tiles (1 = off)
+_DX_SPLIT_CAP = 2  # K slices of a d layer_in GEMM with few output tiles
 
 
 def split_k(M, N, K, batch=1, target_wgs=_SPLITK_TARGET):
@@ -207,7 +200,7 @@ class Workspace:
         self.lengths = torch.empty(B, device=device, dtype=torch.int32)
         # step counters of the multi-CU recurrence (zeroed once; the kernels keep them consistent): only shapes small
         # enough to leave most of the chip idle under the one-CU-per-slice kernels get one
-        nb = L.gru_sync_bytes(B, T, H) if USE_SPLIT_GRU else 0
+        nb = L.gru_sync_bytes(B, T, H)
         self.gru_sync = torch.zeros(nb // 4, device=device, dtype=torch.int32) if nb else None
         # weight-gradient GEMMs run on a side stream next to the (32-CU) recurrence of the layer below
         self.side = side_stream(device, slot) if train else None
@@ -336,8 +329,9 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
              bias=P[f"gru.bias_ih_l{l}"].data_ptr(), tag="gemm_gru_ih", batch=2,
              strides=(0, _pstride(P, wf, wr), N * 3 * H, _pstride(P, f"gru.bias_ih_l{l}", f"gru.bias_ih_l{l}_reverse"), 0))
         drop = train and l < cfg.gru_layers - 1 and cfg.gru_dropout > 0.0
-        # nn.GRU's inter-layer dropout: a by-product of the multi-CU recurrence kernel (its own launch + read of `out` otherwise)
-        fused_drop = drop and ws.gru_sync is not None and FUSE_GRU_DROPOUT
+        # nn.GRU's inter-layer dropout: a by-product of the multi-CU recurrence kernel (its own launch + read of `out` when the
+        # shape has no multi-CU recurrence)
+        fused_drop = drop and ws.gru_sync is not None
         L.call("ss_gru_fwd_drop", ws.gi[l].data_ptr(), P[f"gru.weight_hh_l{l}"].data_ptr(),
                P[f"gru.weight_hh_l{l}_reverse"].data_ptr(), P[f"gru.bias_hh_l{l}"].data_ptr(),
                P[f"gru.bias_hh_l{l}_reverse"].data_ptr(), ws.lengths.data_ptr(), B, T, H, ws.out[l].data_ptr(),
@@ -443,9 +437,9 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
                        ws.splitk_ws.numel(), DW_WIDE_ALONE if l == 0 else 0, L.stream(), tag="gemm_gru_dW")
         # the weight-gradient GEMMs of the upper layers start only when this layer's d layer_in GEMM is through: two
         # MFMA-bound GEMMs side by side gain nothing and the one on the critical path loses half its rate; beside the
-        # latency-bound recurrence of the layer below they fill idle matrix pipes.  Layer 0 has no recurrence left to
-        # hide behind, so its weight gradients run beside its (short) d layer_in GEMM.
-        if not (SIDE_AFTER_DX and l > 0):
+        # latency-bound recurrence of the layer below they fill idle matrix pipes (2.30 against 2.32 ms per step).  Layer 0
+        # has no recurrence left to hide behind, so its weight gradients run beside its (short) d layer_in GEMM.
+        if l == 0:
             side_work()
         # d layer_in = dGi_f . W_ih_f + dGi_r . W_ih_r
         need_dx = (l > 0) or cfg.use_roi or (d_X is not None)
@@ -474,7 +468,7 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
             gemm(1, 0, N, K - c0, 3 * H, ws.dG[l].data_ptr(), 4 * H, _addr(P[wi], c0), K, dst + 4 * c0, ld_dst,
                  accumulate=True, atomic=True, tag="gemm_gru_dX", batch=2, splits=dx_splits,
                  strides=(N * 4 * H, _pstride(P, wi, wir), 0, 0, 0))
-        if SIDE_AFTER_DX and l > 0:
+        if l > 0:
             side_work()
     # ---- ROI CNN
     side_joined = False  # nothing is queued on the side stream after the join in front of the CNN backward
@@ -482,7 +476,7 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
         Hh, Ww = ws.roi_hw
         if d_X is not None:
             L.call("ss_copy_rows_f32", ws.dZ.data_ptr(), cfg.in_dim, d_X.data_ptr(), cfg.x_dim, N, cfg.x_dim, s)
-        if USE_SIDE_STREAM and JOIN_BEFORE_CNN_BWD:
+        if USE_SIDE_STREAM:
             # the persistent ROI-CNN kernel takes every CU for ~1 ms: weight-gradient GEMMs still queued on the side
             # stream at that point would only finish after it (measured: a 180 us tail), so let them drain first --
             # they run beside the d layer_in GEMM above and cost the critical path a few tens of microseconds

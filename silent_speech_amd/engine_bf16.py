@@ -3,11 +3,13 @@
 Same contract as ``engine.py`` (explicit forward / backward over raw device buffers, no aten compute op, no CPU
 fallback); what differs is the kernel set:
 
-    ROI CNN      ss_c5_conv12_fwd (conv1 + conv2 fused) -> ss_c5_conv_fwd(3) -> ss_c5_conv_last_fwd   (cnn_bf16.hip)
+    ROI CNN      ss_c5_conv12_fwd (conv1 + conv2 fused) -> ss_c5_conv_fwd(3) -> ss_c5_conv_last_fwd_feat   (cnn_bf16.hip)
                  pooled maps a2, a3 between the layers: NHWC bf16 in HBM + one argmax byte per element (the training stash);
-                 the pooled conv1 map stays in LDS and is recomputed from the frame by the backward kernels that need it
+                 the pooled conv1 map stays in LDS and is recomputed from the frame by the backward kernels that need it;
+                 Linear(96 -> roi_emb) and its gradients as f32 GEMMs over all frames
     GRU layers   ss_gemm_bf16_batched (input projections, d layer_in, weight gradients) + ss_gru_bf16_fwd / _bwd
-                 (one launch per time step, both directions; W_hh as bf16 copies made once per step by ss_gru_bf16_prep)
+                 (both directions; one persistent launch when ss_gru_bf16_sync_bytes > 0, else one launch per time step;
+                 W_hh as bf16 copies made once per step by ss_gru_bf16_prep)
     tail         the f32 fused AttnPool / head / CE kernels of the f32 path (0.1 % of the FLOPs)
 
 f32 master weights, f32 gradients, f32 Adam: only MFMA operands are bf16.  The reference defines no such model
@@ -16,17 +18,15 @@ f32 master weights, f32 gradients, f32 Adam: only MFMA operands are bf16.  The r
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib as L
+from .engine import INT_MAX, _addr, _pstride, side_stream, zero_buffers
+from .engine import gemm as gemm_f32, split_k as split_k_f32  # the fc GEMMs and the head's weight-gradient GEMMs stay f32
 
-INT_MAX = 2**31 - 1
 USE_SIDE_STREAM = True  # bench.py turns it off for its per-kernel timing pass (HIP-event pairs need one stream)
-FUSE_DGRAD2_WGRAD1 = os.environ.get("SS_C5_UNFUSED_DA1", "0") != "1"  # 0: conv2 dgrad and conv1 wgrad as two kernels (round-2 form)
-USE_PERSISTENT_GRU = os.environ.get("SS_C5_STEP_GRU", "0") != "1"  # 0: one launch per time step (the round-2 form, kept as the fallback)
 CNN_CHANNELS = (16, 32, 64, 96)
 ROI_HW = (96, 96)
 _IDENT = (INT_MAX, 0, 0)
@@ -43,7 +43,7 @@ def gemm(a_kc, b_kc, M, N, K, A, lda, B, ldb, Cm, ldc, bias=None, accumulate=Fal
 
 # K slices of the weight-gradient GEMMs aim at this many workgroups (measured 192 / 384 / 768 / 1536: 6.10 / 6.09 / 6.17 / 6.33 ms
 # per step: the GEMMs run beside the BPTT steps on the side stream, fewer float atomics matter more than their own time)
-_SPLITK_TARGET = int(os.environ.get("SS_C5_SPLITK_TARGET", "384"))
+_SPLITK_TARGET = 384
 
 
 def split_k(M, N, K, batch, target_wgs=None):
@@ -54,16 +54,7 @@ def split_k(M, N, K, batch, target_wgs=None):
 
 # The weight-gradient GEMMs of a GRU layer as ONE launch of the LDS-DMA ring kernel, K dealt evenly over the CUs, + one reduce
 # launch (ss_gemm_bf16_splitk_group) when every K is a whole number of 64-deep tiles (B a multiple of 64); otherwise three
-# launches with K slices and float atomics.  SS_C5_DW_GROUP=0: always the latter (the form of the first half of round 3).
-# conv1's pool winners (37 KB per frame) stashed by the forward kernel for the fused conv2-dgrad / conv1-wgrad kernel (0: recomputed there)
-STASH_I1 = os.environ.get("SS_C5_STASH_I1", "1") != "0"
-# Linear(96 -> roi_emb) behind the CNN and its gradients as GEMMs over all frames instead of per-frame loops inside the last layer's
-# persistent kernels (0: inside the kernels, the form of the first half of round 3)
-FC_AS_GEMM = os.environ.get("SS_C5_FC_GEMM", "1") != "0"
-USE_DW_GROUP = os.environ.get("SS_C5_DW_GROUP", "1") != "0"
-DW_ALL_LAYERS = os.environ.get("SS_C5_DW_ALL_LAYERS", "1") != "0"  # 0: one grouped launch per layer
-# d layer_in = dGi_f W_ih_f + dGi_r W_ih_r as one product with K concatenated (plain stores, no cleared destination, no atomics)
-USE_DX_KCAT = os.environ.get("SS_C5_DX_KCAT", "1") != "0"
+# launches with K slices and float atomics.
 
 
 def dw_problems(cfg, B, T, l, Kp, dg=16, lin=16, hp=16, g_ih=(16, 0), g_hh=(16, 0)):
@@ -84,7 +75,7 @@ def dw_problems(cfg, B, T, l, Kp, dg=16, lin=16, hp=16, g_ih=(16, 0), g_hh=(16, 
 
 
 def dw_group_ok(problems) -> bool:
-    return USE_DW_GROUP and all(q.K % 64 == 0 for q in problems)
+    return all(q.K % 64 == 0 for q in problems)
 
 
 DW_GROUP_MAX = 8  # problems per ss_gemm_bf16_splitk_group launch (csrc/gemm_bf16.hip ring::GROUP_MAX)
@@ -94,7 +85,7 @@ def dw_flush_after(cfg, l: int, pending: int) -> bool:
     """Does backward() launch the pending weight-gradient problems behind layer ``l`` (walking top-down), ``pending`` of them
     queued including this layer's?  One rule for the launches and for the scratch size (WorkspaceBf16 replays it): a group
     holds at most DW_GROUP_MAX problems and a layer adds up to three, so it is flushed as soon as another layer might not fit."""
-    return l == 0 or not DW_ALL_LAYERS or pending + 3 > DW_GROUP_MAX
+    return l == 0 or pending + 3 > DW_GROUP_MAX
 
 
 def dw_group_schedule(cfg, B, T, kp):
@@ -111,14 +102,6 @@ def dw_group_schedule(cfg, B, T, kp):
     if pending:
         groups.append(pending)
     return groups
-
-
-def _pstride(P, a: str, b: str) -> int:
-    return (P[b].data_ptr() - P[a].data_ptr()) // 4
-
-
-def _addr(t: torch.Tensor, offset_elems: int = 0) -> int:
-    return t.data_ptr() + offset_elems * t.element_size()
 
 
 def _pad8(n: int) -> int:
@@ -149,8 +132,6 @@ class WorkspaceBf16:
         # weight-gradient GEMMs of a layer run on a side stream beside the BPTT steps of the layer below (a step is a tiny,
         # latency-bound launch that leaves the matrix pipes idle)
         # (one stream per device and micro-batch slot, shared by all workspaces: engine.side_stream)
-        from .engine import side_stream
-
         self.side = side_stream(device, slot) if train else None
         self.ev_fork = torch.cuda.Event() if train else None
         self.ev_join = torch.cuda.Event() if train else None
@@ -181,7 +162,7 @@ class WorkspaceBf16:
         # the persistent recurrence's exchange area (tagged granules + launch generation): zeroed ONCE, the kernels keep it consistent
         if L.load().ss_gru_bf16_sync_bytes(B, T, H, C.byref(nb)) != 0:
             raise RuntimeError("ss_gru_bf16_sync_bytes failed")
-        self.gru_sync = torch.zeros(nb.value // 4, device=device, dtype=torch.int32) if (nb.value and USE_PERSISTENT_GRU) else None
+        self.gru_sync = torch.zeros(nb.value // 4, device=device, dtype=torch.int32) if nb.value else None
         self.logits = torch.empty(B, cfg.num_classes, **f32)
         self.attn = torch.empty(B, T, **f32)
         self.mid_drop = torch.empty(B, cfg.head_mid, **f32)
@@ -216,13 +197,13 @@ class WorkspaceBf16:
             if cfg.use_roi:
                 c1, c2, c3, c4 = CNN_CHANNELS
                 self.st = torch.empty(N, 2, **f32)
-                self.i1 = torch.empty(N, 48, 48, c1, **u8) if (STASH_I1 and FUSE_DGRAD2_WGRAD1) else None
+                # conv1's pool winners (37 KB per frame), stashed by the forward kernel for the fused conv2-dgrad / conv1-wgrad kernel
+                self.i1 = torch.empty(N, 48, 48, c1, **u8)
                 self.m4 = torch.empty(N, 144, c4, **u8)
                 self.dfeat = torch.empty(N, c4, **f32)
                 # partial weight-gradient sums of the conv layers' persistent workgroups (one per CU): plain stores + a reduce launch
                 cus = torch.cuda.get_device_properties(device).multi_processor_count
                 self.wg_part = torch.empty(min(N, cus) * c4 * c3 * 9, **f32)
-                self.da1 = torch.empty(N, 48, 48, c1, **i16) if not FUSE_DGRAD2_WGRAD1 else None
                 self.da2 = torch.empty(N, 24, 24, c2, **i16)
                 self.da3 = torch.empty(N, 12, 12, c3, **i16)
 
@@ -244,18 +225,13 @@ def forward(P: Dict[str, torch.Tensor], cfg, ws: WorkspaceBf16, X: torch.Tensor,
         L.call("ss_c5_conv12_fwd_i1", R.data_ptr(), N, int(cfg.roi_standardize), w[0], b[0], w[1], b[1], ws.a2.data_ptr(), ws.i2.data_ptr(),
                ws.st.data_ptr() if stash else None, L.ptr(ws.i1) if stash else None, s, tag="ss_c5_conv12_fwd")
         L.call("ss_c5_conv_fwd", 3, ws.a2.data_ptr(), N, w[2], b[2], ws.a3.data_ptr(), ws.i3.data_ptr(), s, tag="ss_c5_conv3_fwd")
-        if FC_AS_GEMM:
-            from .engine import gemm as gemm_f32
-
-            c4 = CNN_CHANNELS[3]
-            L.call("ss_c5_conv_last_fwd_feat", ws.a3.data_ptr(), N, w[3], b[3], ws.m4.data_ptr() if stash else None, ws.feat.data_ptr(), s,
-                   tag="ss_c5_conv_last_fwd")
-            gemm_f32(1, 1, N, cfg.roi_emb, c4, ws.feat.data_ptr(), c4, P["roi_cnn.fc.weight"].data_ptr(), c4, _addr(ws.Z, cfg.x_dim),
-                     cfg.in_dim, bias=P["roi_cnn.fc.bias"].data_ptr(), tag="gemm_fc")
-        else:
-            L.call("ss_c5_conv_last_fwd", ws.a3.data_ptr(), N, w[3], b[3], P["roi_cnn.fc.weight"].data_ptr(), P["roi_cnn.fc.bias"].data_ptr(),
-                   cfg.roi_emb, _addr(ws.Z, cfg.x_dim), cfg.in_dim, ws.m4.data_ptr() if stash else None,
-                   ws.feat.data_ptr() if stash else None, s)
+        # Linear(96 -> roi_emb) behind the CNN (and its gradients) as GEMMs over all frames: the last layer's kernel leaves the
+        # averaged features
+        c4 = CNN_CHANNELS[3]
+        L.call("ss_c5_conv_last_fwd_feat", ws.a3.data_ptr(), N, w[3], b[3], ws.m4.data_ptr() if stash else None, ws.feat.data_ptr(), s,
+               tag="ss_c5_conv_last_fwd")
+        gemm_f32(1, 1, N, cfg.roi_emb, c4, ws.feat.data_ptr(), c4, P["roi_cnn.fc.weight"].data_ptr(), c4, _addr(ws.Z, cfg.x_dim),
+                 cfg.in_dim, bias=P["roi_cnn.fc.bias"].data_ptr(), tag="gemm_fc")
         if ws.train and ws.stagger:  # only when another micro-batch waits for it (train.Trainer)
             ws.ev_cnn_fwd.record()
         layer_in, ld_in = ws.Z.data_ptr(), cfg.in_dim
@@ -297,8 +273,6 @@ def forward(P: Dict[str, torch.Tensor], cfg, ws: WorkspaceBf16, X: torch.Tensor,
 def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: WorkspaceBf16, X: torch.Tensor,
              R: Optional[torch.Tensor], d_logits: torch.Tensor, *, train: bool, seed: int = 0,
              d_X: Optional[torch.Tensor] = None) -> None:
-    from .engine import gemm as gemm_f32, zero_buffers  # the head's two tiny weight-gradient GEMMs stay f32
-
     B, T, H, N = ws.B, ws.T, cfg.hidden, ws.B * ws.T
     s = L.stream()
     Cn, MID = cfg.num_classes, cfg.head_mid
@@ -403,7 +377,9 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: Wo
                 torch.cuda.current_stream().wait_event(ws.ev_zero)
                 zero_waited = True
             # (layer 0 with the ROI branch: 68 output columns = 30 tiles of the ring kernel -- K slices and atomics fill more CUs)
-            if USE_DX_KCAT and (3 * H) % 64 == 0 and K - c0 >= 128:
+            # both directions as one product with K concatenated (plain stores, no cleared destination, no atomics) when the ring
+            # kernel takes it
+            if (3 * H) % 64 == 0 and K - c0 >= 128:
                 L.call("ss_gemm_bf16_batched", 1, 0, N, K - c0, 3 * H, dg, 4 * H, *_IDENT, _addr(ws.wih[l], c0), Kp, *_IDENT, dst, ld_dst,
                        None, 8 | 16, 1, 2, N * 4 * H, 3 * H * Kp, 0, 0, L.stream(), tag="gemm_bf16_dX")
             else:
@@ -425,31 +401,24 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: Wo
         gb = [G[k + ".bias"].data_ptr() for k in _CONV]
         dz = _addr(ws.dZ, cfg.x_dim)
         wfc = P["roi_cnn.fc.weight"].data_ptr()
-        if FC_AS_GEMM:
-            from .engine import split_k as split_k_f32
+        c4, E = CNN_CHANNELS[3], cfg.roi_emb
+        gemm_f32(1, 0, N, c4, E, dz, cfg.in_dim, wfc, c4, ws.dfeat.data_ptr(), c4, tag="gemm_fc")  # d z . W_fc
 
-            c4, E = CNN_CHANNELS[3], cfg.roi_emb
-            gemm_f32(1, 0, N, c4, E, dz, cfg.in_dim, wfc, c4, ws.dfeat.data_ptr(), c4, tag="gemm_fc")  # d z . W_fc
+        def fc_grads():  # d W_fc += d z^T . feat, d b_fc += column sums of d z
+            gemm_f32(0, 0, E, c4, N, dz, cfg.in_dim, ws.feat.data_ptr(), c4, G["roi_cnn.fc.weight"].data_ptr(), c4, accumulate=True,
+                     atomic=True, splits=split_k_f32(E, c4, N), a_colsum=G["roi_cnn.fc.bias"].data_ptr(), tag="gemm_fc")
 
-            def fc_grads():  # d W_fc += d z^T . feat, d b_fc += column sums of d z
-                gemm_f32(0, 0, E, c4, N, dz, cfg.in_dim, ws.feat.data_ptr(), c4, G["roi_cnn.fc.weight"].data_ptr(), c4, accumulate=True,
-                         atomic=True, splits=split_k_f32(E, c4, N), a_colsum=G["roi_cnn.fc.bias"].data_ptr(), tag="gemm_fc")
-
-            if USE_SIDE_STREAM:
-                ws.ev_fork.record()
-                with torch.cuda.stream(ws.side):
-                    ws.side.wait_event(ws.ev_fork)
-                    fc_grads()
-            else:
+        if USE_SIDE_STREAM:
+            ws.ev_fork.record()
+            with torch.cuda.stream(ws.side):
+                ws.side.wait_event(ws.ev_fork)
                 fc_grads()
-            L.call("ss_c5_conv_last_wgrad_df", ws.a3.data_ptr(), ws.dfeat.data_ptr(), ws.m4.data_ptr(), N, gw[3], gb[3],
-                   ws.wg_part.data_ptr(), ws.wg_part.numel(), s, tag="ss_c5_conv_last_wgrad")
-            L.call("ss_c5_conv_last_dgrad_df", ws.dfeat.data_ptr(), ws.m4.data_ptr(), N, w[3], ws.da3.data_ptr(), s,
-                   tag="ss_c5_conv_last_dgrad")
         else:
-            L.call("ss_c5_conv_last_wgrad", ws.a3.data_ptr(), dz, cfg.in_dim, cfg.roi_emb, wfc, ws.m4.data_ptr(), ws.feat.data_ptr(), N,
-                   gw[3], gb[3], G["roi_cnn.fc.weight"].data_ptr(), G["roi_cnn.fc.bias"].data_ptr(), s)
-            L.call("ss_c5_conv_last_dgrad", dz, cfg.in_dim, cfg.roi_emb, wfc, ws.m4.data_ptr(), N, w[3], ws.da3.data_ptr(), s)
+            fc_grads()
+        L.call("ss_c5_conv_last_wgrad_df", ws.a3.data_ptr(), ws.dfeat.data_ptr(), ws.m4.data_ptr(), N, gw[3], gb[3],
+               ws.wg_part.data_ptr(), ws.wg_part.numel(), s, tag="ss_c5_conv_last_wgrad")
+        L.call("ss_c5_conv_last_dgrad_df", ws.dfeat.data_ptr(), ws.m4.data_ptr(), N, w[3], ws.da3.data_ptr(), s,
+               tag="ss_c5_conv_last_dgrad")
         # (partial sums through scratch + a reduce launch pay for the last layer's 55 k elements only: launch time at B = 256, T = 30,
         # tools/c5_fixed_cost.py / c5_last_bench.py with SS_NO_PART=1: layer 4 152 - 156 us against 172 - 174 with float atomics onto the
         # gradient, layer 3 equal, layer 2 (4.6 k elements) 376 against 362)
@@ -458,13 +427,10 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: Wo
         bb = [P[k + ".bias"].data_ptr() for k in _CONV]
         L.call("ss_c5_conv2_wgrad_rc", R.data_ptr(), ws.st.data_ptr(), int(cfg.roi_standardize), w[0], bb[0], ws.da2.data_ptr(),
                ws.i2.data_ptr(), N, gw[1], gb[1], s)
-        if FUSE_DGRAD2_WGRAD1:  # d a1 (the largest gradient map) is born and consumed in LDS: 1.13 GB per step less through HBM
-            L.call("ss_c5_conv2_dgrad_conv1_wgrad_i1", ws.da2.data_ptr(), ws.i2.data_ptr(), N, w[1], R.data_ptr(), ws.st.data_ptr(),
-                   int(cfg.roi_standardize), w[0], bb[0], None, gw[0], gb[0], L.ptr(ws.i1), s, tag="ss_c5_conv2_dgrad_conv1_wgrad")
-        else:
-            L.call("ss_c5_conv_dgrad", 2, ws.da2.data_ptr(), ws.i2.data_ptr(), N, w[1], ws.da1.data_ptr(), s, tag="ss_c5_conv2_dgrad")
-            L.call("ss_c5_conv1_wgrad", R.data_ptr(), N, int(cfg.roi_standardize), ws.st.data_ptr(), ws.da1.data_ptr(), None, w[0],
-                   bb[0], gw[0], gb[0], s)
+        # d a1 (the largest gradient map) is born and consumed in LDS: 1.13 GB per step less through HBM than conv2's data gradient
+        # and conv1's weight gradient as two kernels
+        L.call("ss_c5_conv2_dgrad_conv1_wgrad_i1", ws.da2.data_ptr(), ws.i2.data_ptr(), N, w[1], R.data_ptr(), ws.st.data_ptr(),
+               int(cfg.roi_standardize), w[0], bb[0], None, gw[0], gb[0], L.ptr(ws.i1), s, tag="ss_c5_conv2_dgrad_conv1_wgrad")
     if USE_SIDE_STREAM:  # the caller's next kernels (all-reduce, clip, Adam) read every gradient
         ws.ev_join.record(ws.side)
         torch.cuda.current_stream().wait_event(ws.ev_join)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic: launch time of the last conv layer's kernels against the number of frames (fixed cost per launch = weight staging /
-gradient flush; slope = cycles per frame).  python tools/c5_last_bench.py   (SS_C5_LAST_WS=0: LDS-resident weights)"""
+gradient flush; slope = cycles per frame).  python tools/c5_last_bench.py"""
 import os
 import sys
 

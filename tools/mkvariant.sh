@@ -1,6 +1,6 @@
 #!/bin/bash
 # Diagnostic: build a variant library for tools/cnn_ab.py.
-# usage: tools/mkvariant.sh NAME path/to/source.hip replaced_object_basename ["-DSS_VAR=1"]
+# usage: tools/mkvariant.sh NAME path/to/source.hip replaced_object_basename ["-DSS_FWD_STOP=1"]
 # -> silent_speech_amd/_ab/libNAME.so = the in-tree objects with csrc/<replaced>.o swapped for the given source.
 set -e
 root="$(cd "$(dirname "$0")/.." && pwd)"
