@@ -269,6 +269,31 @@ int ss_batch_gather_f32(const float* src, int D, const int32_t* frame_map, long 
                         const int32_t* noise_map, float noise_std, uint64_t seed, float* dst, ss_stream_t stream);
 int ss_batch_gather_u8(const uint8_t* src, int frame_bytes, const int32_t* frame_map, long rows, uint8_t* dst,
                        ss_stream_t stream);
+/* The plan of an epoch and of a batch made on the device (no map, length or label crosses PCIe).  Both draw Philox4x32-10 blocks:
+ * counter = (draw index low, high, domain tag, sub-draw number), key = seed; the feature-noise stream of ss_batch_gather_f32 uses
+ * tag 0x6e6f6973, these 0x73616d70 (sampler) and 0x706c616e (planner).  Decisions are integer arithmetic on the 32-bit outputs
+ * r0..r3: mulhi(r, n) = (uint64)r * n >> 32 is a uniform integer below n, thr(p) = (uint32)(p * 2^32) computed in double.
+ * ss_epoch_sample: WeightedRandomSampler(1 / count(label), replacement=True) (train_model_official.py:382-397) = a uniform class
+ *   among those that have clips, then a uniform member.  members (n_members) = clip ids grouped by class, class_start
+ *   (n_classes + 1) = where each class begins.  Draw first + k: cls = mulhi(r0, n_classes),
+ *   indices[k] = members[class_start[cls] + mulhi(r1, size(cls))], k < count.  (`first` lets a rank draw its shard of an epoch.)
+ * ss_batch_plan: what NPZWordDataset.__getitem__ decides per clip (train...:143-172), one wave per batch row.  Tables per clip:
+ *   x_off / x_len (rows of the feature store), r_off / r_len (rows of the ROI store, r_off < 0: the clip has none; both NULL: the
+ *   store has no ROI frames, rmap may be NULL), y.  Row b = clip indices[b] with T = x_len frames, draw index first_row + b:
+ *     sub-draw 0: noisy = augment && r0 < thr(noise_prob);  drop = augment && T > 12 && r1 < thr(drop_prob);
+ *                 k = 1 + mulhi(r2, drop_max) frames dropped, the first one p0 = 1 + mulhi(r3, T - 2);
+ *     sub-draw 1: (k == 2) p1 = 1 + mulhi(r0, T - 3), p1 += (p1 >= p0): every pair of distinct interior frames equally likely.
+ *   t_eff = min(T - k, max_t), and min(.., r_len) for a clip with ROI frames; for t < t_eff: xmap[b][t] = x_off + s, where
+ *   s = t stepped over the dropped frames in ascending order; nmap[b][t] = noisy ? 0 : -1; rmap[b][t] = r_off + t (ROI frames
+ *   are not dropped); all three -1 for t >= t_eff; lens[b] = t_eff; y_out[b] = y[indices[b]].  drop_max > 2: SS_ERR_UNSUPPORTED.
+ *   An index outside [0, n_clips) is not dereferenced: the row is an empty clip (lens 0, maps -1, label 0) and *err_flag
+ *   (one device word the caller owns and clears) is set to 1. */
+int ss_epoch_sample(const int32_t* members, int n_members, const int32_t* class_start, int n_classes, uint64_t first, long count,
+                    uint64_t seed, int32_t* indices, ss_stream_t stream);
+int ss_batch_plan(const int32_t* indices, int B, const int32_t* x_off, const int32_t* x_len, const int32_t* r_off,
+                  const int32_t* r_len, const int64_t* y, int n_clips, int max_t, int augment, uint64_t first_row, uint64_t seed,
+                  double noise_prob, double drop_prob, int drop_max, int32_t* xmap, int32_t* nmap, int32_t* rmap, int64_t* lens,
+                  int64_t* y_out, int32_t* err_flag, ss_stream_t stream);
 
 /* ---- sliding-window serving of many streams ---------------------------------------
  * per stream a ring of the last max_t frames (features (S,max_t,D) f32, optional ROI (S,max_t,frame_bytes) u8), a head

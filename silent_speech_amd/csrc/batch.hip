@@ -4,8 +4,10 @@
 // Replaces what NPZWordDataset.__getitem__ and collate_fn do per clip on the host
 // (/root/reference/train_model_official.py:122-204): additive feature noise (:143-145), interior frame drop
 // (:146-152, expressed as a frame map), zero padding / trimming to max_t (:93-118), stacking (:174-204).  Which
-// frames go where is decided on the host (a (B, max_t) int32 map, -1 = padding); the bytes never leave the GPU.
-// Both kernels are pure HBM streams: 16 bytes per lane, one row per wave group.
+// frames go where is a (B, max_t) int32 map, -1 = padding; the bytes never leave the GPU.
+// The two gather kernels are pure HBM streams: 16 bytes per lane, one row per wave group.  The map comes from the host
+// (rng "reference" / "device") or from the two planning kernels below them: the epoch's class-balanced sample order
+// (:382-397) and the augmentation draws + maps of a batch, both on the Philox stream, nothing crossing PCIe.
 #include "ss_common.h"
 
 namespace {
@@ -71,7 +73,118 @@ __global__ __launch_bounds__(256) void batch_gather_u8_kernel(const uint8_t* __r
   }
 }
 
+// ---- planning on the device.  One Philox4x32-10 block per draw: counter = (draw index low, high, domain tag, sub-draw),
+// key = the 64-bit seed.  Every decision is integer arithmetic on the 32-bit outputs, so tests/batch_plan_ref.py restates
+// it bit for bit: mulhi(r, n) is a uniform integer below n, a probability is the threshold (uint32)(p * 2^32) computed in
+// double on the host (as drop_scale4 does), carried in 64 bits so that p = 1 stays "always".
+constexpr uint32_t TAG_SAMPLER = 0x73616d70u;  // "samp"
+constexpr uint32_t TAG_PLANNER = 0x706c616eu;  // "plan"
+
+__device__ __forceinline__ uint32_t mulhi_u32(uint32_t r, uint32_t n) { return (uint32_t)(((uint64_t)r * n) >> 32); }
+
+// WeightedRandomSampler(1 / count(label), replacement=True) (train...:382-397): a uniform class among those present, then a
+// uniform member of it
+__global__ __launch_bounds__(256) void epoch_sample_kernel(const int32_t* __restrict__ members, int n_members,
+                                                           const int32_t* __restrict__ class_start, int n_classes,
+                                                           uint64_t first, long count, uint64_t seed,
+                                                           int32_t* __restrict__ indices) {
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= count) return;
+  const uint64_t j = first + (uint64_t)k;
+  uint32_t r[4];
+  philox4((uint32_t)j, (uint32_t)(j >> 32), TAG_SAMPLER, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+  const int cls = (int)mulhi_u32(r[0], (uint32_t)n_classes);
+  const int lo = class_start[cls], size = class_start[cls + 1] - lo;
+  // a table that is not what the store builds (empty class, offsets past the end) gives -1, which the planner reports
+  const long at = (lo >= 0 && size > 0) ? (long)lo + mulhi_u32(r[1], (uint32_t)size) : -1;
+  indices[k] = (at >= 0 && at < n_members) ? members[at] : -1;
+}
+
+// one wave per batch row, lanes over t (every lane makes the row's few draws itself: cheaper than a broadcast)
+__global__ __launch_bounds__(SS_WAVE) void batch_plan_kernel(
+    const int32_t* __restrict__ indices, const int32_t* __restrict__ x_off, const int32_t* __restrict__ x_len,
+    const int32_t* __restrict__ r_off, const int32_t* __restrict__ r_len, const int64_t* __restrict__ y, int n_clips,
+    int max_t, int augment, uint64_t first_row, uint64_t seed, uint64_t noise_thr, uint64_t drop_thr, int drop_max,
+    int32_t* __restrict__ xmap, int32_t* __restrict__ nmap, int32_t* __restrict__ rmap, int64_t* __restrict__ lens,
+    int64_t* __restrict__ y_out, int32_t* __restrict__ err_flag) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int clip = indices[b];
+  const bool valid = clip >= 0 && clip < n_clips;  // anything else is never dereferenced: an empty row and the flag
+  int xo = 0, ro = -1, t_eff = 0, k = 0, d0 = 0, d1 = 0;
+  bool noisy = false;
+  if (valid) {
+    const int T = x_len[clip];
+    xo = x_off[clip];
+    if (augment) {
+      const uint64_t row = first_row + (uint64_t)b;
+      uint32_t r[4];
+      philox4((uint32_t)row, (uint32_t)(row >> 32), TAG_PLANNER, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+      noisy = (uint64_t)r[0] < noise_thr;
+      if (T > 12 && (uint64_t)r[1] < drop_thr) {  // interior frames only: 0 and T-1 stay (train...:148)
+        k = 1 + (int)mulhi_u32(r[2], (uint32_t)drop_max);
+        d0 = 1 + (int)mulhi_u32(r[3], (uint32_t)(T - 2));
+        if (k == 2) {  // the second one uniform over the other T-3 interior frames: every pair equally likely
+          uint32_t q[4];
+          philox4((uint32_t)row, (uint32_t)(row >> 32), TAG_PLANNER, 1u, (uint32_t)seed, (uint32_t)(seed >> 32), q);
+          int p1 = 1 + (int)mulhi_u32(q[0], (uint32_t)(T - 3));
+          p1 += (p1 >= d0);
+          d1 = p1 > d0 ? p1 : d0;
+          d0 = p1 > d0 ? d0 : p1;
+        }
+      }
+    }
+    t_eff = T - k < max_t ? T - k : max_t;  // clip_pad_trim
+    if (t_eff < 0) t_eff = 0;
+    if (r_off && r_off[clip] >= 0) {        // T_use = min(T_eff, Tr, max_t); the ROI frames are NOT dropped
+      ro = r_off[clip];
+      const int tr = r_len[clip] > 0 ? r_len[clip] : 0;
+      t_eff = t_eff < tr ? t_eff : tr;
+    }
+  }
+  for (int t = lane; t < max_t; t += SS_WAVE) {
+    const bool in = t < t_eff;
+    int s = t;
+    s += (k >= 1 && s >= d0);
+    s += (k == 2 && s >= d1);
+    const long at = (long)b * max_t + t;
+    xmap[at] = in ? xo + s : -1;
+    nmap[at] = (in && noisy) ? 0 : -1;
+    if (rmap) rmap[at] = (in && ro >= 0) ? ro + t : -1;
+  }
+  if (lane == 0) {
+    lens[b] = t_eff;
+    y_out[b] = valid ? y[clip] : 0;
+    if (!valid) atomicOr(err_flag, 1);  // (a vector atomic; the flag's owner clears it when it reads it)
+  }
+}
+
 }  // namespace
+
+extern "C" int ss_epoch_sample(const int32_t* members, int n_members, const int32_t* class_start, int n_classes,
+                               uint64_t first, long count, uint64_t seed, int32_t* indices, ss_stream_t stream) {
+  SS_REQUIRE(members && class_start && indices && n_members > 0 && n_classes > 0 && count > 0, SS_ERR_ARG);
+  SS_REQUIRE((count + 255) / 256 <= 0x7fffffffL, SS_ERR_UNSUPPORTED);
+  hipLaunchKernelGGL(epoch_sample_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), members, n_members, class_start, n_classes, first, count, seed, indices);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_plan(const int32_t* indices, int B, const int32_t* x_off, const int32_t* x_len, const int32_t* r_off,
+                             const int32_t* r_len, const int64_t* y, int n_clips, int max_t, int augment, uint64_t first_row,
+                             uint64_t seed, double noise_prob, double drop_prob, int drop_max, int32_t* xmap, int32_t* nmap,
+                             int32_t* rmap, int64_t* lens, int64_t* y_out, int32_t* err_flag, ss_stream_t stream) {
+  SS_REQUIRE(indices && x_off && x_len && y && xmap && nmap && lens && y_out && err_flag, SS_ERR_ARG);
+  SS_REQUIRE(B > 0 && n_clips > 0 && max_t > 0, SS_ERR_ARG);
+  SS_REQUIRE((r_off == nullptr) == (r_len == nullptr) && (!r_off || rmap), SS_ERR_ARG);
+  SS_REQUIRE(noise_prob >= 0.0 && noise_prob <= 1.0 && drop_prob >= 0.0 && drop_prob <= 1.0, SS_ERR_ARG);
+  SS_REQUIRE(drop_max >= 1, SS_ERR_ARG);
+  SS_REQUIRE(drop_max <= 2, SS_ERR_UNSUPPORTED);  // the pair draw is written for one or two dropped frames
+  const uint64_t noise_thr = (uint64_t)(noise_prob * 4294967296.0), drop_thr = (uint64_t)(drop_prob * 4294967296.0);
+  hipLaunchKernelGGL(batch_plan_kernel, dim3((unsigned)B), dim3(SS_WAVE), 0, static_cast<hipStream_t>(stream), indices, x_off,
+                     x_len, r_off, r_len, y, n_clips, max_t, augment, first_row, seed, noise_thr, drop_thr, drop_max, xmap,
+                     nmap, rmap, lens, y_out, err_flag);
+  return ss_launch_status();
+}
 
 extern "C" int ss_batch_gather_f32(const float* src, int D, const int32_t* frame_map, long rows, const float* noise,
                                    const int32_t* noise_map, float noise_std, uint64_t seed, float* dst,

@@ -7,12 +7,16 @@ reference cannot afford: every clip of the training set is uploaded ONCE (a ragg
 features with probability 0.7, one or two interior frames dropped from the FEATURES only (train...:146-152; the ROI
 frames are not dropped), trim / zero-pad to ``max_t``, lengths aligned to ``min(T, Tr, max_t)``.
 
-Two sources of randomness:
+Three sources of randomness:
   * ``rng="reference"``: the host makes the draws with exactly the calls, order and distributions of the reference's
     ``__getitem__`` (``random.random``, ``np.random.normal``, ``random.randint``, ``np.random.choice``), so a batch is
     bit-identical to ``collate_fn([dataset[i] for i in indices])`` under the same seeds (tests/golden/dataset.npz);
   * ``rng="device"``: the decisions come from a ``numpy.random.Generator`` and the noise itself from the Philox stream
-    inside the gather kernel -- nothing but two small index maps crosses PCIe.
+    inside the gather kernel -- nothing but two small index maps crosses PCIe;
+  * ``rng="philox"``: the plan itself is made on the device (``ss_batch_plan``: one wave per batch row draws the
+    decisions from the Philox stream and writes the maps, the lengths and the labels); with device indices from
+    ``sample_epoch`` (``ss_epoch_sample``, the class-balanced sampler) nothing at all crosses PCIe and the host makes no
+    per-clip step.  tests/batch_plan_ref.py restates both kernels in NumPy integers, bit for bit.
 """
 from __future__ import annotations
 
@@ -24,6 +28,17 @@ import torch
 
 from . import _lib as L
 from .data import DROP_FRAMES_MAX, DROP_FRAMES_PROB, MAX_T, NOISE_STD
+
+NOISE_PROB = 0.7  # train...:144
+_MASK64 = (1 << 64) - 1
+
+
+def philox_noise_seed(seed: int, first_row: int) -> int:
+    """Seed of the gather's feature-noise stream for the ``rng="philox"`` batch whose first row draws index ``first_row``:
+    ``seed XOR ((first_row + 1) * 0x9E3779B97F4A7C15 mod 2^64)``.  The multiplier is odd, so distinct ``first_row`` values
+    give distinct seeds: consecutive batches of an epoch never share a noise stream (the noise counter is the element
+    index inside the batch, the same for every batch)."""
+    return (int(seed) ^ (((int(first_row) + 1) * 0x9E3779B97F4A7C15) & _MASK64)) & _MASK64
 
 
 class DeviceClipStore:
@@ -57,6 +72,18 @@ class DeviceClipStore:
         if self.R is not None and (self.roi_hw[0] * self.roi_hw[1]) % 16:
             raise ValueError("ROI frames must be a multiple of 16 bytes")
         self.y = torch.tensor(ys, dtype=torch.int64, device=self.device)
+        # rng="philox": the per-clip tables the planning kernels read, uploaded once
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)  # noqa: E731
+        self._x_off_d, self._x_len_d = i32(self.x_off), i32(self.x_len)
+        self._r_off_d, self._r_len_d = (i32(self.r_off), i32(self.r_len)) if self.R is not None else (None, None)
+        # the sampler's tables: clip ids grouped by class (ascending class id, classes without clips left out)
+        ya = np.asarray(ys, np.int64)
+        present = np.unique(ya)
+        self._members_d = i32(np.concatenate([np.flatnonzero(ya == c) for c in present]))
+        self._class_start_d = i32(np.concatenate([[0], np.cumsum([(ya == c).sum() for c in present])]))
+        self.n_classes_present = len(present)
+        self._err = torch.zeros(1, dtype=torch.int32, device=self.device)  # set by ss_batch_plan, read by check()
+        self._plan_bufs = {}
 
     def __len__(self):
         return len(self.x_len)
@@ -92,9 +119,81 @@ class DeviceClipStore:
             noises.append(noise)
         return keeps, noises
 
+    # ------------------------------------------------------------------ the plan made on the device (rng="philox")
+    def sample_epoch(self, num_samples: Optional[int] = None, seed: int = 0, first: int = 0) -> torch.Tensor:
+        """One epoch of the reference's ``WeightedRandomSampler(1 / count(label), replacement=True)`` (train...:382-397),
+        drawn on the device: -> ``num_samples`` (default: one per clip) int32 clip ids.  Draw ``k`` of the result is draw
+        ``first + k`` of the stream ``seed``: a data-parallel rank passes its offset and gets its shard of the same epoch."""
+        n = len(self) if num_samples is None else int(num_samples)
+        out = torch.empty(n, dtype=torch.int32, device=self.device)
+        L.call("ss_epoch_sample", self._members_d.data_ptr(), len(self), self._class_start_d.data_ptr(),
+               self.n_classes_present, int(first) & _MASK64, n, int(seed) & _MASK64, out.data_ptr(), L.stream())
+        return out
+
+    def check(self) -> None:
+        """Raises ``IndexError`` if a ``rng="philox"`` batch since the last call was given a device index outside the
+        store (such a row comes back as an empty clip).  Reads one word back, so it synchronises: once per epoch, not per
+        batch."""
+        bad = int(self._err.item())
+        if bad:
+            self._err.zero_()
+            raise IndexError("DeviceClipStore.batch(rng='philox'): a device index was outside [0, %d)" % len(self))
+
+    def _batch_philox(self, indices, augment, seed, first_row):
+        mt, dev = self.max_t, self.device
+        if isinstance(indices, torch.Tensor) and indices.is_cuda:
+            if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
+                raise ValueError("device indices must be a contiguous 1-D int32 tensor (a slice of sample_epoch())")
+            idx_d = indices
+        else:  # host indices are checked here, before anything is launched
+            host = np.asarray(indices.cpu() if isinstance(indices, torch.Tensor) else list(indices), dtype=np.int64).reshape(-1)
+            if host.size and (host.min() < 0 or host.max() >= len(self)):
+                raise IndexError("clip index outside [0, %d)" % len(self))
+            idx_d = torch.from_numpy(host.astype(np.int32)).to(dev)
+        B = idx_d.numel()
+        if B == 0:
+            raise ValueError("an empty batch")
+        # One set of map / length / label buffers per batch size, reused by every batch: the plan kernel, the two gathers
+        # and whatever consumes T and y afterwards are enqueued on L.stream() in order, so the next plan overwrites them
+        # only after this batch's readers have run.  (T and y ARE these buffers: clone them to keep them past the next call.)
+        bufs = self._plan_bufs.get(B)
+        if bufs is None:
+            maps = torch.empty(3, B, mt, dtype=torch.int32, device=dev)
+            bufs = self._plan_bufs[B] = (maps[0], maps[1], maps[2], torch.empty(B, dtype=torch.int64, device=dev),
+                                         torch.empty(B, dtype=torch.int64, device=dev))
+        xmap, nmap, rmap, lens, y = bufs
+        has_roi = self.R is not None
+        s = L.stream()
+        L.call("ss_batch_plan", idx_d.data_ptr(), B, self._x_off_d.data_ptr(), self._x_len_d.data_ptr(), L.ptr(self._r_off_d),
+               L.ptr(self._r_len_d), self.y.data_ptr(), len(self), mt, int(bool(augment)), int(first_row) & _MASK64,
+               int(seed) & _MASK64, NOISE_PROB, float(DROP_FRAMES_PROB), int(DROP_FRAMES_MAX), xmap.data_ptr(), nmap.data_ptr(),
+               rmap.data_ptr() if has_roi else None, lens.data_ptr(), y.data_ptr(), self._err.data_ptr(), s)
+        X = torch.empty(B, mt, self.D, device=dev)
+        L.call("ss_batch_gather_f32", self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, None,
+               nmap.data_ptr() if augment else None, float(NOISE_STD) if augment else 0.0,
+               philox_noise_seed(seed, first_row), X.data_ptr(), s)
+        R = None
+        if has_roi:
+            H, W = self.roi_hw
+            R = torch.empty(B, mt, H, W, device=dev, dtype=torch.uint8)
+            L.call("ss_batch_gather_u8", self.R.data_ptr(), H * W, rmap.data_ptr(), B * mt, R.data_ptr(), s)
+        X._ss_keep = (idx_d,)
+        return X, lens, R, y
+
     def batch(self, indices: Sequence[int], augment: bool = False, rng: str = "device",
-              generator: Optional[np.random.Generator] = None, seed: int = 0):
-        """-> X (B,max_t,D) f32, T (B,) i64, R (B,max_t,H,W) u8 or None, y (B,) i64 -- all on the device."""
+              generator: Optional[np.random.Generator] = None, seed: int = 0, first_row: int = 0):
+        """-> X (B,max_t,D) f32, T (B,) i64, R (B,max_t,H,W) u8 or None, y (B,) i64 -- all on the device.
+
+        ``rng="philox"``: the plan is made by ``ss_batch_plan`` on the device.  ``indices`` is a device int32 tensor (a
+        slice of ``sample_epoch()``; out-of-range entries give empty rows and are reported by ``check()``) or a host
+        sequence (validated here, ``IndexError`` before any launch).  Row ``b`` draws index ``first_row + b`` of the stream
+        ``seed``: pass the position of the batch in the run so that no two batches share draws; the gather's noise seed is
+        ``philox_noise_seed(seed, first_row)``.  ``generator`` is not used.  ``R`` is returned whenever the store holds ROI
+        frames (clips without ROI get zero frames, as ``collate_fn`` does when any clip of the batch has ROI); the
+        per-batch "no clip has ROI -> ``R = None``" rule needs a read-back and is left to the host modes.  ``T`` and ``y``
+        are buffers the store reuses for the next batch of the same size (safe in stream order; clone to keep them)."""
+        if rng == "philox":
+            return self._batch_philox(indices, augment, seed, first_row)
         indices = list(indices)
         B, mt = len(indices), self.max_t
         gen = generator or np.random.default_rng(seed)

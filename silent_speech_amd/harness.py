@@ -9,7 +9,8 @@ Counterparts, by reference line (/root/reference/train_model_official.py):
   fit               :417-506   epochs, save-best checkpoint (:486-500), early stopping (:501-505)
 
 The clips live in a ``DeviceClipStore`` (uploaded once), batches are assembled on the device, the step is
-``Trainer.step``; nothing here touches the arithmetic of the hot path.
+``Trainer.step``; nothing here touches the arithmetic of the hot path.  ``fit(plan="device")`` also draws the sample
+order and plans every batch on the device (``sample_epoch``, ``batch(rng="philox")``): an epoch is enqueue-only.
 """
 from __future__ import annotations
 
@@ -89,8 +90,13 @@ def class_balanced_indices(labels: Sequence[str], num_samples: Optional[int] = N
 
 
 @torch.no_grad()
-def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = BATCH_SIZE, label_smoothing: float = 0.05):
-    """-> (mean loss, accuracy, y_true, y_pred) over every clip of ``store``, in order, eval mode, no augmentation."""
+def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = BATCH_SIZE, label_smoothing: float = 0.05,
+             plan: str = "host"):
+    """-> (mean loss, accuracy, y_true, y_pred) over every clip of ``store``, in order, eval mode, no augmentation.
+    ``plan="device"``: the batches are planned by the kernel (``store.batch(rng="philox")``) -- the same batches, since
+    nothing is drawn without augmentation."""
+    if plan not in ("host", "device"):
+        raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
     from . import _lib as L
     from .checkpoint import softmax_topk
 
@@ -100,9 +106,13 @@ def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = B
     dev = model.flat_params.device
     loss_sum = torch.zeros(1, device=dev, dtype=torch.float32)   # sum of the per-clip losses (denom = 1)
     correct = torch.zeros(1, device=dev, dtype=torch.int32)
+    every = torch.arange(len(store), dtype=torch.int32, device=store.device) if plan == "device" else None
     for lo in range(0, len(store), batch_size):
-        idx = list(range(lo, min(len(store), lo + batch_size)))
-        X, T, R, y = store.batch(idx, augment=False)
+        if plan == "device":
+            X, T, R, y = store.batch(every[lo:lo + batch_size], augment=False, rng="philox")
+        else:
+            idx = list(range(lo, min(len(store), lo + batch_size)))
+            X, T, R, y = store.batch(idx, augment=False)
         logits = model(X, T, R if model.use_roi else None).contiguous()
         y = y.to(torch.int64).contiguous()
         # loss and hit count by the path's own cross-entropy kernel, predictions by its top-k kernel (no aten op)
@@ -119,9 +129,17 @@ def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = B
 
 def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BATCH_SIZE, patience: int = PATIENCE,
         max_t: int = 90, lr: float = 3e-4, seed: int = SEED, use_roi_if_present: bool = True, device="cuda",
-        log=print) -> float:
+        log=print, plan: str = "host") -> float:
     """The reference's ``main()``: scan, split, train with class-balanced sampling and on-device augmentation, evaluate
-    every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement."""
+    every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement.
+
+    ``plan="host"``: the sample order is a ``torch.multinomial`` on the CPU and every batch is planned in Python
+    (``store.batch(rng="device")``).  ``plan="device"``: an epoch is enqueue-only -- one ``store.sample_epoch`` launch draws
+    the order, every batch (validation too) is planned by ``ss_batch_plan``; draw ``epoch_base + lo`` belongs to row ``lo`` of
+    the epoch (``epoch_base`` = clips drawn in the epochs before), so no two rows of a run share draws.  The store's
+    out-of-range flag is read once per epoch."""
+    if plan not in ("host", "device"):
+        raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
     random.seed(seed)
     np.random.seed(seed)
     torch.manual_seed(seed)
@@ -137,16 +155,26 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     gen = np.random.default_rng(seed)
     best, bad = 0.0, 0
     for ep in range(1, epochs + 1):
-        order = class_balanced_indices(train_labels)
+        epoch_base = (ep - 1) * len(train_store)
+        if plan == "device":
+            order = train_store.sample_epoch(seed=seed, first=epoch_base)
+        else:
+            order = class_balanced_indices(train_labels)
         tr_loss = torch.zeros((), device=device)
         tr_ok = torch.zeros((), device=device, dtype=torch.int64)
         for lo in range(0, len(order), batch_size):
             idx = order[lo:lo + batch_size]
-            X, T, R, y = train_store.batch(idx, augment=True, rng="device", generator=gen)
+            if plan == "device":
+                X, T, R, y = train_store.batch(idx, augment=True, rng="philox", seed=seed, first_row=epoch_base + lo)
+            else:
+                X, T, R, y = train_store.batch(idx, augment=True, rng="device", generator=gen)
             loss, correct = trainer.step(X, T, R if use_roi else None, y)
             tr_loss += loss * len(idx)
             tr_ok += correct
-        va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size)
+        va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size, plan=plan)
+        if plan == "device":
+            train_store.check()  # (the evaluation above has synchronised)
+            val_store.check()
         confs = top_confusions(y_true, y_pred, info["id_to_label"], k=6)
         n = max(1, len(order))
         log(f"ep {ep:02d} | train loss {float(tr_loss) / n:.4f} acc {int(tr_ok) / n:.3f} | val loss {va_loss:.4f} acc {va_acc:.3f}"

@@ -1,0 +1,137 @@
+"""What the training loop of ``harness.fit`` costs around the step: batches planned on the host (``rng="device"``) against
+batches planned by the kernel (``rng="philox"``), with ``Trainer.step`` on a resident batch as the yardstick.
+
+    python tools/fit_bench.py [--steps 200] [--windows 5] [--warmup 20]
+
+One JSON line.  Per shape (config 2: B=256, T=30, D=84, 64x64 ROI; shipped: B=16, T=90, D=180, 48x96 ROI):
+  clips_per_s.{resident, host_plan, device_plan}  median (min, max) over the windows; the three loops alternate window by window
+                                                  inside this one process, every window ends in a device synchronise
+  assemble_ms.{host_plan, device_plan}            the batch() calls alone (no step), same alternation: ms per batch
+  enqueue_ms.{host_plan, device_plan}             host wall time of one batch() call while the GPU is idle (no synchronise
+                                                  inside the timed region: what the call costs the Python thread)
+  kernels_ms.{host_plan, device_plan}             HIP-event time per launch of the kernels batch() enqueues (L.PROFILE)
+The synthetic clip directory is the one ``bench.py --mode assemble`` builds: 64 clips, ragged lengths in [T, T + 8).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import silent_speech_amd as ss  # noqa: E402
+from silent_speech_amd import _lib as L  # noqa: E402
+from silent_speech_amd import data as Dm  # noqa: E402
+
+SHAPES = {"config2": dict(B=256, T=30, D=84, roi=(64, 64), C=5), "shipped": dict(B=16, T=90, D=180, roi=(48, 96), C=10)}
+SEED = 1
+
+
+def make_store(T, D, roi, C, dev):
+    rs = np.random.default_rng(0)
+    with tempfile.TemporaryDirectory() as tmp:
+        files = []
+        for k in range(64):
+            Tk = int(rs.integers(T, T + 8))
+            p = os.path.join(tmp, f"c{k}.npz")
+            Dm.save_clip(p, rs.normal(size=(Tk, D)).astype("float32"), range(Tk), "w%d" % (k % C), "me", range(4),
+                         rs.integers(0, 256, (Tk,) + tuple(roi), dtype="uint8"))
+            files.append(p)
+        return ss.DeviceClipStore(files, {"w%d" % c: c for c in range(C)}, max_t=T, device=dev)
+
+
+def summary(vals, digits=1):
+    return {"median": round(statistics.median(vals), digits), "min": round(min(vals), digits), "max": round(max(vals), digits)}
+
+
+def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev):
+    store = make_store(T, D, roi, C, dev)
+    model = ss.BiGRUClassifier(D, C, use_roi=True, roi_emb=32, hidden=192).to(dev).train()
+    trainer = ss.Trainer(model)
+    gen = np.random.default_rng(SEED)
+    host_order = [[int(v) for v in gen.integers(0, len(store), B)] for _ in range(steps)]  # drawn outside the timed loops
+    dev_order = store.sample_epoch(num_samples=B * steps, seed=SEED)
+    resident = tuple(t.clone() for t in store.batch(host_order[0], augment=True, rng="device", generator=gen))
+    row = [0]  # rows drawn so far: no two device-planned batches of the run share draws
+
+    def host_batch(i):
+        return store.batch(host_order[i], augment=True, rng="device", generator=gen)
+
+    def dev_batch(i):
+        row[0] += B
+        return store.batch(dev_order[i * B:(i + 1) * B], augment=True, rng="philox", seed=SEED, first_row=row[0])
+
+    def window(make_batch, step, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(n):
+            Xb, Tb, Rb, yb = make_batch(i % steps) if make_batch else resident
+            if step:
+                trainer.step(Xb, Tb, Rb, yb)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    loops = {"resident": (None, True), "host_plan": (host_batch, True), "device_plan": (dev_batch, True)}
+    asm = {"host_plan": (host_batch, False), "device_plan": (dev_batch, False)}
+    for mk, st in list(loops.values()) + list(asm.values()):  # every shape and code path of the timed windows, warmed up
+        window(mk, st, warmup)
+    rate = {k: [] for k in loops}
+    asm_ms = {k: [] for k in asm}
+    for _ in range(windows):  # alternate: a drift of the box hits every loop alike
+        for k, (mk, st) in loops.items():
+            rate[k].append(B * steps / window(mk, st, steps))
+        for k, (mk, st) in asm.items():
+            asm_ms[k].append(1000 * window(mk, st, steps) / steps)
+    enq, kern = {}, {}
+    for k, (mk, _) in asm.items():
+        per_call = []
+        for _ in range(windows):
+            torch.cuda.synchronize()  # GPU idle: the time below is the host's alone
+            t0 = time.perf_counter()
+            for i in range(20):
+                mk(i)
+            per_call.append(1000 * (time.perf_counter() - t0) / 20)
+            torch.cuda.synchronize()
+        enq[k] = summary(per_call, 4)
+        L.PROFILE = {}
+        for i in range(min(steps, 50)):
+            mk(i)
+        torch.cuda.synchronize()
+        prof, L.PROFILE = L.PROFILE, None
+        kern[k] = {tag: round(sum(a.elapsed_time(b) for a, b in evs) / len(evs), 4) for tag, evs in prof.items()}
+    store.check()
+    med = {k: statistics.median(v) for k, v in rate.items()}
+    return {"shape": dict(B=B, T=T, D=D, roi="%dx%d" % tuple(roi), classes=C),
+            "clips_per_s": {k: summary(v) for k, v in rate.items()},
+            "of_resident": {k: round(med[k] / med["resident"], 4) for k in ("host_plan", "device_plan")},
+            "assemble_ms": {k: summary(v, 4) for k, v in asm_ms.items()},
+            "enqueue_ms": enq, "kernels_ms": kern}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--steps", type=int, default=200, help="steps per timed window")
+    ap.add_argument("--windows", type=int, default=5, help="timed windows per loop (alternating)")
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--shapes", default="config2,shipped")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("fit_bench.py measures on the GPU: no device found")
+    dev = torch.device("cuda")
+    out = {"metric": "clips/s of the training loop: resident batch, host-planned batches, device-planned batches",
+           "steps_per_window": args.steps, "windows": args.windows, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
+    for name in args.shapes.split(","):
+        out[name] = run_shape(name, steps=args.steps, windows=args.windows, warmup=args.warmup, dev=dev, **SHAPES[name])
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
