@@ -280,4 +280,15 @@ struct MaskLoad {
   }
 };
 
+// Launch of a persistent CNN kernel: min(N, wgs_per_cu x CUs) workgroups, each walking its share of the N frames.
+// wgs_per_cu: workgroups the LDS footprint lets a CU hold, so one workgroup's commit / barrier phases run under another's MFMAs
+// lds_bytes: a constant of the kernel instance (ss_dynamic_lds raises the limit at the first launch only)
+template <class P, class K>
+int launch_persistent(K kernel, const P& p, int lds_bytes, int N, hipStream_t s, int wgs_per_cu = 1) {
+  if (lds_bytes > 160 * 1024 / wgs_per_cu) return SS_ERR_UNSUPPORTED;
+  if (lds_bytes > 0 && ss_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes) != SS_OK) return SS_ERR_LAUNCH;
+  hipLaunchKernelGGL(kernel, dim3(ss_persistent_grid(N, wgs_per_cu)), dim3(NT), lds_bytes, s, p);
+  return ss_launch_status();
+}
+
 }  // namespace c5

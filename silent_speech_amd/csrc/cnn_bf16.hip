@@ -16,8 +16,6 @@
 
 #include "cnn_bf16.h"
 
-extern int ss_cnn_max_wgs;  // roi_cnn.hip: test hook, workgroups per launch (0 = one per CU)
-
 namespace {
 using namespace c5;
 
@@ -553,17 +551,6 @@ template <int CIN, int COUT, int H, int W, bool LAST>
 constexpr int conv_fwd_lds() {
   return Img<CIN, H, W>::BYTES + round_up(Wmat<CIN, COUT>::BYTES, 16) +
          round_up(LAST ? H * W * COUT : (H / 2) * (W / 2) * COUT * 3, 16) + 16 + 2 * COUT * 4;
-}
-
-template <class P, class K>
-int launch_persistent(K kernel, const P& p, int lds_bytes, int N, hipStream_t s) {
-  if (lds_bytes > 160 * 1024) return SS_ERR_UNSUPPORTED;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-    return SS_ERR_LAUNCH;
-  const int cap = ss_cnn_max_wgs > 0 ? ss_cnn_max_wgs : ss_device_cus();  // (the cap makes a test walk many frames per workgroup)
-  const int grid = N < cap ? N : cap;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), lds_bytes, s, p);
-  return ss_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------ conv1 + conv2 fused

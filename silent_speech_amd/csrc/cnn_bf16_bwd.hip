@@ -19,8 +19,6 @@
 
 #include "cnn_bf16.h"
 
-extern int ss_cnn_max_wgs;  // roi_cnn.hip: test hook, workgroups per launch (0 = one per CU)
-
 namespace {
 using namespace c5;
 
@@ -1127,25 +1125,10 @@ __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Param
   }
 }
 
-// wgs_per_cu: workgroups the LDS footprint lets a CU hold; the grid is that many times the 256 CUs (a persistent workgroup walks
-// its share of the frames), so one workgroup's commit / barrier phases run under another's MFMAs
-template <class P, class K>
-int launch_persistent(K kernel, const P& p, int lds_bytes, int N, hipStream_t s, int wgs_per_cu = 1) {
-  if (lds_bytes > 160 * 1024 / wgs_per_cu) return SS_ERR_UNSUPPORTED;
-  if (lds_bytes > 0 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-    return SS_ERR_LAUNCH;
-  const int cap = (ss_cnn_max_wgs > 0 ? ss_cnn_max_wgs : ss_device_cus()) * wgs_per_cu;  // (the cap makes a test walk many frames per workgroup)
-  const int grid = N < cap ? N : cap;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), lds_bytes, s, p);
-  return ss_launch_status();
-}
-
 // weight-gradient launch with the partial sums through `part` (may be null: float atomics) + the reduce launch
 template <class K>
 int launch_wgrad(K kernel, ConvBwdParams& p, int lds_bytes, int N, int total, float* part, long part_floats, hipStream_t s) {
-  const int cap = ss_cnn_max_wgs > 0 ? ss_cnn_max_wgs : ss_device_cus();
-  const int grid = N < cap ? N : cap;
+  const int grid = ss_persistent_grid(N);
   p.part = (part && part_floats >= (long)grid * total) ? part : nullptr;
   const int st = launch_persistent(kernel, p, lds_bytes, N, s);
   if (st != SS_OK || !p.part) return st;

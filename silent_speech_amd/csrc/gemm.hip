@@ -1107,13 +1107,7 @@ extern "C" int ss_gemm_f32_batched(int a_kcontig, int b_kcontig, int M, int N, i
       w.gx = ceil_div(N, wide::WT); w.gy = ceil_div(M, wide::WT);
       w.sA = stride_a; w.sB = stride_b; w.sC = stride_c; w.sBias = stride_bias;
       constexpr size_t wide_lds = (size_t)DSTAGES * wide::W_STAGE * sizeof(float);
-      static bool attr_set = false;
-      if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wide::gemm_wide_kc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)wide_lds) != hipSuccess)
-          return SS_ERR_LAUNCH;
-        attr_set = true;
-      }
+      SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(wide::gemm_wide_kc_kernel), (int)wide_lds) == SS_OK, SS_ERR_LAUNCH);
       hipLaunchKernelGGL(wide::gemm_wide_kc_kernel, dim3((unsigned)(w.gx * w.gy), (unsigned)batch), dim3(wide::WNT), wide_lds, s, w);
       return ss_launch_status();
     }
@@ -1149,7 +1143,8 @@ static bool wide_plan(const ss_gemm_problem* pr, int n, wide::WideGroup* out, lo
   for (int j = 0; j < n; ++j) work += (long)ceil_div(pr[j].M, WT) * ceil_div(pr[j].N, WT) * pr[j].batch * pr[j].K;
   // k rows per workgroup: the chip's share of the work, raised until the workgroups of the group fit the chip in ONE round (a
   // workgroup holds a CU: 264 of them on 256 CUs took twice as long as 252 -- layer 0 of config 2, first version)
-  long kt = work / ss_device_cus() > 4 * BK ? work / ss_device_cus() : 4 * BK;
+  const int cus = ss_device_cus();
+  long kt = work / cus > 4 * BK ? work / cus : 4 * BK;
   auto slices = [&](int K, long kt_, int* ksplit) {
     int nz = (int)((K + kt_ / 2) / kt_);
     nz = nz < 1 ? 1 : nz;
@@ -1161,7 +1156,7 @@ static bool wide_plan(const ss_gemm_problem* pr, int n, wide::WideGroup* out, lo
   for (int it = 0; it < 64; ++it) {
     long wgs = 0;
     for (int j = 0; j < n; ++j) wgs += (long)ceil_div(pr[j].M, WT) * ceil_div(pr[j].N, WT) * pr[j].batch * slices(pr[j].K, kt, nullptr);
-    if (wgs <= ss_device_cus()) break;
+    if (wgs <= cus) break;
     kt += kt / 32 + 1;
   }
   long off = 0;
@@ -1230,14 +1225,8 @@ extern "C" int ss_gemm_f32_splitk_group(const ss_gemm_problem* problems, int n, 
     if ((flags & 1) && wide_plan(problems, n, &wg, nullptr)) {
       for (int j = 0; j < n; ++j) SS_REQUIRE(problems[j].C && problems[j].ldc >= problems[j].N, SS_ERR_ARG);
       wg.ws = ws;
-      static bool attr_set = false;
       constexpr size_t wide_lds = (size_t)DSTAGES * wide::W_STAGE * sizeof(float);
-      if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(wide::gemm_wide_group_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_lds) != hipSuccess)
-          return SS_ERR_LAUNCH;
-        attr_set = true;
-      }
+      SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(wide::gemm_wide_group_kernel), (int)wide_lds) == SS_OK, SS_ERR_LAUNCH);
       hipStream_t s = static_cast<hipStream_t>(stream);
       hipLaunchKernelGGL(wide::gemm_wide_group_kernel, dim3((unsigned)wg.first[n]), dim3(wide::WNT), wide_lds, s, wg);
       if (ss_launch_status() != SS_OK) return SS_ERR_LAUNCH;

@@ -646,13 +646,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(GemmBfParams p, 
 
 template <int AKC, int BKC>
 int launch_ring(const GemmBfParams& p, int batch, int kcat, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_ring_kernel<AKC, BKC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            LDS_BYTES) != hipSuccess)
-      return SS_ERR_LAUNCH;
-    attr_set = true;
-  }
+  SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16_ring_kernel<AKC, BKC>), LDS_BYTES) == SS_OK, SS_ERR_LAUNCH);
   const int gx = ceil_div(p.N, RBN), gy = ceil_div(p.M, RBM);
   const int nz = (kcat > 1 ? 1 : batch) * p.splits;
   hipLaunchKernelGGL((gemm_bf16_ring_kernel<AKC, BKC>), dim3((unsigned)(gx * gy * nz)), dim3(512), LDS_BYTES, s, p, gx, gy, kcat);
@@ -772,13 +766,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_ring_group_reduce_kernel(RingGr
 template <int AKC, int BKC, int SRC16>
 int launch_one(const GemmBfParams& p, dim3 grid, hipStream_t s) {
   constexpr size_t lds = 4 * Tile<SRC16 ? 64 : 32>::ELEMS * sizeof(bf16_t);
-  static bool attr_set = false;  // the bf16-operand tiles take 72 KB of dynamic LDS: above the 64 KB a launch gets by default
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_kernel<AKC, BKC, SRC16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return SS_ERR_LAUNCH;
-    attr_set = true;
-  }
+  // the bf16-operand tiles take 72 KB of dynamic LDS: above the 64 KB a launch gets by default
+  SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(gemm_bf16_kernel<AKC, BKC, SRC16>), (int)lds) == SS_OK, SS_ERR_LAUNCH);
   hipLaunchKernelGGL((gemm_bf16_kernel<AKC, BKC, SRC16>), grid, dim3(256), lds, s, p);
   return ss_launch_status();
 }
@@ -794,7 +783,6 @@ int launch_gemm_bf16(int a_kcontig, int b_kcontig, const GemmBfParams& p, dim3 g
 }  // namespace
 
 // ---- grouped weight-gradient GEMMs (ring kernel, stream-K over the group; see gemm_bf16_ring_group_kernel)
-static int ring_group_cus() { return ss_device_cus(); }
 static int ring_group_prepare(const ss_gemm_problem* pr, int n, float* ws, ring::RingGroup* out, int* wgs, long* floats) {
   SS_REQUIRE(pr && n >= 1 && n <= ring::GROUP_MAX, SS_ERR_ARG);
   ring::RingGroup& gg = *out;
@@ -822,13 +810,14 @@ static int ring_group_prepare(const ss_gemm_problem* pr, int n, float* ws, ring:
   }
   for (int j = n; j < ring::GROUP_MAX; ++j) { gg.ubase[j + 1] = gg.ubase[n]; gg.tbase[j + 1] = gg.tbase[n]; gg.gx[j] = gg.gy[j] = gg.nkt[j] = 1; }
   const int units = gg.ubase[n];
-  const int W = units < ring_group_cus() ? units : ring_group_cus();
+  const int cus = ss_device_cus();
+  const int W = units < cus ? units : cus;
   gg.U = ceil_div(units, W);
   gg.maxc = (nkt_max - 1) / gg.U + 2;
   *wgs = ceil_div(units, gg.U);
   *floats = (long)gg.tbase[n] * gg.maxc * ring::SLAB_FLOATS;
   // at least half a chip of output tiles (and no more than a chip): one workgroup per tile, no K split
-  gg.whole = (2 * gg.tbase[n] >= ring_group_cus() && gg.tbase[n] <= ring_group_cus()) ? 1 : 0;
+  gg.whole = (2 * gg.tbase[n] >= cus && gg.tbase[n] <= cus) ? 1 : 0;
   if (gg.whole) *wgs = gg.tbase[n];
   return SS_OK;
 }
@@ -848,13 +837,7 @@ extern "C" int ss_gemm_bf16_splitk_group(const ss_gemm_problem* problems, int n,
   const int st = ring_group_prepare(problems, n, ws, &gg, &wgs, &floats);
   if (st != SS_OK) return st;
   SS_REQUIRE(gg.whole || ws_floats >= floats, SS_ERR_ARG);  // (one workgroup per tile over all of K stores no slabs)
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(ring::gemm_bf16_ring_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            ring::LDS_BYTES) != hipSuccess)
-      return SS_ERR_LAUNCH;
-    attr_set = true;
-  }
+  SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(ring::gemm_bf16_ring_group_kernel), ring::LDS_BYTES) == SS_OK, SS_ERR_LAUNCH);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ring::gemm_bf16_ring_group_kernel, dim3((unsigned)wgs), dim3(512), ring::LDS_BYTES, s, gg);
   if (ss_launch_status() != SS_OK) return SS_ERR_LAUNCH;

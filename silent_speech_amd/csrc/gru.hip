@@ -316,7 +316,6 @@ __global__ __launch_bounds__(H * 4) void gru_bwd_kernel(GruBwdParams p) {
 
 STAMP_TABLE(ss_debug_stamps_gru)
 
-extern int ss_cnn_max_wgs;  // roi_cnn.hip: the CU cap of the persistent CNN kernels (0 = none)
 #include "gru_split.h"
 
 extern "C" int ss_gru_sync_bytes(int B, int T, int H, long* bytes) {

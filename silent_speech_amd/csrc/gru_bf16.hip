@@ -321,8 +321,6 @@ __global__ __launch_bounds__(256) void cvt_bf16_rows_kernel(const float* __restr
   }
 }
 
-int device_cus() { return ss_device_cus(); }
-
 void cvt_rows(const float* x, int ld_x, bf16_t* y, int ld_y, long rows, int cols, float drop_p, uint64_t seed, uint64_t offset,
               hipStream_t st) {
   const long total = rows * (ld_y / 4);
@@ -383,7 +381,7 @@ extern "C" int ss_gru_bf16_sync_bytes(int B, int T, int H, long* bytes) {
   SS_REQUIRE(bytes && B > 0 && T > 0 && H > 0, SS_ERR_ARG);
   *bytes = 0;
   if (!pers_supported(H) || T > 1022) return SS_OK;  // step tags are 10 bits
-  const int chunk = pers_chunk_clips(B, H, device_cus());
+  const int chunk = pers_chunk_clips(B, H, ss_device_cus());
   if (chunk <= 0) return SS_OK;
   const int gmax = 2 * ceil_div(chunk, PSLICE);
   *bytes = SYNC_HDR_WORDS * 4L + (pers_xid_granules(gmax, H / PUNITS) + pers_fwd_granules(gmax, H) + pers_bwd_granules(gmax, H)) * 8;
@@ -409,7 +407,7 @@ extern "C" int ss_gru_bf16_fwd(const float* gi, const uint16_t* whh_bf16, const 
   SS_REQUIRE(B > 0 && T > 0 && drop_p >= 0.f && drop_p < 1.f, SS_ERR_ARG);
   SS_REQUIRE(H >= 128 && H % 128 == 0, SS_ERR_UNSUPPORTED);  // (step kernels: four waves x whole 32-deep k steps; built: 128..512, 1024)
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int chunk = (sync_ws && pers_supported(H) && T <= 1022) ? pers_chunk_clips(B, H, device_cus()) : 0;
+  const int chunk = (sync_ws && pers_supported(H) && T <= 1022) ? pers_chunk_clips(B, H, ss_device_cus()) : 0;
   if (chunk > 0) {
     long need = 0;
     if (ss_gru_bf16_sync_bytes(B, T, H, &need) != SS_OK) return SS_ERR_ARG;
@@ -454,7 +452,7 @@ extern "C" int ss_gru_bf16_bwd(const float* d_out, const float* out, const float
   const bool want_bias = g_bih_f || g_bhh_f || g_bih_r || g_bhh_r;
   SS_REQUIRE(!want_bias || (g_bih_f && g_bhh_f && g_bih_r && g_bhh_r), SS_ERR_ARG);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int chunk = (sync_ws && pers_supported(H) && T <= 1022) ? pers_chunk_clips(B, H, device_cus()) : 0;
+  const int chunk = (sync_ws && pers_supported(H) && T <= 1022) ? pers_chunk_clips(B, H, ss_device_cus()) : 0;
   if (chunk > 0) {
     long need = 0;
     if (ss_gru_bf16_sync_bytes(B, T, H, &need) != SS_OK) return SS_ERR_ARG;

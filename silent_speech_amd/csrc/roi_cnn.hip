@@ -24,7 +24,6 @@
 
 STAMP_TABLE(ss_debug_stamps_fwd)
 
-int ss_cnn_max_wgs = 0;  // shared with roi_cnn_bwd.hip; set through ss_roi_cnn_set_max_workgroups
 extern "C" int ss_roi_cnn_set_max_workgroups(int n) {
   if (n < 0 || n > 4096) return SS_ERR_ARG;
   ss_cnn_max_wgs = n;
@@ -543,16 +542,8 @@ template <class G>
 int launch_fwd(const CnnFwdParams& p, hipStream_t s) {
   constexpr size_t lds_bytes = (size_t)FwdLds<G>::total * sizeof(float);
   static_assert(lds_bytes <= 80 * 1024, "two workgroups per CU: the LDS image must stay under half a CU");
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(roi_cnn_fwd_kernel<G>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            80 * 1024) != hipSuccess)
-      return SS_ERR_LAUNCH;
-    attr_set = true;
-  }
-  const int cap = 2 * (ss_cnn_max_wgs > 0 ? ss_cnn_max_wgs : ss_device_cus());  // the cap counts CUs
-  const int grid = p.N < cap ? p.N : cap;
-  hipLaunchKernelGGL(roi_cnn_fwd_kernel<G>, dim3(grid), dim3(NT), lds_bytes, s, p);
+  SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(roi_cnn_fwd_kernel<G>), 80 * 1024) == SS_OK, SS_ERR_LAUNCH);
+  hipLaunchKernelGGL(roi_cnn_fwd_kernel<G>, dim3(ss_persistent_grid(p.N, 2)), dim3(NT), lds_bytes, s, p);
   return ss_launch_status();
 }
 

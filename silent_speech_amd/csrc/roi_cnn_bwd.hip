@@ -35,8 +35,6 @@
 
 STAMP_TABLE(ss_debug_stamps_bwd)
 
-extern int ss_cnn_max_wgs;  // roi_cnn.hip
-
 namespace {
 
 constexpr int NT = 512;
@@ -1026,17 +1024,9 @@ int launch_bwd(const CnnBwdParams& p, hipStream_t s) {
   static_assert(lds_bytes <= 160 * 1024, "ROI size does not fit the CU's LDS");
   // the K = pixel splits need whole 4-pixel k-steps per wave; mask / argmax-2 maps are one 16-byte piece per thread
   static_assert(G::P % (4 * NWV) == 0 && G::HW2 % (4 * NWV) == 0 && 24 * G::P <= 16 * NT, "unsupported ROI size");
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (const void* fn : {reinterpret_cast<const void*>(roi_cnn_bwd_kernel<G, false>),
-                           reinterpret_cast<const void*>(roi_cnn_bwd_kernel<G, true>)})
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return SS_ERR_LAUNCH;
-    attr_set = true;
-  }
-  const int cap = ss_cnn_max_wgs > 0 ? ss_cnn_max_wgs : ss_device_cus();
-  const int grid = p.N < cap ? p.N : cap;
-  if (p.frames) hipLaunchKernelGGL((roi_cnn_bwd_kernel<G, true>), dim3(grid), dim3(NT), lds_bytes, s, p);
-  else hipLaunchKernelGGL((roi_cnn_bwd_kernel<G, false>), dim3(grid), dim3(NT), lds_bytes, s, p);
+  const auto kernel = !p.frames ? roi_cnn_bwd_kernel<G, false> : roi_cnn_bwd_kernel<G, true>;
+  SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(kernel), 160 * 1024) == SS_OK, SS_ERR_LAUNCH);
+  hipLaunchKernelGGL(kernel, dim3(ss_persistent_grid(p.N)), dim3(NT), lds_bytes, s, p);
   return ss_launch_status();
 }
 
