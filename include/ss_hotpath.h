@@ -267,6 +267,12 @@ int ss_colsum_f32(const float* A, int rows, int cols, int lda, float* out, ss_st
  * u8 : dst (rows, frame_bytes), frame_bytes a multiple of 16 (ROI frames). */
 int ss_batch_gather_f32(const float* src, int D, const int32_t* frame_map, long rows, const float* noise,
                         const int32_t* noise_map, float noise_std, uint64_t seed, float* dst, ss_stream_t stream);
+/* ss_batch_gather_f32 with Philox noise for a batch that is a run of rows of a larger one (a data-parallel rank's shard of the
+ * global batch): element q of dst draws what element noise_first + q of the larger batch draws under the same seed, so the
+ * shards of all ranks, concatenated, are the batch one process gathers, bit for bit.  noise_first = (first row of the shard
+ * inside the larger batch) * D * max_t; any value, not only multiples of 4.  noise_map as above (required). */
+int ss_batch_gather_f32_at(const float* src, int D, const int32_t* frame_map, long rows, const int32_t* noise_map, float noise_std,
+                           uint64_t seed, uint64_t noise_first, float* dst, ss_stream_t stream);
 int ss_batch_gather_u8(const uint8_t* src, int frame_bytes, const int32_t* frame_map, long rows, uint8_t* dst,
                        ss_stream_t stream);
 /* The plan of an epoch and of a batch made on the device (no map, length or label crosses PCIe).  Both draw Philox4x32-10 blocks:
@@ -547,6 +553,21 @@ int ss_tail_bwd(const float* h, const int32_t* lengths, const float* w_score, co
  * correct (1) int32 accumulated: argmax == y count (train_model_official.py:442). */
 int ss_ce_ls_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float label_smoothing, float denom,
                      float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream);
+
+/* Validation kept on the device (train_model_official.py:449-475 and the confusion list of :79-91): one launch per
+ * validation batch, nothing read back.  Per clip the arithmetic of ss_ce_ls_fwd_bwd with denom = 1 (same order of
+ * operations, lowest index among equal maxima), accumulated into state that reduces over ranks with one collective:
+ *   loss_sum (1) f32    += sum of the per-clip losses (per-wave partial sums, one float atomic per wave)
+ *   correct (1) i32     += #(argmax == y)
+ *   confusion (C,C) i32 [true][pred] += 1 for every row, hits included
+ *   first_seen (C,C) i32 = min(first_seen, first_row + b) over the rows of the cell; the caller fills it with INT32_MAX.
+ *                         first_row = position of row 0 in the evaluated set (ties of the confusion list break by it)
+ *   y_true_out / y_pred_out (B) i32, each may be NULL: the label and the argmax of every row
+ * A label outside [0, C) is never used as an index: the row adds nothing anywhere, both outputs get -1 and *err_flag
+ * (one device word the caller owns and clears) is set to 1.  first_row < 0 or first_row + B past INT32_MAX: SS_ERR_ARG. */
+int ss_eval_accum(const float* logits, const int64_t* y, int B, int C, float label_smoothing, int first_row,
+                  float* loss_sum, int32_t* correct, int32_t* confusion, int32_t* first_seen, int32_t* y_true_out,
+                  int32_t* y_pred_out, int32_t* err_flag, ss_stream_t stream);
 
 /* a12: softmax over the classes + the k most probable of every clip, largest first
  * (topk_from_logits, live_infer_official.py:223-226: softmax -> argsort descending -> first k).

@@ -82,6 +82,7 @@ SIGNATURES = {
     "ss_zero_f32x2": [_vp, _l, _vp, _l, _vp],
     "ss_train_prologue": [_vp, _l, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp],
     "ss_batch_gather_f32": [_vp, _i, _vp, _l, _vp, _vp, _f, _u64, _vp, _vp],
+    "ss_batch_gather_f32_at": [_vp, _i, _vp, _l, _vp, _f, _u64, _u64, _vp, _vp],
     "ss_batch_gather_u8": [_vp, _i, _vp, _l, _vp, _vp],
     "ss_epoch_sample": [_vp, _i, _vp, _i, _u64, _l, _u64, _vp, _vp],
     "ss_batch_plan": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _u64, _u64, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -105,6 +106,7 @@ SIGNATURES = {
     "ss_layernorm_bwd": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "ss_dropout": [_vp, _vp, _l, _f, _u64, _u64, _vp, _vp],
     "ss_ce_ls_fwd_bwd": [_vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp],
+    "ss_eval_accum": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ss_softmax_topk": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "ss_sumsq_f32": [_vp, _l, _vp, _vp],
     "ss_adam_clip": [_vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _vp],

@@ -61,6 +61,64 @@ __global__ __launch_bounds__(256) void batch_gather_f32_kernel(const float* __re
   }
 }
 
+// The Philox branch of the kernel above for a batch that is rows [first, first + rows) of a larger one (a data-parallel
+// rank's shard of the global batch): element q of dst is element noise_first + q of the larger batch's noise stream, so the
+// shards of all ranks, put together, are the batch a single process gathers, bit for bit.  noise_first need not be a
+// multiple of 4: a 16-byte chunk of dst then takes its four values from two neighbouring Philox blocks.
+__device__ __forceinline__ void gather_noise4(uint64_t ctr, uint64_t seed, float* n) {
+  uint32_t rnd[4];
+  philox4((uint32_t)ctr, (uint32_t)(ctr >> 32), 0x6e6f6973u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
+  const float u0 = ((float)rnd[0] + 1.0f) * 2.3283064e-10f, u1 = (float)rnd[1] * 2.3283064e-10f;
+  const float u2 = ((float)rnd[2] + 1.0f) * 2.3283064e-10f, u3 = (float)rnd[3] * 2.3283064e-10f;
+  const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
+  n[0] = ra * __cosf(6.2831853f * u1);
+  n[1] = ra * __sinf(6.2831853f * u1);
+  n[2] = rb * __cosf(6.2831853f * u3);
+  n[3] = rb * __sinf(6.2831853f * u3);
+}
+
+__global__ __launch_bounds__(256) void batch_gather_f32_at_kernel(const float* __restrict__ src, int D,
+                                                                  const int32_t* __restrict__ frame_map, long rows,
+                                                                  const int32_t* __restrict__ noise_map, float noise_std,
+                                                                  uint64_t seed, uint64_t noise_first,
+                                                                  float* __restrict__ dst) {
+  const long total = rows * D;
+  const int shift = (int)(noise_first & 3);  // the same for every chunk
+  for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 4; q < total; q += (long)gridDim.x * 256 * 4) {
+    float v[4];
+    bool noisy[4];
+    long r = q / D;
+    int d = (int)(q - r * D);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float x = 0.f;
+      noisy[e] = false;
+      if (q + e < total) {
+        const int m = frame_map[r];
+        if (m >= 0) x = src[(long)m * D + d];
+        noisy[e] = m >= 0 && noise_map[r] >= 0;
+      }
+      v[e] = x;
+      if (++d == D) { d = 0; ++r; }
+    }
+    if (noise_std > 0.f) {
+      const uint64_t ctr = (noise_first + (uint64_t)q) >> 2;
+      float n[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      gather_noise4(ctr, seed, n);
+      if (shift) gather_noise4(ctr + 1, seed, n + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        // n[shift + e] by selects: the index is not a compile-time constant, an array would go to scratch
+        const float ne = shift == 0 ? n[e] : shift == 1 ? n[e + 1] : shift == 2 ? n[e + 2] : n[e + 3];
+        if (noisy[e]) v[e] += noise_std * ne;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (q + e < total) dst[q + e] = v[e];
+  }
+}
+
 // dst[r][0:frame_bytes] = map[r] >= 0 ? src[map[r]] : 0; frame_bytes % 16 == 0, one workgroup walks whole rows
 __global__ __launch_bounds__(256) void batch_gather_u8_kernel(const uint8_t* __restrict__ src, int chunks /* 16-byte */,
                                                               const int32_t* __restrict__ frame_map, long rows,
@@ -197,6 +255,18 @@ extern "C" int ss_batch_gather_f32(const float* src, int D, const int32_t* frame
   blocks = blocks > 4096 ? 4096 : blocks;
   hipLaunchKernelGGL(batch_gather_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), src, D,
                      frame_map, rows, noise, noise_map, noise_std, seed, dst);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_gather_f32_at(const float* src, int D, const int32_t* frame_map, long rows, const int32_t* noise_map,
+                                      float noise_std, uint64_t seed, uint64_t noise_first, float* dst, ss_stream_t stream) {
+  SS_REQUIRE(src && frame_map && noise_map && dst && D > 0 && rows > 0 && noise_std >= 0.f, SS_ERR_ARG);
+  SS_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 3) == 0, SS_ERR_ARG);
+  const long chunks = (rows * D + 3) / 4;
+  long blocks = (chunks + 255) / 256;
+  blocks = blocks > 4096 ? 4096 : blocks;
+  hipLaunchKernelGGL(batch_gather_f32_at_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), src, D,
+                     frame_map, rows, noise_map, noise_std, seed, noise_first, dst);
   return ss_launch_status();
 }
 

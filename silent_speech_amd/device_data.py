@@ -139,7 +139,15 @@ class DeviceClipStore:
             self._err.zero_()
             raise IndexError("DeviceClipStore.batch(rng='philox'): a device index was outside [0, %d)" % len(self))
 
-    def _batch_philox(self, indices, augment, seed, first_row):
+    def empty_batch(self):
+        """A batch of no clips, shaped like ``batch()``'s: what a data-parallel rank hands ``Trainer.step`` when its shard of a
+        global batch is empty (it still takes the step: the gradient all-reduce is collective)."""
+        dev, mt = self.device, self.max_t
+        R = torch.empty((0, mt) + tuple(self.roi_hw), device=dev, dtype=torch.uint8) if self.R is not None else None
+        return (torch.empty(0, mt, self.D, device=dev), torch.empty(0, dtype=torch.int64, device=dev), R,
+                torch.empty(0, dtype=torch.int64, device=dev))
+
+    def _batch_philox(self, indices, augment, seed, first_row, batch_first_row=None):
         mt, dev = self.max_t, self.device
         if isinstance(indices, torch.Tensor) and indices.is_cuda:
             if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
@@ -169,9 +177,17 @@ class DeviceClipStore:
                int(seed) & _MASK64, NOISE_PROB, float(DROP_FRAMES_PROB), int(DROP_FRAMES_MAX), xmap.data_ptr(), nmap.data_ptr(),
                rmap.data_ptr() if has_roi else None, lens.data_ptr(), y.data_ptr(), self._err.data_ptr(), s)
         X = torch.empty(B, mt, self.D, device=dev)
-        L.call("ss_batch_gather_f32", self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, None,
-               nmap.data_ptr() if augment else None, float(NOISE_STD) if augment else 0.0,
-               philox_noise_seed(seed, first_row), X.data_ptr(), s)
+        ahead = 0 if batch_first_row is None else int(first_row) - int(batch_first_row)
+        if ahead < 0:
+            raise ValueError("batch_first_row lies behind first_row")
+        if augment and ahead:
+            # rows [ahead, ahead + B) of the batch that starts at draw batch_first_row: that batch's noise stream, from this row on
+            L.call("ss_batch_gather_f32_at", self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, nmap.data_ptr(), float(NOISE_STD),
+                   philox_noise_seed(seed, batch_first_row), ahead * mt * self.D, X.data_ptr(), s)
+        else:
+            L.call("ss_batch_gather_f32", self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, None,
+                   nmap.data_ptr() if augment else None, float(NOISE_STD) if augment else 0.0,
+                   philox_noise_seed(seed, first_row), X.data_ptr(), s)
         R = None
         if has_roi:
             H, W = self.roi_hw
@@ -181,19 +197,25 @@ class DeviceClipStore:
         return X, lens, R, y
 
     def batch(self, indices: Sequence[int], augment: bool = False, rng: str = "device",
-              generator: Optional[np.random.Generator] = None, seed: int = 0, first_row: int = 0):
+              generator: Optional[np.random.Generator] = None, seed: int = 0, first_row: int = 0,
+              batch_first_row: Optional[int] = None):
         """-> X (B,max_t,D) f32, T (B,) i64, R (B,max_t,H,W) u8 or None, y (B,) i64 -- all on the device.
 
         ``rng="philox"``: the plan is made by ``ss_batch_plan`` on the device.  ``indices`` is a device int32 tensor (a
         slice of ``sample_epoch()``; out-of-range entries give empty rows and are reported by ``check()``) or a host
         sequence (validated here, ``IndexError`` before any launch).  Row ``b`` draws index ``first_row + b`` of the stream
         ``seed``: pass the position of the batch in the run so that no two batches share draws; the gather's noise seed is
-        ``philox_noise_seed(seed, first_row)``.  ``generator`` is not used.  ``R`` is returned whenever the store holds ROI
+        ``philox_noise_seed(seed, first_row)``.  ``batch_first_row`` (``rng="philox"`` only): these rows are rows
+        ``first_row - batch_first_row`` onwards of a larger batch whose first row draws ``batch_first_row`` -- a data-parallel
+        rank's shard of the global batch; the noise then continues that batch's stream, so the shards of all ranks,
+        concatenated, are bit for bit the batch a single process assembles.  ``generator`` is not used.  ``R`` is returned whenever the store holds ROI
         frames (clips without ROI get zero frames, as ``collate_fn`` does when any clip of the batch has ROI); the
         per-batch "no clip has ROI -> ``R = None``" rule needs a read-back and is left to the host modes.  ``T`` and ``y``
         are buffers the store reuses for the next batch of the same size (safe in stream order; clone to keep them)."""
         if rng == "philox":
-            return self._batch_philox(indices, augment, seed, first_row)
+            return self._batch_philox(indices, augment, seed, first_row, batch_first_row)
+        if batch_first_row is not None:
+            raise ValueError("batch_first_row belongs to rng='philox'")
         indices = list(indices)
         B, mt = len(indices), self.max_t
         gen = generator or np.random.default_rng(seed)

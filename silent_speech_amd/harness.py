@@ -8,6 +8,12 @@ Counterparts, by reference line (/root/reference/train_model_official.py):
   top_confusions    :79-91     "actual→predicted(count)" strings of the most frequent errors
   fit               :417-506   epochs, save-best checkpoint (:486-500), early stopping (:501-505)
 
+Data parallelism (the reference has none): ``fit(rank=, world_size=, process_group=)`` -- every rank holds
+the whole store and draws the whole epoch order, ``epoch_shards`` gives it its rows of every global batch, the validation
+state stays on the device (``evaluate_device``: ``ss_eval_accum``) in a form that ``reduce_epoch_metrics`` reduces with two
+collectives per epoch, and ``top_confusions_from_matrix`` prints from the reduced matrices what ``top_confusions`` prints
+from the lists.
+
 The clips live in a ``DeviceClipStore`` (uploaded once), batches are assembled on the device, the step is
 ``Trainer.step``; nothing here touches the arithmetic of the hot path.  ``fit(plan="device")`` also draws the sample
 order and plans every batch on the device (``sample_epoch``, ``batch(rng="philox")``): an epoch is enqueue-only.
@@ -15,10 +21,11 @@ order and plans every batch on the device (``sample_epoch``, ``batch(rng="philox
 from __future__ import annotations
 
 import collections
+import dataclasses
 import glob
 import os
 import random
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -26,9 +33,10 @@ import torch
 from .checkpoint import save_checkpoint
 from .device_data import DeviceClipStore
 from .model import BiGRUClassifier
-from .train import Trainer
+from .train import Trainer, shard_range
 
 VAL_FRAC, SEED, PATIENCE, EPOCHS, BATCH_SIZE = 0.15, 42, 12, 80, 16
+I32_MAX = 2 ** 31 - 1  # "no clip yet" in a first_seen matrix
 
 
 def scan_clips(clip_dir: str):
@@ -127,19 +135,144 @@ def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = B
     return float(loss_sum) / n, int(correct) / n, y_true, y_pred
 
 
+def top_confusions_from_matrix(confusion, first_seen, id_to_label: Dict[int, str], k: int = 8) -> List[str]:
+    """``top_confusions`` from the (C, C) ``[true][pred]`` counts and the position at which every cell first occurred: the
+    off-diagonal cells by count descending, ties by first occurrence -- the order of ``Counter.most_common``."""
+    confusion, first_seen = np.asarray(confusion), np.asarray(first_seen)
+    cells = [(-int(confusion[t, p]), int(first_seen[t, p]), t, p) for t, p in zip(*np.nonzero(confusion)) if t != p]
+    return [f"{id_to_label[int(t)]}→{id_to_label[int(p)]}({-n})" for n, _, t, p in sorted(cells)[:k]]
+
+
+def epoch_shards(n_draws: int, batch_size: int, rank: int = 0, world_size: int = 1) -> Iterator[Tuple[int, int, int, int]]:
+    """The steps of one epoch of ``n_draws`` rows for rank ``rank``: -> ``(lo, hi, first_row, global_batch)`` per step.  The
+    global batches are ``[g, min(n_draws, g + batch_size))`` (``batch_size`` is the GLOBAL batch), of which the rank takes the
+    ``shard_range`` rows ``[lo, hi)`` of the epoch order; ``first_row`` = position in the epoch of row ``lo`` (what
+    ``store.batch(first_row=)`` wants, added to the rows of the epochs before), ``global_batch`` = rows of all ranks in the
+    step (``Trainer.step(global_batch=)``).  ``hi == lo`` is a legal empty shard: the rank still takes the step, since the
+    gradient all-reduce is collective.  Every rank takes the same number of steps."""
+    if batch_size <= 0 or world_size <= 0 or not 0 <= rank < world_size:
+        raise ValueError("epoch_shards: batch_size and world_size must be positive and rank inside [0, world_size)")
+    for g in range(0, n_draws, batch_size):
+        n = min(n_draws, g + batch_size) - g
+        lo, hi = shard_range(n, rank, world_size)
+        yield g + lo, g + hi, g + lo, n
+
+
+def reduce_epoch_metrics(sums: torch.Tensor, confusion: torch.Tensor, first_seen: torch.Tensor, process_group=None) -> None:
+    """Reduce an epoch's metrics over the ranks, in place, on whatever device the tensors are on: ``sums`` (any 1-D float64
+    vector of things that add: loss sums, hit counts, clip counts, flags) and ``confusion`` (C, C) by SUM in ONE collective
+    (the counts ride in the float64 vector: exact below 2^53), ``first_seen`` (C, C) by MIN in a second one.  Two
+    collectives per epoch besides the per-step gradient all-reduce.  Without a group: nothing to do; a one-rank group still
+    issues both (sums over one rank: the identity), like ``Trainer(always_allreduce=True)``."""
+    if process_group is None:
+        return
+    import torch.distributed as dist
+
+    if sums.dtype != torch.float64 or sums.dim() != 1:
+        raise ValueError("sums must be a 1-D float64 tensor")
+    packed = torch.cat([sums, confusion.reshape(-1).to(torch.float64)])
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=process_group)
+    dist.all_reduce(first_seen, op=dist.ReduceOp.MIN, group=process_group)
+    sums.copy_(packed[:sums.numel()])
+    confusion.copy_(packed[sums.numel():].reshape(confusion.shape))  # (float64 -> the matrix's integer type: exact)
+
+
+@dataclasses.dataclass
+class EvalResult:
+    """What ``evaluate_device`` returns.  ``loss``, ``acc``, ``n``, ``confusion`` and ``first_seen`` are those of the whole
+    store (reduced over the ranks); ``y_true`` / ``y_pred`` are device int32 tensors of THIS rank's shard, in store order."""
+    loss: float
+    acc: float
+    n: int
+    confusion: np.ndarray   # (C, C) int64, [true][pred], hits included
+    first_seen: np.ndarray  # (C, C) int64, index in the store of the first clip of the cell; I32_MAX: none
+    y_true: torch.Tensor
+    y_pred: torch.Tensor
+    bad_labels: bool = False  # a label outside the model's classes (always False on a result that was returned)
+    extra: Optional[np.ndarray] = None  # the reduced ``extra_sums`` of the call, if any
+
+
+@torch.no_grad()
+def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = BATCH_SIZE, label_smoothing: float = 0.05,
+                    rank: int = 0, world_size: int = 1, process_group=None,
+                    extra_sums: Optional[torch.Tensor] = None) -> EvalResult:
+    """``evaluate`` with the validation state kept on the device.  The rank evaluates the clips
+    ``shard_range(len(store), rank, world_size)`` of the store, in order, eval mode, no augmentation: batches planned by
+    ``store.batch(rng="philox")``, one ``ss_eval_accum`` launch per batch (``first_row`` = the clip's index in the store),
+    nothing read back inside the loop.  Then ``reduce_epoch_metrics`` (two collectives when there is a group) and ONE host
+    read of everything.  ``extra_sums`` (device float32 / float64 values that add over ranks, e.g. the epoch's train loss sum
+    and hit count) ride in the same reduction and the same read: ``EvalResult.extra``.
+    The kernel's bad-label flag travels in the same sum and the same read; if any rank saw a label outside the model's classes
+    (such clips count nowhere) every rank raises ``ValueError`` here, the way ``store.check()`` raises for the store's flag."""
+    from . import _lib as L
+
+    C, dev = model.cfg.num_classes, model.flat_params.device
+    lo, hi = shard_range(len(store), rank, world_size)
+    loss_sum = torch.zeros(1, device=dev, dtype=torch.float32)
+    counts = torch.zeros(2, device=dev, dtype=torch.int32)  # [correct, bad-label flag]
+    confusion = torch.zeros(C, C, device=dev, dtype=torch.int32)
+    first_seen = torch.full((C, C), I32_MAX, device=dev, dtype=torch.int32)
+    y_true = torch.empty(hi - lo, device=dev, dtype=torch.int32)
+    y_pred = torch.empty(hi - lo, device=dev, dtype=torch.int32)
+    every = torch.arange(len(store), dtype=torch.int32, device=store.device)
+    was_training = model.training
+    model.eval()
+    for b0 in range(lo, hi, batch_size):
+        b1 = min(hi, b0 + batch_size)
+        X, T, R, y = store.batch(every[b0:b1], augment=False, rng="philox")
+        logits = model(X, T, R if model.use_roi else None).contiguous()
+        L.call("ss_eval_accum", logits.data_ptr(), y.data_ptr(), b1 - b0, C, label_smoothing, b0, loss_sum.data_ptr(),
+               counts.data_ptr(), confusion.data_ptr(), first_seen.data_ptr(), y_true.data_ptr() + 4 * (b0 - lo),
+               y_pred.data_ptr() + 4 * (b0 - lo), counts.data_ptr() + 4, L.stream())
+    model.train(was_training)
+    n_extra = 0 if extra_sums is None else extra_sums.numel()
+    sums = torch.cat([loss_sum.double(), counts.double(), torch.full((1,), float(hi - lo), device=dev, dtype=torch.float64)]
+                     + ([extra_sums.reshape(-1).to(device=dev, dtype=torch.float64)] if n_extra else []))
+    reduce_epoch_metrics(sums, confusion, first_seen, process_group)
+    host = torch.cat([sums, confusion.reshape(-1).double(), first_seen.reshape(-1).double()]).cpu().numpy()  # the one read
+    model.check_health()  # (the read above has synchronised)
+    tot_loss, correct, bad, n = float(host[0]), int(host[1]), int(host[2]), int(host[3])
+    if bad:
+        raise ValueError("evaluate_device: a label of the store is outside the model's %d classes" % C)
+    mats = host[4 + n_extra:].astype(np.int64)
+    return EvalResult(loss=tot_loss / max(1, n), acc=correct / max(1, n), n=n, confusion=mats[:C * C].reshape(C, C),
+                      first_seen=mats[C * C:].reshape(C, C), y_true=y_true, y_pred=y_pred,
+                      extra=host[4:4 + n_extra].copy() if n_extra else None)
+
+
 def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BATCH_SIZE, patience: int = PATIENCE,
         max_t: int = 90, lr: float = 3e-4, seed: int = SEED, use_roi_if_present: bool = True, device="cuda",
-        log=print, plan: str = "host") -> float:
+        log=print, plan: str = "host", rank: int = 0, world_size: int = 1, process_group=None,
+        history: Optional[list] = None) -> float:
     """The reference's ``main()``: scan, split, train with class-balanced sampling and on-device augmentation, evaluate
     every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement.
 
     ``plan="host"``: the sample order is a ``torch.multinomial`` on the CPU and every batch is planned in Python
     (``store.batch(rng="device")``).  ``plan="device"``: an epoch is enqueue-only -- one ``store.sample_epoch`` launch draws
     the order, every batch (validation too) is planned by ``ss_batch_plan``; draw ``epoch_base + lo`` belongs to row ``lo`` of
-    the epoch (``epoch_base`` = clips drawn in the epochs before), so no two rows of a run share draws.  The store's
-    out-of-range flag is read once per epoch."""
+    the epoch (``epoch_base`` = clips drawn in the epochs before), so no two rows of a run share draws.  Validation is
+    ``evaluate_device``: the epoch ends in one host read (the train scalars ride in it) and the store's out-of-range flag is
+    read once per epoch.
+
+    Data parallel (``world_size`` > 1 or a ``process_group``; needs ``plan="device"``): one process per GPU calls ``fit`` with
+    its ``rank``.  Every rank holds the whole store and draws the whole epoch order (same seed, same ``first``), walks
+    ``epoch_shards`` -- ``batch_size`` is the GLOBAL batch -- and trains on its rows of every global batch, which together
+    are the batch a single process would have drawn, clip for clip and draw for draw.  Parameters are broadcast from rank 0
+    before the first step, the gradients are summed per step (``Trainer``), the epoch's scalars and confusion matrices per
+    epoch (``reduce_epoch_metrics``); every rank then holds the same metrics and takes the same save / early-stop decisions
+    without another exchange.  Rank 0 alone logs and writes the checkpoint; all ranks pass a barrier before ``fit``
+    returns, and all return ``best``.  (Verified on one rank over RCCL and on two over gloo; more than one GPU is unmeasured.)
+
+    ``history``: a list that gets one ``dict(epoch, train_loss, train_acc, val_loss, val_acc)`` per epoch, unrounded."""
     if plan not in ("host", "device"):
         raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
+    if world_size < 1 or not 0 <= rank < world_size:
+        raise ValueError(f"rank {rank} is outside world_size {world_size}")
+    parallel = world_size > 1 or process_group is not None
+    if parallel and plan != "device":
+        raise ValueError("data-parallel fit needs plan='device': only there is an epoch a pure function of (seed, draw index)")
+    if rank != 0:
+        log = lambda *a, **k: None  # noqa: E731  (rank 0 alone logs)
     random.seed(seed)
     np.random.seed(seed)
     torch.manual_seed(seed)
@@ -150,7 +283,13 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     val_store = DeviceClipStore(val_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
     train_labels = [str(np.load(f, allow_pickle=True)["label"]) for f in train_files]
     model = BiGRUClassifier(info["x_dim"], len(info["uniq"]), use_roi=use_roi, roi_emb=32, hidden=192).to(device).train()
-    trainer = Trainer(model, lr=lr)
+    if process_group is not None:
+        import torch.distributed as dist
+
+        dist.broadcast(model.flat_params, src=dist.get_global_rank(process_group, 0), group=process_group)
+    trainer = Trainer(model, lr=lr, world_size=world_size, process_group=process_group,
+                      always_allreduce=process_group is not None)
+    trainer.rank = rank
     roi_hw = train_store.roi_hw or (48, 96)
     gen = np.random.default_rng(seed)
     best, bad = 0.0, 0
@@ -162,30 +301,50 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
             order = class_balanced_indices(train_labels)
         tr_loss = torch.zeros((), device=device)
         tr_ok = torch.zeros((), device=device, dtype=torch.int64)
-        for lo in range(0, len(order), batch_size):
-            idx = order[lo:lo + batch_size]
-            if plan == "device":
-                X, T, R, y = train_store.batch(idx, augment=True, rng="philox", seed=seed, first_row=epoch_base + lo)
-            else:
-                X, T, R, y = train_store.batch(idx, augment=True, rng="device", generator=gen)
-            loss, correct = trainer.step(X, T, R if use_roi else None, y)
-            tr_loss += loss * len(idx)
-            tr_ok += correct
-        va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size, plan=plan)
         if plan == "device":
+            for lo, hi, first_row, global_batch in epoch_shards(len(order), batch_size, rank, world_size):
+                if hi > lo:
+                    X, T, R, y = train_store.batch(order[lo:hi], augment=True, rng="philox", seed=seed,
+                                                   first_row=epoch_base + first_row,
+                                                   batch_first_row=epoch_base + lo - lo % batch_size)
+                else:
+                    X, T, R, y = train_store.empty_batch()
+                # (the loss is this rank's part of the global mean: the parts of all ranks sum to it)
+                loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch)
+                tr_loss += loss * global_batch
+                tr_ok += correct
+            res = evaluate_device(model, val_store, batch_size, rank=rank, world_size=world_size, process_group=process_group,
+                                  extra_sums=torch.stack([tr_loss.double(), tr_ok.double()]))
             train_store.check()  # (the evaluation above has synchronised)
             val_store.check()
-        confs = top_confusions(y_true, y_pred, info["id_to_label"], k=6)
+            va_loss, va_acc, tr_loss, tr_ok = res.loss, res.acc, res.extra[0], res.extra[1]
+            confs = top_confusions_from_matrix(res.confusion, res.first_seen, info["id_to_label"], k=6)
+        else:
+            for lo in range(0, len(order), batch_size):
+                idx = order[lo:lo + batch_size]
+                X, T, R, y = train_store.batch(idx, augment=True, rng="device", generator=gen)
+                loss, correct = trainer.step(X, T, R if use_roi else None, y)
+                tr_loss += loss * len(idx)
+                tr_ok += correct
+            va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size, plan=plan)
+            confs = top_confusions(y_true, y_pred, info["id_to_label"], k=6)
         n = max(1, len(order))
+        if history is not None:
+            history.append(dict(epoch=ep, train_loss=float(tr_loss) / n, train_acc=int(tr_ok) / n, val_loss=va_loss, val_acc=va_acc))
         log(f"ep {ep:02d} | train loss {float(tr_loss) / n:.4f} acc {int(tr_ok) / n:.3f} | val loss {va_loss:.4f} acc {va_acc:.3f}"
             + ((" | top confusions: " + ", ".join(confs)) if confs else ""))
         if va_acc > best:
             best, bad = va_acc, 0
-            save_checkpoint(out_path, model, info["uniq"], max_t=max_t, roi_w=roi_hw[1], roi_h=roi_hw[0], seed=seed)
+            if rank == 0:
+                save_checkpoint(out_path, model, info["uniq"], max_t=max_t, roi_w=roi_hw[1], roi_h=roi_hw[0], seed=seed)
             log(f"  saved {out_path} (best val acc {best:.3f})")
         else:
             bad += 1
             if bad >= patience:
                 log(f"Early stopping. Best val acc: {best:.3f}")
                 break
+    if process_group is not None:
+        import torch.distributed as dist
+
+        dist.barrier(group=process_group)
     return best

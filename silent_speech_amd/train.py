@@ -105,7 +105,10 @@ class Trainer:
         loss = this shard's contribution to the global mean loss (sum over ranks = global loss).
         ``global_batch`` = clips of ALL ranks in this step; needed only when the shards are unequal (``shard_range``
         with a world size that does not divide the batch): the loss is divided by it, so the summed bucket is the
-        global-mean gradient whatever each rank holds.  Default: B * world_size (equal shards)."""
+        global-mean gradient whatever each rank holds.  Default: B * world_size (equal shards).
+        An empty shard (``X.shape[0] == 0``; ``harness.epoch_shards`` deals them when a global batch has fewer clips than there
+        are ranks) is a legal step: the bucket and the scalars are zeroed, forward and backward are skipped, and the rank joins
+        the all-reduce, the clip and Adam like every other rank.  It returns zero loss and zero hits."""
         model, cfg = self.model, self.model.cfg
         if model._bucket_version != self._bucket_version:
             self._bind_bucket()
@@ -117,7 +120,7 @@ class Trainer:
         # dropout streams must differ between ranks (clip b of every rank would otherwise draw the same Philox masks)
         base_seed = self.step_count * self.world + self.rank
         M = self.micro_batches if (self.micro_batches > 1 and B % self.micro_batches == 0 and B // self.micro_batches >= 16) else 1
-        fused_prologue = (M == 1 and lengths.dtype == torch.int64 and lengths.is_cuda and lengths.is_contiguous()
+        fused_prologue = (B > 0 and M == 1 and lengths.dtype == torch.int64 and lengths.is_cuda and lengths.is_contiguous()
                           and X.is_contiguous())
         if fused_prologue:
             # zero_grad, the scalars, the int32 lengths and the landmark half of the GRU input: one launch instead of six
@@ -131,7 +134,9 @@ class Trainer:
             model.flat_grads.zero_()
             self.scal.zero_()
             self.correct.zero_()
-        if M == 1:
+        if B == 0:
+            pass  # an empty shard: this rank's gradient is the zero bucket
+        elif M == 1:
             self._fwd_bwd(X, lengths, R, y, denom, train, seed=base_seed, slot=0, phase="both",
                           prologue_done=fused_prologue)
         else:

@@ -10,6 +10,10 @@ One JSON line.  Per shape (config 2: B=256, T=30, D=84, 64x64 ROI; shipped: B=16
   enqueue_ms.{host_plan, device_plan}             host wall time of one batch() call while the GPU is idle (no synchronise
                                                   inside the timed region: what the call costs the Python thread)
   kernels_ms.{host_plan, device_plan}             HIP-event time per launch of the kernels batch() enqueues (L.PROFILE)
+  validation_ms.{evaluate, evaluate_device}       (config2 only, --eval-clips N, 0 = skip) one validation pass over N clips in batches of
+                                                  B: ``harness.evaluate`` (two read-backs per batch, confusions counted on the host)
+                                                  against ``harness.evaluate_device`` (``ss_eval_accum``, one read at the end);
+                                                  wall ms per pass, the two alternating pass by pass
 The synthetic clip directory is the one ``bench.py --mode assemble`` builds: 64 clips, ragged lengths in [T, T + 8).
 """
 import argparse
@@ -35,11 +39,11 @@ SHAPES = {"config2": dict(B=256, T=30, D=84, roi=(64, 64), C=5), "shipped": dict
 SEED = 1
 
 
-def make_store(T, D, roi, C, dev):
+def make_store(T, D, roi, C, dev, n_clips=64):
     rs = np.random.default_rng(0)
     with tempfile.TemporaryDirectory() as tmp:
         files = []
-        for k in range(64):
+        for k in range(n_clips):
             Tk = int(rs.integers(T, T + 8))
             p = os.path.join(tmp, f"c{k}.npz")
             Dm.save_clip(p, rs.normal(size=(Tk, D)).astype("float32"), range(Tk), "w%d" % (k % C), "me", range(4),
@@ -52,7 +56,25 @@ def summary(vals, digits=1):
     return {"median": round(statistics.median(vals), digits), "min": round(min(vals), digits), "max": round(max(vals), digits)}
 
 
-def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev):
+def time_validation(model, B, T, D, roi, C, n_clips, windows, dev):
+    from silent_speech_amd import harness as Hn
+
+    store = make_store(T, D, roi, C, dev, n_clips)
+    passes = {"evaluate": lambda: Hn.evaluate(model, store, batch_size=B), "evaluate_device": lambda: Hn.evaluate_device(model, store, batch_size=B)}
+    ms = {k: [] for k in passes}
+    for it in range(2 + max(3, windows)):  # two warm-up rounds, then alternate
+        for k, fn in passes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if it >= 2:
+                ms[k].append(1000 * (time.perf_counter() - t0))
+    model.train()
+    return {"clips": n_clips, "batches": -(-n_clips // B), **{k: summary(v, 3) for k, v in ms.items()}}
+
+
+def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0):
     store = make_store(T, D, roi, C, dev)
     model = ss.BiGRUClassifier(D, C, use_roi=True, roi_emb=32, hidden=192).to(dev).train()
     trainer = ss.Trainer(model)
@@ -109,7 +131,8 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev):
         kern[k] = {tag: round(sum(a.elapsed_time(b) for a, b in evs) / len(evs), 4) for tag, evs in prof.items()}
     store.check()
     med = {k: statistics.median(v) for k, v in rate.items()}
-    return {"shape": dict(B=B, T=T, D=D, roi="%dx%d" % tuple(roi), classes=C),
+    extra = {"validation_ms": time_validation(model, B, T, D, roi, C, eval_clips, windows, dev)} if eval_clips and name == "config2" else {}
+    return {**extra, "shape": dict(B=B, T=T, D=D, roi="%dx%d" % tuple(roi), classes=C),
             "clips_per_s": {k: summary(v) for k, v in rate.items()},
             "of_resident": {k: round(med[k] / med["resident"], 4) for k in ("host_plan", "device_plan")},
             "assemble_ms": {k: summary(v, 4) for k, v in asm_ms.items()},
@@ -122,6 +145,7 @@ def main():
     ap.add_argument("--windows", type=int, default=5, help="timed windows per loop (alternating)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shapes", default="config2,shipped")
+    ap.add_argument("--eval-clips", type=int, default=1024, help="clips of the timed validation pass (config2; 0 = skip)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("fit_bench.py measures on the GPU: no device found")
@@ -129,7 +153,7 @@ def main():
     out = {"metric": "clips/s of the training loop: resident batch, host-planned batches, device-planned batches",
            "steps_per_window": args.steps, "windows": args.windows, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     for name in args.shapes.split(","):
-        out[name] = run_shape(name, steps=args.steps, windows=args.windows, warmup=args.warmup, dev=dev, **SHAPES[name])
+        out[name] = run_shape(name, steps=args.steps, windows=args.windows, warmup=args.warmup, dev=dev, eval_clips=args.eval_clips, **SHAPES[name])
     print(json.dumps(out))
 
 
