@@ -535,6 +535,19 @@ int ss_tail_fwd(const float* h, const int32_t* lengths, const float* w_score, co
                 int B, int T, int D, int MID, int C, float ln_eps, float drop_p, uint64_t seed, uint64_t offset,
                 float label_smoothing, float denom, float* attn, float* xhat, float* rstd, float* ln, float* mid,
                 float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream);
+/* ss_tail_fwd with the class-weighted loss CrossEntropyLoss(weight=cw, label_smoothing) (train_model_official.py:406-414):
+ * cw (C) class weights, den (1) a DEVICE float read by the kernel = sum of cw[y] over the normalising set (the global batch:
+ * ss_class_weight_sum) in place of the host `denom`; y, cw and den must not be NULL.  Per row
+ *   l = (1-ls) * (-cw[y] lp[y]) + (ls/C) * (-sum_c cw[c] lp[c]),    loss_sum += l / *den,
+ *   d_logits[c] = [ (1-ls) cw[y] (p_c - [c==y]) + (ls/C) (p_c sum_k cw[k] - cw[c]) ] / *den.
+ * A row whose label is outside [0, C) gets a zero d_logits row and adds nothing.  With every cw[c] == 1 and *den == denom the
+ * logits, d_logits and the loss are bit for bit those of ss_tail_fwd.  ss_tail_bwd serves both. */
+int ss_tail_fwd_w(const float* h, const int32_t* lengths, const float* w_score, const float* b_score, const float* gamma,
+                  const float* beta, const float* w1, const float* b1, const float* w4, const float* b4, const int64_t* y,
+                  int B, int T, int D, int MID, int C, float ln_eps, float drop_p, uint64_t seed, uint64_t offset,
+                  float label_smoothing, const float* cw, const float* den, float* attn, float* xhat, float* rstd, float* ln,
+                  float* mid, float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct,
+                  ss_stream_t stream);
 /* Backward of the tail from d_logits (B,C) down to d_h (B,T,D) (written) and d_mid (B,MID) (written: the input of the
  * first Linear's weight-gradient GEMM); g_gamma, g_beta (D), g_wscore (D), g_bscore (1) are accumulated -- unless
  * col_part (B,3,D) is given: then every clip STORES its terms of g_gamma | g_beta | g_wscore there and the caller adds the
@@ -554,6 +567,18 @@ int ss_tail_bwd(const float* h, const int32_t* lengths, const float* w_score, co
 int ss_ce_ls_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float label_smoothing, float denom,
                      float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream);
 
+/* The class-weighted form (CrossEntropyLoss(weight=w, label_smoothing), train_model_official.py:406-414) with the
+ * normaliser on the device: w (C) class weights, den (1) a device float = sum of w[y] over the normalising set (the rows of
+ * ALL ranks' batch; ss_class_weight_sum writes it) in place of `denom`.  Per-row loss and gradient as under ss_tail_fwd_w;
+ * loss_sum += sum of l / *den, correct as above; d_logits, loss_sum and correct may each be NULL.  A row whose label is
+ * outside [0, C) gets a zero gradient row and adds nothing.  Every w[c] == 1 and *den == denom: the bits of ss_ce_ls_fwd_bwd. */
+int ss_ce_ls_w_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float label_smoothing, const float* w,
+                       const float* den, float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream);
+/* out[0] = sum of w[y_i] over the n int64 labels y (device), written (not accumulated).  One workgroup, a fixed reduction
+ * order: the result is a pure function of (the labels in order, w), so ranks that hold the same labels get the same bits.
+ * A label outside [0, C) adds nothing. */
+int ss_class_weight_sum(const int64_t* y, long n, const float* w, int C, float* out, ss_stream_t stream);
+
 /* Validation kept on the device (train_model_official.py:449-475 and the confusion list of :79-91): one launch per
  * validation batch, nothing read back.  Per clip the arithmetic of ss_ce_ls_fwd_bwd with denom = 1 (same order of
  * operations, lowest index among equal maxima), accumulated into state that reduces over ranks with one collective:
@@ -568,6 +593,14 @@ int ss_ce_ls_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float 
 int ss_eval_accum(const float* logits, const int64_t* y, int B, int C, float label_smoothing, int first_row,
                   float* loss_sum, int32_t* correct, int32_t* confusion, int32_t* first_seen, int32_t* y_true_out,
                   int32_t* y_pred_out, int32_t* err_flag, ss_stream_t stream);
+
+/* ss_eval_accum under class weights w (C): loss_sum (1) += sum of the per-clip weighted losses l (un-normalised),
+ * wsum (1) += sum of w[y] over the same clips; the weighted mean loss of a set is loss_sum / wsum, and both sums add over
+ * batches and over ranks.  Everything else, rows with a label outside [0, C) (they add to neither sum) and the flag
+ * included, is ss_eval_accum. */
+int ss_eval_accum_w(const float* logits, const int64_t* y, int B, int C, float label_smoothing, int first_row, const float* w,
+                    float* loss_sum, float* wsum, int32_t* correct, int32_t* confusion, int32_t* first_seen,
+                    int32_t* y_true_out, int32_t* y_pred_out, int32_t* err_flag, ss_stream_t stream);
 
 /* a12: softmax over the classes + the k most probable of every clip, largest first
  * (topk_from_logits, live_infer_official.py:223-226: softmax -> argsort descending -> first k).

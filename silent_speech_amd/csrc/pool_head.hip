@@ -3,6 +3,7 @@
 // reductions, coalesced row reads; none of these is matmul-shaped enough for MFMA (the two head
 // Linear layers go through ss_gemm_f32).
 #include "ss_common.h"
+#include "ce_row.h"
 
 namespace {
 
@@ -197,38 +198,51 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------- cross entropy
-// one thread per clip (C is a handful of words)
+// one thread per clip (C is a handful of words); the row arithmetic is ce_row (ce_row.h).  WEIGHTED: class weights w (C) and the
+// normaliser read from the device (*den = sum of w[y] over the normalising set, ss_class_weight_sum); a row whose label is
+// outside [0, C) is never an index there: zero gradient, nothing added.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void ce_ls_kernel(const float* __restrict__ logits, const int64_t* __restrict__ y, int B,
-                                                    int C, float eps, float denom, float* __restrict__ d_logits,
+                                                    int C, float eps, float denom, const float* __restrict__ w,
+                                                    const float* __restrict__ den, float* __restrict__ d_logits,
                                                     float* __restrict__ loss_sum, int* __restrict__ correct) {
   const int b = blockIdx.x * 256 + threadIdx.x;
+  if constexpr (WEIGHTED) denom = den[0];
   float loss = 0.f;
   int ok = 0;
   if (b < B) {
-    const float* lr = logits + (long)b * C;
-    const int yy = (int)y[b];
-    float m = lr[0];
-    int am = 0;
-    for (int c = 1; c < C; ++c)
-      if (lr[c] > m) { m = lr[c]; am = c; }
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(lr[c] - m);
-    const float lse = m + logf(se);
-    float slp = 0.f;
-    for (int c = 0; c < C; ++c) slp += lr[c] - lse;
-    loss = (1.0f - eps) * (lse - lr[yy]) + eps * (-slp / C);
-    if (d_logits) {
-      for (int c = 0; c < C; ++c) {
-        float pr = expf(lr[c] - lse);
-        float tgt = (c == yy ? (1.0f - eps) : 0.f) + eps / C;
-        d_logits[(long)b * C + c] = (pr - tgt) / denom;
-      }
+    float* d_row = d_logits ? d_logits + (long)b * C : nullptr;
+    bool valid = true;
+    if constexpr (WEIGHTED) valid = y[b] >= 0 && y[b] < (int64_t)C;
+    if (valid) {
+      const int yy = (int)y[b];
+      int am;
+      loss = ce_row<WEIGHTED>(logits + (long)b * C, yy, C, eps, w, denom, d_row, &am);
+      ok = (am == yy);
+    } else if (d_row) {
+      for (int c = 0; c < C; ++c) d_row[c] = 0.f;
     }
-    ok = (am == yy);
   }
   loss = wave_sum(loss / denom);
   if ((threadIdx.x & 63) == 0 && loss_sum) atomicAdd(loss_sum, loss);
   if (correct && ok) atomicAdd(correct, 1);
+}
+
+// sum of w[y_i] over n labels by ONE workgroup in a fixed order -- thread t adds its labels t, t + 256, ... in order, the wave
+// and the four waves combine in a fixed tree -- so the result is a pure function of (labels in order, w): every rank that
+// holds the same global labels gets the same bits.  A label outside [0, C) adds nothing.
+__global__ __launch_bounds__(256) void class_weight_sum_kernel(const int64_t* __restrict__ y, long n, const float* __restrict__ w,
+                                                               int C, float* __restrict__ out) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (long i = threadIdx.x; i < n; i += 256) {
+    const int64_t label = y[i];
+    if (label >= 0 && label < (int64_t)C) s += w[label];
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // softmax + top-k of every logit row (live_infer_official.py:223-226): one wave per clip, probabilities as
@@ -330,7 +344,22 @@ extern "C" int ss_ce_ls_fwd_bwd(const float* logits, const int64_t* y, int B, in
                                 float denom, float* d_logits, float* loss_sum, int32_t* correct,
                                 ss_stream_t stream) {
   SS_REQUIRE(logits && y && B > 0 && C > 0 && denom > 0.f, SS_ERR_ARG);
-  hipLaunchKernelGGL(ce_ls_kernel, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, y,
-                     B, C, label_smoothing, denom, d_logits, loss_sum, correct);
+  hipLaunchKernelGGL(ce_ls_kernel<false>, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, y,
+                     B, C, label_smoothing, denom, nullptr, nullptr, d_logits, loss_sum, correct);
+  return ss_launch_status();
+}
+
+extern "C" int ss_ce_ls_w_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float label_smoothing,
+                                  const float* w, const float* den, float* d_logits, float* loss_sum, int32_t* correct,
+                                  ss_stream_t stream) {
+  SS_REQUIRE(logits && y && w && den && B > 0 && C > 0, SS_ERR_ARG);
+  hipLaunchKernelGGL(ce_ls_kernel<true>, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, y,
+                     B, C, label_smoothing, 1.0f, w, den, d_logits, loss_sum, correct);
+  return ss_launch_status();
+}
+
+extern "C" int ss_class_weight_sum(const int64_t* y, long n, const float* w, int C, float* out, ss_stream_t stream) {
+  SS_REQUIRE(y && w && out && n > 0 && C > 0, SS_ERR_ARG);
+  hipLaunchKernelGGL(class_weight_sum_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), y, n, w, C, out);
   return ss_launch_status();
 }

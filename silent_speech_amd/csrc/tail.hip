@@ -7,6 +7,7 @@
 // registers; the two weight matrices stream from L2 (196 KB per workgroup).  The weight gradients of the two
 // Linear layers stay batched GEMMs over the clips (ss_gemm_f32, K = B) on what this kernel stashes.
 #include "ss_common.h"
+#include "ce_row.h"
 
 namespace {
 
@@ -45,10 +46,18 @@ struct TailFwdParams {
   uint64_t seed, offset;
   float *attn, *xhat, *rstd, *ln, *mid, *mid_d, *logits, *d_logits, *loss_sum;
   int* correct;
+  static constexpr bool weighted = false;
+};
+
+// the class-weighted loss (ss_tail_fwd_w): class weights cw (C) and the normaliser on the device (*den) instead of `denom`
+struct TailFwdParamsW : TailFwdParams {
+  const float *cw, *den;
+  static constexpr bool weighted = true;
 };
 
 // dynamic LDS: sc[T] | pooled[D] | lnv[D] | midv[MID] | lg[C]
-__global__ __launch_bounds__(TNT) void tail_fwd_kernel(TailFwdParams p) {
+template <class Params>
+__global__ __launch_bounds__(TNT) void tail_fwd_kernel(Params p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   __shared__ float red[2 * NWT];
   const int T = p.T, D = p.D, MID = p.MID, C = p.C;
@@ -212,35 +221,27 @@ __global__ __launch_bounds__(TNT) void tail_fwd_kernel(TailFwdParams p) {
   }
   if (!p.y) return;
   __syncthreads();
-  // ---- CrossEntropyLoss(label_smoothing), mean over `denom` clips; d(loss)/d(logits)
+  // ---- CrossEntropyLoss(label_smoothing), mean over `denom` clips; d(loss)/d(logits): ce_row_wave (ce_row.h)
   if (wv == 0) {
-    const int yy = (int)p.y[b];
-    float mx = -3.4e38f;
-    int am = 0;
-    for (int c = lane; c < C; c += 64)
-      if (lg[c] > mx) { mx = lg[c]; am = c; }
-    // wave arg-max, first index on ties (torch.argmax)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(mx, o, 64);
-      const int oa = __shfl_xor(am, o, 64);
-      if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
+    float* d_row = p.d_logits + (long)b * C;
+    float denom = p.denom;
+    const float* cw = nullptr;
+    bool valid = true;
+    if constexpr (Params::weighted) {
+      denom = p.den[0];
+      cw = p.cw;
+      valid = p.y[b] >= 0 && p.y[b] < (int64_t)C;  // a label outside the classes is never an index here: the row adds nothing
     }
-    float se = 0.f, sl = 0.f;
-    for (int c = lane; c < C; c += 64) se += expf(lg[c] - mx);
-    se = wave_sum(se);
-    const float lse = mx + logf(se);
-    for (int c = lane; c < C; c += 64) sl += lg[c] - lse;
-    sl = wave_sum(sl);
-    for (int c = lane; c < C; c += 64) {
-      const float pr = expf(lg[c] - lse);
-      const float tgt = (c == yy ? (1.0f - p.ls) : 0.f) + p.ls / C;
-      p.d_logits[(long)b * C + c] = (pr - tgt) / p.denom;
-    }
-    if (lane == 0) {
-      const float loss = (1.0f - p.ls) * (lse - lg[yy]) + p.ls * (-sl / C);
-      if (p.loss_sum) atomicAdd(p.loss_sum, loss / p.denom);
-      if (p.correct && am == yy) atomicAdd(p.correct, 1);
+    if (valid) {
+      const int yy = (int)p.y[b];
+      int am;
+      const float loss = ce_row_wave<Params::weighted>(lg, yy, C, lane, p.ls, cw, denom, d_row, &am);
+      if (lane == 0) {
+        if (p.loss_sum) atomicAdd(p.loss_sum, loss / denom);
+        if (p.correct && am == yy) atomicAdd(p.correct, 1);
+      }
+    } else {
+      for (int c = lane; c < C; c += 64) d_row[c] = 0.f;
     }
   }
 }
@@ -346,26 +347,56 @@ __global__ __launch_bounds__(TNT) void tail_bwd_kernel(TailBwdParams p) {
 
 }  // namespace
 
-extern "C" int ss_tail_fwd(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
+// cw == NULL: the unweighted loss divided by `denom`; else the class-weighted one divided by *den
+static int tail_fwd_launch(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
                            const float* gamma, const float* beta, const float* w1, const float* b1, const float* w4,
                            const float* b4, const int64_t* y, int B, int T, int D, int MID, int C, float ln_eps,
                            float drop_p, uint64_t seed, uint64_t offset, float label_smoothing, float denom,
-                           float* attn, float* xhat, float* rstd, float* ln, float* mid, float* mid_d, float* logits,
-                           float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream) {
+                           const float* cw, const float* den, float* attn, float* xhat, float* rstd, float* ln, float* mid,
+                           float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct,
+                           ss_stream_t stream) {
   SS_REQUIRE(h && lengths && w_score && b_score && gamma && beta && w1 && b1 && w4 && b4 && logits, SS_ERR_ARG);
   SS_REQUIRE(B > 0 && T > 0 && D > 0 && MID > 0 && C > 0 && drop_p >= 0.f && drop_p < 1.f, SS_ERR_ARG);
   SS_REQUIRE(!y || (d_logits && denom > 0.f), SS_ERR_ARG);
   const size_t lds = (size_t)(T + 2 * D + MID + C) * sizeof(float);
   SS_REQUIRE(lds <= 60 * 1024, SS_ERR_UNSUPPORTED);
-  TailFwdParams p;
+  TailFwdParamsW p;
+  p.cw = cw; p.den = den;
   p.h = h; p.lengths = lengths; p.w_score = w_score; p.b_score = b_score; p.gamma = gamma; p.beta = beta;
   p.w1 = w1; p.b1 = b1; p.w4 = w4; p.b4 = b4; p.y = y;
   p.B = B; p.T = T; p.D = D; p.MID = MID; p.C = C;
   p.eps = ln_eps; p.drop_p = drop_p; p.ls = label_smoothing; p.denom = denom; p.seed = seed; p.offset = offset;
   p.attn = attn; p.xhat = xhat; p.rstd = rstd; p.ln = ln; p.mid = mid; p.mid_d = mid_d; p.logits = logits;
   p.d_logits = d_logits; p.loss_sum = loss_sum; p.correct = correct;
-  hipLaunchKernelGGL(tail_fwd_kernel, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream), p);
+  if (cw)
+    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParamsW>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream), p);
+  else
+    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParams>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream),
+                       static_cast<const TailFwdParams&>(p));
   return ss_launch_status();
+}
+
+extern "C" int ss_tail_fwd(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
+                           const float* gamma, const float* beta, const float* w1, const float* b1, const float* w4,
+                           const float* b4, const int64_t* y, int B, int T, int D, int MID, int C, float ln_eps,
+                           float drop_p, uint64_t seed, uint64_t offset, float label_smoothing, float denom,
+                           float* attn, float* xhat, float* rstd, float* ln, float* mid, float* mid_d, float* logits,
+                           float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream) {
+  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4, y, B, T, D, MID, C, ln_eps, drop_p, seed,
+                         offset, label_smoothing, denom, nullptr, nullptr, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits,
+                         loss_sum, correct, stream);
+}
+
+extern "C" int ss_tail_fwd_w(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
+                             const float* gamma, const float* beta, const float* w1, const float* b1, const float* w4,
+                             const float* b4, const int64_t* y, int B, int T, int D, int MID, int C, float ln_eps,
+                             float drop_p, uint64_t seed, uint64_t offset, float label_smoothing, const float* cw,
+                             const float* den, float* attn, float* xhat, float* rstd, float* ln, float* mid, float* mid_d,
+                             float* logits, float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream) {
+  SS_REQUIRE(y && cw && den, SS_ERR_ARG);
+  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4, y, B, T, D, MID, C, ln_eps, drop_p, seed,
+                         offset, label_smoothing, 1.0f, cw, den, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits, loss_sum,
+                         correct, stream);
 }
 
 extern "C" int ss_tail_bwd(const float* h, const int32_t* lengths, const float* w_score, const float* gamma,

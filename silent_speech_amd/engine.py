@@ -281,7 +281,9 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
     embeddings were made when the frames arrived (sliding-window serving) -- and the ROI branch is skipped (inference only).
     ``train`` turns the two dropouts on (p from cfg); ``stash`` keeps what ``backward`` needs (needs a
     Workspace built with train=True).  ``ce = (y_ptr, label_smoothing, denom, loss_ptr, correct_ptr)`` makes the
-    fused tail kernel also evaluate the loss and leave d(loss)/d(logits) in ``ws.d_logits``."""
+    fused tail kernel also evaluate the loss and leave d(loss)/d(logits) in ``ws.d_logits``; two more entries,
+    ``(..., class_weights_ptr, den_ptr)``, make it the class-weighted loss divided by the device float ``*den_ptr``
+    (``ss_tail_fwd_w``; ``denom`` is then unused)."""
     if ws.bf16:
         from . import engine_bf16
 
@@ -346,12 +348,14 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
     top = ws.out[cfg.gru_layers - 1]
     # ---- AttnPool + head (+ loss): one fused launch, a workgroup per clip
     p_drop = cfg.head_dropout if train else 0.0
-    y_ptr, ls, denom, loss_ptr, correct_ptr = ce if ce is not None else (None, 0.0, 1.0, None, None)
-    L.call("ss_tail_fwd", top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
+    y_ptr, ls, denom, loss_ptr, correct_ptr, cw_ptr, den_ptr = (tuple(ce) + (None, None))[:7] if ce is not None else (None, 0.0, 1.0, None, None, None, None)
+    # (class weights: the same launch with the weights and the device-side normaliser in place of the host denom)
+    tail_fwd, ce_norm = ("ss_tail_fwd_w", (cw_ptr, den_ptr)) if cw_ptr else ("ss_tail_fwd", (denom,))
+    L.call(tail_fwd, top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
            P["pool.score.bias"].data_ptr(), P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(),
            P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(), P["head.4.weight"].data_ptr(),
            P["head.4.bias"].data_ptr(), y_ptr, B, T, 2 * H, cfg.head_mid, cfg.num_classes, cfg.ln_eps, p_drop, seed,
-           7 << 40, ls, denom, ws.attn.data_ptr() if stash else None, ws.xhat.data_ptr() if stash else None,
+           7 << 40, ls, *ce_norm, ws.attn.data_ptr() if stash else None, ws.xhat.data_ptr() if stash else None,
            ws.rstd.data_ptr() if stash else None, ws.ln.data_ptr() if stash else None,
            ws.mid.data_ptr() if stash else None, ws.mid_drop.data_ptr() if stash else None, ws.logits.data_ptr(),
            ws.d_logits.data_ptr() if ce is not None else None, loss_ptr, correct_ptr, s)

@@ -7,6 +7,7 @@ Counterparts, by reference line (/root/reference/train_model_official.py):
   evaluate          :449-475   loss / accuracy / predictions over a validation set, forward only
   top_confusions    :79-91     "actual→predicted(count)" strings of the most frequent errors
   fit               :417-506   epochs, save-best checkpoint (:486-500), early stopping (:501-505)
+  balanced_class_weights :406-412   the weights of the commented-out class-weighted loss (``fit(class_weights="balanced")``)
 
 Data parallelism (the reference has none): ``fit(rank=, world_size=, process_group=)`` -- every rank holds
 the whole store and draws the whole epoch order, ``epoch_shards`` gives it its rows of every global batch, the validation
@@ -33,7 +34,7 @@ import torch
 from .checkpoint import save_checkpoint
 from .device_data import DeviceClipStore
 from .model import BiGRUClassifier
-from .train import Trainer, shard_range
+from .train import Trainer, check_class_weights, shard_range
 
 VAL_FRAC, SEED, PATIENCE, EPOCHS, BATCH_SIZE = 0.15, 42, 12, 80, 16
 I32_MAX = 2 ** 31 - 1  # "no clip yet" in a first_seen matrix
@@ -97,14 +98,28 @@ def class_balanced_indices(labels: Sequence[str], num_samples: Optional[int] = N
     return torch.multinomial(w, n, replacement=True, generator=generator).tolist()
 
 
+def balanced_class_weights(train_labels: Sequence[str], id_to_label: Dict[int, str]) -> np.ndarray:
+    """The class weights of the reference's commented-out loss (:407-412): float32 ``1 / count(label of class i)`` over the
+    training clips, divided by its mean -- the average weight is 1."""
+    counts = collections.Counter(train_labels)
+    w = torch.tensor([1.0 / counts[id_to_label[i]] for i in range(len(id_to_label))], dtype=torch.float32)
+    w = w / w.mean()
+    return w.numpy()
+
+
 @torch.no_grad()
 def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = BATCH_SIZE, label_smoothing: float = 0.05,
-             plan: str = "host"):
+             plan: str = "host", class_weights=None):
     """-> (mean loss, accuracy, y_true, y_pred) over every clip of ``store``, in order, eval mode, no augmentation.
     ``plan="device"``: the batches are planned by the kernel (``store.batch(rng="philox")``) -- the same batches, since
-    nothing is drawn without augmentation."""
+    nothing is drawn without augmentation.
+    ``class_weights`` (one finite positive number per class): the loss is that of ``CrossEntropyLoss(weight=, label_smoothing=)``
+    over the WHOLE store, sum of the per-clip weighted losses / sum of w[label].  On purpose not the reference's average of
+    per-batch means (:441 and its validation loop): that figure depends on how the store is cut into batches, and so on
+    ``batch_size`` and, data parallel, on the world size; this one does not."""
     if plan not in ("host", "device"):
         raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
+    cw = None if class_weights is None else check_class_weights(class_weights, model.cfg.num_classes)
     from . import _lib as L
     from .checkpoint import softmax_topk
 
@@ -115,6 +130,8 @@ def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = B
     loss_sum = torch.zeros(1, device=dev, dtype=torch.float32)   # sum of the per-clip losses (denom = 1)
     correct = torch.zeros(1, device=dev, dtype=torch.int32)
     every = torch.arange(len(store), dtype=torch.int32, device=store.device) if plan == "device" else None
+    if cw is not None:
+        cw_d, one = torch.from_numpy(cw).to(dev), torch.ones(1, device=dev, dtype=torch.float32)
     for lo in range(0, len(store), batch_size):
         if plan == "device":
             X, T, R, y = store.batch(every[lo:lo + batch_size], augment=False, rng="philox")
@@ -124,14 +141,21 @@ def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = B
         logits = model(X, T, R if model.use_roi else None).contiguous()
         y = y.to(torch.int64).contiguous()
         # loss and hit count by the path's own cross-entropy kernel, predictions by its top-k kernel (no aten op)
-        L.call("ss_ce_ls_fwd_bwd", logits.data_ptr(), y.data_ptr(), logits.shape[0], logits.shape[1], label_smoothing, 1.0,
-               None, loss_sum.data_ptr(), correct.data_ptr(), L.stream())
+        if cw is None:
+            L.call("ss_ce_ls_fwd_bwd", logits.data_ptr(), y.data_ptr(), logits.shape[0], logits.shape[1], label_smoothing, 1.0,
+                   None, loss_sum.data_ptr(), correct.data_ptr(), L.stream())
+        else:  # (normaliser 1: the sum of the weighted per-clip losses)
+            L.call("ss_ce_ls_w_fwd_bwd", logits.data_ptr(), y.data_ptr(), logits.shape[0], logits.shape[1], label_smoothing,
+                   cw_d.data_ptr(), one.data_ptr(), None, loss_sum.data_ptr(), correct.data_ptr(), L.stream())
         _, top = softmax_topk(logits, 1)
         y_true += y.cpu().tolist()
         y_pred += top[:, 0].cpu().tolist()
     model.train(was_training)
     model.check_health()  # the loop above has synchronised anyway
     n = max(1, len(store))
+    if cw is not None:  # the labels are on the host already: their weights are summed there, in float64
+        wsum = float(cw.astype(np.float64)[np.asarray(y_true, np.int64)].sum()) if y_true else 1.0
+        return float(loss_sum) / wsum, int(correct) / n, y_true, y_pred
     return float(loss_sum) / n, int(correct) / n, y_true, y_pred
 
 
@@ -190,12 +214,14 @@ class EvalResult:
     y_pred: torch.Tensor
     bad_labels: bool = False  # a label outside the model's classes (always False on a result that was returned)
     extra: Optional[np.ndarray] = None  # the reduced ``extra_sums`` of the call, if any
+    loss_sum: float = 0.0     # numerator of ``loss``: the sum of the per-clip (weighted) losses
+    weight_sum: float = 0.0   # its denominator: ``n``, or under class weights the sum of w[label]
 
 
 @torch.no_grad()
 def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = BATCH_SIZE, label_smoothing: float = 0.05,
                     rank: int = 0, world_size: int = 1, process_group=None,
-                    extra_sums: Optional[torch.Tensor] = None) -> EvalResult:
+                    extra_sums: Optional[torch.Tensor] = None, class_weights=None) -> EvalResult:
     """``evaluate`` with the validation state kept on the device.  The rank evaluates the clips
     ``shard_range(len(store), rank, world_size)`` of the store, in order, eval mode, no augmentation: batches planned by
     ``store.batch(rng="philox")``, one ``ss_eval_accum`` launch per batch (``first_row`` = the clip's index in the store),
@@ -203,12 +229,19 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
     read of everything.  ``extra_sums`` (device float32 / float64 values that add over ranks, e.g. the epoch's train loss sum
     and hit count) ride in the same reduction and the same read: ``EvalResult.extra``.
     The kernel's bad-label flag travels in the same sum and the same read; if any rank saw a label outside the model's classes
-    (such clips count nowhere) every rank raises ``ValueError`` here, the way ``store.check()`` raises for the store's flag."""
+    (such clips count nowhere) every rank raises ``ValueError`` here, the way ``store.check()`` raises for the store's flag.
+    ``class_weights`` (one finite positive number per class): ``ss_eval_accum_w`` keeps two sums, the per-clip weighted losses
+    and w[label]; both add over ranks (the second rides in the same ``sums`` vector: no new collective) and ``loss`` is their
+    quotient over the whole store -- ``EvalResult.loss_sum / weight_sum``.  As in ``evaluate`` this is not the reference's
+    average of per-batch means, which would change with the batch size and the world size."""
     from . import _lib as L
 
+    cw = None if class_weights is None else check_class_weights(class_weights, model.cfg.num_classes)
     C, dev = model.cfg.num_classes, model.flat_params.device
     lo, hi = shard_range(len(store), rank, world_size)
     loss_sum = torch.zeros(1, device=dev, dtype=torch.float32)
+    if cw is not None:
+        cw_d, wsum = torch.from_numpy(cw).to(dev), torch.zeros(1, device=dev, dtype=torch.float32)
     counts = torch.zeros(2, device=dev, dtype=torch.int32)  # [correct, bad-label flag]
     confusion = torch.zeros(C, C, device=dev, dtype=torch.int32)
     first_seen = torch.full((C, C), I32_MAX, device=dev, dtype=torch.int32)
@@ -221,29 +254,38 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
         b1 = min(hi, b0 + batch_size)
         X, T, R, y = store.batch(every[b0:b1], augment=False, rng="philox")
         logits = model(X, T, R if model.use_roi else None).contiguous()
-        L.call("ss_eval_accum", logits.data_ptr(), y.data_ptr(), b1 - b0, C, label_smoothing, b0, loss_sum.data_ptr(),
-               counts.data_ptr(), confusion.data_ptr(), first_seen.data_ptr(), y_true.data_ptr() + 4 * (b0 - lo),
-               y_pred.data_ptr() + 4 * (b0 - lo), counts.data_ptr() + 4, L.stream())
+        if cw is None:
+            L.call("ss_eval_accum", logits.data_ptr(), y.data_ptr(), b1 - b0, C, label_smoothing, b0, loss_sum.data_ptr(),
+                   counts.data_ptr(), confusion.data_ptr(), first_seen.data_ptr(), y_true.data_ptr() + 4 * (b0 - lo),
+                   y_pred.data_ptr() + 4 * (b0 - lo), counts.data_ptr() + 4, L.stream())
+        else:
+            L.call("ss_eval_accum_w", logits.data_ptr(), y.data_ptr(), b1 - b0, C, label_smoothing, b0, cw_d.data_ptr(),
+                   loss_sum.data_ptr(), wsum.data_ptr(), counts.data_ptr(), confusion.data_ptr(), first_seen.data_ptr(),
+                   y_true.data_ptr() + 4 * (b0 - lo), y_pred.data_ptr() + 4 * (b0 - lo), counts.data_ptr() + 4, L.stream())
     model.train(was_training)
     n_extra = 0 if extra_sums is None else extra_sums.numel()
+    # [loss sum, correct, bad-label flag, n] + extra_sums (+ under class weights, last: the sum of w[label])
     sums = torch.cat([loss_sum.double(), counts.double(), torch.full((1,), float(hi - lo), device=dev, dtype=torch.float64)]
-                     + ([extra_sums.reshape(-1).to(device=dev, dtype=torch.float64)] if n_extra else []))
+                     + ([extra_sums.reshape(-1).to(device=dev, dtype=torch.float64)] if n_extra else [])
+                     + ([wsum.double()] if cw is not None else []))
     reduce_epoch_metrics(sums, confusion, first_seen, process_group)
     host = torch.cat([sums, confusion.reshape(-1).double(), first_seen.reshape(-1).double()]).cpu().numpy()  # the one read
     model.check_health()  # (the read above has synchronised)
     tot_loss, correct, bad, n = float(host[0]), int(host[1]), int(host[2]), int(host[3])
     if bad:
         raise ValueError("evaluate_device: a label of the store is outside the model's %d classes" % C)
-    mats = host[4 + n_extra:].astype(np.int64)
-    return EvalResult(loss=tot_loss / max(1, n), acc=correct / max(1, n), n=n, confusion=mats[:C * C].reshape(C, C),
-                      first_seen=mats[C * C:].reshape(C, C), y_true=y_true, y_pred=y_pred,
-                      extra=host[4:4 + n_extra].copy() if n_extra else None)
+    n_sums = sums.numel()
+    mats = host[n_sums:].astype(np.int64)
+    weight_sum = float(host[n_sums - 1]) if cw is not None else float(n)
+    return EvalResult(loss=tot_loss / (weight_sum if weight_sum > 0 else 1.0), acc=correct / max(1, n), n=n,
+                      confusion=mats[:C * C].reshape(C, C), first_seen=mats[C * C:].reshape(C, C), y_true=y_true, y_pred=y_pred,
+                      extra=host[4:4 + n_extra].copy() if n_extra else None, loss_sum=tot_loss, weight_sum=weight_sum)
 
 
 def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BATCH_SIZE, patience: int = PATIENCE,
         max_t: int = 90, lr: float = 3e-4, seed: int = SEED, use_roi_if_present: bool = True, device="cuda",
         log=print, plan: str = "host", rank: int = 0, world_size: int = 1, process_group=None,
-        history: Optional[list] = None) -> float:
+        history: Optional[list] = None, class_weights=None) -> float:
     """The reference's ``main()``: scan, split, train with class-balanced sampling and on-device augmentation, evaluate
     every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement.
 
@@ -263,7 +305,15 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     without another exchange.  Rank 0 alone logs and writes the checkpoint; all ranks pass a barrier before ``fit``
     returns, and all return ``best``.  (Verified on one rank over RCCL and on two over gloo; more than one GPU is unmeasured.)
 
-    ``history``: a list that gets one ``dict(epoch, train_loss, train_acc, val_loss, val_acc)`` per epoch, unrounded."""
+    ``history``: a list that gets one ``dict(epoch, train_loss, train_acc, val_loss, val_acc)`` per epoch, unrounded.
+
+    ``class_weights``: None (the reference's live loss, :405), ``"balanced"`` (``balanced_class_weights`` of the training clips:
+    the reference's commented-out loss, :406-414) or one finite positive number per class.  Training and validation then use
+    ``CrossEntropyLoss(weight=, label_smoothing=0.05)``.  In the device-planned loop every rank passes the labels of the step's
+    whole global batch to ``Trainer.step(y_global=)`` -- gathered once per epoch from the store's device label table by the
+    epoch order, nothing read back -- so the weighted mean is that of the global batch whatever the world size.  The logged
+    train loss stays the sum of loss x batch over the clip count, as the reference logs it (:441); the validation loss is
+    the weighted mean over the whole validation set (``evaluate``)."""
     if plan not in ("host", "device"):
         raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
     if world_size < 1 or not 0 <= rank < world_size:
@@ -277,18 +327,22 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     np.random.seed(seed)
     torch.manual_seed(seed)
     info = scan_clips(clip_dir)
+    if class_weights is not None and not (isinstance(class_weights, str) and class_weights == "balanced"):
+        class_weights = check_class_weights(class_weights, len(info["uniq"]))  # (before anything is uploaded)
     train_files, val_files = split_by_label(info["files"], info["labels"], VAL_FRAC, seed=seed)
     use_roi = use_roi_if_present and info["has_roi"] > 0
     train_store = DeviceClipStore(train_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
     val_store = DeviceClipStore(val_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
     train_labels = [str(np.load(f, allow_pickle=True)["label"]) for f in train_files]
+    if isinstance(class_weights, str):
+        class_weights = check_class_weights(balanced_class_weights(train_labels, info["id_to_label"]), len(info["uniq"]))
     model = BiGRUClassifier(info["x_dim"], len(info["uniq"]), use_roi=use_roi, roi_emb=32, hidden=192).to(device).train()
     if process_group is not None:
         import torch.distributed as dist
 
         dist.broadcast(model.flat_params, src=dist.get_global_rank(process_group, 0), group=process_group)
     trainer = Trainer(model, lr=lr, world_size=world_size, process_group=process_group,
-                      always_allreduce=process_group is not None)
+                      always_allreduce=process_group is not None, class_weights=class_weights)
     trainer.rank = rank
     roi_hw = train_store.roi_hw or (48, 96)
     gen = np.random.default_rng(seed)
@@ -302,7 +356,9 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
         tr_loss = torch.zeros((), device=device)
         tr_ok = torch.zeros((), device=device, dtype=torch.int64)
         if plan == "device":
-            for lo, hi, first_row, global_batch in epoch_shards(len(order), batch_size, rank, world_size):
+            # class weights: the labels of the whole epoch order, one gather on the device; a step's global batch is a slice
+            y_epoch = train_store.y[order.long()] if class_weights is not None else None
+            for k, (lo, hi, first_row, global_batch) in enumerate(epoch_shards(len(order), batch_size, rank, world_size)):
                 if hi > lo:
                     X, T, R, y = train_store.batch(order[lo:hi], augment=True, rng="philox", seed=seed,
                                                    first_row=epoch_base + first_row,
@@ -310,11 +366,12 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                 else:
                     X, T, R, y = train_store.empty_batch()
                 # (the loss is this rank's part of the global mean: the parts of all ranks sum to it)
-                loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch)
+                loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch,
+                                             y_global=None if y_epoch is None else y_epoch[k * batch_size:k * batch_size + global_batch])
                 tr_loss += loss * global_batch
                 tr_ok += correct
             res = evaluate_device(model, val_store, batch_size, rank=rank, world_size=world_size, process_group=process_group,
-                                  extra_sums=torch.stack([tr_loss.double(), tr_ok.double()]))
+                                  extra_sums=torch.stack([tr_loss.double(), tr_ok.double()]), class_weights=class_weights)
             train_store.check()  # (the evaluation above has synchronised)
             val_store.check()
             va_loss, va_acc, tr_loss, tr_ok = res.loss, res.acc, res.extra[0], res.extra[1]
@@ -326,7 +383,7 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                 loss, correct = trainer.step(X, T, R if use_roi else None, y)
                 tr_loss += loss * len(idx)
                 tr_ok += correct
-            va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size, plan=plan)
+            va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size, plan=plan, class_weights=class_weights)
             confs = top_confusions(y_true, y_pred, info["id_to_label"], k=6)
         n = max(1, len(order))
         if history is not None:

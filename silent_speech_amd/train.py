@@ -14,6 +14,7 @@ from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -37,6 +38,27 @@ def allreduce_flat_grads(flat: torch.Tensor, group=None, always: bool = False) -
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
 
 
+def check_class_weights(class_weights, num_classes: int) -> np.ndarray:
+    """The class weights of ``CrossEntropyLoss(weight=)`` as a float32 array of ``num_classes`` entries.  ``ValueError`` unless
+    they are that many finite, strictly positive numbers (as float32 too): the normaliser sum of w[y] then is positive whatever the
+    batch holds, so torch's NaN for a batch of zero-weight rows has no counterpart here."""
+    if isinstance(class_weights, str):
+        raise ValueError(f"class_weights must be a sequence of {num_classes} numbers, not {class_weights!r}")
+    if isinstance(class_weights, torch.Tensor):
+        class_weights = class_weights.detach().cpu().numpy()
+    try:
+        w64 = np.asarray(class_weights, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"class_weights must be a sequence of {num_classes} numbers") from e
+    if w64.shape != (num_classes,):
+        raise ValueError(f"class_weights must hold one weight per class: shape ({num_classes},), not {w64.shape}")
+    with np.errstate(over="ignore"):
+        w = w64.astype(np.float32)
+    if not (np.isfinite(w).all() and (w > 0).all()):
+        raise ValueError("class_weights must be finite and strictly positive")
+    return np.ascontiguousarray(w)
+
+
 class Trainer:
     """``micro_batches`` > 1 splits this rank's clips into that many equal slices which travel through forward and
     backward on their own HIP streams.  The GRU recurrence is latency-bound and occupies only one CU per
@@ -46,14 +68,22 @@ class Trainer:
 
     Measured on MI355X at B=256: 2 staggered slices gain 1 % (3.66 vs 3.71 ms/step) -- the overlap is
     real (the second slice's CNN forward runs under the first slice's recurrence) but the half-size persistent CNN
-    launches on 224 CUs lose what it wins -- so the default stays 1."""
+    launches on 224 CUs lose what it wins -- so the default stays 1.
+
+    ``class_weights`` (``num_classes`` finite positive numbers, or None): ``CrossEntropyLoss(weight=class_weights,
+    label_smoothing=)``, the reference's commented-out loss (train_model_official.py:406-414).  The weighted mean divides by the
+    sum of w[y] over the GLOBAL batch; that sum is taken on the device, per step, by one ``ss_class_weight_sum`` launch over
+    ``step(y_global=)`` and read by the fused tail from device memory -- no read-back, no collective.  Without weights a step
+    issues exactly the launches it always has."""
 
     # CUs left to the other micro-batch's recurrence while a persistent ROI-CNN kernel runs (2 directions x 8 slices)
     CNN_RESERVED_CUS = 32
 
     def __init__(self, model: BiGRUClassifier, lr: float = 3e-4, max_norm: float = 1.0,
                  label_smoothing: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
-                 process_group=None, dropout: bool = True, micro_batches: int = 1, always_allreduce: bool = False):
+                 process_group=None, dropout: bool = True, micro_batches: int = 1, always_allreduce: bool = False,
+                 class_weights=None):
+        cw = None if class_weights is None else check_class_weights(class_weights, model.cfg.num_classes)
         if model.flat_params is None or not model.flat_params.is_cuda:
             raise RuntimeError("Trainer needs the model on a HIP device")
         L.load()
@@ -70,6 +100,9 @@ class Trainer:
         # [loss_sum, sumsq] fp32 and [correct] int32 live on the device
         self.scal = torch.zeros(2, device=dev, dtype=torch.float32)
         self.correct = torch.zeros(1, device=dev, dtype=torch.int32)
+        # class weights (uploaded once) and the step's normaliser, sum of w[y] over the global batch: both stay on the device
+        self.cw = None if cw is None else torch.from_numpy(cw).to(dev)
+        self.den = None if cw is None else torch.zeros(1, device=dev, dtype=torch.float32)
         self.step_count = 0
         self.rank = 0
         if world_size > 1:
@@ -95,12 +128,14 @@ class Trainer:
                 raise RuntimeError("the model's parameter layout changed under the Trainer")
             self.m, self.v = self.m.to(flat.device), self.v.to(flat.device)
             self.scal, self.correct = self.scal.to(flat.device), self.correct.to(flat.device)
+            if self.cw is not None:
+                self.cw, self.den = self.cw.to(flat.device), self.den.to(flat.device)
         self.G = model._views_of(model.flat_grads)
         model.attach_flat_grads()
         self._bucket_version = model._bucket_version
 
     def step(self, X: torch.Tensor, lengths: torch.Tensor, R: Optional[torch.Tensor], y: torch.Tensor,
-             global_batch: Optional[int] = None):
+             global_batch: Optional[int] = None, y_global: Optional[torch.Tensor] = None):
         """One optimiser step on this rank's shard.  Returns (loss, correct) device tensors:
         loss = this shard's contribution to the global mean loss (sum over ranks = global loss).
         ``global_batch`` = clips of ALL ranks in this step; needed only when the shards are unequal (``shard_range``
@@ -108,7 +143,11 @@ class Trainer:
         global-mean gradient whatever each rank holds.  Default: B * world_size (equal shards).
         An empty shard (``X.shape[0] == 0``; ``harness.epoch_shards`` deals them when a global batch has fewer clips than there
         are ranks) is a legal step: the bucket and the scalars are zeroed, forward and backward are skipped, and the rank joins
-        the all-reduce, the clip and Adam like every other rank.  It returns zero loss and zero hits."""
+        the all-reduce, the clip and Adam like every other rank.  It returns zero loss and zero hits.
+        ``y_global`` (class weights only): the int64 device labels of ALL ranks' clips of this step, in any one order that is the
+        same on every rank; default ``y``, which is right for one process.  The loss is divided by the sum of w[label] over them
+        instead of ``global_batch`` -- taken by one fixed-order launch, so every rank divides by the same bits -- and the returned
+        loss is this rank's part of the global weighted mean.  Every micro-batch uses the same sum."""
         model, cfg = self.model, self.model.cfg
         if model._bucket_version != self._bucket_version:
             self._bind_bucket()
@@ -134,6 +173,18 @@ class Trainer:
             model.flat_grads.zero_()
             self.scal.zero_()
             self.correct.zero_()
+        ce_w = (None, None)
+        if self.cw is not None and B > 0:
+            yg = y if y_global is None else y_global
+            if not yg.is_cuda or yg.dim() != 1 or yg.numel() == 0:
+                raise ValueError("y_global must be a non-empty 1-D device tensor of labels")
+            if yg.dtype != torch.int64 or not yg.is_contiguous():
+                yg = yg.to(torch.int64).contiguous()
+            # (before the micro-batch streams fork: they wait for ev_start, recorded behind this launch)
+            L.call("ss_class_weight_sum", yg.data_ptr(), yg.numel(), self.cw.data_ptr(), cfg.num_classes, self.den.data_ptr(),
+                   L.stream())
+            ce_w = (self.cw.data_ptr(), self.den.data_ptr())
+        self._ce_w = ce_w
         if B == 0:
             pass  # an empty shard: this rank's gradient is the zero bucket
         elif M == 1:
@@ -190,7 +241,7 @@ class Trainer:
             if not prologue_done:
                 ws.lengths.copy_(lengths.to(torch.int32), non_blocking=True)
             E.forward(P, cfg, ws, X, R, train=train, stash=True, seed=seed, x_in_place=prologue_done,
-                      ce=(y.data_ptr(), self.ls, denom, self.scal.data_ptr(), self.correct.data_ptr()))
+                      ce=(y.data_ptr(), self.ls, denom, self.scal.data_ptr(), self.correct.data_ptr()) + self._ce_w)
         if phase in ("bwd", "both"):
             E.backward(P, self.G, cfg, ws, X, R, ws.d_logits, train=train, seed=seed)
 

@@ -6,6 +6,10 @@ batches planned by the kernel (``rng="philox"``), with ``Trainer.step`` on a res
 One JSON line.  Per shape (config 2: B=256, T=30, D=84, 64x64 ROI; shipped: B=16, T=90, D=180, 48x96 ROI):
   clips_per_s.{resident, host_plan, device_plan}  median (min, max) over the windows; the three loops alternate window by window
                                                   inside this one process, every window ends in a device synchronise
+  clips_per_s.resident_weighted, class_weight_us  (--class-weights) the resident loop through ``Trainer(class_weights=)``, a fourth loop
+                                                  in the same alternation, and what its step costs more than the unweighted one
+                                                  (the one ``ss_class_weight_sum`` launch): median over the windows of the difference
+                                                  in us per step between neighbouring windows
   assemble_ms.{host_plan, device_plan}            the batch() calls alone (no step), same alternation: ms per batch
   enqueue_ms.{host_plan, device_plan}             host wall time of one batch() call while the GPU is idle (no synchronise
                                                   inside the timed region: what the call costs the Python thread)
@@ -74,10 +78,12 @@ def time_validation(model, B, T, D, roi, C, n_clips, windows, dev):
     return {"clips": n_clips, "batches": -(-n_clips // B), **{k: summary(v, 3) for k, v in ms.items()}}
 
 
-def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0):
+def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, class_weights=False):
     store = make_store(T, D, roi, C, dev)
     model = ss.BiGRUClassifier(D, C, use_roi=True, roi_emb=32, hidden=192).to(dev).train()
     trainer = ss.Trainer(model)
+    # (a second trainer on the same model: its own Adam moments, the same buckets and workspaces)
+    weighted = ss.Trainer(model, class_weights=np.linspace(0.5, 1.5, C)) if class_weights else None
     gen = np.random.default_rng(SEED)
     host_order = [[int(v) for v in gen.integers(0, len(store), B)] for _ in range(steps)]  # drawn outside the timed loops
     dev_order = store.sample_epoch(num_samples=B * steps, seed=SEED)
@@ -92,16 +98,19 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0):
         return store.batch(dev_order[i * B:(i + 1) * B], augment=True, rng="philox", seed=SEED, first_row=row[0])
 
     def window(make_batch, step, n):
+        tr = weighted if step == "weighted" else trainer
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(n):
             Xb, Tb, Rb, yb = make_batch(i % steps) if make_batch else resident
             if step:
-                trainer.step(Xb, Tb, Rb, yb)
+                tr.step(Xb, Tb, Rb, yb)
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
     loops = {"resident": (None, True), "host_plan": (host_batch, True), "device_plan": (dev_batch, True)}
+    if weighted is not None:
+        loops = {"resident": (None, True), "resident_weighted": (None, "weighted"), **loops}
     asm = {"host_plan": (host_batch, False), "device_plan": (dev_batch, False)}
     for mk, st in list(loops.values()) + list(asm.values()):  # every shape and code path of the timed windows, warmed up
         window(mk, st, warmup)
@@ -131,7 +140,11 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0):
         kern[k] = {tag: round(sum(a.elapsed_time(b) for a, b in evs) / len(evs), 4) for tag, evs in prof.items()}
     store.check()
     med = {k: statistics.median(v) for k, v in rate.items()}
-    extra = {"validation_ms": time_validation(model, B, T, D, roi, C, eval_clips, windows, dev)} if eval_clips and name == "config2" else {}
+    if weighted is not None:
+        extra_us = [1e6 * B * (1 / w - 1 / u) for u, w in zip(rate["resident"], rate["resident_weighted"])]
+    extra = {} if not (eval_clips and name == "config2") else {"validation_ms": time_validation(model, B, T, D, roi, C, eval_clips, windows, dev)}
+    if weighted is not None:
+        extra["class_weight_us"] = summary(extra_us, 2)
     return {**extra, "shape": dict(B=B, T=T, D=D, roi="%dx%d" % tuple(roi), classes=C),
             "clips_per_s": {k: summary(v) for k, v in rate.items()},
             "of_resident": {k: round(med[k] / med["resident"], 4) for k in ("host_plan", "device_plan")},
@@ -145,6 +158,7 @@ def main():
     ap.add_argument("--windows", type=int, default=5, help="timed windows per loop (alternating)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shapes", default="config2,shipped")
+    ap.add_argument("--class-weights", action="store_true", help="also time the resident loop with class weights")
     ap.add_argument("--eval-clips", type=int, default=1024, help="clips of the timed validation pass (config2; 0 = skip)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -153,7 +167,8 @@ def main():
     out = {"metric": "clips/s of the training loop: resident batch, host-planned batches, device-planned batches",
            "steps_per_window": args.steps, "windows": args.windows, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     for name in args.shapes.split(","):
-        out[name] = run_shape(name, steps=args.steps, windows=args.windows, warmup=args.warmup, dev=dev, eval_clips=args.eval_clips, **SHAPES[name])
+        out[name] = run_shape(name, steps=args.steps, windows=args.windows, warmup=args.warmup, dev=dev, eval_clips=args.eval_clips, class_weights=args.class_weights,
+                              **SHAPES[name])
     print(json.dumps(out))
 
 
