@@ -300,6 +300,40 @@ int ss_batch_plan(const int32_t* indices, int B, const int32_t* x_off, const int
                   const int32_t* r_len, const int64_t* y, int n_clips, int max_t, int augment, uint64_t first_row, uint64_t seed,
                   double noise_prob, double drop_prob, int drop_max, int32_t* xmap, int32_t* nmap, int32_t* rmap, int64_t* lens,
                   int64_t* y_out, int32_t* err_flag, ss_stream_t stream);
+/* The opt-in augmentation policy of the device-planned path: a time warp of the whole clip (features and ROI frames together),
+ * a scale factor on the features, an integer shift of the ROI frames with edge replication.  ss_batch_plan is untouched; with
+ * the three probabilities 0 ss_batch_plan_aug writes the same maps, lengths and labels, bit for bit.
+ * ss_batch_plan_aug: ss_batch_plan's arguments and rules (sub-draws 0 and 1 as there), plus, from sub-draw 2 (w0..w3) and
+ *   sub-draw 3 (s0..s3) of the same row counter:
+ *     warp : T > 10 && w0 < thr(warp_prob): f = warp_lo_pm + mulhi(w1, warp_hi_pm - warp_lo_pm + 1) (permille),
+ *            L = max(5, T * f / 1000); else L = T.  Warped position j reads source frame Wp(j) = j * (T - 1) / (L - 1) (integer
+ *            division; j when L == T): np.linspace(0, T - 1, L).astype(int) without its float rounding.
+ *     drop : the rule of ss_batch_plan on the warped clip: L > 12, positions in [1, L - 2]; features only.
+ *     maps : xmap[b][t] = x_off + Wp(t stepped over the dropped positions), rmap[b][t] = r_off + Wp(t);
+ *            n_r = L if r_len >= T, else (r_len * (L - 1) + T - 2) / (T - 1) (warped positions whose source frame the ROI track
+ *            has; 0 for r_len = 0); t_eff = min(L - k, max_t, n_r for a clip with ROI frames).
+ *     scale: w2 < thr(scale_prob): u = (float)(w3 >> 8) * 2^-24, row_scale[b] = fl(scale_lo + fl(scale_span * u)); else 1.0f.
+ *     shift: clip has ROI frames && s0 < thr(shift_prob): row_shift[b] = (mulhi(s1, 2 mx + 1) - mx, mulhi(s2, 2 my + 1) - my),
+ *            mx = shift_max_x, my = shift_max_y; else (0, 0).
+ *   row_scale (B) f32, row_shift (B, 2) int32 (dx, dy).  An invalid index writes scale 1 and shift (0, 0).  SS_ERR_ARG: a
+ *   probability outside [0, 1], not 0 < warp_lo_pm <= warp_hi_pm <= 4000, scale_lo <= 0, scale_span < 0, shift_max_* < 0.
+ * ss_batch_gather_f32_aug: ss_batch_gather_f32_at (noise_first = 0: the stream of ss_batch_gather_f32) with every element of dst
+ *   row r multiplied, after the noise, by row_scale[r / rows_per_clip] (one rounded product).  rows % rows_per_clip == 0.
+ * ss_batch_gather_u8_shift: dst[r][y][x] = src[frame_map[r]][clamp(y - dy, 0, H-1)][clamp(x - dx, 0, W-1)], (dx, dy) =
+ *   row_shift[r / rows_per_clip]; zeros where frame_map[r] < 0.  H * W % 16 == 0; W % 16 == 0 is the streaming path, other widths
+ *   go byte by byte.  shift_max_x / shift_max_y: the bounds the table was planned with, shift_max_x >= W or shift_max_y >= H is
+ *   SS_ERR_ARG; whatever the table holds, no byte outside the mapped frame is read. */
+int ss_batch_plan_aug(const int32_t* indices, int B, const int32_t* x_off, const int32_t* x_len, const int32_t* r_off,
+                      const int32_t* r_len, const int64_t* y, int n_clips, int max_t, int augment, uint64_t first_row, uint64_t seed,
+                      double noise_prob, double drop_prob, int drop_max, double warp_prob, int warp_lo_pm, int warp_hi_pm,
+                      double scale_prob, float scale_lo, float scale_span, double shift_prob, int shift_max_x, int shift_max_y,
+                      int32_t* xmap, int32_t* nmap, int32_t* rmap, int64_t* lens, int64_t* y_out, float* row_scale,
+                      int32_t* row_shift, int32_t* err_flag, ss_stream_t stream);
+int ss_batch_gather_f32_aug(const float* src, int D, const int32_t* frame_map, long rows, const int32_t* noise_map, float noise_std,
+                            uint64_t seed, uint64_t noise_first, const float* row_scale, int rows_per_clip, float* dst,
+                            ss_stream_t stream);
+int ss_batch_gather_u8_shift(const uint8_t* src, int H, int W, const int32_t* frame_map, long rows, const int32_t* row_shift,
+                             int rows_per_clip, int shift_max_x, int shift_max_y, uint8_t* dst, ss_stream_t stream);
 
 /* ---- sliding-window serving of many streams ---------------------------------------
  * per stream a ring of the last max_t frames (features (S,max_t,D) f32, optional ROI (S,max_t,frame_bytes) u8), a head

@@ -8,7 +8,7 @@ there is no CPU or PyTorch-op fallback.
 """
 from . import checkpoint, data, features, harness, serving
 from .checkpoint import load_classifier, save_checkpoint, topk_from_logits
-from .device_data import DeviceClipStore
+from .device_data import AugmentPolicy, DeviceClipStore
 from .engine import Config
 from .features import crop_boxes, crop_rois, extract_features
 from .infer import GraphedInference
@@ -16,6 +16,6 @@ from .serving import ClipGateServer, LiveFrontEnd, StreamServer, mouth_openness
 from .model import AttnPool, BiGRUClassifier, TinyROICNN
 from .train import Trainer, allreduce_flat_grads, shard_range
 
-__all__ = ["Config", "BiGRUClassifier", "TinyROICNN", "AttnPool", "Trainer", "allreduce_flat_grads", "shard_range",
+__all__ = ["AugmentPolicy", "Config", "BiGRUClassifier", "TinyROICNN", "AttnPool", "Trainer", "allreduce_flat_grads", "shard_range",
            "extract_features", "crop_boxes", "GraphedInference", "load_classifier", "save_checkpoint", "topk_from_logits", "features",
            "data", "checkpoint"]

@@ -119,6 +119,57 @@ __global__ __launch_bounds__(256) void batch_gather_f32_at_kernel(const float* _
   }
 }
 
+// The kernel above with a per-clip factor on every gathered element (the augmentation policy's scale jitter): row r of dst
+// belongs to clip r / rows_per_clip, and x_after_noise * row_scale[clip] is one rounded product (__fmul_rn: no contraction with
+// the noise term, so NumPy's fl(x * s) restates it).  Padding rows stay 0.
+__global__ __launch_bounds__(256) void batch_gather_f32_aug_kernel(const float* __restrict__ src, int D,
+                                                                   const int32_t* __restrict__ frame_map, long rows,
+                                                                   const int32_t* __restrict__ noise_map, float noise_std,
+                                                                   uint64_t seed, uint64_t noise_first,
+                                                                   const float* __restrict__ row_scale, int rows_per_clip,
+                                                                   float* __restrict__ dst) {
+  const long total = rows * D;
+  const int shift = (int)(noise_first & 3);
+  for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 4; q < total; q += (long)gridDim.x * 256 * 4) {
+    float v[4], sc[4];
+    bool noisy[4];
+    long r = q / D;
+    int d = (int)(q - r * D);
+    float s = row_scale[r / rows_per_clip];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float x = 0.f;
+      noisy[e] = false;
+      if (q + e < total) {
+        const int m = frame_map[r];
+        if (m >= 0) x = src[(long)m * D + d];
+        noisy[e] = m >= 0 && noise_map[r] >= 0;
+      }
+      v[e] = x;
+      sc[e] = s;
+      if (++d == D) {
+        d = 0;
+        ++r;
+        if (r < rows) s = row_scale[r / rows_per_clip];
+      }
+    }
+    if (noise_std > 0.f) {
+      const uint64_t ctr = (noise_first + (uint64_t)q) >> 2;
+      float n[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      gather_noise4(ctr, seed, n);
+      if (shift) gather_noise4(ctr + 1, seed, n + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float ne = shift == 0 ? n[e] : shift == 1 ? n[e + 1] : shift == 2 ? n[e + 2] : n[e + 3];
+        if (noisy[e]) v[e] += noise_std * ne;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (q + e < total) dst[q + e] = __fmul_rn(v[e], sc[e]);
+  }
+}
+
 // dst[r][0:frame_bytes] = map[r] >= 0 ? src[map[r]] : 0; frame_bytes % 16 == 0, one workgroup walks whole rows
 __global__ __launch_bounds__(256) void batch_gather_u8_kernel(const uint8_t* __restrict__ src, int chunks /* 16-byte */,
                                                               const int32_t* __restrict__ frame_map, long rows,
@@ -128,6 +179,79 @@ __global__ __launch_bounds__(256) void batch_gather_u8_kernel(const uint8_t* __r
     const uint4* s4 = reinterpret_cast<const uint4*>(src) + (long)(m < 0 ? 0 : m) * chunks;
     uint4* d4 = reinterpret_cast<uint4*>(dst) + r * chunks;
     for (int c = threadIdx.x; c < chunks; c += 256) d4[c] = m >= 0 ? s4[c] : uint4{0, 0, 0, 0};
+  }
+}
+
+// The gather above with a per-clip integer shift of the frame, edges replicated (the augmentation policy's ROI jitter):
+//   dst[r][y][x] = src[map[r]][clamp(y - dy, 0, H-1)][clamp(x - dx, 0, W-1)],  (dx, dy) = row_shift[2 * (r / rows_per_clip)].
+// Still an HBM stream: one workgroup walks whole frames, one 16-byte store per lane.  WIDE (W % 16 == 0): a destination chunk
+// lies inside one image row, its 16 source bytes start at byte x0 - dx of the (clamped) source row.  Where that run lies inside
+// the row it is fetched whole (load16_at); only the chunks that reach over the left or right edge go byte by byte, every
+// byte address clamped into the row.  !WIDE: every byte on its own (correctness for odd widths, not speed).  No load touches a
+// byte outside [src + map[r] * H * W, + H * W): row and column are clamped before any address is formed, and dx, dy
+// themselves are clamped to +-W, +-H first (the same result, and no overflow whatever the table holds).
+struct __attribute__((packed, aligned(1))) bytes16 { uint32_t w[4]; };  // a 16-byte load the compiler may not assume aligned
+
+// 16 bytes from byte offset `at` of a row, 0 <= at and at + 16 <= row length: ONE global load at the byte address.  (Measured
+// against two aligned 16-byte loads + v_alignbyte: never slower, 3 - 7 % faster where clips are shifted)
+__device__ __forceinline__ uint4 load16_at(const uint8_t* __restrict__ row, int at) {
+  const bytes16 b = *reinterpret_cast<const bytes16*>(row + at);
+  return uint4{b.w[0], b.w[1], b.w[2], b.w[3]};
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void batch_gather_u8_shift_kernel(const uint8_t* __restrict__ src, int H, int W,
+                                                                    const int32_t* __restrict__ frame_map, long rows,
+                                                                    const int32_t* __restrict__ row_shift, int rows_per_clip,
+                                                                    uint8_t* __restrict__ dst) {
+  const int chunks = (H * W) >> 4;
+  const int row_chunks = W >> 4;  // WIDE only
+  for (long r = blockIdx.x; r < rows; r += gridDim.x) {
+    const int m = frame_map[r];
+    uint4* d4 = reinterpret_cast<uint4*>(dst) + r * chunks;
+    if (m < 0) {
+      for (int c = threadIdx.x; c < chunks; c += 256) d4[c] = uint4{0, 0, 0, 0};
+      continue;
+    }
+    const long clip = r / rows_per_clip;
+    const int dx = clampi(row_shift[2 * clip], -W, W), dy = clampi(row_shift[2 * clip + 1], -H, H);
+    const uint8_t* frame = src + (long)m * H * W;
+    for (int c = threadIdx.x; c < chunks; c += 256) {
+      uint32_t o[4];
+      if constexpr (WIDE) {
+        const int y = (int)((uint32_t)c / (uint32_t)row_chunks);
+        const int x0 = (c - y * row_chunks) << 4;
+        const uint8_t* row = frame + clampi(y - dy, 0, H - 1) * W;
+        const int at = x0 - dx;
+        if (at >= 0 && at + 16 <= W) {
+          d4[c] = load16_at(row, at);
+          continue;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          uint32_t word = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) word |= (uint32_t)row[clampi(at + 4 * i + j, 0, W - 1)] << (8 * j);
+          o[i] = word;
+        }
+      } else {
+        int y = (int)((uint32_t)(c << 4) / (uint32_t)W);
+        int x = (c << 4) - y * W;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          uint32_t word = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            word |= (uint32_t)frame[clampi(y - dy, 0, H - 1) * W + clampi(x - dx, 0, W - 1)] << (8 * j);
+            if (++x == W) { x = 0; ++y; }
+          }
+          o[i] = word;
+        }
+      }
+      d4[c] = uint4{o[0], o[1], o[2], o[3]};
+    }
   }
 }
 
@@ -216,6 +340,98 @@ __global__ __launch_bounds__(SS_WAVE) void batch_plan_kernel(
   }
 }
 
+// batch_plan_kernel with the augmentation policy: a time warp of the whole clip (features and ROI frames together), the
+// drop on the warped length, a scale factor for the features and an integer shift for the ROI frames.  Sub-draws 0 and 1 are
+// used exactly as above; the new decisions come from sub-draw 2 (w) and sub-draw 3 (s).  Warped position j of a clip of T
+// frames warped to L reads source frame Wp(j) = j * (T - 1) / (L - 1) (integer division; j when L == T).
+__global__ __launch_bounds__(SS_WAVE) void batch_plan_aug_kernel(
+    const int32_t* __restrict__ indices, const int32_t* __restrict__ x_off, const int32_t* __restrict__ x_len,
+    const int32_t* __restrict__ r_off, const int32_t* __restrict__ r_len, const int64_t* __restrict__ y, int n_clips,
+    int max_t, int augment, uint64_t first_row, uint64_t seed, uint64_t noise_thr, uint64_t drop_thr, int drop_max,
+    uint64_t warp_thr, int warp_lo_pm, int warp_hi_pm, uint64_t scale_thr, float scale_lo, float scale_span,
+    uint64_t shift_thr, int shift_max_x, int shift_max_y, int32_t* __restrict__ xmap, int32_t* __restrict__ nmap,
+    int32_t* __restrict__ rmap, int64_t* __restrict__ lens, int64_t* __restrict__ y_out, float* __restrict__ row_scale,
+    int32_t* __restrict__ row_shift, int32_t* __restrict__ err_flag) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int clip = indices[b];
+  const bool valid = clip >= 0 && clip < n_clips;
+  int xo = 0, ro = -1, t_eff = 0, k = 0, d0 = 0, d1 = 0, T = 0, Lw = 0, n_r = 0, dx = 0, dy = 0;
+  float scale = 1.0f;
+  bool noisy = false;
+  if (valid) {
+    T = x_len[clip];
+    Lw = T;
+    xo = x_off[clip];
+    const bool has_roi = r_off && r_off[clip] >= 0;
+    if (augment) {
+      const uint64_t row = first_row + (uint64_t)b;
+      const uint32_t r0 = (uint32_t)row, r1 = (uint32_t)(row >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+      uint32_t r[4], w[4], s[4];
+      philox4(r0, r1, TAG_PLANNER, 0u, k0, k1, r);
+      philox4(r0, r1, TAG_PLANNER, 2u, k0, k1, w);
+      philox4(r0, r1, TAG_PLANNER, 3u, k0, k1, s);
+      noisy = (uint64_t)r[0] < noise_thr;
+      if (T > 10 && (uint64_t)w[0] < warp_thr) {
+        const long f = warp_lo_pm + (long)mulhi_u32(w[1], (uint32_t)(warp_hi_pm - warp_lo_pm + 1));
+        const long l = (long)T * f / 1000;
+        Lw = l < 5 ? 5 : l > 0x7fffffffL ? 0x7fffffff : (int)l;
+      }
+      if (Lw > 12 && (uint64_t)r[1] < drop_thr) {  // the rule above on the warped clip: positions 0 and Lw-1 stay
+        k = 1 + (int)mulhi_u32(r[2], (uint32_t)drop_max);
+        d0 = 1 + (int)mulhi_u32(r[3], (uint32_t)(Lw - 2));
+        if (k == 2) {
+          uint32_t q[4];
+          philox4(r0, r1, TAG_PLANNER, 1u, k0, k1, q);
+          int p1 = 1 + (int)mulhi_u32(q[0], (uint32_t)(Lw - 3));
+          p1 += (p1 >= d0);
+          d1 = p1 > d0 ? p1 : d0;
+          d0 = p1 > d0 ? d0 : p1;
+        }
+      }
+      if ((uint64_t)w[2] < scale_thr) {
+        const float u = (float)(w[3] >> 8) * 5.9604644775390625e-8f;  // 24 bits: exact
+        scale = __fadd_rn(scale_lo, __fmul_rn(scale_span, u));
+      }
+      if (has_roi && (uint64_t)s[0] < shift_thr) {
+        dx = (int)mulhi_u32(s[1], (uint32_t)(2 * shift_max_x + 1)) - shift_max_x;
+        dy = (int)mulhi_u32(s[2], (uint32_t)(2 * shift_max_y + 1)) - shift_max_y;
+      }
+    }
+    t_eff = Lw - k < max_t ? Lw - k : max_t;
+    if (t_eff < 0) t_eff = 0;
+    if (has_roi) {  // the warped positions whose source frame the ROI track has
+      ro = r_off[clip];
+      const int tr = r_len[clip] > 0 ? r_len[clip] : 0;
+      n_r = tr >= T ? Lw : tr == 0 ? 0 : (int)(((long)tr * (Lw - 1) + T - 2) / (T - 1));
+      t_eff = t_eff < n_r ? t_eff : n_r;
+    }
+  }
+  const bool warped = Lw != T;  // (then T > 10 and Lw >= 5: no division by zero)
+  for (int t = lane; t < max_t; t += SS_WAVE) {
+    const bool in = t < t_eff;
+    int s = t;
+    s += (k >= 1 && s >= d0);
+    s += (k == 2 && s >= d1);
+    int fx = s, fr = t;
+    if (warped && in) {
+      fx = (int)((long)s * (T - 1) / (Lw - 1));
+      fr = (int)((long)t * (T - 1) / (Lw - 1));
+    }
+    const long at = (long)b * max_t + t;
+    xmap[at] = in ? xo + fx : -1;
+    nmap[at] = (in && noisy) ? 0 : -1;
+    if (rmap) rmap[at] = (in && ro >= 0) ? ro + fr : -1;
+  }
+  if (lane == 0) {
+    lens[b] = t_eff;
+    y_out[b] = valid ? y[clip] : 0;
+    row_scale[b] = scale;
+    row_shift[2 * b] = dx;
+    row_shift[2 * b + 1] = dy;
+    if (!valid) atomicOr(err_flag, 1);
+  }
+}
+
 }  // namespace
 
 extern "C" int ss_epoch_sample(const int32_t* members, int n_members, const int32_t* class_start, int n_classes,
@@ -278,5 +494,64 @@ extern "C" int ss_batch_gather_u8(const uint8_t* src, int frame_bytes, const int
   long blocks = rows > 8192 ? 8192 : rows;
   hipLaunchKernelGGL(batch_gather_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), src,
                      frame_bytes / 16, frame_map, rows, dst);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_plan_aug(const int32_t* indices, int B, const int32_t* x_off, const int32_t* x_len, const int32_t* r_off,
+                                 const int32_t* r_len, const int64_t* y, int n_clips, int max_t, int augment, uint64_t first_row,
+                                 uint64_t seed, double noise_prob, double drop_prob, int drop_max, double warp_prob, int warp_lo_pm,
+                                 int warp_hi_pm, double scale_prob, float scale_lo, float scale_span, double shift_prob,
+                                 int shift_max_x, int shift_max_y, int32_t* xmap, int32_t* nmap, int32_t* rmap, int64_t* lens,
+                                 int64_t* y_out, float* row_scale, int32_t* row_shift, int32_t* err_flag, ss_stream_t stream) {
+  SS_REQUIRE(indices && x_off && x_len && y && xmap && nmap && lens && y_out && row_scale && row_shift && err_flag, SS_ERR_ARG);
+  SS_REQUIRE(B > 0 && n_clips > 0 && max_t > 0, SS_ERR_ARG);
+  SS_REQUIRE((r_off == nullptr) == (r_len == nullptr) && (!r_off || rmap), SS_ERR_ARG);
+  SS_REQUIRE(noise_prob >= 0.0 && noise_prob <= 1.0 && drop_prob >= 0.0 && drop_prob <= 1.0, SS_ERR_ARG);
+  SS_REQUIRE(warp_prob >= 0.0 && warp_prob <= 1.0 && scale_prob >= 0.0 && scale_prob <= 1.0, SS_ERR_ARG);
+  SS_REQUIRE(shift_prob >= 0.0 && shift_prob <= 1.0, SS_ERR_ARG);
+  SS_REQUIRE(0 < warp_lo_pm && warp_lo_pm <= warp_hi_pm && warp_hi_pm <= 4000, SS_ERR_ARG);
+  SS_REQUIRE(scale_lo > 0.f && scale_span >= 0.f, SS_ERR_ARG);  // (a NaN fails both)
+  SS_REQUIRE(shift_max_x >= 0 && shift_max_y >= 0 && shift_max_x < (1 << 30) && shift_max_y < (1 << 30), SS_ERR_ARG);
+  SS_REQUIRE(drop_max >= 1, SS_ERR_ARG);
+  SS_REQUIRE(drop_max <= 2, SS_ERR_UNSUPPORTED);
+  const double two32 = 4294967296.0;
+  hipLaunchKernelGGL(batch_plan_aug_kernel, dim3((unsigned)B), dim3(SS_WAVE), 0, static_cast<hipStream_t>(stream), indices, x_off,
+                     x_len, r_off, r_len, y, n_clips, max_t, augment, first_row, seed, (uint64_t)(noise_prob * two32),
+                     (uint64_t)(drop_prob * two32), drop_max, (uint64_t)(warp_prob * two32), warp_lo_pm, warp_hi_pm,
+                     (uint64_t)(scale_prob * two32), scale_lo, scale_span, (uint64_t)(shift_prob * two32), shift_max_x,
+                     shift_max_y, xmap, nmap, rmap, lens, y_out, row_scale, row_shift, err_flag);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_gather_f32_aug(const float* src, int D, const int32_t* frame_map, long rows, const int32_t* noise_map,
+                                       float noise_std, uint64_t seed, uint64_t noise_first, const float* row_scale,
+                                       int rows_per_clip, float* dst, ss_stream_t stream) {
+  SS_REQUIRE(src && frame_map && noise_map && row_scale && dst && D > 0 && rows > 0 && noise_std >= 0.f, SS_ERR_ARG);
+  SS_REQUIRE(rows_per_clip > 0 && rows % rows_per_clip == 0, SS_ERR_ARG);
+  SS_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 3) == 0, SS_ERR_ARG);
+  const long chunks = (rows * D + 3) / 4;
+  long blocks = (chunks + 255) / 256;
+  blocks = blocks > 4096 ? 4096 : blocks;
+  hipLaunchKernelGGL(batch_gather_f32_aug_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), src, D,
+                     frame_map, rows, noise_map, noise_std, seed, noise_first, row_scale, rows_per_clip, dst);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_gather_u8_shift(const uint8_t* src, int H, int W, const int32_t* frame_map, long rows,
+                                        const int32_t* row_shift, int rows_per_clip, int shift_max_x, int shift_max_y,
+                                        uint8_t* dst, ss_stream_t stream) {
+  SS_REQUIRE(src && frame_map && row_shift && dst && H > 0 && W > 0 && rows > 0, SS_ERR_ARG);
+  SS_REQUIRE(rows_per_clip > 0 && rows % rows_per_clip == 0, SS_ERR_ARG);
+  SS_REQUIRE(shift_max_x >= 0 && shift_max_y >= 0 && shift_max_x < W && shift_max_y < H, SS_ERR_ARG);
+  SS_REQUIRE((long)H * W <= 0x7fffffffL, SS_ERR_UNSUPPORTED);
+  SS_REQUIRE(((H * W) & 15) == 0, SS_ERR_UNSUPPORTED);
+  SS_REQUIRE((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0, SS_ERR_ARG);
+  const long blocks = rows > 8192 ? 8192 : rows;
+  if ((W & 15) == 0)
+    hipLaunchKernelGGL(batch_gather_u8_shift_kernel<true>, dim3((unsigned)blocks), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), src, H, W, frame_map, rows, row_shift, rows_per_clip, dst);
+  else
+    hipLaunchKernelGGL(batch_gather_u8_shift_kernel<false>, dim3((unsigned)blocks), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), src, H, W, frame_map, rows, row_shift, rows_per_clip, dst);
   return ss_launch_status();
 }

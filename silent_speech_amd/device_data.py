@@ -17,11 +17,17 @@ Three sources of randomness:
     decisions from the Philox stream and writes the maps, the lengths and the labels); with device indices from
     ``sample_epoch`` (``ss_epoch_sample``, the class-balanced sampler) nothing at all crosses PCIe and the host makes no
     per-clip step.  tests/batch_plan_ref.py restates both kernels in NumPy integers, bit for bit.
+
+``AugmentPolicy`` (``batch(rng="philox", augment=True, policy=)``) adds what the reference's lineage had and its official
+script dropped (inactive/train_reduced.py:103-123: time warp, scale jitter) and a per-clip shift of the ROI frames, planned and
+applied on the device as well (``ss_batch_plan_aug``, ``ss_batch_gather_f32_aug``, ``ss_batch_gather_u8_shift``;
+tests/aug_plan_ref.py restates them).  Without a policy the launches are the three above, unchanged.
 """
 from __future__ import annotations
 
 import random
-from typing import List, Optional, Sequence
+from dataclasses import dataclass, replace
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -39,6 +45,59 @@ def philox_noise_seed(seed: int, first_row: int) -> int:
     give distinct seeds: consecutive batches of an epoch never share a noise stream (the noise counter is the element
     index inside the batch, the same for every batch)."""
     return (int(seed) ^ (((int(first_row) + 1) * 0x9E3779B97F4A7C15) & _MASK64)) & _MASK64
+
+
+@dataclass(frozen=True)
+class AugmentPolicy:
+    """Opt-in augmentations of the device-planned path, drawn per clip from the planner's Philox stream.
+
+    ``time_warp_prob`` / ``time_warp_range``: a clip of more than 10 frames is re-timed to ``max(5, T * f)`` frames, ``f``
+    uniform over the permille steps of the range; features and ROI frames follow the same warp (source frame
+    ``j * (T - 1) // (L - 1)``); the reference's frame drop then acts on the warped clip.  ``scale_prob`` / ``scale_range``: the
+    features (after the noise) times one factor uniform in the range.  ``roi_shift_prob`` / ``roi_shift_max`` = (dx, dy): the
+    ROI frames of a clip moved by an integer offset uniform in [-dx, dx] x [-dy, dy], edges replicated (a crop box that
+    jitters with the landmarks)."""
+    time_warp_prob: float = 0.0
+    time_warp_range: Tuple[float, float] = (0.8, 1.2)
+    scale_prob: float = 0.0
+    scale_range: Tuple[float, float] = (0.95, 1.05)
+    roi_shift_prob: float = 0.0
+    roi_shift_max: Tuple[int, int] = (0, 0)
+
+    def __post_init__(self):
+        for name in ("time_warp_prob", "scale_prob", "roi_shift_prob"):
+            p = getattr(self, name)
+            if not (isinstance(p, (int, float)) and 0.0 <= p <= 1.0):
+                raise ValueError(f"{name} must lie in [0, 1], not {p!r}")
+        for name in ("time_warp_range", "scale_range", "roi_shift_max"):
+            v = getattr(self, name)
+            if not (isinstance(v, (tuple, list)) and len(v) == 2):
+                raise ValueError(f"{name} must be a pair, not {v!r}")
+            object.__setattr__(self, name, tuple(v))
+        lo_pm, hi_pm = self.warp_permille()
+        if not 0 < lo_pm <= hi_pm <= 4000:
+            raise ValueError(f"time_warp_range must satisfy 0 < lo <= hi <= 4 (in steps of 0.001), not {self.time_warp_range!r}")
+        lo, span = self.scale_lo_span()
+        if not (np.isfinite(lo) and np.isfinite(span) and lo > 0 and self.scale_range[1] >= self.scale_range[0]):
+            raise ValueError(f"scale_range must satisfy 0 < lo <= hi, not {self.scale_range!r}")
+        mx, my = self.roi_shift_max
+        if not all(isinstance(m, (int, np.integer)) and 0 <= m < 2 ** 30 for m in (mx, my)):
+            raise ValueError(f"roi_shift_max must be two integers >= 0, not {self.roi_shift_max!r}")
+
+    @classmethod
+    def lineage(cls, **overrides) -> "AugmentPolicy":
+        """The values of inactive/train_reduced.py:103-123 (warp 0.5 / 0.8-1.2, scale 0.3 / 0.95-1.05), no ROI shift."""
+        return replace(cls(time_warp_prob=0.5, time_warp_range=(0.8, 1.2), scale_prob=0.3, scale_range=(0.95, 1.05)), **overrides)
+
+    def warp_permille(self) -> Tuple[int, int]:
+        """The warp range as the planner takes it: integers, permille."""
+        lo, hi = self.time_warp_range
+        return int(round(float(lo) * 1000)), int(round(float(hi) * 1000))
+
+    def scale_lo_span(self) -> Tuple[float, float]:
+        """The scale range as the planner takes it: low end and hi - lo, each rounded to f32 once."""
+        lo, hi = self.scale_range
+        return float(np.float32(lo)), float(np.float32(float(hi) - float(lo)))
 
 
 class DeviceClipStore:
@@ -84,6 +143,7 @@ class DeviceClipStore:
         self.n_classes_present = len(present)
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)  # set by ss_batch_plan, read by check()
         self._plan_bufs = {}
+        self._policy_bufs = {}  # batch size -> (row_scale, row_shift) of the AugmentPolicy path
 
     def __len__(self):
         return len(self.x_len)
@@ -147,7 +207,7 @@ class DeviceClipStore:
         return (torch.empty(0, mt, self.D, device=dev), torch.empty(0, dtype=torch.int64, device=dev), R,
                 torch.empty(0, dtype=torch.int64, device=dev))
 
-    def _batch_philox(self, indices, augment, seed, first_row, batch_first_row=None):
+    def _batch_philox(self, indices, augment, seed, first_row, batch_first_row=None, policy=None):
         mt, dev = self.max_t, self.device
         if isinstance(indices, torch.Tensor) and indices.is_cuda:
             if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
@@ -172,6 +232,8 @@ class DeviceClipStore:
         xmap, nmap, rmap, lens, y = bufs
         has_roi = self.R is not None
         s = L.stream()
+        if policy is not None:
+            return self._gather_policy(idx_d, B, bufs, seed, first_row, batch_first_row, policy, s)
         L.call("ss_batch_plan", idx_d.data_ptr(), B, self._x_off_d.data_ptr(), self._x_len_d.data_ptr(), L.ptr(self._r_off_d),
                L.ptr(self._r_len_d), self.y.data_ptr(), len(self), mt, int(bool(augment)), int(first_row) & _MASK64,
                int(seed) & _MASK64, NOISE_PROB, float(DROP_FRAMES_PROB), int(DROP_FRAMES_MAX), xmap.data_ptr(), nmap.data_ptr(),
@@ -196,9 +258,43 @@ class DeviceClipStore:
         X._ss_keep = (idx_d,)
         return X, lens, R, y
 
+    def _gather_policy(self, idx_d, B, bufs, seed, first_row, batch_first_row, policy, s):
+        """The three launches of a batch with an ``AugmentPolicy`` (augment is on)."""
+        mt, dev = self.max_t, self.device
+        xmap, nmap, rmap, lens, y = bufs
+        has_roi = self.R is not None
+        aug = self._policy_bufs.get(B)
+        if aug is None:
+            aug = self._policy_bufs[B] = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, 2, dtype=torch.int32, device=dev))
+        row_scale, row_shift = aug
+        (lo_pm, hi_pm), (sc_lo, sc_span), (mx, my) = policy.warp_permille(), policy.scale_lo_span(), policy.roi_shift_max
+        if has_roi and (mx >= self.roi_hw[1] or my >= self.roi_hw[0]):
+            raise ValueError("roi_shift_max %r does not fit %dx%d ROI frames" % ((mx, my), self.roi_hw[0], self.roi_hw[1]))
+        L.call("ss_batch_plan_aug", idx_d.data_ptr(), B, self._x_off_d.data_ptr(), self._x_len_d.data_ptr(), L.ptr(self._r_off_d),
+               L.ptr(self._r_len_d), self.y.data_ptr(), len(self), mt, 1, int(first_row) & _MASK64, int(seed) & _MASK64,
+               NOISE_PROB, float(DROP_FRAMES_PROB), int(DROP_FRAMES_MAX), float(policy.time_warp_prob), lo_pm, hi_pm,
+               float(policy.scale_prob), sc_lo, sc_span, float(policy.roi_shift_prob), int(mx), int(my), xmap.data_ptr(),
+               nmap.data_ptr(), rmap.data_ptr() if has_roi else None, lens.data_ptr(), y.data_ptr(), row_scale.data_ptr(),
+               row_shift.data_ptr(), self._err.data_ptr(), s)
+        first = first_row if batch_first_row is None else batch_first_row
+        ahead = int(first_row) - int(first)
+        if ahead < 0:
+            raise ValueError("batch_first_row lies behind first_row")
+        X = torch.empty(B, mt, self.D, device=dev)
+        L.call("ss_batch_gather_f32_aug", self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, nmap.data_ptr(), float(NOISE_STD),
+               philox_noise_seed(seed, first), ahead * mt * self.D, row_scale.data_ptr(), mt, X.data_ptr(), s)
+        R = None
+        if has_roi:
+            H, W = self.roi_hw
+            R = torch.empty(B, mt, H, W, device=dev, dtype=torch.uint8)
+            L.call("ss_batch_gather_u8_shift", self.R.data_ptr(), H, W, rmap.data_ptr(), B * mt, row_shift.data_ptr(), mt, int(mx),
+                   int(my), R.data_ptr(), s)
+        X._ss_keep = (idx_d,)
+        return X, lens, R, y
+
     def batch(self, indices: Sequence[int], augment: bool = False, rng: str = "device",
               generator: Optional[np.random.Generator] = None, seed: int = 0, first_row: int = 0,
-              batch_first_row: Optional[int] = None):
+              batch_first_row: Optional[int] = None, policy: Optional[AugmentPolicy] = None):
         """-> X (B,max_t,D) f32, T (B,) i64, R (B,max_t,H,W) u8 or None, y (B,) i64 -- all on the device.
 
         ``rng="philox"``: the plan is made by ``ss_batch_plan`` on the device.  ``indices`` is a device int32 tensor (a
@@ -211,9 +307,19 @@ class DeviceClipStore:
         concatenated, are bit for bit the batch a single process assembles.  ``generator`` is not used.  ``R`` is returned whenever the store holds ROI
         frames (clips without ROI get zero frames, as ``collate_fn`` does when any clip of the batch has ROI); the
         per-batch "no clip has ROI -> ``R = None``" rule needs a read-back and is left to the host modes.  ``T`` and ``y``
-        are buffers the store reuses for the next batch of the same size (safe in stream order; clone to keep them)."""
+        are buffers the store reuses for the next batch of the same size (safe in stream order; clone to keep them).
+
+        ``policy`` (``rng="philox"`` with ``augment=True`` only, ``ValueError`` otherwise): an ``AugmentPolicy``; the batch is
+        then planned and gathered by ``ss_batch_plan_aug`` / ``ss_batch_gather_f32_aug`` / ``ss_batch_gather_u8_shift``.  The
+        decisions are keyed by the row's draw index like the rest of the plan, so shards (``batch_first_row``) stay bit-equal
+        to the single-process batch.  ``None``: exactly the three launches described above."""
+        if policy is not None:
+            if not isinstance(policy, AugmentPolicy):
+                raise TypeError("policy must be an AugmentPolicy")
+            if rng != "philox" or not augment:
+                raise ValueError("an AugmentPolicy needs rng='philox' and augment=True")
         if rng == "philox":
-            return self._batch_philox(indices, augment, seed, first_row, batch_first_row)
+            return self._batch_philox(indices, augment, seed, first_row, batch_first_row, policy)
         if batch_first_row is not None:
             raise ValueError("batch_first_row belongs to rng='philox'")
         indices = list(indices)

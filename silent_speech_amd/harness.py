@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from .checkpoint import save_checkpoint
-from .device_data import DeviceClipStore
+from .device_data import AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier
 from .train import Trainer, check_class_weights, shard_range
 
@@ -285,7 +285,7 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
 def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BATCH_SIZE, patience: int = PATIENCE,
         max_t: int = 90, lr: float = 3e-4, seed: int = SEED, use_roi_if_present: bool = True, device="cuda",
         log=print, plan: str = "host", rank: int = 0, world_size: int = 1, process_group=None,
-        history: Optional[list] = None, class_weights=None) -> float:
+        history: Optional[list] = None, class_weights=None, augment_policy=None) -> float:
     """The reference's ``main()``: scan, split, train with class-balanced sampling and on-device augmentation, evaluate
     every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement.
 
@@ -313,9 +313,17 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     whole global batch to ``Trainer.step(y_global=)`` -- gathered once per epoch from the store's device label table by the
     epoch order, nothing read back -- so the weighted mean is that of the global batch whatever the world size.  The logged
     train loss stays the sum of loss x batch over the clip count, as the reference logs it (:441); the validation loss is
-    the weighted mean over the whole validation set (``evaluate``)."""
+    the weighted mean over the whole validation set (``evaluate``).
+
+    ``augment_policy``: an ``AugmentPolicy`` for the training batches (time warp, scale jitter, ROI shift, planned on the
+    device); needs ``plan="device"``.  Validation batches are never augmented.  None: the reference's two augmentations only."""
     if plan not in ("host", "device"):
         raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
+    if augment_policy is not None:
+        if not isinstance(augment_policy, AugmentPolicy):
+            raise TypeError("augment_policy must be an AugmentPolicy")
+        if plan != "device":
+            raise ValueError("augment_policy needs plan='device': the policy is drawn by the planning kernel")
     if world_size < 1 or not 0 <= rank < world_size:
         raise ValueError(f"rank {rank} is outside world_size {world_size}")
     parallel = world_size > 1 or process_group is not None
@@ -362,7 +370,7 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                 if hi > lo:
                     X, T, R, y = train_store.batch(order[lo:hi], augment=True, rng="philox", seed=seed,
                                                    first_row=epoch_base + first_row,
-                                                   batch_first_row=epoch_base + lo - lo % batch_size)
+                                                   batch_first_row=epoch_base + lo - lo % batch_size, policy=augment_policy)
                 else:
                     X, T, R, y = train_store.empty_batch()
                 # (the loss is this rank's part of the global mean: the parts of all ranks sum to it)

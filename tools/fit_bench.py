@@ -4,16 +4,24 @@ batches planned by the kernel (``rng="philox"``), with ``Trainer.step`` on a res
     python tools/fit_bench.py [--steps 200] [--windows 5] [--warmup 20]
 
 One JSON line.  Per shape (config 2: B=256, T=30, D=84, 64x64 ROI; shipped: B=16, T=90, D=180, 48x96 ROI):
-  clips_per_s.{resident, host_plan, device_plan}  median (min, max) over the windows; the three loops alternate window by window
-                                                  inside this one process, every window ends in a device synchronise
+  clips_per_s.{resident, host_plan, device_plan, device_plan_policy}
+                                                  median (min, max) over the windows; the four loops alternate window by window
+                                                  inside this one process, every window ends in a device synchronise.
+                                                  device_plan_policy: ``batch(policy=AugmentPolicy.lineage(roi_shift_prob=0.5,
+                                                  roi_shift_max=(4, 2)))`` -- time warp, scale jitter and ROI shift
+  policy_of_device_plan                           median device_plan_policy / median device_plan of this run, and device_plan's own
+                                                  (max - min) / median beside it: the yardstick is this run's device_plan loop
   clips_per_s.resident_weighted, class_weight_us  (--class-weights) the resident loop through ``Trainer(class_weights=)``, a fourth loop
                                                   in the same alternation, and what its step costs more than the unweighted one
                                                   (the one ``ss_class_weight_sum`` launch): median over the windows of the difference
                                                   in us per step between neighbouring windows
-  assemble_ms.{host_plan, device_plan}            the batch() calls alone (no step), same alternation: ms per batch
+  assemble_ms.{host_plan, device_plan, device_plan_policy}
+                                                  the batch() calls alone (no step), same alternation: ms per batch
   enqueue_ms.{host_plan, device_plan}             host wall time of one batch() call while the GPU is idle (no synchronise
                                                   inside the timed region: what the call costs the Python thread)
-  kernels_ms.{host_plan, device_plan}             HIP-event time per launch of the kernels batch() enqueues (L.PROFILE)
+  kernels_ms.{host_plan, device_plan, device_plan_policy}
+                                                  HIP-event time per launch of the kernels batch() enqueues (L.PROFILE); the policy's
+                                                  are ss_batch_plan_aug, ss_batch_gather_f32_aug and ss_batch_gather_u8_shift
   validation_ms.{evaluate, evaluate_device}       (config2 only, --eval-clips N, 0 = skip) one validation pass over N clips in batches of
                                                   B: ``harness.evaluate`` (two read-backs per batch, confusions counted on the host)
                                                   against ``harness.evaluate_device`` (``ss_eval_accum``, one read at the end);
@@ -97,6 +105,12 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         row[0] += B
         return store.batch(dev_order[i * B:(i + 1) * B], augment=True, rng="philox", seed=SEED, first_row=row[0])
 
+    policy = ss.AugmentPolicy.lineage(roi_shift_prob=0.5, roi_shift_max=(4, 2))
+
+    def policy_batch(i):
+        row[0] += B
+        return store.batch(dev_order[i * B:(i + 1) * B], augment=True, rng="philox", seed=SEED, first_row=row[0], policy=policy)
+
     def window(make_batch, step, n):
         tr = weighted if step == "weighted" else trainer
         torch.cuda.synchronize()
@@ -108,10 +122,11 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
-    loops = {"resident": (None, True), "host_plan": (host_batch, True), "device_plan": (dev_batch, True)}
+    loops = {"resident": (None, True), "host_plan": (host_batch, True), "device_plan": (dev_batch, True),
+             "device_plan_policy": (policy_batch, True)}
     if weighted is not None:
         loops = {"resident": (None, True), "resident_weighted": (None, "weighted"), **loops}
-    asm = {"host_plan": (host_batch, False), "device_plan": (dev_batch, False)}
+    asm = {"host_plan": (host_batch, False), "device_plan": (dev_batch, False), "device_plan_policy": (policy_batch, False)}
     for mk, st in list(loops.values()) + list(asm.values()):  # every shape and code path of the timed windows, warmed up
         window(mk, st, warmup)
     rate = {k: [] for k in loops}
@@ -147,7 +162,9 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         extra["class_weight_us"] = summary(extra_us, 2)
     return {**extra, "shape": dict(B=B, T=T, D=D, roi="%dx%d" % tuple(roi), classes=C),
             "clips_per_s": {k: summary(v) for k, v in rate.items()},
-            "of_resident": {k: round(med[k] / med["resident"], 4) for k in ("host_plan", "device_plan")},
+            "of_resident": {k: round(med[k] / med["resident"], 4) for k in ("host_plan", "device_plan", "device_plan_policy")},
+            "policy_of_device_plan": {"ratio": round(med["device_plan_policy"] / med["device_plan"], 4),
+                                      "device_plan_spread": round((max(rate["device_plan"]) - min(rate["device_plan"])) / med["device_plan"], 4)},
             "assemble_ms": {k: summary(v, 4) for k, v in asm_ms.items()},
             "enqueue_ms": enq, "kernels_ms": kern}
 
@@ -164,7 +181,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("fit_bench.py measures on the GPU: no device found")
     dev = torch.device("cuda")
-    out = {"metric": "clips/s of the training loop: resident batch, host-planned batches, device-planned batches",
+    out = {"metric": "clips/s of the training loop: resident batch, host-planned batches, device-planned batches, device-planned with an AugmentPolicy",
            "steps_per_window": args.steps, "windows": args.windows, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     for name in args.shapes.split(","):
         out[name] = run_shape(name, steps=args.steps, windows=args.windows, warmup=args.warmup, dev=dev, eval_clips=args.eval_clips, class_weights=args.class_weights,
