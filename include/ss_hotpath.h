@@ -264,7 +264,8 @@ int ss_colsum_f32(const float* A, int rows, int cols, int lda, float* out, ss_st
  * f32: dst (rows, D) = gathered rows + noise on the rows whose noise_map entry is >= 0 (NULL map: none):
  *      noise != NULL -> noise[noise_map[r]] (host-drawn, bit-exact with the reference's np.random.normal);
  *      noise == NULL and noise_std > 0 -> noise_std * N(0,1) from the Philox stream (seed, element index).
- * u8 : dst (rows, frame_bytes), frame_bytes a multiple of 16 (ROI frames). */
+ * u8 : dst (rows, frame_bytes), frame_bytes a multiple of 16 (ROI frames).
+ * (ss_batch_gather_f32, _at and _aug are instantiations of one kernel, ss_batch_plan and ss_batch_plan_aug of another.) */
 int ss_batch_gather_f32(const float* src, int D, const int32_t* frame_map, long rows, const float* noise,
                         const int32_t* noise_map, float noise_std, uint64_t seed, float* dst, ss_stream_t stream);
 /* ss_batch_gather_f32 with Philox noise for a batch that is a run of rows of a larger one (a data-parallel rank's shard of the

@@ -5,168 +5,113 @@
 // (/root/reference/train_model_official.py:122-204): additive feature noise (:143-145), interior frame drop
 // (:146-152, expressed as a frame map), zero padding / trimming to max_t (:93-118), stacking (:174-204).  Which
 // frames go where is a (B, max_t) int32 map, -1 = padding; the bytes never leave the GPU.
-// The two gather kernels are pure HBM streams: 16 bytes per lane, one row per wave group.  The map comes from the host
-// (rng "reference" / "device") or from the two planning kernels below them: the epoch's class-balanced sample order
+// The gathers are pure HBM streams: 16 bytes per lane, one row per wave group.  The map comes from the host
+// (rng "reference" / "device") or from the planning kernels below them: the epoch's class-balanced sample order
 // (:382-397) and the augmentation draws + maps of a batch, both on the Philox stream, nothing crossing PCIe.
+//
+// Five kernels behind the eight entry points:
+//   batch_gather_f32_kernel<HOST_NOISE, SCALE>  ss_batch_gather_f32 (<true, false> with a noise table, else <false, false>),
+//                                               ss_batch_gather_f32_at (<false, false>), ss_batch_gather_f32_aug (<false, true>)
+//   batch_gather_u8_kernel                      ss_batch_gather_u8
+//   batch_gather_u8_shift_kernel<WIDE>          ss_batch_gather_u8_shift (WIDE: W % 16 == 0)
+//   epoch_sample_kernel                         ss_epoch_sample
+//   batch_plan_kernel<POLICY>                   ss_batch_plan (<false>), ss_batch_plan_aug (<true>)
 #include "ss_common.h"
 
 namespace {
 
-// dst[r][:] = (map[r] >= 0 ? src[map[r]][:] : 0) + noise term (only on rows whose noise_map[r] >= 0):
-//   noise != NULL : noise[noise_map[r]][:]           (host-drawn noise, the reference's np.random.normal)
-//   noise == NULL : noise_std * N(0,1), Box-Muller on the Philox stream (seed, element index of dst)
-__global__ __launch_bounds__(256) void batch_gather_f32_kernel(const float* __restrict__ src, int D,
-                                                               const int32_t* __restrict__ frame_map, long rows,
-                                                               const float* __restrict__ noise,
-                                                               const int32_t* __restrict__ noise_map, float noise_std,
-                                                               uint64_t seed, float* __restrict__ dst) {
-  const long total = rows * D;
-  for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 4; q < total; q += (long)gridDim.x * 256 * 4) {
-    // D need not be a multiple of 4: walk the four elements of this 16-byte destination chunk
-    float v[4];
-    bool noisy[4];
-    long r = q / D;           // one division per 16-byte chunk, then walk
-    int d = (int)(q - r * D);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float x = 0.f;
-      noisy[e] = false;
-      if (q + e < total) {
-        const int m = frame_map[r];
-        if (m >= 0) x = src[(long)m * D + d];
-        const int nm = noise_map ? noise_map[r] : -1;
-        if (nm >= 0 && noise) x += noise[(long)nm * D + d];
-        noisy[e] = m >= 0 && nm >= 0;
-      }
-      v[e] = x;
-      if (++d == D) { d = 0; ++r; }
-    }
-    if (!noise && noise_std > 0.f && noise_map) {
-      uint32_t rnd[4];
-      const uint64_t ctr = (uint64_t)(q >> 2);
-      philox4((uint32_t)ctr, (uint32_t)(ctr >> 32), 0x6e6f6973u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
-      // two Box-Muller pairs from four uniforms in (0, 1]
-      const float u0 = ((float)rnd[0] + 1.0f) * 2.3283064e-10f, u1 = (float)rnd[1] * 2.3283064e-10f;
-      const float u2 = ((float)rnd[2] + 1.0f) * 2.3283064e-10f, u3 = (float)rnd[3] * 2.3283064e-10f;
-      const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
-      const float n[4] = {ra * __cosf(6.2831853f * u1), ra * __sinf(6.2831853f * u1), rb * __cosf(6.2831853f * u3),
-                          rb * __sinf(6.2831853f * u3)};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (noisy[e]) v[e] += noise_std * n[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (q + e < total) dst[q + e] = v[e];
-  }
-}
-
-// The Philox branch of the kernel above for a batch that is rows [first, first + rows) of a larger one (a data-parallel
-// rank's shard of the global batch): element q of dst is element noise_first + q of the larger batch's noise stream, so the
-// shards of all ranks, put together, are the batch a single process gathers, bit for bit.  noise_first need not be a
-// multiple of 4: a 16-byte chunk of dst then takes its four values from two neighbouring Philox blocks.
-__device__ __forceinline__ void gather_noise4(uint64_t ctr, uint64_t seed, float* n) {
+// Four N(0,1) values of the feature-noise stream: Philox block `ctr` under `seed`, two Box-Muller pairs from four uniforms in
+// (0, 1].  Returned by value: the callers select among named components, nothing is indexed at run time.
+__device__ __forceinline__ float4 gather_noise4(uint64_t ctr, uint64_t seed) {
   uint32_t rnd[4];
   philox4((uint32_t)ctr, (uint32_t)(ctr >> 32), 0x6e6f6973u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
   const float u0 = ((float)rnd[0] + 1.0f) * 2.3283064e-10f, u1 = (float)rnd[1] * 2.3283064e-10f;
   const float u2 = ((float)rnd[2] + 1.0f) * 2.3283064e-10f, u3 = (float)rnd[3] * 2.3283064e-10f;
   const float ra = sqrtf(-2.0f * __logf(u0)), rb = sqrtf(-2.0f * __logf(u2));
-  n[0] = ra * __cosf(6.2831853f * u1);
-  n[1] = ra * __sinf(6.2831853f * u1);
-  n[2] = rb * __cosf(6.2831853f * u3);
-  n[3] = rb * __sinf(6.2831853f * u3);
+  return float4{ra * __cosf(6.2831853f * u1), ra * __sinf(6.2831853f * u1), rb * __cosf(6.2831853f * u3),
+                rb * __sinf(6.2831853f * u3)};
 }
 
-__global__ __launch_bounds__(256) void batch_gather_f32_at_kernel(const float* __restrict__ src, int D,
-                                                                  const int32_t* __restrict__ frame_map, long rows,
-                                                                  const int32_t* __restrict__ noise_map, float noise_std,
-                                                                  uint64_t seed, uint64_t noise_first,
-                                                                  float* __restrict__ dst) {
+// The f32 gather, one template for the three entry points:
+//   dst[r][:] = ((map[r] >= 0 ? src[map[r]][:] : 0) + noise term) * scale term.
+// Noise term, HOST_NOISE (ss_batch_gather_f32 with a noise table): noise[noise_map[r]][:] on every row with noise_map[r] >= 0
+//   (host-drawn, the reference's np.random.normal); no Philox in this instantiation.
+// Noise term, !HOST_NOISE: noise_std * N(0,1) on the rows with map[r] >= 0 and noise_map[r] >= 0 (a NULL noise_map or
+//   noise_std == 0: none).  Element q of dst is element noise_first + q of the stream (seed, element index); four elements
+//   share a Philox block.  noise_first is 0 for ss_batch_gather_f32; for a batch that is rows [first, first + rows) of a
+//   larger one (a data-parallel rank's shard of the global batch; _at and _aug) it is that batch's element offset, so the shards
+//   of all ranks, put together, are the batch a single process gathers, bit for bit.  It need not be a multiple of 4: a 16-byte
+//   chunk of dst then takes its four values from two neighbouring blocks (the second one is drawn only then).
+// Scale term, SCALE (ss_batch_gather_f32_aug, the augmentation policy's scale jitter): row r of dst belongs to clip
+//   r / rows_per_clip, and x_after_noise * row_scale[clip] is one rounded product (__fmul_rn: no contraction with the noise
+//   term, so NumPy's fl(x * s) restates it).  Padding rows stay 0.  Without SCALE row_scale is never read.
+template <bool HOST_NOISE, bool SCALE>
+__global__ __launch_bounds__(256) void batch_gather_f32_kernel(const float* __restrict__ src, int D,
+                                                               const int32_t* __restrict__ frame_map, long rows,
+                                                               const float* __restrict__ noise,
+                                                               const int32_t* __restrict__ noise_map, float noise_std,
+                                                               uint64_t seed, uint64_t noise_first,
+                                                               const float* __restrict__ row_scale, int rows_per_clip,
+                                                               float* __restrict__ dst) {
   const long total = rows * D;
+  const bool philox = !HOST_NOISE && noise_map && noise_std > 0.f;
   const int shift = (int)(noise_first & 3);  // the same for every chunk
   for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 4; q < total; q += (long)gridDim.x * 256 * 4) {
-    float v[4];
-    bool noisy[4];
-    long r = q / D;
-    int d = (int)(q - r * D);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float x = 0.f;
-      noisy[e] = false;
-      if (q + e < total) {
-        const int m = frame_map[r];
-        if (m >= 0) x = src[(long)m * D + d];
-        noisy[e] = m >= 0 && noise_map[r] >= 0;
-      }
-      v[e] = x;
-      if (++d == D) { d = 0; ++r; }
-    }
-    if (noise_std > 0.f) {
-      const uint64_t ctr = (noise_first + (uint64_t)q) >> 2;
-      float n[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      gather_noise4(ctr, seed, n);
-      if (shift) gather_noise4(ctr + 1, seed, n + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        // n[shift + e] by selects: the index is not a compile-time constant, an array would go to scratch
-        const float ne = shift == 0 ? n[e] : shift == 1 ? n[e + 1] : shift == 2 ? n[e + 2] : n[e + 3];
-        if (noisy[e]) v[e] += noise_std * ne;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (q + e < total) dst[q + e] = v[e];
-  }
-}
-
-// The kernel above with a per-clip factor on every gathered element (the augmentation policy's scale jitter): row r of dst
-// belongs to clip r / rows_per_clip, and x_after_noise * row_scale[clip] is one rounded product (__fmul_rn: no contraction with
-// the noise term, so NumPy's fl(x * s) restates it).  Padding rows stay 0.
-__global__ __launch_bounds__(256) void batch_gather_f32_aug_kernel(const float* __restrict__ src, int D,
-                                                                   const int32_t* __restrict__ frame_map, long rows,
-                                                                   const int32_t* __restrict__ noise_map, float noise_std,
-                                                                   uint64_t seed, uint64_t noise_first,
-                                                                   const float* __restrict__ row_scale, int rows_per_clip,
-                                                                   float* __restrict__ dst) {
-  const long total = rows * D;
-  const int shift = (int)(noise_first & 3);
-  for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 4; q < total; q += (long)gridDim.x * 256 * 4) {
+    // D need not be a multiple of 4: walk the four elements of this 16-byte destination chunk
     float v[4], sc[4];
-    bool noisy[4];
-    long r = q / D;
+    unsigned noisy = 0;  // bit e: element e takes Philox noise
+    long r = q / D;           // one division per 16-byte chunk, then walk
     int d = (int)(q - r * D);
-    float s = row_scale[r / rows_per_clip];
+    float s = 1.0f;
+    if constexpr (SCALE) s = row_scale[r / rows_per_clip];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float x = 0.f;
-      noisy[e] = false;
       if (q + e < total) {
         const int m = frame_map[r];
         if (m >= 0) x = src[(long)m * D + d];
-        noisy[e] = m >= 0 && noise_map[r] >= 0;
+        const int nm = noise_map ? noise_map[r] : -1;
+        if constexpr (HOST_NOISE) {
+          if (nm >= 0) x += noise[(long)nm * D + d];
+        } else {
+          noisy |= (unsigned)(m >= 0 && nm >= 0) << e;
+        }
       }
       v[e] = x;
       sc[e] = s;
       if (++d == D) {
         d = 0;
         ++r;
-        if (r < rows) s = row_scale[r / rows_per_clip];
+        if constexpr (SCALE)
+          if (r < rows) s = row_scale[r / rows_per_clip];
       }
     }
-    if (noise_std > 0.f) {
+    if (philox) {
       const uint64_t ctr = (noise_first + (uint64_t)q) >> 2;
-      float n[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      gather_noise4(ctr, seed, n);
-      if (shift) gather_noise4(ctr + 1, seed, n + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float ne = shift == 0 ? n[e] : shift == 1 ? n[e + 1] : shift == 2 ? n[e + 2] : n[e + 3];
-        if (noisy[e]) v[e] += noise_std * ne;
+      auto add = [&](int e, float n) {
+        if (noisy >> e & 1) v[e] += noise_std * n;
+      };
+      // element e takes value shift + e of the eight that this block and the next one hold; this block's share is added
+      // before the next block is drawn, so the two are never live together
+      const float4 a = gather_noise4(ctr, seed);
+      switch (shift) {
+        case 0: add(0, a.x); add(1, a.y); add(2, a.z); add(3, a.w); break;
+        case 1: add(0, a.y); add(1, a.z); add(2, a.w); break;
+        case 2: add(0, a.z); add(1, a.w); break;
+        default: add(0, a.w);
+      }
+      if (shift) {
+        const float4 b = gather_noise4(ctr + 1, seed);
+        switch (shift) {
+          case 1: add(3, b.x); break;
+          case 2: add(2, b.x); add(3, b.y); break;
+          default: add(1, b.x); add(2, b.y); add(3, b.z);
+        }
       }
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (q + e < total) dst[q + e] = __fmul_rn(v[e], sc[e]);
+      if (q + e < total) dst[q + e] = SCALE ? __fmul_rn(v[e], sc[e]) : v[e];
   }
 }
 
@@ -282,80 +227,38 @@ __global__ __launch_bounds__(256) void epoch_sample_kernel(const int32_t* __rest
   indices[k] = (at >= 0 && at < n_members) ? members[at] : -1;
 }
 
-// one wave per batch row, lanes over t (every lane makes the row's few draws itself: cheaper than a broadcast)
+// What ss_batch_plan_aug takes beyond ss_batch_plan: the policy's thresholds and ranges, and where the per-clip scale factor
+// and ROI shift go
+struct PlanPolicy {
+  uint64_t warp_thr;
+  int warp_lo_pm, warp_hi_pm;
+  uint64_t scale_thr;
+  float scale_lo, scale_span;
+  uint64_t shift_thr;
+  int shift_max_x, shift_max_y;
+  float* row_scale;
+  int32_t* row_shift;
+};
+
+// The plan of a batch, one template for ss_batch_plan (POLICY false) and ss_batch_plan_aug (POLICY true).  One wave per batch
+// row, lanes over t (every lane makes the row's few draws itself: cheaper than a broadcast).  Sub-draw 0 decides noise and
+// drop, sub-draw 1 the second dropped frame.  POLICY adds the augmentation policy from sub-draws 2 (w) and 3 (s): a time warp
+// of the whole clip (features and ROI frames together; the drop then acts on the warped length Lw), a scale factor for the
+// features and an integer shift for the ROI frames.  Warped position j of a clip of T frames warped to Lw reads source frame
+// Wp(j) = j * (T - 1) / (Lw - 1) (integer division; j when Lw == T).  Without POLICY Lw == T, and neither those two Philox
+// blocks nor the warp arithmetic nor the row_scale / row_shift stores exist; with its three probabilities 0 the policy
+// instantiation writes the same plan.
+template <bool POLICY>
 __global__ __launch_bounds__(SS_WAVE) void batch_plan_kernel(
     const int32_t* __restrict__ indices, const int32_t* __restrict__ x_off, const int32_t* __restrict__ x_len,
     const int32_t* __restrict__ r_off, const int32_t* __restrict__ r_len, const int64_t* __restrict__ y, int n_clips,
     int max_t, int augment, uint64_t first_row, uint64_t seed, uint64_t noise_thr, uint64_t drop_thr, int drop_max,
-    int32_t* __restrict__ xmap, int32_t* __restrict__ nmap, int32_t* __restrict__ rmap, int64_t* __restrict__ lens,
-    int64_t* __restrict__ y_out, int32_t* __restrict__ err_flag) {
+    PlanPolicy pol, int32_t* __restrict__ xmap, int32_t* __restrict__ nmap, int32_t* __restrict__ rmap,
+    int64_t* __restrict__ lens, int64_t* __restrict__ y_out, int32_t* __restrict__ err_flag) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int clip = indices[b];
   const bool valid = clip >= 0 && clip < n_clips;  // anything else is never dereferenced: an empty row and the flag
-  int xo = 0, ro = -1, t_eff = 0, k = 0, d0 = 0, d1 = 0;
-  bool noisy = false;
-  if (valid) {
-    const int T = x_len[clip];
-    xo = x_off[clip];
-    if (augment) {
-      const uint64_t row = first_row + (uint64_t)b;
-      uint32_t r[4];
-      philox4((uint32_t)row, (uint32_t)(row >> 32), TAG_PLANNER, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-      noisy = (uint64_t)r[0] < noise_thr;
-      if (T > 12 && (uint64_t)r[1] < drop_thr) {  // interior frames only: 0 and T-1 stay (train...:148)
-        k = 1 + (int)mulhi_u32(r[2], (uint32_t)drop_max);
-        d0 = 1 + (int)mulhi_u32(r[3], (uint32_t)(T - 2));
-        if (k == 2) {  // the second one uniform over the other T-3 interior frames: every pair equally likely
-          uint32_t q[4];
-          philox4((uint32_t)row, (uint32_t)(row >> 32), TAG_PLANNER, 1u, (uint32_t)seed, (uint32_t)(seed >> 32), q);
-          int p1 = 1 + (int)mulhi_u32(q[0], (uint32_t)(T - 3));
-          p1 += (p1 >= d0);
-          d1 = p1 > d0 ? p1 : d0;
-          d0 = p1 > d0 ? d0 : p1;
-        }
-      }
-    }
-    t_eff = T - k < max_t ? T - k : max_t;  // clip_pad_trim
-    if (t_eff < 0) t_eff = 0;
-    if (r_off && r_off[clip] >= 0) {        // T_use = min(T_eff, Tr, max_t); the ROI frames are NOT dropped
-      ro = r_off[clip];
-      const int tr = r_len[clip] > 0 ? r_len[clip] : 0;
-      t_eff = t_eff < tr ? t_eff : tr;
-    }
-  }
-  for (int t = lane; t < max_t; t += SS_WAVE) {
-    const bool in = t < t_eff;
-    int s = t;
-    s += (k >= 1 && s >= d0);
-    s += (k == 2 && s >= d1);
-    const long at = (long)b * max_t + t;
-    xmap[at] = in ? xo + s : -1;
-    nmap[at] = (in && noisy) ? 0 : -1;
-    if (rmap) rmap[at] = (in && ro >= 0) ? ro + t : -1;
-  }
-  if (lane == 0) {
-    lens[b] = t_eff;
-    y_out[b] = valid ? y[clip] : 0;
-    if (!valid) atomicOr(err_flag, 1);  // (a vector atomic; the flag's owner clears it when it reads it)
-  }
-}
-
-// batch_plan_kernel with the augmentation policy: a time warp of the whole clip (features and ROI frames together), the
-// drop on the warped length, a scale factor for the features and an integer shift for the ROI frames.  Sub-draws 0 and 1 are
-// used exactly as above; the new decisions come from sub-draw 2 (w) and sub-draw 3 (s).  Warped position j of a clip of T
-// frames warped to L reads source frame Wp(j) = j * (T - 1) / (L - 1) (integer division; j when L == T).
-__global__ __launch_bounds__(SS_WAVE) void batch_plan_aug_kernel(
-    const int32_t* __restrict__ indices, const int32_t* __restrict__ x_off, const int32_t* __restrict__ x_len,
-    const int32_t* __restrict__ r_off, const int32_t* __restrict__ r_len, const int64_t* __restrict__ y, int n_clips,
-    int max_t, int augment, uint64_t first_row, uint64_t seed, uint64_t noise_thr, uint64_t drop_thr, int drop_max,
-    uint64_t warp_thr, int warp_lo_pm, int warp_hi_pm, uint64_t scale_thr, float scale_lo, float scale_span,
-    uint64_t shift_thr, int shift_max_x, int shift_max_y, int32_t* __restrict__ xmap, int32_t* __restrict__ nmap,
-    int32_t* __restrict__ rmap, int64_t* __restrict__ lens, int64_t* __restrict__ y_out, float* __restrict__ row_scale,
-    int32_t* __restrict__ row_shift, int32_t* __restrict__ err_flag) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const int clip = indices[b];
-  const bool valid = clip >= 0 && clip < n_clips;
-  int xo = 0, ro = -1, t_eff = 0, k = 0, d0 = 0, d1 = 0, T = 0, Lw = 0, n_r = 0, dx = 0, dy = 0;
+  int xo = 0, ro = -1, t_eff = 0, k = 0, d0 = 0, d1 = 0, T = 0, Lw = 0, dx = 0, dy = 0;
   float scale = 1.0f;
   bool noisy = false;
   if (valid) {
@@ -366,20 +269,31 @@ __global__ __launch_bounds__(SS_WAVE) void batch_plan_aug_kernel(
     if (augment) {
       const uint64_t row = first_row + (uint64_t)b;
       const uint32_t r0 = (uint32_t)row, r1 = (uint32_t)(row >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-      uint32_t r[4], w[4], s[4];
+      uint32_t r[4];
       philox4(r0, r1, TAG_PLANNER, 0u, k0, k1, r);
-      philox4(r0, r1, TAG_PLANNER, 2u, k0, k1, w);
-      philox4(r0, r1, TAG_PLANNER, 3u, k0, k1, s);
       noisy = (uint64_t)r[0] < noise_thr;
-      if (T > 10 && (uint64_t)w[0] < warp_thr) {
-        const long f = warp_lo_pm + (long)mulhi_u32(w[1], (uint32_t)(warp_hi_pm - warp_lo_pm + 1));
-        const long l = (long)T * f / 1000;
-        Lw = l < 5 ? 5 : l > 0x7fffffffL ? 0x7fffffff : (int)l;
+      if constexpr (POLICY) {
+        uint32_t w[4], s[4];
+        philox4(r0, r1, TAG_PLANNER, 2u, k0, k1, w);
+        philox4(r0, r1, TAG_PLANNER, 3u, k0, k1, s);
+        if (T > 10 && (uint64_t)w[0] < pol.warp_thr) {
+          const long f = pol.warp_lo_pm + (long)mulhi_u32(w[1], (uint32_t)(pol.warp_hi_pm - pol.warp_lo_pm + 1));
+          const long l = (long)T * f / 1000;
+          Lw = l < 5 ? 5 : l > 0x7fffffffL ? 0x7fffffff : (int)l;
+        }
+        if ((uint64_t)w[2] < pol.scale_thr) {
+          const float u = (float)(w[3] >> 8) * 5.9604644775390625e-8f;  // 24 bits: exact
+          scale = __fadd_rn(pol.scale_lo, __fmul_rn(pol.scale_span, u));
+        }
+        if (has_roi && (uint64_t)s[0] < pol.shift_thr) {
+          dx = (int)mulhi_u32(s[1], (uint32_t)(2 * pol.shift_max_x + 1)) - pol.shift_max_x;
+          dy = (int)mulhi_u32(s[2], (uint32_t)(2 * pol.shift_max_y + 1)) - pol.shift_max_y;
+        }
       }
-      if (Lw > 12 && (uint64_t)r[1] < drop_thr) {  // the rule above on the warped clip: positions 0 and Lw-1 stay
+      if (Lw > 12 && (uint64_t)r[1] < drop_thr) {  // interior frames only: 0 and Lw-1 stay (train...:148)
         k = 1 + (int)mulhi_u32(r[2], (uint32_t)drop_max);
         d0 = 1 + (int)mulhi_u32(r[3], (uint32_t)(Lw - 2));
-        if (k == 2) {
+        if (k == 2) {  // the second one uniform over the other Lw-3 interior frames: every pair equally likely
           uint32_t q[4];
           philox4(r0, r1, TAG_PLANNER, 1u, k0, k1, q);
           int p1 = 1 + (int)mulhi_u32(q[0], (uint32_t)(Lw - 3));
@@ -388,25 +302,18 @@ __global__ __launch_bounds__(SS_WAVE) void batch_plan_aug_kernel(
           d0 = p1 > d0 ? d0 : p1;
         }
       }
-      if ((uint64_t)w[2] < scale_thr) {
-        const float u = (float)(w[3] >> 8) * 5.9604644775390625e-8f;  // 24 bits: exact
-        scale = __fadd_rn(scale_lo, __fmul_rn(scale_span, u));
-      }
-      if (has_roi && (uint64_t)s[0] < shift_thr) {
-        dx = (int)mulhi_u32(s[1], (uint32_t)(2 * shift_max_x + 1)) - shift_max_x;
-        dy = (int)mulhi_u32(s[2], (uint32_t)(2 * shift_max_y + 1)) - shift_max_y;
-      }
     }
-    t_eff = Lw - k < max_t ? Lw - k : max_t;
+    t_eff = Lw - k < max_t ? Lw - k : max_t;  // clip_pad_trim
     if (t_eff < 0) t_eff = 0;
-    if (has_roi) {  // the warped positions whose source frame the ROI track has
+    if (has_roi) {  // T_use = min(T_eff, n_r, max_t); the ROI frames are NOT dropped
       ro = r_off[clip];
       const int tr = r_len[clip] > 0 ? r_len[clip] : 0;
-      n_r = tr >= T ? Lw : tr == 0 ? 0 : (int)(((long)tr * (Lw - 1) + T - 2) / (T - 1));
+      int n_r = tr;  // the positions the ROI track has a frame for; of a warped clip: those whose source frame it has
+      if constexpr (POLICY) n_r = tr >= T ? Lw : tr == 0 ? 0 : (int)(((long)tr * (Lw - 1) + T - 2) / (T - 1));
       t_eff = t_eff < n_r ? t_eff : n_r;
     }
   }
-  const bool warped = Lw != T;  // (then T > 10 and Lw >= 5: no division by zero)
+  const bool warped = POLICY && Lw != T;  // (then T > 10 and Lw >= 5: no division by zero)
   for (int t = lane; t < max_t; t += SS_WAVE) {
     const bool in = t < t_eff;
     int s = t;
@@ -425,12 +332,47 @@ __global__ __launch_bounds__(SS_WAVE) void batch_plan_aug_kernel(
   if (lane == 0) {
     lens[b] = t_eff;
     y_out[b] = valid ? y[clip] : 0;
-    row_scale[b] = scale;
-    row_shift[2 * b] = dx;
-    row_shift[2 * b + 1] = dy;
-    if (!valid) atomicOr(err_flag, 1);
+    if constexpr (POLICY) {
+      pol.row_scale[b] = scale;
+      pol.row_shift[2 * b] = dx;
+      pol.row_shift[2 * b + 1] = dy;
+    }
+    if (!valid) atomicOr(err_flag, 1);  // (a vector atomic; the flag's owner clears it when it reads it)
   }
 }
+
+// the launch of the f32 gather shared by its three entry points: one lane per 16-byte chunk of dst, at most 4096 workgroups
+template <bool HOST_NOISE, bool SCALE>
+int launch_gather_f32(const float* src, int D, const int32_t* frame_map, long rows, const float* noise, const int32_t* noise_map,
+                      float noise_std, uint64_t seed, uint64_t noise_first, const float* row_scale, int rows_per_clip, float* dst,
+                      ss_stream_t stream) {
+  SS_REQUIRE(src && frame_map && dst && D > 0 && rows > 0 && noise_std >= 0.f, SS_ERR_ARG);
+  SS_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 3) == 0, SS_ERR_ARG);
+  const long chunks = (rows * D + 3) / 4;
+  long blocks = (chunks + 255) / 256;
+  blocks = blocks > 4096 ? 4096 : blocks;
+  hipLaunchKernelGGL((batch_gather_f32_kernel<HOST_NOISE, SCALE>), dim3((unsigned)blocks), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), src, D, frame_map, rows, noise, noise_map, noise_std, seed, noise_first,
+                     row_scale, rows_per_clip, dst);
+  return ss_launch_status();
+}
+
+// what ss_batch_plan and ss_batch_plan_aug both refuse
+int plan_args_status(const int32_t* indices, int B, const int32_t* x_off, const int32_t* x_len, const int32_t* r_off,
+                     const int32_t* r_len, const int64_t* y, int n_clips, int max_t, double noise_prob, double drop_prob,
+                     int drop_max, const int32_t* xmap, const int32_t* nmap, const int32_t* rmap, const int64_t* lens,
+                     const int64_t* y_out, const int32_t* err_flag) {
+  SS_REQUIRE(indices && x_off && x_len && y && xmap && nmap && lens && y_out && err_flag, SS_ERR_ARG);
+  SS_REQUIRE(B > 0 && n_clips > 0 && max_t > 0, SS_ERR_ARG);
+  SS_REQUIRE((r_off == nullptr) == (r_len == nullptr) && (!r_off || rmap), SS_ERR_ARG);
+  SS_REQUIRE(noise_prob >= 0.0 && noise_prob <= 1.0 && drop_prob >= 0.0 && drop_prob <= 1.0, SS_ERR_ARG);
+  SS_REQUIRE(drop_max >= 1, SS_ERR_ARG);
+  SS_REQUIRE(drop_max <= 2, SS_ERR_UNSUPPORTED);  // the pair draw is written for one or two dropped frames
+  return SS_OK;
+}
+
+// a probability as the planner compares it with a 32-bit draw: carried in 64 bits so that p = 1 stays "always"
+uint64_t prob_threshold(double p) { return (uint64_t)(p * 4294967296.0); }
 
 }  // namespace
 
@@ -447,43 +389,28 @@ extern "C" int ss_batch_plan(const int32_t* indices, int B, const int32_t* x_off
                              const int32_t* r_len, const int64_t* y, int n_clips, int max_t, int augment, uint64_t first_row,
                              uint64_t seed, double noise_prob, double drop_prob, int drop_max, int32_t* xmap, int32_t* nmap,
                              int32_t* rmap, int64_t* lens, int64_t* y_out, int32_t* err_flag, ss_stream_t stream) {
-  SS_REQUIRE(indices && x_off && x_len && y && xmap && nmap && lens && y_out && err_flag, SS_ERR_ARG);
-  SS_REQUIRE(B > 0 && n_clips > 0 && max_t > 0, SS_ERR_ARG);
-  SS_REQUIRE((r_off == nullptr) == (r_len == nullptr) && (!r_off || rmap), SS_ERR_ARG);
-  SS_REQUIRE(noise_prob >= 0.0 && noise_prob <= 1.0 && drop_prob >= 0.0 && drop_prob <= 1.0, SS_ERR_ARG);
-  SS_REQUIRE(drop_max >= 1, SS_ERR_ARG);
-  SS_REQUIRE(drop_max <= 2, SS_ERR_UNSUPPORTED);  // the pair draw is written for one or two dropped frames
-  const uint64_t noise_thr = (uint64_t)(noise_prob * 4294967296.0), drop_thr = (uint64_t)(drop_prob * 4294967296.0);
-  hipLaunchKernelGGL(batch_plan_kernel, dim3((unsigned)B), dim3(SS_WAVE), 0, static_cast<hipStream_t>(stream), indices, x_off,
-                     x_len, r_off, r_len, y, n_clips, max_t, augment, first_row, seed, noise_thr, drop_thr, drop_max, xmap,
-                     nmap, rmap, lens, y_out, err_flag);
+  const int status = plan_args_status(indices, B, x_off, x_len, r_off, r_len, y, n_clips, max_t, noise_prob, drop_prob, drop_max,
+                                      xmap, nmap, rmap, lens, y_out, err_flag);
+  if (status != SS_OK) return status;
+  hipLaunchKernelGGL(batch_plan_kernel<false>, dim3((unsigned)B), dim3(SS_WAVE), 0, static_cast<hipStream_t>(stream), indices,
+                     x_off, x_len, r_off, r_len, y, n_clips, max_t, augment, first_row, seed, prob_threshold(noise_prob),
+                     prob_threshold(drop_prob), drop_max, PlanPolicy{}, xmap, nmap, rmap, lens, y_out, err_flag);
   return ss_launch_status();
 }
 
 extern "C" int ss_batch_gather_f32(const float* src, int D, const int32_t* frame_map, long rows, const float* noise,
                                    const int32_t* noise_map, float noise_std, uint64_t seed, float* dst,
                                    ss_stream_t stream) {
-  SS_REQUIRE(src && frame_map && dst && D > 0 && rows > 0 && noise_std >= 0.f, SS_ERR_ARG);
   SS_REQUIRE(!noise || noise_map, SS_ERR_ARG);
-  SS_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 3) == 0, SS_ERR_ARG);
-  const long chunks = (rows * D + 3) / 4;
-  long blocks = (chunks + 255) / 256;
-  blocks = blocks > 4096 ? 4096 : blocks;
-  hipLaunchKernelGGL(batch_gather_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), src, D,
-                     frame_map, rows, noise, noise_map, noise_std, seed, dst);
-  return ss_launch_status();
+  if (noise) return launch_gather_f32<true, false>(src, D, frame_map, rows, noise, noise_map, noise_std, seed, 0, nullptr, 1, dst, stream);
+  return launch_gather_f32<false, false>(src, D, frame_map, rows, nullptr, noise_map, noise_std, seed, 0, nullptr, 1, dst, stream);
 }
 
 extern "C" int ss_batch_gather_f32_at(const float* src, int D, const int32_t* frame_map, long rows, const int32_t* noise_map,
                                       float noise_std, uint64_t seed, uint64_t noise_first, float* dst, ss_stream_t stream) {
-  SS_REQUIRE(src && frame_map && noise_map && dst && D > 0 && rows > 0 && noise_std >= 0.f, SS_ERR_ARG);
-  SS_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 3) == 0, SS_ERR_ARG);
-  const long chunks = (rows * D + 3) / 4;
-  long blocks = (chunks + 255) / 256;
-  blocks = blocks > 4096 ? 4096 : blocks;
-  hipLaunchKernelGGL(batch_gather_f32_at_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), src, D,
-                     frame_map, rows, noise_map, noise_std, seed, noise_first, dst);
-  return ss_launch_status();
+  SS_REQUIRE(noise_map, SS_ERR_ARG);
+  return launch_gather_f32<false, false>(src, D, frame_map, rows, nullptr, noise_map, noise_std, seed, noise_first, nullptr, 1, dst,
+                                         stream);
 }
 
 extern "C" int ss_batch_gather_u8(const uint8_t* src, int frame_bytes, const int32_t* frame_map, long rows, uint8_t* dst,
@@ -503,38 +430,31 @@ extern "C" int ss_batch_plan_aug(const int32_t* indices, int B, const int32_t* x
                                  int warp_hi_pm, double scale_prob, float scale_lo, float scale_span, double shift_prob,
                                  int shift_max_x, int shift_max_y, int32_t* xmap, int32_t* nmap, int32_t* rmap, int64_t* lens,
                                  int64_t* y_out, float* row_scale, int32_t* row_shift, int32_t* err_flag, ss_stream_t stream) {
-  SS_REQUIRE(indices && x_off && x_len && y && xmap && nmap && lens && y_out && row_scale && row_shift && err_flag, SS_ERR_ARG);
-  SS_REQUIRE(B > 0 && n_clips > 0 && max_t > 0, SS_ERR_ARG);
-  SS_REQUIRE((r_off == nullptr) == (r_len == nullptr) && (!r_off || rmap), SS_ERR_ARG);
-  SS_REQUIRE(noise_prob >= 0.0 && noise_prob <= 1.0 && drop_prob >= 0.0 && drop_prob <= 1.0, SS_ERR_ARG);
+  SS_REQUIRE(row_scale && row_shift, SS_ERR_ARG);
   SS_REQUIRE(warp_prob >= 0.0 && warp_prob <= 1.0 && scale_prob >= 0.0 && scale_prob <= 1.0, SS_ERR_ARG);
   SS_REQUIRE(shift_prob >= 0.0 && shift_prob <= 1.0, SS_ERR_ARG);
   SS_REQUIRE(0 < warp_lo_pm && warp_lo_pm <= warp_hi_pm && warp_hi_pm <= 4000, SS_ERR_ARG);
   SS_REQUIRE(scale_lo > 0.f && scale_span >= 0.f, SS_ERR_ARG);  // (a NaN fails both)
   SS_REQUIRE(shift_max_x >= 0 && shift_max_y >= 0 && shift_max_x < (1 << 30) && shift_max_y < (1 << 30), SS_ERR_ARG);
-  SS_REQUIRE(drop_max >= 1, SS_ERR_ARG);
-  SS_REQUIRE(drop_max <= 2, SS_ERR_UNSUPPORTED);
-  const double two32 = 4294967296.0;
-  hipLaunchKernelGGL(batch_plan_aug_kernel, dim3((unsigned)B), dim3(SS_WAVE), 0, static_cast<hipStream_t>(stream), indices, x_off,
-                     x_len, r_off, r_len, y, n_clips, max_t, augment, first_row, seed, (uint64_t)(noise_prob * two32),
-                     (uint64_t)(drop_prob * two32), drop_max, (uint64_t)(warp_prob * two32), warp_lo_pm, warp_hi_pm,
-                     (uint64_t)(scale_prob * two32), scale_lo, scale_span, (uint64_t)(shift_prob * two32), shift_max_x,
-                     shift_max_y, xmap, nmap, rmap, lens, y_out, row_scale, row_shift, err_flag);
+  // (every refusal above is SS_ERR_ARG, so the shared checks may follow: their one SS_ERR_UNSUPPORTED still comes last)
+  const int status = plan_args_status(indices, B, x_off, x_len, r_off, r_len, y, n_clips, max_t, noise_prob, drop_prob, drop_max,
+                                      xmap, nmap, rmap, lens, y_out, err_flag);
+  if (status != SS_OK) return status;
+  const PlanPolicy pol{prob_threshold(warp_prob), warp_lo_pm, warp_hi_pm, prob_threshold(scale_prob), scale_lo, scale_span,
+                       prob_threshold(shift_prob), shift_max_x, shift_max_y, row_scale, row_shift};
+  hipLaunchKernelGGL(batch_plan_kernel<true>, dim3((unsigned)B), dim3(SS_WAVE), 0, static_cast<hipStream_t>(stream), indices,
+                     x_off, x_len, r_off, r_len, y, n_clips, max_t, augment, first_row, seed, prob_threshold(noise_prob),
+                     prob_threshold(drop_prob), drop_max, pol, xmap, nmap, rmap, lens, y_out, err_flag);
   return ss_launch_status();
 }
 
 extern "C" int ss_batch_gather_f32_aug(const float* src, int D, const int32_t* frame_map, long rows, const int32_t* noise_map,
                                        float noise_std, uint64_t seed, uint64_t noise_first, const float* row_scale,
                                        int rows_per_clip, float* dst, ss_stream_t stream) {
-  SS_REQUIRE(src && frame_map && noise_map && row_scale && dst && D > 0 && rows > 0 && noise_std >= 0.f, SS_ERR_ARG);
+  SS_REQUIRE(noise_map && row_scale, SS_ERR_ARG);
   SS_REQUIRE(rows_per_clip > 0 && rows % rows_per_clip == 0, SS_ERR_ARG);
-  SS_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 3) == 0, SS_ERR_ARG);
-  const long chunks = (rows * D + 3) / 4;
-  long blocks = (chunks + 255) / 256;
-  blocks = blocks > 4096 ? 4096 : blocks;
-  hipLaunchKernelGGL(batch_gather_f32_aug_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), src, D,
-                     frame_map, rows, noise_map, noise_std, seed, noise_first, row_scale, rows_per_clip, dst);
-  return ss_launch_status();
+  return launch_gather_f32<false, true>(src, D, frame_map, rows, nullptr, noise_map, noise_std, seed, noise_first, row_scale,
+                                        rows_per_clip, dst, stream);
 }
 
 extern "C" int ss_batch_gather_u8_shift(const uint8_t* src, int H, int W, const int32_t* frame_map, long rows,

@@ -22,6 +22,12 @@ Three sources of randomness:
 script dropped (inactive/train_reduced.py:103-123: time warp, scale jitter) and a per-clip shift of the ROI frames, planned and
 applied on the device as well (``ss_batch_plan_aug``, ``ss_batch_gather_f32_aug``, ``ss_batch_gather_u8_shift``;
 tests/aug_plan_ref.py restates them).  Without a policy the launches are the three above, unchanged.
+
+In ``csrc/batch.hip`` the entry points are instantiations of a few kernels: ``ss_batch_plan`` / ``ss_batch_plan_aug`` of one plan
+kernel (without / with the policy), ``ss_batch_gather_f32`` / ``_at`` / ``_aug`` of one feature gather (host-drawn or Philox noise,
+the latter from any element offset of the stream, with or without the per-clip scale).  Here ``_batch_philox`` is the one
+``rng="philox"`` path -- only its choice of entry points depends on the policy -- and ``_gather`` the one place that allocates
+``X`` and ``R`` and launches the two gathers, for every rng.
 """
 from __future__ import annotations
 
@@ -142,8 +148,7 @@ class DeviceClipStore:
         self._class_start_d = i32(np.concatenate([[0], np.cumsum([(ya == c).sum() for c in present])]))
         self.n_classes_present = len(present)
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)  # set by ss_batch_plan, read by check()
-        self._plan_bufs = {}
-        self._policy_bufs = {}  # batch size -> (row_scale, row_shift) of the AugmentPolicy path
+        self._plan_bufs = {}  # batch size -> (xmap, nmap, rmap, lens, y, row_scale, row_shift)
 
     def __len__(self):
         return len(self.x_len)
@@ -152,29 +157,21 @@ class DeviceClipStore:
     def _plan(self, indices, augment, rng, gen):
         """Per clip: kept feature frames, whether noise is added (and, in reference mode, the noise itself)."""
         keeps, noises = [], []
+        if rng == "reference":  # the reference's calls, in its order (train...:143-152)
+            uniform, n_drop, choose = random.random, lambda: random.randint(1, DROP_FRAMES_MAX), np.random.choice
+        else:
+            uniform, n_drop, choose = gen.random, lambda: int(gen.integers(1, DROP_FRAMES_MAX + 1)), gen.choice
         for i in indices:
             T = self.x_len[i]
             keep = np.arange(T)
             noise = None
             if augment:
-                if rng == "reference":  # the reference's draws, in its order (train...:143-152)
-                    if random.random() < 0.7:
-                        noise = np.random.normal(0, NOISE_STD, size=(T, self.D)).astype(np.float32)
-                    if T > 12 and random.random() < DROP_FRAMES_PROB:
-                        k = random.randint(1, DROP_FRAMES_MAX)
-                        drop = np.random.choice(np.arange(1, T - 1), size=k, replace=False)
-                        m = np.ones(T, dtype=bool)
-                        m[drop] = False
-                        keep = keep[m]
-                else:
-                    if gen.random() < 0.7:
-                        noise = True
-                    if T > 12 and gen.random() < DROP_FRAMES_PROB:
-                        k = int(gen.integers(1, DROP_FRAMES_MAX + 1))
-                        drop = gen.choice(np.arange(1, T - 1), size=k, replace=False)
-                        m = np.ones(T, dtype=bool)
-                        m[drop] = False
-                        keep = keep[m]
+                if uniform() < 0.7:
+                    noise = np.random.normal(0, NOISE_STD, size=(T, self.D)).astype(np.float32) if rng == "reference" else True
+                if T > 12 and uniform() < DROP_FRAMES_PROB:  # mask out k interior frames: 0 and T-1 stay
+                    m = np.ones(T, dtype=bool)
+                    m[choose(np.arange(1, T - 1), size=n_drop(), replace=False)] = False
+                    keep = keep[m]
             keeps.append(keep)
             noises.append(noise)
         return keeps, noises
@@ -207,6 +204,23 @@ class DeviceClipStore:
         return (torch.empty(0, mt, self.D, device=dev), torch.empty(0, dtype=torch.int64, device=dev), R,
                 torch.empty(0, dtype=torch.int64, device=dev))
 
+    def _gather(self, B, xmap, rmap, f32, shift=None):
+        """Allocates ``X`` (and ``R`` when ``rmap`` is given) and launches the two gathers through the device maps.  ``f32``: the
+        feature gather's entry point and its arguments between ``rows`` and ``dst``; ``shift``: those of ``ss_batch_gather_u8_shift``
+        between ``rows`` and ``dst`` (``None``: the plain ``ss_batch_gather_u8``)."""
+        mt, dev, s = self.max_t, self.device, L.stream()
+        X = torch.empty(B, mt, self.D, device=dev)
+        L.call(f32[0], self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, *f32[1:], X.data_ptr(), s)
+        R = None
+        if rmap is not None:
+            H, W = self.roi_hw
+            R = torch.empty(B, mt, H, W, device=dev, dtype=torch.uint8)
+            if shift is None:
+                L.call("ss_batch_gather_u8", self.R.data_ptr(), H * W, rmap.data_ptr(), B * mt, R.data_ptr(), s)
+            else:
+                L.call("ss_batch_gather_u8_shift", self.R.data_ptr(), H, W, rmap.data_ptr(), B * mt, *shift, R.data_ptr(), s)
+        return X, R
+
     def _batch_philox(self, indices, augment, seed, first_row, batch_first_row=None, policy=None):
         mt, dev = self.max_t, self.device
         if isinstance(indices, torch.Tensor) and indices.is_cuda:
@@ -221,74 +235,48 @@ class DeviceClipStore:
         B = idx_d.numel()
         if B == 0:
             raise ValueError("an empty batch")
-        # One set of map / length / label buffers per batch size, reused by every batch: the plan kernel, the two gathers
-        # and whatever consumes T and y afterwards are enqueued on L.stream() in order, so the next plan overwrites them
-        # only after this batch's readers have run.  (T and y ARE these buffers: clone them to keep them past the next call.)
-        bufs = self._plan_bufs.get(B)
-        if bufs is None:
-            maps = torch.empty(3, B, mt, dtype=torch.int32, device=dev)
-            bufs = self._plan_bufs[B] = (maps[0], maps[1], maps[2], torch.empty(B, dtype=torch.int64, device=dev),
-                                         torch.empty(B, dtype=torch.int64, device=dev))
-        xmap, nmap, rmap, lens, y = bufs
-        has_roi = self.R is not None
-        s = L.stream()
-        if policy is not None:
-            return self._gather_policy(idx_d, B, bufs, seed, first_row, batch_first_row, policy, s)
-        L.call("ss_batch_plan", idx_d.data_ptr(), B, self._x_off_d.data_ptr(), self._x_len_d.data_ptr(), L.ptr(self._r_off_d),
-               L.ptr(self._r_len_d), self.y.data_ptr(), len(self), mt, int(bool(augment)), int(first_row) & _MASK64,
-               int(seed) & _MASK64, NOISE_PROB, float(DROP_FRAMES_PROB), int(DROP_FRAMES_MAX), xmap.data_ptr(), nmap.data_ptr(),
-               rmap.data_ptr() if has_roi else None, lens.data_ptr(), y.data_ptr(), self._err.data_ptr(), s)
-        X = torch.empty(B, mt, self.D, device=dev)
-        ahead = 0 if batch_first_row is None else int(first_row) - int(batch_first_row)
-        if ahead < 0:
-            raise ValueError("batch_first_row lies behind first_row")
-        if augment and ahead:
-            # rows [ahead, ahead + B) of the batch that starts at draw batch_first_row: that batch's noise stream, from this row on
-            L.call("ss_batch_gather_f32_at", self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, nmap.data_ptr(), float(NOISE_STD),
-                   philox_noise_seed(seed, batch_first_row), ahead * mt * self.D, X.data_ptr(), s)
-        else:
-            L.call("ss_batch_gather_f32", self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, None,
-                   nmap.data_ptr() if augment else None, float(NOISE_STD) if augment else 0.0,
-                   philox_noise_seed(seed, first_row), X.data_ptr(), s)
-        R = None
-        if has_roi:
-            H, W = self.roi_hw
-            R = torch.empty(B, mt, H, W, device=dev, dtype=torch.uint8)
-            L.call("ss_batch_gather_u8", self.R.data_ptr(), H * W, rmap.data_ptr(), B * mt, R.data_ptr(), s)
-        X._ss_keep = (idx_d,)
-        return X, lens, R, y
-
-    def _gather_policy(self, idx_d, B, bufs, seed, first_row, batch_first_row, policy, s):
-        """The three launches of a batch with an ``AugmentPolicy`` (augment is on)."""
-        mt, dev = self.max_t, self.device
-        xmap, nmap, rmap, lens, y = bufs
-        has_roi = self.R is not None
-        aug = self._policy_bufs.get(B)
-        if aug is None:
-            aug = self._policy_bufs[B] = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, 2, dtype=torch.int32, device=dev))
-        row_scale, row_shift = aug
-        (lo_pm, hi_pm), (sc_lo, sc_span), (mx, my) = policy.warp_permille(), policy.scale_lo_span(), policy.roi_shift_max
-        if has_roi and (mx >= self.roi_hw[1] or my >= self.roi_hw[0]):
-            raise ValueError("roi_shift_max %r does not fit %dx%d ROI frames" % ((mx, my), self.roi_hw[0], self.roi_hw[1]))
-        L.call("ss_batch_plan_aug", idx_d.data_ptr(), B, self._x_off_d.data_ptr(), self._x_len_d.data_ptr(), L.ptr(self._r_off_d),
-               L.ptr(self._r_len_d), self.y.data_ptr(), len(self), mt, 1, int(first_row) & _MASK64, int(seed) & _MASK64,
-               NOISE_PROB, float(DROP_FRAMES_PROB), int(DROP_FRAMES_MAX), float(policy.time_warp_prob), lo_pm, hi_pm,
-               float(policy.scale_prob), sc_lo, sc_span, float(policy.roi_shift_prob), int(mx), int(my), xmap.data_ptr(),
-               nmap.data_ptr(), rmap.data_ptr() if has_roi else None, lens.data_ptr(), y.data_ptr(), row_scale.data_ptr(),
-               row_shift.data_ptr(), self._err.data_ptr(), s)
+        # rows [ahead, ahead + B) of the batch that starts at draw ``first``: that batch's noise stream, from this row on
         first = first_row if batch_first_row is None else batch_first_row
         ahead = int(first_row) - int(first)
         if ahead < 0:
             raise ValueError("batch_first_row lies behind first_row")
-        X = torch.empty(B, mt, self.D, device=dev)
-        L.call("ss_batch_gather_f32_aug", self.X.data_ptr(), self.D, xmap.data_ptr(), B * mt, nmap.data_ptr(), float(NOISE_STD),
-               philox_noise_seed(seed, first), ahead * mt * self.D, row_scale.data_ptr(), mt, X.data_ptr(), s)
-        R = None
-        if has_roi:
-            H, W = self.roi_hw
-            R = torch.empty(B, mt, H, W, device=dev, dtype=torch.uint8)
-            L.call("ss_batch_gather_u8_shift", self.R.data_ptr(), H, W, rmap.data_ptr(), B * mt, row_shift.data_ptr(), mt, int(mx),
-                   int(my), R.data_ptr(), s)
+        noise_seed, noise_first = philox_noise_seed(seed, first), ahead * mt * self.D
+        # One set of map / length / label buffers (and the policy's per-clip scale and shift) per batch size, reused by every
+        # batch: the plan kernel, the two gathers and whatever consumes T and y afterwards are enqueued on L.stream() in order,
+        # so the next plan overwrites them only after this batch's readers have run.  (T and y ARE these buffers: clone them to
+        # keep them past the next call.)
+        bufs = self._plan_bufs.get(B)
+        if bufs is None:
+            maps = torch.empty(3, B, mt, dtype=torch.int32, device=dev)
+            bufs = self._plan_bufs[B] = (maps[0], maps[1], maps[2], torch.empty(B, dtype=torch.int64, device=dev),
+                                         torch.empty(B, dtype=torch.int64, device=dev),
+                                         torch.empty(B, dtype=torch.float32, device=dev),
+                                         torch.empty(B, 2, dtype=torch.int32, device=dev))
+        xmap, nmap, rmap, lens, y, row_scale, row_shift = bufs
+        if self.R is None:
+            rmap = None
+        s = L.stream()
+        head = (idx_d.data_ptr(), B, self._x_off_d.data_ptr(), self._x_len_d.data_ptr(), L.ptr(self._r_off_d), L.ptr(self._r_len_d),
+                self.y.data_ptr(), len(self), mt, int(bool(augment)), int(first_row) & _MASK64, int(seed) & _MASK64, NOISE_PROB,
+                float(DROP_FRAMES_PROB), int(DROP_FRAMES_MAX))
+        outs = (xmap.data_ptr(), nmap.data_ptr(), L.ptr(rmap), lens.data_ptr(), y.data_ptr())
+        if policy is None:
+            L.call("ss_batch_plan", *head, *outs, self._err.data_ptr(), s)
+            if augment and ahead:
+                f32 = ("ss_batch_gather_f32_at", nmap.data_ptr(), float(NOISE_STD), noise_seed, noise_first)
+            else:
+                f32 = ("ss_batch_gather_f32", None, nmap.data_ptr() if augment else None, float(NOISE_STD) if augment else 0.0, noise_seed)
+            shift = None
+        else:
+            (lo_pm, hi_pm), (sc_lo, sc_span), (mx, my) = policy.warp_permille(), policy.scale_lo_span(), policy.roi_shift_max
+            if rmap is not None and (mx >= self.roi_hw[1] or my >= self.roi_hw[0]):
+                raise ValueError("roi_shift_max %r does not fit %dx%d ROI frames" % ((mx, my), self.roi_hw[0], self.roi_hw[1]))
+            L.call("ss_batch_plan_aug", *head, float(policy.time_warp_prob), lo_pm, hi_pm, float(policy.scale_prob), sc_lo, sc_span,
+                   float(policy.roi_shift_prob), int(mx), int(my), *outs, row_scale.data_ptr(), row_shift.data_ptr(),
+                   self._err.data_ptr(), s)
+            f32 = ("ss_batch_gather_f32_aug", nmap.data_ptr(), float(NOISE_STD), noise_seed, noise_first, row_scale.data_ptr(), mt)
+            shift = (row_shift.data_ptr(), mt, int(mx), int(my))
+        X, R = self._gather(B, xmap, rmap, f32, shift)
         X._ss_keep = (idx_d,)
         return X, lens, R, y
 
@@ -351,19 +339,14 @@ class DeviceClipStore:
             lens[b] = t_eff
         dev = self.device
         xmap_d, nmap_d = torch.from_numpy(xmap).to(dev), torch.from_numpy(nmap).to(dev)
-        X = torch.empty(B, mt, self.D, device=dev)
+        rmap_d = torch.from_numpy(rmap).to(dev) if any_roi else None
         noise_d = torch.from_numpy(np.concatenate(host_noise, 0)).to(dev) if host_noise else None
         use_noise = augment and (noise_d is not None or rng != "reference")
-        L.call("ss_batch_gather_f32", self.X.data_ptr(), self.D, xmap_d.data_ptr(), B * mt, L.ptr(noise_d),
-               nmap_d.data_ptr() if use_noise else None, float(NOISE_STD) if (use_noise and noise_d is None) else 0.0,
-               int(gen.integers(0, 2 ** 62)) if rng != "reference" else 0, X.data_ptr(), L.stream())
-        R = None
-        if any_roi:
-            H, W = self.roi_hw
-            rmap_d = torch.from_numpy(rmap).to(dev)
-            R = torch.empty(B, mt, H, W, device=dev, dtype=torch.uint8)
-            L.call("ss_batch_gather_u8", self.R.data_ptr(), H * W, rmap_d.data_ptr(), B * mt, R.data_ptr(), L.stream())
-            # keep the maps alive until the launches have consumed them
-            R._ss_keep = (rmap_d,)
+        X, R = self._gather(B, xmap_d, rmap_d, ("ss_batch_gather_f32", L.ptr(noise_d), nmap_d.data_ptr() if use_noise else None,
+                                                float(NOISE_STD) if (use_noise and noise_d is None) else 0.0,
+                                                int(gen.integers(0, 2 ** 62)) if rng != "reference" else 0))
+        # keep the maps alive until the launches have consumed them
         X._ss_keep = (xmap_d, nmap_d, noise_d)
+        if R is not None:
+            R._ss_keep = (rmap_d,)
         return X, torch.from_numpy(lens).to(dev), R, self.y[torch.as_tensor(indices, device=dev)]

@@ -135,6 +135,48 @@ def test_epoch_sample_equals_the_restatement(L):
     assert torch.equal(whole[600:], part)
 
 
+def test_noise_stream_from_every_offset_equals_the_whole_gather(L):
+    """C ABI only: ss_batch_gather_f32_at and ss_batch_gather_f32_aug on rows [r0, 12) of a 12-row gather, noise_first = r0 * D,
+    against the rows of ss_batch_gather_f32 (Philox noise) over all 12 -- bit for bit, for every r0.  D = 7 makes noise_first & 3
+    take all four values (the shard tests use D = 10: only even offsets), so a destination chunk takes its four normals from
+    one Philox block or from two neighbouring ones at every split.  The scale of _aug is one rounded product on top."""
+    D, rows, std, seed = 7, 12, 0.01, 0xF23456789ABCDEF1
+    rng = np.random.default_rng(7)
+    src = rng.normal(size=(9, D)).astype(np.float32)
+    fmap = np.array([0, 3, -1, 8, 2, 2, 5, -1, 1, 7, 4, 6], np.int32)
+    nmap = np.array([0, 0, 0, -1, 0, -1, 0, 0, 0, 0, -1, 0], np.int32)
+    scale = (0.9 + 0.02 * np.arange(rows)).astype(np.float32)
+    assert (fmap < 0).sum() == 2 and (nmap < 0).any() and [(r0 * D) & 3 for r0 in range(4)] == [0, 3, 2, 1]
+    src_d, fmap_d, nmap_d = torch.from_numpy(src).cuda(), i32(fmap), i32(nmap)
+    ones_d, scale_d = torch.ones(rows, device="cuda"), torch.from_numpy(scale).cuda()
+
+    def bits(t):
+        sync()
+        return t.cpu().numpy().view(np.uint32)
+
+    whole_d = torch.full((rows, D), 7.0, device="cuda")
+    L.call("ss_batch_gather_f32", src_d.data_ptr(), D, fmap_d.data_ptr(), rows, None, nmap_d.data_ptr(), std, seed,
+           whole_d.data_ptr(), L.stream())
+    sync()
+    whole = whole_d.cpu().numpy()
+    noisy = (fmap >= 0) & (nmap >= 0)
+    plain = np.where(fmap[:, None] >= 0, src[np.maximum(fmap, 0)], np.float32(0))
+    assert all(np.array_equal(whole[r], plain[r]) != noisy[r] for r in range(rows))  # noise exactly where both maps say so
+    for r0 in range(rows):
+        n = rows - r0
+        want = whole[r0:].view(np.uint32)
+        head = (src_d.data_ptr(), D, fmap_d[r0:].data_ptr(), n, nmap_d[r0:].data_ptr(), std, seed, r0 * D)
+        out = torch.full((n, D), 7.0, device="cuda")  # poisoned: every element must be written
+        L.call("ss_batch_gather_f32_at", *head, out.data_ptr(), L.stream())
+        assert np.array_equal(bits(out), want), r0
+        out = torch.full((n, D), 7.0, device="cuda")
+        L.call("ss_batch_gather_f32_aug", *head, ones_d.data_ptr(), 1, out.data_ptr(), L.stream())
+        assert np.array_equal(bits(out), want), r0
+        out = torch.full((n, D), 7.0, device="cuda")
+        L.call("ss_batch_gather_f32_aug", *head, scale_d[r0:].data_ptr(), 1, out.data_ptr(), L.stream())
+        assert np.array_equal(bits(out), np.float32(whole[r0:] * scale[r0:, None]).view(np.uint32)), r0
+
+
 def golden_store(tmp_path):
     from test_host_formats import _golden_clips
     import silent_speech_amd as ss
