@@ -651,6 +651,17 @@ int ss_sumsq_f32(const float* x, long n, float* sumsq, ss_stream_t stream);
 int ss_adam_clip(float* p, const float* g, float* m, float* v, long n, const float* sumsq, float grad_scale,
                  float max_norm, float lr, float beta1, float beta2, float eps, int step, ss_stream_t stream);
 
+/* ss_adam_clip with an exponential moving average of the weights in the same pass: after p, m, v are updated exactly as
+ * ss_adam_clip updates them (the same bits for the same inputs), ema[q] = ema_decay * ema[q] + (1 - ema_decay) * p[q] with the
+ * p[q] just written; 1 - ema_decay is taken once, in f32.  0 <= ema_decay < 1 (0: ema becomes p).  ema (n) must not overlap p;
+ * p, g, m, v, ema 16-byte aligned.  SS_ERR_ARG otherwise, and nothing is written. */
+int ss_adam_clip_ema(float* p, const float* g, float* m, float* v, float* ema, long n, const float* sumsq, float grad_scale,
+                     float max_norm, float lr, float beta1, float beta2, float eps, int step, float ema_decay, ss_stream_t stream);
+
+/* exchanges the contents of two f32 buffers of n elements in place (the weights and their average, Trainer.ema_weights).
+ * Both 16-byte aligned; ranges that overlap are SS_ERR_ARG. */
+int ss_swap_f32(float* a, float* b, long n, ss_stream_t stream);
+
 /* strided row copy dst[r*ld_dst + c] = src[r*ld_src + c], c < cols (places X into Z, train_model_official.py:297) */
 int ss_copy_rows_f32(const float* src, int ld_src, float* dst, int ld_dst, int rows, int cols, ss_stream_t stream);
 

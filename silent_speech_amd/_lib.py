@@ -118,6 +118,8 @@ SIGNATURES = {
     "ss_softmax_topk": [_vp, _i, _i, _i, _vp, _vp, _vp],
     "ss_sumsq_f32": [_vp, _l, _vp, _vp],
     "ss_adam_clip": [_vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _vp],
+    "ss_adam_clip_ema": [_vp, _vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _vp],
+    "ss_swap_f32": [_vp, _vp, _l, _vp],
     "ss_copy_rows_f32": [_vp, _i, _vp, _i, _i, _i, _vp],
 }
 _RESTYPES = {"ss_status_string": C.c_char_p}

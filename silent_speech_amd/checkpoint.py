@@ -3,10 +3,15 @@
 Writer: the dict of /root/reference/train_model_official.py:489-500.  Reader: ``load_classifier`` of
 /root/reference/live_infer_official.py:198-221 (accepts the optional ``gru_layers`` key, hard-codes roi_emb=32 and
 hidden=192 like the reference).  ``topk_from_logits``: live_infer_official.py:223-226.
+
+The train-state file of ``harness.fit(state_path=)`` is a format of this project (the reference cannot resume): written
+atomically by ``save_train_state``, read by ``load_train_state`` with ``weights_only=True``; ``fingerprint_difference`` names the
+first setting in which a saved run and the resuming call disagree.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -37,6 +42,58 @@ def load_classifier(path: str, device="cuda", roi_standardize: bool = True):
     model.load_state_dict(ckpt["model"])
     model.to(device).eval()
     return model, ckpt["id_to_label"], max_t, use_roi
+
+
+TRAIN_STATE_FORMAT = 1
+# the order in which a resuming ``fit`` compares the fingerprint of the saved run with its own (the first difference is named)
+FINGERPRINT_FIELDS = ("seed", "batch_size", "world_size", "max_t", "lr", "labels", "x_dim", "use_roi", "n_train", "n_val",
+                      "class_weights", "augment_policy", "ema_decay")
+
+
+def _plain(v):
+    """Tensors to the CPU, tuples to lists, recursively: what ``torch.load(weights_only=True)`` reads back unchanged."""
+    if isinstance(v, torch.Tensor):
+        return v.detach().cpu()
+    if isinstance(v, dict):
+        return {k: _plain(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_plain(x) for x in v]
+    return v
+
+
+def save_train_state(path: str, state: dict) -> None:
+    """``torch.save`` of ``state`` (tensors, numbers, strings, lists, dicts, None) to ``path``, atomically: the bytes go to a
+    temporary name in the same directory and ``os.replace`` puts the finished file in place, so a writer that dies midway
+    leaves the previous file as it was."""
+    tmp = f"{path}.tmp.{os.getpid()}"
+    try:
+        with open(tmp, "wb") as f:
+            torch.save(_plain(state), f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def load_train_state(path: str) -> dict:
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(state, dict) or state.get("format") != TRAIN_STATE_FORMAT:
+        raise ValueError(f"{path} is not a train-state file of format {TRAIN_STATE_FORMAT}")
+    return state
+
+
+def fingerprint_difference(saved: dict, current: dict) -> Optional[str]:
+    """The first field of ``FINGERPRINT_FIELDS`` (then any other key, sorted) whose values differ between the two
+    fingerprints, or None.  Pure host code: values are numbers, strings, None, lists and dicts of these."""
+    rest = sorted((set(saved) | set(current)) - set(FINGERPRINT_FIELDS))
+    missing = object()
+    for name in list(FINGERPRINT_FIELDS) + rest:
+        if _plain(saved.get(name, missing)) != _plain(current.get(name, missing)):
+            return name
+    return None
 
 
 def softmax_topk(logits: torch.Tensor, k: int = 3) -> Tuple[torch.Tensor, torch.Tensor]:

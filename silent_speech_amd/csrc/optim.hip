@@ -45,17 +45,89 @@ struct AdamParams {
   float grad_scale, max_norm, step_size, beta1, beta2, eps, inv_sqrt_bc2;
 };
 
-__global__ __launch_bounds__(256) void adam_clip_kernel(AdamParams a) {
+// The clip coefficient and one element of clip + Adam, written once for adam_clip_kernel and adam_clip_ema_kernel: the same
+// expressions, hence the same contractions, hence the same bits of p, m, v from both entry points.
+__device__ __forceinline__ float adam_clip_coef(const AdamParams& a) {
   const float total = sqrtf(a.sumsq[0]) * a.grad_scale;
-  const float coef = a.grad_scale * fminf(1.0f, a.max_norm / (total + 1e-6f));
+  return a.grad_scale * fminf(1.0f, a.max_norm / (total + 1e-6f));
+}
+
+// (two halves, so that adam_clip_kernel can go on reading p behind its stores of m and v, as it always has)
+__device__ __forceinline__ float adam_clip_moments(const AdamParams& a, float coef, float g_raw, float& m, float& v) {
+  const float g = g_raw * coef;
+  m = a.beta1 * m + (1.0f - a.beta1) * g;
+  v = a.beta2 * v + (1.0f - a.beta2) * g * g;
+  const float denom = sqrtf(v) * a.inv_sqrt_bc2 + a.eps;
+  return m / denom;
+}
+__device__ __forceinline__ float adam_clip_apply(const AdamParams& a, float p, float quot) { return p - a.step_size * quot; }
+
+__global__ __launch_bounds__(256) void adam_clip_kernel(AdamParams a) {
+  const float coef = adam_clip_coef(a);
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < a.n; q += (long)gridDim.x * 256) {
-    const float g = a.g[q] * coef;
-    const float m = a.beta1 * a.m[q] + (1.0f - a.beta1) * g;
-    const float v = a.beta2 * a.v[q] + (1.0f - a.beta2) * g * g;
+    float m = a.m[q], v = a.v[q];
+    const float quot = adam_clip_moments(a, coef, a.g[q], m, v);
     a.m[q] = m;
     a.v[q] = v;
-    const float denom = sqrtf(v) * a.inv_sqrt_bc2 + a.eps;
-    a.p[q] -= a.step_size * (m / denom);
+    a.p[q] = adam_clip_apply(a, a.p[q], quot);
+  }
+}
+
+// adam_clip_kernel + the weight average ema = d * ema + (1 - d) * p_new in the same pass: five 16-byte loads and four 16-byte
+// stores per lane and iteration (nine streams of n floats against seven), the n & 3 last elements by block 0.  omd = 1 - d,
+// taken once on the host in f32.  d = 0: 0 * ema + 1 * p_new, p_new exactly.
+__device__ __forceinline__ float ema_elem(float d, float omd, float ema, float p_new) { return d * ema + omd * p_new; }
+
+__global__ __launch_bounds__(256) void adam_clip_ema_kernel(AdamParams a, float* ema, float d, float omd) {
+  const float coef = adam_clip_coef(a);
+  const long n4 = a.n >> 2;
+  f32x4* p4 = reinterpret_cast<f32x4*>(a.p);
+  const f32x4* g4 = reinterpret_cast<const f32x4*>(a.g);
+  f32x4* m4 = reinterpret_cast<f32x4*>(a.m);
+  f32x4* v4 = reinterpret_cast<f32x4*>(a.v);
+  f32x4* e4 = reinterpret_cast<f32x4*>(ema);
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long)gridDim.x * 256) {
+    f32x4 p = p4[q], m = m4[q], v = v4[q], e = e4[q];
+    const f32x4 g = g4[q];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float mk = m[k], vk = v[k];
+      p[k] = adam_clip_apply(a, p[k], adam_clip_moments(a, coef, g[k], mk, vk));
+      m[k] = mk;
+      v[k] = vk;
+      e[k] = ema_elem(d, omd, e[k], p[k]);
+    }
+    m4[q] = m;
+    v4[q] = v;
+    p4[q] = p;
+    e4[q] = e;
+  }
+  if (blockIdx.x == 0 && (long)threadIdx.x < (a.n & 3)) {
+    const long q = (n4 << 2) + threadIdx.x;
+    float m = a.m[q], v = a.v[q];
+    const float p = adam_clip_apply(a, a.p[q], adam_clip_moments(a, coef, a.g[q], m, v));
+    a.m[q] = m;
+    a.v[q] = v;
+    a.p[q] = p;
+    ema[q] = ema_elem(d, omd, ema[q], p);
+  }
+}
+
+// a <-> b, two disjoint 16-byte aligned buffers of n floats: 16-byte lanes, the n & 3 last elements by block 0
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+  const long n4 = n >> 2;
+  f32x4* a4 = reinterpret_cast<f32x4*>(a);
+  f32x4* b4 = reinterpret_cast<f32x4*>(b);
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n4; q += (long)gridDim.x * 256) {
+    const f32x4 x = a4[q], y = b4[q];
+    a4[q] = y;
+    b4[q] = x;
+  }
+  if (blockIdx.x == 0 && (long)threadIdx.x < (n & 3)) {
+    const long q = (n4 << 2) + threadIdx.x;
+    const float x = a[q], y = b[q];
+    a[q] = y;
+    b[q] = x;
   }
 }
 
@@ -245,20 +317,57 @@ extern "C" int ss_sumsq_f32(const float* x, long n, float* sumsq, ss_stream_t st
   return ss_launch_status();
 }
 
-extern "C" int ss_adam_clip(float* p, const float* g, float* m, float* v, long n, const float* sumsq,
-                            float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int step,
-                            ss_stream_t stream) {
-  SS_REQUIRE(p && g && m && v && sumsq && n > 0 && step >= 1, SS_ERR_ARG);
-  AdamParams a;
+static void adam_params(AdamParams& a, float* p, const float* g, float* m, float* v, long n, const float* sumsq, float grad_scale,
+                        float max_norm, float lr, float beta1, float beta2, float eps, int step) {
   a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.sumsq = sumsq;
   a.grad_scale = grad_scale; a.max_norm = max_norm;
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   a.step_size = (float)((double)lr / bc1);
   a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+}
+
+extern "C" int ss_adam_clip(float* p, const float* g, float* m, float* v, long n, const float* sumsq,
+                            float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int step,
+                            ss_stream_t stream) {
+  SS_REQUIRE(p && g && m && v && sumsq && n > 0 && step >= 1, SS_ERR_ARG);
+  AdamParams a;
+  adam_params(a, p, g, m, v, n, sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, step);
   int blocks = (int)((n + 255) / 256);
   blocks = blocks > 2048 ? 2048 : blocks;
   hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return ss_launch_status();
+}
+
+static bool disjoint_f32(const float* a, const float* b, long n) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * 4;
+  return x + bytes <= y || y + bytes <= x;
+}
+
+extern "C" int ss_adam_clip_ema(float* p, const float* g, float* m, float* v, float* ema, long n, const float* sumsq,
+                                float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int step,
+                                float ema_decay, ss_stream_t stream) {
+  SS_REQUIRE(p && g && m && v && ema && sumsq && n > 0 && step >= 1, SS_ERR_ARG);
+  SS_REQUIRE(ema_decay >= 0.0f && ema_decay < 1.0f, SS_ERR_ARG);  // (a NaN fails both)
+  SS_REQUIRE(ema != p && disjoint_f32(ema, p, n), SS_ERR_ARG);
+  SS_REQUIRE(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+               reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(ema)) & 15) == 0, SS_ERR_ARG);
+  AdamParams a;
+  adam_params(a, p, g, m, v, n, sumsq, grad_scale, max_norm, lr, beta1, beta2, eps, step);
+  long blocks = ((n >> 2) + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  hipLaunchKernelGGL(adam_clip_ema_kernel, dim3((int)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, ema, ema_decay,
+                     1.0f - ema_decay);
+  return ss_launch_status();
+}
+
+extern "C" int ss_swap_f32(float* a, float* b, long n, ss_stream_t stream) {
+  SS_REQUIRE(a && b && n > 0, SS_ERR_ARG);
+  SS_REQUIRE(disjoint_f32(a, b, n), SS_ERR_ARG);
+  SS_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0, SS_ERR_ARG);
+  long blocks = ((n >> 2) + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+  hipLaunchKernelGGL(swap_kernel, dim3((int)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, b, n);
   return ss_launch_status();
 }
 

@@ -22,6 +22,7 @@ order and plans every batch on the device (``sample_epoch``, ``batch(rng="philox
 from __future__ import annotations
 
 import collections
+import contextlib
 import dataclasses
 import glob
 import os
@@ -31,7 +32,8 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .checkpoint import save_checkpoint
+from .checkpoint import (TRAIN_STATE_FORMAT, fingerprint_difference, load_train_state, save_checkpoint,
+                         save_train_state)
 from .device_data import AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier
 from .train import Trainer, check_class_weights, shard_range
@@ -282,10 +284,24 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
                       extra=host[4:4 + n_extra].copy() if n_extra else None, loss_sum=tot_loss, weight_sum=weight_sum)
 
 
+def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_roi, n_train, n_val, class_weights,
+                    augment_policy, ema_decay) -> dict:
+    """What a resumable ``fit`` run depends on, as plain values (``checkpoint.FINGERPRINT_FIELDS``): a train-state file is
+    resumed only by a call whose fingerprint equals the saved one.  ``epochs`` and ``patience`` are not part of it: a run may be
+    resumed to train longer."""
+    return dict(seed=int(seed), batch_size=int(batch_size), world_size=int(world_size), max_t=int(max_t), lr=float(lr),
+                labels=[str(lab) for lab in labels], x_dim=int(x_dim), use_roi=bool(use_roi), n_train=int(n_train),
+                n_val=int(n_val), class_weights=None if class_weights is None else [float(w) for w in class_weights],
+                augment_policy=None if augment_policy is None else {k: (list(v) if isinstance(v, tuple) else v) for k, v in
+                                                                    dataclasses.asdict(augment_policy).items()},
+                ema_decay=None if ema_decay is None else float(ema_decay))
+
+
 def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BATCH_SIZE, patience: int = PATIENCE,
         max_t: int = 90, lr: float = 3e-4, seed: int = SEED, use_roi_if_present: bool = True, device="cuda",
         log=print, plan: str = "host", rank: int = 0, world_size: int = 1, process_group=None,
-        history: Optional[list] = None, class_weights=None, augment_policy=None) -> float:
+        history: Optional[list] = None, class_weights=None, augment_policy=None, ema_decay: Optional[float] = None,
+        state_path: Optional[str] = None, resume: bool = False) -> float:
     """The reference's ``main()``: scan, split, train with class-balanced sampling and on-device augmentation, evaluate
     every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement.
 
@@ -316,7 +332,22 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     the weighted mean over the whole validation set (``evaluate``).
 
     ``augment_policy``: an ``AugmentPolicy`` for the training batches (time warp, scale jitter, ROI shift, planned on the
-    device); needs ``plan="device"``.  Validation batches are never augmented.  None: the reference's two augmentations only."""
+    device); needs ``plan="device"``.  Validation batches are never augmented.  None: the reference's two augmentations only.
+
+    ``ema_decay`` (``d`` in [0, 1); the reference has no averaged model): ``Trainer(ema_decay=d)`` keeps an exponential moving
+    average of the weights inside the Adam launch.  Every epoch's validation, under both plans, runs on the AVERAGED weights
+    (``trainer.ema_weights()``), the checkpoint written on improvement holds them -- in the reference schema, so
+    ``load_classifier`` and the reference's live script read it unchanged -- and early stopping follows their accuracy.  The
+    train loss and accuracy stay those of the raw weights, which are what the steps run on.
+
+    ``state_path`` (needs ``plan="device"``, where an epoch is a pure function of (seed, draw index) and the dropout seeds one
+    of the step count): after every epoch rank 0 writes one train-state file there, atomically (``save_train_state``): the raw
+    ``model.state_dict()``, ``trainer.state_dict()``, the epoch just finished, ``best``, ``bad``, whether the run has stopped
+    early, and ``run_fingerprint``.  ``resume=True`` with such a file: every rank loads it, a fingerprint that differs from this
+    call's raises ``ValueError`` naming the first differing field, model, trainer, ``best`` and ``bad`` are restored and the run
+    continues at the next epoch -- up to the order of the float atomics it is the uninterrupted run.  A saved run that had
+    reached ``epochs`` or had stopped early returns ``best`` without training.  ``resume=True`` without a file starts fresh.
+    ``history`` gets only the epochs this call ran."""
     if plan not in ("host", "device"):
         raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
     if augment_policy is not None:
@@ -329,6 +360,11 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     parallel = world_size > 1 or process_group is not None
     if parallel and plan != "device":
         raise ValueError("data-parallel fit needs plan='device': only there is an epoch a pure function of (seed, draw index)")
+    if (state_path is not None or resume) and plan != "device":
+        raise ValueError("state_path / resume need plan='device': the sample order of plan='host' lives in the host's global "
+                         "random state, which is not saved")
+    if resume and state_path is None:
+        raise ValueError("resume=True needs state_path")
     if rank != 0:
         log = lambda *a, **k: None  # noqa: E731  (rank 0 alone logs)
     random.seed(seed)
@@ -339,23 +375,47 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
         class_weights = check_class_weights(class_weights, len(info["uniq"]))  # (before anything is uploaded)
     train_files, val_files = split_by_label(info["files"], info["labels"], VAL_FRAC, seed=seed)
     use_roi = use_roi_if_present and info["has_roi"] > 0
-    train_store = DeviceClipStore(train_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
-    val_store = DeviceClipStore(val_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
     train_labels = [str(np.load(f, allow_pickle=True)["label"]) for f in train_files]
     if isinstance(class_weights, str):
         class_weights = check_class_weights(balanced_class_weights(train_labels, info["id_to_label"]), len(info["uniq"]))
+    saved, fingerprint = None, None
+    if state_path is not None:
+        fingerprint = run_fingerprint(seed, batch_size, world_size, max_t, lr, info["uniq"], info["x_dim"], use_roi,
+                                      len(train_files), len(val_files), class_weights, augment_policy, ema_decay)
+        if resume and os.path.exists(state_path):
+            saved = load_train_state(state_path)
+            field = fingerprint_difference(saved["fingerprint"], fingerprint)
+            if field is not None:
+                raise ValueError(f"cannot resume from {state_path}: {field} differs (saved {saved['fingerprint'].get(field)!r}, "
+                                 f"this call {fingerprint.get(field)!r})")
+            if saved["stopped"] or saved["epoch"] >= epochs:  # nothing left to train: no store, no model
+                log(f"Nothing to resume: {state_path} ends at epoch {saved['epoch']}. Best val acc: {saved['best']:.3f}")
+                if process_group is not None:
+                    import torch.distributed as dist
+
+                    dist.barrier(group=process_group)
+                return float(saved["best"])
+    train_store = DeviceClipStore(train_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
+    val_store = DeviceClipStore(val_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
     model = BiGRUClassifier(info["x_dim"], len(info["uniq"]), use_roi=use_roi, roi_emb=32, hidden=192).to(device).train()
     if process_group is not None:
         import torch.distributed as dist
 
         dist.broadcast(model.flat_params, src=dist.get_global_rank(process_group, 0), group=process_group)
     trainer = Trainer(model, lr=lr, world_size=world_size, process_group=process_group,
-                      always_allreduce=process_group is not None, class_weights=class_weights)
+                      always_allreduce=process_group is not None, class_weights=class_weights, ema_decay=ema_decay)
     trainer.rank = rank
+    # validation and the checkpoint see the averaged weights when there are any (two swap launches around each)
+    averaged = trainer.ema_weights if ema_decay is not None else contextlib.nullcontext
     roi_hw = train_store.roi_hw or (48, 96)
     gen = np.random.default_rng(seed)
-    best, bad = 0.0, 0
-    for ep in range(1, epochs + 1):
+    best, bad, first_epoch = 0.0, 0, 1
+    if saved is not None:  # (every rank: the file overrides the broadcast above with the same bits everywhere)
+        model.load_state_dict(saved["model"])
+        trainer.load_state_dict(saved["trainer"])
+        best, bad, first_epoch = float(saved["best"]), int(saved["bad"]), int(saved["epoch"]) + 1
+        log(f"Resuming from {state_path} at epoch {first_epoch} (best val acc {best:.3f})")
+    for ep in range(first_epoch, epochs + 1):
         epoch_base = (ep - 1) * len(train_store)
         if plan == "device":
             order = train_store.sample_epoch(seed=seed, first=epoch_base)
@@ -378,8 +438,9 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                                              y_global=None if y_epoch is None else y_epoch[k * batch_size:k * batch_size + global_batch])
                 tr_loss += loss * global_batch
                 tr_ok += correct
-            res = evaluate_device(model, val_store, batch_size, rank=rank, world_size=world_size, process_group=process_group,
-                                  extra_sums=torch.stack([tr_loss.double(), tr_ok.double()]), class_weights=class_weights)
+            with averaged():
+                res = evaluate_device(model, val_store, batch_size, rank=rank, world_size=world_size, process_group=process_group,
+                                      extra_sums=torch.stack([tr_loss.double(), tr_ok.double()]), class_weights=class_weights)
             train_store.check()  # (the evaluation above has synchronised)
             val_store.check()
             va_loss, va_acc, tr_loss, tr_ok = res.loss, res.acc, res.extra[0], res.extra[1]
@@ -391,23 +452,30 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                 loss, correct = trainer.step(X, T, R if use_roi else None, y)
                 tr_loss += loss * len(idx)
                 tr_ok += correct
-            va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size, plan=plan, class_weights=class_weights)
+            with averaged():
+                va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size, plan=plan, class_weights=class_weights)
             confs = top_confusions(y_true, y_pred, info["id_to_label"], k=6)
         n = max(1, len(order))
         if history is not None:
             history.append(dict(epoch=ep, train_loss=float(tr_loss) / n, train_acc=int(tr_ok) / n, val_loss=va_loss, val_acc=va_acc))
         log(f"ep {ep:02d} | train loss {float(tr_loss) / n:.4f} acc {int(tr_ok) / n:.3f} | val loss {va_loss:.4f} acc {va_acc:.3f}"
             + ((" | top confusions: " + ", ".join(confs)) if confs else ""))
+        stop = False
         if va_acc > best:
             best, bad = va_acc, 0
             if rank == 0:
-                save_checkpoint(out_path, model, info["uniq"], max_t=max_t, roi_w=roi_hw[1], roi_h=roi_hw[0], seed=seed)
+                with averaged():
+                    save_checkpoint(out_path, model, info["uniq"], max_t=max_t, roi_w=roi_hw[1], roi_h=roi_hw[0], seed=seed)
             log(f"  saved {out_path} (best val acc {best:.3f})")
         else:
             bad += 1
-            if bad >= patience:
-                log(f"Early stopping. Best val acc: {best:.3f}")
-                break
+            stop = bad >= patience
+        if state_path is not None and rank == 0:
+            save_train_state(state_path, dict(format=TRAIN_STATE_FORMAT, model=model.state_dict(), trainer=trainer.state_dict(),
+                                              epoch=ep, best=float(best), bad=int(bad), stopped=bool(stop), fingerprint=fingerprint))
+        if stop:
+            log(f"Early stopping. Best val acc: {best:.3f}")
+            break
     if process_group is not None:
         import torch.distributed as dist
 

@@ -12,6 +12,7 @@ batch exactly as a single process would.  ``torch.distributed`` backend "nccl" i
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional
 
 import numpy as np
@@ -59,6 +60,14 @@ def check_class_weights(class_weights, num_classes: int) -> np.ndarray:
     return np.ascontiguousarray(w)
 
 
+def ema_decay_at(decay: float, t: int, warmup: bool = True) -> float:
+    """The decay of the weight average at step ``t`` (``Trainer.step_count`` of the step being taken: 1 for the first), in
+    double: ``min(decay, (1 + t) / (10 + t))`` -- the early steps, whose average would otherwise be dominated by the initial
+    weights, average over a short window -- or ``decay`` itself without warm-up."""
+    decay = float(decay)
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
 class Trainer:
     """``micro_batches`` > 1 splits this rank's clips into that many equal slices which travel through forward and
     backward on their own HIP streams.  The GRU recurrence is latency-bound and occupies only one CU per
@@ -74,7 +83,15 @@ class Trainer:
     label_smoothing=)``, the reference's commented-out loss (train_model_official.py:406-414).  The weighted mean divides by the
     sum of w[y] over the GLOBAL batch; that sum is taken on the device, per step, by one ``ss_class_weight_sum`` launch over
     ``step(y_global=)`` and read by the fused tail from device memory -- no read-back, no collective.  Without weights a step
-    issues exactly the launches it always has."""
+    issues exactly the launches it always has.
+
+    ``ema_decay`` (None, or ``d`` in [0, 1) as float32): ``self.ema``, an exponential moving average of the flat parameter bucket,
+    starts as a copy of the parameters and is updated by the SAME launch that applies Adam (``ss_adam_clip_ema`` in place of
+    ``ss_adam_clip``: nine streams of the bucket instead of seven), with the decay ``ema_decay_at(d, step_count, ema_warmup)`` of
+    the step.  An empty shard updates it like every other rank's, so the ranks' averages stay the same bits as their parameters
+    do.  ``ema_weights()`` puts the average behind the module's parameters for a block of code; ``state_dict()`` /
+    ``load_state_dict()`` carry the moments, the average and the step count (``harness.fit(state_path=)``).  Without
+    ``ema_decay`` a step issues exactly the launches it always has."""
 
     # CUs left to the other micro-batch's recurrence while a persistent ROI-CNN kernel runs (2 directions x 8 slices)
     CNN_RESERVED_CUS = 32
@@ -82,8 +99,12 @@ class Trainer:
     def __init__(self, model: BiGRUClassifier, lr: float = 3e-4, max_norm: float = 1.0,
                  label_smoothing: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  process_group=None, dropout: bool = True, micro_batches: int = 1, always_allreduce: bool = False,
-                 class_weights=None):
+                 class_weights=None, ema_decay: Optional[float] = None, ema_warmup: bool = True):
         cw = None if class_weights is None else check_class_weights(class_weights, model.cfg.num_classes)
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.0 <= float(np.float32(ema_decay)) < 1.0:  # (the kernel takes it as float32)
+                raise ValueError(f"ema_decay must lie in [0, 1) as float32, not {ema_decay!r}")
         if model.flat_params is None or not model.flat_params.is_cuda:
             raise RuntimeError("Trainer needs the model on a HIP device")
         L.load()
@@ -97,6 +118,9 @@ class Trainer:
         dev = model.flat_params.device
         self.m = torch.zeros_like(model.flat_params)
         self.v = torch.zeros_like(model.flat_params)
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self.ema = None if ema_decay is None else model.flat_params.detach().clone()
+        self._ema_swapped = False  # inside ema_weights(): the bucket holds the average, ``ema`` the raw weights
         # [loss_sum, sumsq] fp32 and [correct] int32 live on the device
         self.scal = torch.zeros(2, device=dev, dtype=torch.float32)
         self.correct = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -127,6 +151,8 @@ class Trainer:
             if self.m.numel() != flat.numel():
                 raise RuntimeError("the model's parameter layout changed under the Trainer")
             self.m, self.v = self.m.to(flat.device), self.v.to(flat.device)
+            if self.ema is not None:
+                self.ema = self.ema.to(flat.device)
             self.scal, self.correct = self.scal.to(flat.device), self.correct.to(flat.device)
             if self.cw is not None:
                 self.cw, self.den = self.cw.to(flat.device), self.den.to(flat.device)
@@ -149,6 +175,8 @@ class Trainer:
         instead of ``global_batch`` -- taken by one fixed-order launch, so every rank divides by the same bits -- and the returned
         loss is this rank's part of the global weighted mean.  Every micro-batch uses the same sum."""
         model, cfg = self.model, self.model.cfg
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.step inside ema_weights(): the parameters are the averaged ones there")
         if model._bucket_version != self._bucket_version:
             self._bind_bucket()
         B = X.shape[0]
@@ -227,10 +255,78 @@ class Trainer:
         n_el = model.flat_grads.numel()
         L.call("ss_sumsq_f32", model.flat_grads.data_ptr(), n_el, self.scal.data_ptr() + 4, s)
         # d_logits already carries 1/(B*world), so the summed bucket IS the global-mean gradient
-        L.call("ss_adam_clip", model.flat_params.data_ptr(), model.flat_grads.data_ptr(), self.m.data_ptr(),
-               self.v.data_ptr(), n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr, self.betas[0],
-               self.betas[1], self.eps, self.step_count, s)
+        if self.ema is None:
+            L.call("ss_adam_clip", model.flat_params.data_ptr(), model.flat_grads.data_ptr(), self.m.data_ptr(),
+                   self.v.data_ptr(), n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr, self.betas[0],
+                   self.betas[1], self.eps, self.step_count, s)
+        else:  # the same update of p, m, v, and the weight average in the same pass over the bucket
+            L.call("ss_adam_clip_ema", model.flat_params.data_ptr(), model.flat_grads.data_ptr(), self.m.data_ptr(),
+                   self.v.data_ptr(), self.ema.data_ptr(), n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr,
+                   self.betas[0], self.betas[1], self.eps, self.step_count,
+                   ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup), s)
         return self.scal[0], self.correct[0]
+
+    def _swap_ema(self):
+        if self.model._bucket_version != self._bucket_version:
+            self._bind_bucket()
+        flat = self.model.flat_params
+        L.call("ss_swap_f32", flat.data_ptr(), self.ema.data_ptr(), flat.numel(), L.stream())
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the module's parameters ARE the averaged weights: one ``ss_swap_f32`` launch exchanges the flat
+        bucket with ``self.ema`` in place on entry and one exchanges them back on exit (also when the block raises).  The
+        parameters are views of the bucket, so no pointer changes and no workspace is rebuilt; neither engine keeps converted
+        copies of the weights beyond a forward (the bf16 engine converts its GRU weights inside every forward), so there is
+        nothing to invalidate.  Meanwhile ``self.ema`` holds the raw weights: ``step`` and ``state_dict`` raise inside the
+        block, and so does a nested ``ema_weights()``."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights() needs Trainer(ema_decay=)")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() does not nest")
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_swapped = False
+
+    def state_dict(self) -> dict:
+        """Everything a resumed run needs besides the model: copies (on the device) of the Adam moments and of the weight
+        average (None without one), the step count -- the dropout seeds are a function of it -- and the hyperparameters the
+        step uses.  Plain tensors, numbers and lists: ``torch.save`` writes it and ``torch.load(weights_only=True)`` reads it."""
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.state_dict inside ema_weights(): the weights and their average are exchanged there")
+        return dict(m=self.m.detach().clone(), v=self.v.detach().clone(), ema=None if self.ema is None else self.ema.detach().clone(),
+                    step_count=int(self.step_count), ema_decay=self.ema_decay, ema_warmup=bool(self.ema_warmup),
+                    betas=[float(b) for b in self.betas], eps=float(self.eps), lr=float(self.lr), max_norm=float(self.max_norm),
+                    numel=int(self.model.flat_params.numel()))
+
+    def load_state_dict(self, state: dict) -> None:
+        """Take over a ``state_dict()``: the tensors are copied into this trainer's device buffers (nothing is re-allocated), the
+        step count and the hyperparameters are set.  ``ValueError`` when the bucket has another element count, or when one side
+        keeps a weight average and the other does not."""
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.load_state_dict inside ema_weights()")
+        if self.model._bucket_version != self._bucket_version:
+            self._bind_bucket()
+        n = self.model.flat_params.numel()
+        if int(state["numel"]) != n or any(state[k].numel() != n for k in ("m", "v")):
+            raise ValueError(f"the saved trainer state is for a bucket of {int(state['numel'])} elements, this model's has {n}")
+        if (state["ema"] is None) != (self.ema is None):
+            raise ValueError("the saved trainer state and this Trainer disagree about ema_decay: "
+                             f"saved {state['ema_decay']!r}, this one {self.ema_decay!r}")
+        if self.ema is not None and state["ema"].numel() != n:
+            raise ValueError("the saved weight average does not fit this model's bucket")
+        self.m.copy_(state["m"].reshape(-1))
+        self.v.copy_(state["v"].reshape(-1))
+        if self.ema is not None:
+            self.ema.copy_(state["ema"].reshape(-1))
+            self.ema_decay, self.ema_warmup = float(state["ema_decay"]), bool(state["ema_warmup"])
+        self.step_count = int(state["step_count"])
+        self.betas, self.eps = (float(state["betas"][0]), float(state["betas"][1])), float(state["eps"])
+        self.lr, self.max_norm = float(state["lr"]), float(state["max_norm"])
 
     def _fwd_bwd(self, X, lengths, R, y, denom, train, seed, slot, phase, prologue_done=False):
         """Forward + CE ("fwd"), backward ("bwd") or both of one micro-batch on the current stream."""
