@@ -12,6 +12,12 @@ Data layout (fp32 row-major unless noted; N = B*T frames):
     dG_l   (2, N, 4, H)      d gi_r, d gi_z, d gi_n, d(W_hn h+b_hn) (training only)
     CNN stash: pooled maps a1 (N,8,H/2,W/2), a2 (N,16,H/4,W/4), pool argmaxes (u8), conv3 sign
     mask (u8), averaged features (N,24)                            (training only)
+
+``engine_bf16.py`` runs the same model with bf16 MFMA operands.  The two ``forward`` / ``backward`` bodies differ between the GRU
+input and the top GRU output and stay apart; what is the same in both lives here once: the fields both workspaces hold
+(``WorkspaceBase``), the fused tail launches (``tail_fwd``, ``tail_bwd``), the head's parameter gradients (``head_grads``), the
+fork to and the join of the side stream (``fork``, ``on_side``, ``join_side``) and the builder of a GRU layer's weight-gradient
+records (``dw_records``).
 """
 from __future__ import annotations
 
@@ -104,32 +110,39 @@ def dw_shapes(cfg, B, T, l):
     return out
 
 
-def dw_problems(ws, G, cfg, l, lin, ld_in):
-    """The weight-gradient GEMMs of GRU layer ``l`` as ss_gemm_problem records (one grouped launch, both directions each):
+def dw_records(cfg, B, T, l, esize, ld_in, dg, lin, hp, g_ih, g_hh, splits=None):
+    """The weight-gradient GEMMs of GRU layer ``l`` as ss_gemm_problem records (both directions each):
     d W_ih = dGi^T . layer_in;  d W_hh = dGh^T . h_prev in two pieces (rows r|z from columns [0, 2H) of dG, rows n from
     columns [3H, 4H) = d(W_hn h + b_hn)).  Rows (b,t) of dG pair with out rows (b,t-1) (forward) / (b,t+1) (reverse): with the
     row remap (group T-1 of stride T, A offset 1, B offset 0) the reverse direction is the same pairing seen from one row
-    earlier in dG and one row later in out, i.e. two pointer shifts."""
-    B, T, H = ws.B, ws.T, cfg.hidden
-    N, K = B * T, (cfg.in_dim if l == 0 else 2 * H)
-    dg = ws.dG[l].data_ptr()
-    wi, wir = f"gru.weight_ih_l{l}", f"gru.weight_ih_l{l}_reverse"
-    wh, whr = f"gru.weight_hh_l{l}", f"gru.weight_hh_l{l}_reverse"
-    ident = (INT_MAX, 0, 0)
-
-    def prob(M, Nn, Kk, A, B_, Cm, ldc, splits, a_map, b_map, sa, sb, sc):
-        return L.GemmProblem(0, 0, M, Nn, Kk, A, 4 * H, a_map[0], a_map[1], a_map[2], B_, ld_in if b_map is ident else 2 * H,
-                             b_map[0], b_map[1], b_map[2], Cm, ldc, splits, 2, sa, sb, sc)
-
+    earlier in dG and one row later in out, i.e. two pointer shifts (the batch strides).
+    ``esize``: bytes per element of the operands ``dg`` (2, N, 4, H), ``lin`` (N, ld_in) and ``hp`` (N, 2H), addresses; ``g_ih`` /
+    ``g_hh``: (address of the forward direction's f32 gradient, element stride to the reverse direction's); ``splits``: K slices of
+    the three (default: those of ``dw_shapes``).  Null addresses give shape-only records for the scratch-size queries."""
+    H, N = cfg.hidden, B * T
     shapes = dw_shapes(cfg, B, T, l)
-    out = [prob(*shapes[0][:3], dg, lin, G[wi].data_ptr(), K, shapes[0][3], ident, ident, N * 4 * H, 0, _pstride(G, wi, wir))]
+    splits = splits or [sh[3] for sh in shapes]
+    K = shapes[0][1]
+
+    def rec(shape, A, a_map, B_, ldb, b_map, Cm, ldc, sp, sa, sb, sc):
+        return L.GemmProblem(0, 0, *shape[:3], A, 4 * H, *a_map, B_, ldb, *b_map, Cm, ldc, sp, 2, sa, sb, sc)
+
+    ident = (INT_MAX, 0, 0)
+    out = [rec(shapes[0], dg, ident, lin, ld_in, ident, g_ih[0], K, splits[0], N * 4 * H, 0, g_ih[1])]
     if T > 1:
         am, bm = (T - 1, T, 1), (T - 1, T, 0)
-        sa, sb, sc = N * 4 * H - 4 * H, H + 2 * H, _pstride(G, wh, whr)
-        gw, hp = G[wh], ws.out[l].data_ptr()
-        out.append(prob(*shapes[1][:3], dg, hp, gw.data_ptr(), H, shapes[1][3], am, bm, sa, sb, sc))
-        out.append(prob(*shapes[2][:3], dg + 3 * H * 4, hp, _addr(gw, 2 * H * H), H, shapes[2][3], am, bm, sa, sb, sc))
+        sa, sb = N * 4 * H - 4 * H, H + 2 * H
+        out.append(rec(shapes[1], dg, am, hp, 2 * H, bm, g_hh[0], H, splits[1], sa, sb, g_hh[1]))
+        out.append(rec(shapes[2], dg + 3 * H * esize, am, hp, 2 * H, bm, g_hh[0] + 2 * H * H * 4, H, splits[2], sa, sb, g_hh[1]))
     return out
+
+
+def dw_problems(ws, G, cfg, l, lin, ld_in):
+    """``dw_records`` of the f32 engine: one grouped launch (ss_gemm_f32_splitk_group) per layer."""
+    wi, wir = f"gru.weight_ih_l{l}", f"gru.weight_ih_l{l}_reverse"
+    wh, whr = f"gru.weight_hh_l{l}", f"gru.weight_hh_l{l}_reverse"
+    return dw_records(cfg, ws.B, ws.T, l, 4, ld_in, ws.dG[l].data_ptr(), lin, ws.out[l].data_ptr(),
+                      (G[wi].data_ptr(), _pstride(G, wi, wir)), (G[wh].data_ptr(), _pstride(G, wh, whr)))
 
 
 def _pstride(P, a: str, b: str) -> int:
@@ -186,30 +199,63 @@ def make_workspace(cfg: Config, B: int, T: int, roi_hw, device, train: bool, slo
     return Workspace(cfg, B, T, roi_hw, device, train, slot)
 
 
-class Workspace:
-    """Activation / gradient buffers for one (B, T, H, W) shape; reused across steps (hipGraph friendly)."""
-
-    bf16 = False
+class WorkspaceBase:
+    """What both engines keep for one (B, T) shape: the f32 buffers around the GRU layers and behind them, the side stream and the
+    events.  ``Workspace`` / ``engine_bf16.WorkspaceBf16`` add what their kernels need between the GRU input and the top output."""
 
     def __init__(self, cfg: Config, B: int, T: int, roi_hw, device, train: bool, slot=0):
         self.cfg, self.B, self.T, self.roi_hw, self.train = cfg, B, T, roi_hw, train
         self.stash_gen, self.stash_live = 0, False  # model._Fn: which autograd node the stashed activations belong to
         N, H = B * T, cfg.hidden
         f32 = dict(device=device, dtype=torch.float32)
-        u8 = dict(device=device, dtype=torch.uint8)
         self.lengths = torch.empty(B, device=device, dtype=torch.int32)
-        # step counters of the multi-CU recurrence (zeroed once; the kernels keep them consistent): only shapes small
-        # enough to leave most of the chip idle under the one-CU-per-slice kernels get one
-        nb = L.gru_sync_bytes(B, T, H)
-        self.gru_sync = torch.zeros(nb // 4, device=device, dtype=torch.int32) if nb else None
-        # weight-gradient GEMMs run on a side stream next to the (32-CU) recurrence of the layer below
+        # weight-gradient GEMMs run on a side stream next to the recurrence of the layer below (the f32 engine's 32-CU kernel;
+        # a BPTT step of the bf16 engine is a tiny, latency-bound launch that leaves the matrix pipes idle)
+        # (one stream per device and micro-batch slot, shared by all workspaces: side_stream)
         self.side = side_stream(device, slot) if train else None
         self.ev_fork = torch.cuda.Event() if train else None
         self.ev_join = torch.cuda.Event() if train else None
         self.ev_cnn_fwd = torch.cuda.Event() if train else None  # recorded after the ROI-CNN forward (micro-batch stagger)
+        self.ev_zero = torch.cuda.Event() if train else None     # the cleared d layer_in destinations (side stream)
         self.stagger = False  # set by the trainer when another micro-batch waits for ev_cnn_fwd
         # roi_hw None with use_roi: a workspace for forward(..., z_ready=True) -- rows that already hold the embeddings (serving.py)
         self.Z = torch.empty(N, cfg.in_dim, **f32) if cfg.use_roi and roi_hw is not None else None
+        self.frames = self.frames_seen = None  # the f32 engine's list of the frames inside their clips (Workspace)
+        self.gi = [torch.empty(2, N, 3 * H, **f32) for _ in range(cfg.gru_layers)]
+        self.out = [torch.empty(N, 2 * H, **f32) for _ in range(cfg.gru_layers)]
+        self.attn = torch.empty(B, T, **f32)
+        self.ln = torch.empty(B, 2 * H, **f32)
+        self.mid = torch.empty(B, cfg.head_mid, **f32)
+        self.mid_drop = torch.empty(B, cfg.head_mid, **f32)
+        self.logits = torch.empty(B, cfg.num_classes, **f32)
+        if train:
+            self.save = [torch.empty(2, N, 4, H, **f32) for _ in range(cfg.gru_layers)]
+            self.d_out = torch.empty(N, 2 * H, **f32)
+            # gradient w.r.t. the output of layer l-1 (destination of layer l's d layer_in GEMM, l >= 1): zeroed on the side
+            # stream while the top of the backward pass runs, summed into with atomics by both directions
+            self.d_lower = [None] + [torch.empty(N, 2 * H, **f32) for _ in range(1, cfg.gru_layers)]
+            self.xhat = torch.empty(B, 2 * H, **f32)
+            self.rstd = torch.empty(B, **f32)
+            self.d_logits = torch.empty(B, cfg.num_classes, **f32)
+            self.d_mid = torch.empty(B, cfg.head_mid, **f32)
+            self.tail_part = torch.empty(B, 3, 2 * H, **f32)  # per-clip terms of d gamma | d beta | d w_score (tail_bwd)
+            self.dZ = torch.empty(N, cfg.in_dim, **f32) if cfg.use_roi else None
+
+
+class Workspace(WorkspaceBase):
+    """Activation / gradient buffers for one (B, T, H, W) shape; reused across steps (hipGraph friendly)."""
+
+    bf16 = False
+
+    def __init__(self, cfg: Config, B: int, T: int, roi_hw, device, train: bool, slot=0):
+        super().__init__(cfg, B, T, roi_hw, device, train, slot)
+        N, H = B * T, cfg.hidden
+        f32 = dict(device=device, dtype=torch.float32)
+        u8 = dict(device=device, dtype=torch.uint8)
+        # step counters of the multi-CU recurrence (zeroed once; the kernels keep them consistent): only shapes small
+        # enough to leave most of the chip idle under the one-CU-per-slice kernels get one
+        nb = L.gru_sync_bytes(B, T, H)
+        self.gru_sync = torch.zeros(nb // 4, device=device, dtype=torch.int32) if nb else None
         # ROI sizes the fused, LDS-resident CNN kernels are not built for run layer by layer (cnn_generic.py)
         self.cnn_generic = None
         if cfg.use_roi and roi_hw is not None:
@@ -217,38 +263,12 @@ class Workspace:
 
             if not cnn_generic.fused_supported(*roi_hw):
                 self.cnn_generic = cnn_generic.GenericCnn(N, roi_hw[0], roi_hw[1], device, train)
-        self.gi = [torch.empty(2, N, 3 * H, **f32) for _ in range(cfg.gru_layers)]
-        self.out = [torch.empty(N, 2 * H, **f32) for _ in range(cfg.gru_layers)]
-        self.attn = torch.empty(B, T, **f32)
-        self.pooled = torch.empty(B, 2 * H, **f32)
-        self.ln = torch.empty(B, 2 * H, **f32)
-        self.mid = torch.empty(B, cfg.head_mid, **f32)
-        self.logits = torch.empty(B, cfg.num_classes, **f32)
         self.out_drop = [torch.empty(N, 2 * H, **f32) for _ in range(cfg.gru_layers - 1)]
-        self.mid_drop = torch.empty(B, cfg.head_mid, **f32)
         if train:
-            self.save = [torch.empty(2, N, 4, H, **f32) for _ in range(cfg.gru_layers)]
             self.dG = [torch.empty(2, N, 4, H, **f32) for _ in range(cfg.gru_layers)]
-            self.d_out = torch.empty(N, 2 * H, **f32)
-            # gradient w.r.t. the output of layer l-1 (destination of layer l's d layer_in GEMM, l >= 1): zeroed on the side
-            # stream while the top of the backward pass runs, summed into with atomics by both directions
             # scratch for the K slices of one layer's weight-gradient GEMMs (the layers follow each other on the side stream)
-            need = 0
-            for l in range(cfg.gru_layers):
-                probs = [L.GemmProblem(0, 0, m_, n_, k_, None, 0, 1, 0, 0, None, 0, 1, 0, 0, None, 0, sp_, 2, 0, 0, 0)
-                         for (m_, n_, k_, sp_) in dw_shapes(cfg, B, T, l)]
-                need = max(need, L.gemm_group_ws_floats(probs))
-            self.splitk_ws = torch.empty(need, **f32)
-            self.d_lower = [None] + [torch.empty(N, 2 * H, **f32) for _ in range(1, cfg.gru_layers)]
-            self.ev_zero = torch.cuda.Event()
-            self.xhat = torch.empty(B, 2 * H, **f32)
-            self.rstd = torch.empty(B, **f32)
-            self.d_logits = torch.empty(B, cfg.num_classes, **f32)
-            self.d_mid = torch.empty(B, cfg.head_mid, **f32)
-            self.tail_part = torch.empty(B, 3, 2 * H, **f32)  # per-clip terms of d gamma | d beta | d w_score (tail_bwd)
-            self.d_ln = torch.empty(B, 2 * H, **f32)
-            self.d_pooled = torch.empty(B, 2 * H, **f32)
-            self.dZ = torch.empty(N, cfg.in_dim, **f32) if cfg.use_roi else None
+            self.splitk_ws = torch.empty(max(L.gemm_group_ws_floats(dw_records(cfg, B, T, l, 4, 0, 0, 0, 0, (0, 0), (0, 0)))
+                                             for l in range(cfg.gru_layers)), **f32)
             if cfg.use_roi and self.cnn_generic is None:
                 Hh, Ww = roi_hw
                 # every size comes from the library (the kernels' own LDS images, kept as they are) and goes back to it with
@@ -262,16 +282,90 @@ class Workspace:
                 self.st_m3 = torch.empty(N, n_m3, **u8)     # (H/4 * W/4, 32)
                 self.st_feat = torch.empty(N, n_feat, **f32)  # 24 features, 24 counts, mean, std, pad
         # [0] = how many rows (b, t) lie inside their clip, [1 ...] = those rows: the fused CNN kernels walk only them
-        self.frames = (torch.empty(1 + N, device=device, dtype=torch.int32)
-                       if cfg.use_roi and roi_hw is not None and self.cnn_generic is None and SKIP_PADDED_FRAMES else None)
+        if cfg.use_roi and roi_hw is not None and self.cnn_generic is None and SKIP_PADDED_FRAMES:
+            self.frames = torch.empty(1 + N, device=device, dtype=torch.int32)
         # The backward kernel pays 1 % for the list (roi_cnn_bwd.hip: 48 instead of 38 spilled scalar registers), so a training
         # workspace keeps the count of the last batch it has SEEN FINISH in pinned memory -- an 8-byte copy on the side stream,
         # never waited for -- and a step that follows a batch of full clips launches the kernels without the list.  A wrong guess
         # walks the padding frames as the reference does: slower, never different.  walk_listed = this step's choice (the
         # forward makes it, the backward follows: the stash slots of frames the forward skipped are not there to read).
-        self.frames_seen = (torch.full((1,), -1, dtype=torch.int32).pin_memory()
-                            if self.frames is not None and train else None)
+        if self.frames is not None and train:
+            self.frames_seen = torch.full((1,), -1, dtype=torch.int32).pin_memory()
         self.walk_listed = self.frames is not None
+
+
+# the f32 ROI CNN's parameters in the order its entry points take them
+CNN_PARAMS = ("roi_cnn.net.0.weight", "roi_cnn.net.0.bias", "roi_cnn.net.3.weight", "roi_cnn.net.3.bias",
+              "roi_cnn.net.6.weight", "roi_cnn.net.6.bias", "roi_cnn.fc.weight", "roi_cnn.fc.bias")
+
+
+def tail_fwd(P, cfg: Config, ws, top, train, stash, seed, ce):
+    """AttnPool + head (+ loss) of both engines: one fused launch, a workgroup per clip; ``ce`` as ``forward`` takes it."""
+    p_drop = cfg.head_dropout if train else 0.0
+    y_ptr, ls, denom, loss_ptr, correct_ptr, cw_ptr, den_ptr = (tuple(ce) + (None, None))[:7] if ce is not None else (None, 0.0, 1.0, None, None, None, None)
+    # (class weights: the same launch with the weights and the device-side normaliser in place of the host denom)
+    name, ce_norm = ("ss_tail_fwd_w", (cw_ptr, den_ptr)) if cw_ptr else ("ss_tail_fwd", (denom,))
+    L.call(name, top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
+           P["pool.score.bias"].data_ptr(), P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(),
+           P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(), P["head.4.weight"].data_ptr(),
+           P["head.4.bias"].data_ptr(), y_ptr, ws.B, ws.T, 2 * cfg.hidden, cfg.head_mid, cfg.num_classes, cfg.ln_eps, p_drop, seed,
+           7 << 40, ls, *ce_norm, ws.attn.data_ptr() if stash else None, ws.xhat.data_ptr() if stash else None,
+           ws.rstd.data_ptr() if stash else None, ws.ln.data_ptr() if stash else None,
+           ws.mid.data_ptr() if stash else None, ws.mid_drop.data_ptr() if stash else None, ws.logits.data_ptr(),
+           ws.d_logits.data_ptr() if ce is not None else None, loss_ptr, correct_ptr, L.stream())
+    return ws.logits
+
+
+def tail_bwd(P, G, cfg: Config, ws, d_logits, train, seed):
+    """The tail's backward of both engines: one fused launch down to ``ws.d_out`` of the top GRU layer."""
+    L.call("ss_tail_bwd", ws.out[-1].data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
+           P["head.0.weight"].data_ptr(), P["head.1.weight"].data_ptr(), P["head.4.weight"].data_ptr(),
+           ws.attn.data_ptr(), ws.xhat.data_ptr(), ws.rstd.data_ptr(), ws.mid.data_ptr(), d_logits.data_ptr(), ws.B, ws.T,
+           2 * cfg.hidden, cfg.head_mid, cfg.num_classes, cfg.head_dropout if train else 0.0, seed, 7 << 40, ws.d_mid.data_ptr(),
+           ws.d_out.data_ptr(), G["head.0.weight"].data_ptr(), G["head.0.bias"].data_ptr(), G["pool.score.weight"].data_ptr(),
+           G["pool.score.bias"].data_ptr(), ws.tail_part.data_ptr(), L.stream())
+
+
+def head_grads(G, cfg: Config, ws, d_logits):
+    """What both engines run on the side stream behind the top layer's BPTT launch."""
+    B, H, C, MID = ws.B, cfg.hidden, cfg.num_classes, cfg.head_mid
+    # the atomically summed destinations of the d layer_in GEMMs: cleared here, off the critical path, and first --
+    # the top layer's d layer_in GEMM waits for them
+    zero_buffers(ws.d_lower[1:] + ([ws.dZ] if cfg.use_roi else []))
+    ws.ev_zero.record()
+    if ws.frames_seen is not None:  # how many frames of this batch lay inside a clip: read by a later step's forward
+        ws.frames_seen.copy_(ws.frames[:1], non_blocking=True)
+    # LayerNorm gamma / beta and score-weight gradients: column sums of the rows the tail kernel left per clip
+    for k_, name_ in enumerate(("head.0.weight", "head.0.bias", "pool.score.weight")):
+        L.call("ss_colsum_f32", _addr(ws.tail_part, k_ * 2 * H), B, 2 * H, 3 * 2 * H, G[name_].data_ptr(), L.stream())
+    # the two Linear weight gradients, batched over the clips (f32, K = B: latency-bound launches that leave the chip empty --
+    # beside the top layer's BPTT kernel they are free)
+    gemm(0, 0, C, MID, B, d_logits.data_ptr(), C, ws.mid_drop.data_ptr(), MID, G["head.4.weight"].data_ptr(), MID,
+         accumulate=True, atomic=True, a_colsum=G["head.4.bias"].data_ptr())
+    gemm(0, 0, MID, 2 * H, B, ws.d_mid.data_ptr(), MID, ws.ln.data_ptr(), 2 * H, G["head.1.weight"].data_ptr(),
+         2 * H, accumulate=True, atomic=True, a_colsum=G["head.1.bias"].data_ptr())
+
+
+# Fork and join of the side stream.  ``on`` is the calling engine's USE_SIDE_STREAM, read when it calls: off, the work runs inline
+# on the caller's stream and no event is recorded or waited for.  Recording the fork and queueing the work are two calls because
+# the head's fork is recorded in front of the top layer's BPTT launch and its work is enqueued behind it (``backward``).
+def fork(ws, on: bool) -> None:
+    if on:
+        ws.ev_fork.record()
+
+
+def on_side(ws, on: bool, work) -> None:
+    if not on:
+        return work()
+    with torch.cuda.stream(ws.side):
+        ws.side.wait_event(ws.ev_fork)
+        work()
+
+
+def join_side(ws, on: bool) -> None:
+    if on:
+        ws.ev_join.record(ws.side)
+        torch.cuda.current_stream().wait_event(ws.ev_join)
 
 
 def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Tensor, R: Optional[torch.Tensor], *,
@@ -305,9 +399,7 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
         if ws.cnn_generic is not None:  # an ROI size outside the fused kernels' set: layer by layer (cnn_generic.py)
             ws.cnn_generic.forward(P, R, cfg.roi_standardize, cfg.roi_emb, _addr(ws_Z, cfg.x_dim), cfg.in_dim, stash)
         else:
-            cw = [P[k].data_ptr() for k in ("roi_cnn.net.0.weight", "roi_cnn.net.0.bias", "roi_cnn.net.3.weight",
-                                            "roi_cnn.net.3.bias", "roi_cnn.net.6.weight", "roi_cnn.net.6.bias",
-                                            "roi_cnn.fc.weight", "roi_cnn.fc.bias")]
+            cw = [P[k].data_ptr() for k in CNN_PARAMS]
             st = ([ws.st_a1.data_ptr(), ws.st_i1.data_ptr(), ws.st_a2.data_ptr(), ws.st_i2.data_ptr(),
                    ws.st_m3.data_ptr(), ws.st_feat.data_ptr()] if stash else [None] * 6)
             if ws.frames is not None and not x_in_place:  # (the trainer's prologue kernel has listed them already)
@@ -345,21 +437,8 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
                 L.call("ss_dropout", ws.out[l].data_ptr(), ws.out_drop[l].data_ptr(), N * 2 * H, cfg.gru_dropout, seed,
                        (l + 1) << 40, None, s)
             layer_in = ws.out_drop[l].data_ptr()
-    top = ws.out[cfg.gru_layers - 1]
     # ---- AttnPool + head (+ loss): one fused launch, a workgroup per clip
-    p_drop = cfg.head_dropout if train else 0.0
-    y_ptr, ls, denom, loss_ptr, correct_ptr, cw_ptr, den_ptr = (tuple(ce) + (None, None))[:7] if ce is not None else (None, 0.0, 1.0, None, None, None, None)
-    # (class weights: the same launch with the weights and the device-side normaliser in place of the host denom)
-    tail_fwd, ce_norm = ("ss_tail_fwd_w", (cw_ptr, den_ptr)) if cw_ptr else ("ss_tail_fwd", (denom,))
-    L.call(tail_fwd, top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
-           P["pool.score.bias"].data_ptr(), P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(),
-           P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(), P["head.4.weight"].data_ptr(),
-           P["head.4.bias"].data_ptr(), y_ptr, B, T, 2 * H, cfg.head_mid, cfg.num_classes, cfg.ln_eps, p_drop, seed,
-           7 << 40, ls, *ce_norm, ws.attn.data_ptr() if stash else None, ws.xhat.data_ptr() if stash else None,
-           ws.rstd.data_ptr() if stash else None, ws.ln.data_ptr() if stash else None,
-           ws.mid.data_ptr() if stash else None, ws.mid_drop.data_ptr() if stash else None, ws.logits.data_ptr(),
-           ws.d_logits.data_ptr() if ce is not None else None, loss_ptr, correct_ptr, s)
-    return ws.logits
+    return tail_fwd(P, cfg, ws, ws.out[cfg.gru_layers - 1], train, stash, seed, ce)
 
 
 def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Tensor,
@@ -373,40 +452,13 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
         return engine_bf16.backward(P, G, cfg, ws, X, R, d_logits, train=train, seed=seed, d_X=d_X)
     B, T, H, N = ws.B, ws.T, cfg.hidden, ws.B * ws.T
     s = L.stream()
-    C, MID = cfg.num_classes, cfg.head_mid
-    p_drop = cfg.head_dropout if train else 0.0
-    top = ws.out[cfg.gru_layers - 1]
     # ---- tail: one fused launch down to d_out of the top GRU layer ...
-    L.call("ss_tail_bwd", top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
-           P["head.0.weight"].data_ptr(), P["head.1.weight"].data_ptr(), P["head.4.weight"].data_ptr(),
-           ws.attn.data_ptr(), ws.xhat.data_ptr(), ws.rstd.data_ptr(), ws.mid.data_ptr(), d_logits.data_ptr(), B, T,
-           2 * H, MID, C, p_drop, seed, 7 << 40, ws.d_mid.data_ptr(), ws.d_out.data_ptr(),
-           G["head.0.weight"].data_ptr(), G["head.0.bias"].data_ptr(), G["pool.score.weight"].data_ptr(),
-           G["pool.score.bias"].data_ptr(), ws.tail_part.data_ptr(), s)
+    tail_bwd(P, G, cfg, ws, d_logits, train, seed)
     # ... while the two Linear weight gradients (batched over the clips) go to the side stream.  The fork event is recorded here,
-    # the side stream's launches are ENQUEUED behind the top layer's BPTT launch (head_side_work, called in the loop below): the
+    # the side stream's launches are ENQUEUED behind the top layer's BPTT launch (head_grads, in the loop below): the
     # host needs ~30 us for these seven launches and the main queue sat empty meanwhile (15 us between tail_bwd and the BPTT
     # kernel in the kernel trace, tools/step_gaps.py; 6 us of it is the event's barrier packet and stays)
-    side = ws.side if USE_SIDE_STREAM else torch.cuda.current_stream()
-    ws.ev_fork.record()
-
-    def head_side_work():
-        with torch.cuda.stream(side):
-            side.wait_event(ws.ev_fork)
-            # the atomically summed destinations of the d layer_in GEMMs: cleared here, off the critical path, and first --
-            # the top layer's d layer_in GEMM waits for them
-            zero_buffers(ws.d_lower[1:] + ([ws.dZ] if cfg.use_roi else []))
-            ws.ev_zero.record()
-            if ws.frames_seen is not None:  # how many frames of this batch lay inside a clip: read by a later step's forward
-                ws.frames_seen.copy_(ws.frames[:1], non_blocking=True)
-            # LayerNorm gamma / beta and score-weight gradients: column sums of the rows the tail kernel left per clip
-            for k_, name_ in enumerate(("head.0.weight", "head.0.bias", "pool.score.weight")):
-                L.call("ss_colsum_f32", _addr(ws.tail_part, k_ * 2 * H), B, 2 * H, 3 * 2 * H, G[name_].data_ptr(), L.stream())
-            gemm(0, 0, C, MID, B, d_logits.data_ptr(), C, ws.mid_drop.data_ptr(), MID, G["head.4.weight"].data_ptr(), MID,
-                 accumulate=True, atomic=True, a_colsum=G["head.4.bias"].data_ptr())
-            gemm(0, 0, MID, 2 * H, B, ws.d_mid.data_ptr(), MID, ws.ln.data_ptr(), 2 * H, G["head.1.weight"].data_ptr(),
-                 2 * H, accumulate=True, atomic=True, a_colsum=G["head.1.bias"].data_ptr())
-
+    fork(ws, USE_SIDE_STREAM)
     # ---- GRU layers, top down
     use_drop = train and cfg.gru_dropout > 0.0
     zero_waited = False
@@ -422,7 +474,7 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
                G[f"gru.bias_ih_l{l}"].data_ptr(), G[f"gru.bias_hh_l{l}"].data_ptr(),
                G[f"gru.bias_ih_l{l}_reverse"].data_ptr(), G[f"gru.bias_hh_l{l}_reverse"].data_ptr(), L.ptr(ws.gru_sync), s)
         if top_layer:
-            head_side_work()
+            on_side(ws, USE_SIDE_STREAM, lambda: head_grads(G, cfg, ws, d_logits))
         if l == 0:
             if cfg.use_roi:
                 lin, ld_in = ws.Z.data_ptr(), cfg.in_dim
@@ -431,14 +483,12 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
         else:
             use_drop = train and cfg.gru_dropout > 0.0
             lin, ld_in = (ws.out_drop[l - 1] if use_drop else ws.out[l - 1]).data_ptr(), 2 * H
-        def side_work(l=l, K=K, lin=lin, ld_in=ld_in):
+        def side_work(l=l, lin=lin, ld_in=ld_in):
             # fork: everything that only feeds the parameter gradients of this layer goes to the side stream
-            side = ws.side if USE_SIDE_STREAM else torch.cuda.current_stream()
-            ws.ev_fork.record()
-            with torch.cuda.stream(side):
-                side.wait_event(ws.ev_fork)
-                L.call("ss_gemm_f32_splitk_group", *L.gemm_group(dw_problems(ws, G, cfg, l, lin, ld_in)), ws.splitk_ws.data_ptr(),
-                       ws.splitk_ws.numel(), DW_WIDE_ALONE if l == 0 else 0, L.stream(), tag="gemm_gru_dW")
+            fork(ws, USE_SIDE_STREAM)
+            on_side(ws, USE_SIDE_STREAM, lambda: L.call(
+                "ss_gemm_f32_splitk_group", *L.gemm_group(dw_problems(ws, G, cfg, l, lin, ld_in)), ws.splitk_ws.data_ptr(),
+                ws.splitk_ws.numel(), DW_WIDE_ALONE if l == 0 else 0, L.stream(), tag="gemm_gru_dW"))
         # the weight-gradient GEMMs of the upper layers start only when this layer's d layer_in GEMM is through: two
         # MFMA-bound GEMMs side by side gain nothing and the one on the critical path loses half its rate; beside the
         # latency-bound recurrence of the layer below they fill idle matrix pipes (2.30 against 2.32 ms per step).  Layer 0
@@ -459,7 +509,7 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
             else:
                 dst, ld_dst = d_X.data_ptr(), cfg.x_dim
                 zero_buffers([d_X])
-            if not zero_waited:  # once per backward pass: every cleared buffer is behind the same event
+            if USE_SIDE_STREAM and not zero_waited:  # once per backward pass: every cleared buffer is behind the same event
                 torch.cuda.current_stream().wait_event(ws.ev_zero)
                 zero_waited = True
             wi, wir = f"gru.weight_ih_l{l}", f"gru.weight_ih_l{l}_reverse"
@@ -475,28 +525,19 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
         if l > 0:
             side_work()
     # ---- ROI CNN
-    side_joined = False  # nothing is queued on the side stream after the join in front of the CNN backward
+    if cfg.use_roi and d_X is not None:
+        L.call("ss_copy_rows_f32", ws.dZ.data_ptr(), cfg.in_dim, d_X.data_ptr(), cfg.x_dim, N, cfg.x_dim, s)
+    # join the side stream: the caller's next kernels (all-reduce, clip, Adam) read every gradient, and in front of the CNN
+    # backward at that: the persistent ROI-CNN kernel takes every CU for ~1 ms, weight-gradient GEMMs still queued on the side
+    # stream at that point would only finish after it (measured: a 180 us tail), so let them drain first -- they run beside the
+    # d layer_in GEMM above and cost the critical path a few tens of microseconds.  (Nothing is queued there behind the join.)
+    join_side(ws, USE_SIDE_STREAM)
     if cfg.use_roi:
         Hh, Ww = ws.roi_hw
-        if d_X is not None:
-            L.call("ss_copy_rows_f32", ws.dZ.data_ptr(), cfg.in_dim, d_X.data_ptr(), cfg.x_dim, N, cfg.x_dim, s)
-        if USE_SIDE_STREAM:
-            # the persistent ROI-CNN kernel takes every CU for ~1 ms: weight-gradient GEMMs still queued on the side
-            # stream at that point would only finish after it (measured: a 180 us tail), so let them drain first --
-            # they run beside the d layer_in GEMM above and cost the critical path a few tens of microseconds
-            ws.ev_join.record(ws.side)
-            torch.cuda.current_stream().wait_event(ws.ev_join)
-            side_joined = True
-        names = ("roi_cnn.net.0.weight", "roi_cnn.net.0.bias", "roi_cnn.net.3.weight", "roi_cnn.net.3.bias",
-                 "roi_cnn.net.6.weight", "roi_cnn.net.6.bias", "roi_cnn.fc.weight", "roi_cnn.fc.bias")
         if ws.cnn_generic is not None:
             ws.cnn_generic.backward(P, G, cfg.roi_emb, _addr(ws.dZ, cfg.x_dim), cfg.in_dim)
         else:
-            L.call("ss_roi_cnn_bwd_frames", R.data_ptr(), N, Hh, Ww, int(cfg.roi_standardize), *[P[k].data_ptr() for k in names],
+            L.call("ss_roi_cnn_bwd_frames", R.data_ptr(), N, Hh, Ww, int(cfg.roi_standardize), *[P[k].data_ptr() for k in CNN_PARAMS],
                    cfg.roi_emb, ws.st_a1.data_ptr(), ws.st_i1.data_ptr(), ws.st_a2.data_ptr(), ws.st_i2.data_ptr(),
                    ws.st_m3.data_ptr(), ws.st_feat.data_ptr(), ws.cnn_sizes.ptr, _addr(ws.dZ, cfg.x_dim), cfg.in_dim,
-                   *[G[k].data_ptr() for k in names], L.ptr(ws.frames) if ws.walk_listed else None, s, tag="ss_roi_cnn_bwd")
-    # join the side stream: the caller's next kernels (all-reduce, clip, Adam) read every gradient
-    if USE_SIDE_STREAM and not side_joined:
-        ws.ev_join.record(ws.side)
-        torch.cuda.current_stream().wait_event(ws.ev_join)
+                   *[G[k].data_ptr() for k in CNN_PARAMS], L.ptr(ws.frames) if ws.walk_listed else None, s, tag="ss_roi_cnn_bwd")

@@ -12,6 +12,9 @@ fallback); what differs is the kernel set:
                  W_hh as bf16 copies made once per step by ss_gru_bf16_prep)
     tail         the f32 fused AttnPool / head / CE kernels of the f32 path (0.1 % of the FLOPs)
 
+What is the same in both engines is written once, in ``engine.py``, and called from here: the shared workspace fields
+(``WorkspaceBase``), ``tail_fwd`` / ``tail_bwd``, ``head_grads``, ``fork`` / ``on_side`` / ``join_side`` and ``dw_records``.
+
 f32 master weights, f32 gradients, f32 Adam: only MFMA operands are bf16.  The reference defines no such model
 (SURVEY.md 8d row 5); the module is train_model_official.py:209-310 with wider layers.
 """
@@ -23,7 +26,8 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib as L
-from .engine import INT_MAX, _addr, _pstride, side_stream, zero_buffers
+from .engine import (INT_MAX, WorkspaceBase, _addr, _pstride, dw_records, fork, head_grads, join_side, on_side, tail_bwd, tail_fwd,
+                     zero_buffers)
 from .engine import gemm as gemm_f32, split_k as split_k_f32  # the fc GEMMs and the head's weight-gradient GEMMs stay f32
 
 USE_SIDE_STREAM = True  # bench.py turns it off for its per-kernel timing pass (HIP-event pairs need one stream)
@@ -58,20 +62,9 @@ def split_k(M, N, K, batch, target_wgs=None):
 
 
 def dw_problems(cfg, B, T, l, Kp, dg=16, lin=16, hp=16, g_ih=(16, 0), g_hh=(16, 0)):
-    """ss_gemm_problem records of layer ``l``'s weight gradients (both directions each; bf16 operands): d W_ih = dGi^T . layer_in;
-    d W_hh = dGh^T . h_prev in two pieces (rows r|z from columns [0, 2H) of dG, rows n from columns [3H, 4H)).  Rows (b,t) of dG
-    pair with out rows (b,t-1) (forward) / (b,t+1) (reverse): the same pairing seen from one row earlier in dG and one row later
-    in out (two pointer shifts = the batch strides).  Pointer defaults: shape-only records for the workspace-size query."""
-    H, N = cfg.hidden, B * T
-    K = cfg.in_dim if l == 0 else 2 * H
-    out = [L.GemmProblem(0, 0, 3 * H, K, N, dg, 4 * H, INT_MAX, 0, 0, lin, Kp, INT_MAX, 0, 0, g_ih[0], K, 1, 2, N * 4 * H, 0, g_ih[1])]
-    if T > 1:
-        Kh = B * (T - 1)
-        sa, sb = N * 4 * H - 4 * H, H + 2 * H
-        out.append(L.GemmProblem(0, 0, 2 * H, H, Kh, dg, 4 * H, T - 1, T, 1, hp, 2 * H, T - 1, T, 0, g_hh[0], H, 1, 2, sa, sb, g_hh[1]))
-        out.append(L.GemmProblem(0, 0, H, H, Kh, dg + 3 * H * 2, 4 * H, T - 1, T, 1, hp, 2 * H, T - 1, T, 0, g_hh[0] + 2 * H * H * 4, H,
-                                 1, 2, sa, sb, g_hh[1]))
-    return out
+    """``engine.dw_records`` of layer ``l`` with bf16 operands (the layer input in rows of ``Kp`` elements) and no K slices.
+    Pointer defaults: shape-only records for the workspace-size query."""
+    return dw_records(cfg, B, T, l, 2, Kp, dg, lin, hp, g_ih, g_hh, splits=(1, 1, 1))
 
 
 def dw_group_ok(problems) -> bool:
@@ -119,37 +112,24 @@ def check_config(cfg, roi_hw) -> None:
                            "conversion)")
 
 
-class WorkspaceBf16:
+class WorkspaceBf16(WorkspaceBase):
     """Activation / gradient buffers of the bf16 path for one (B, T) shape."""
 
     bf16 = True
 
     def __init__(self, cfg, B: int, T: int, roi_hw, device, train: bool, slot=0):
         check_config(cfg, roi_hw if cfg.use_roi else ROI_HW)
-        self.cfg, self.B, self.T, self.roi_hw, self.train = cfg, B, T, roi_hw, train
-        self.stash_gen, self.stash_live = 0, False
-        self.stagger = False
-        # weight-gradient GEMMs of a layer run on a side stream beside the BPTT steps of the layer below (a step is a tiny,
-        # latency-bound launch that leaves the matrix pipes idle)
-        # (one stream per device and micro-batch slot, shared by all workspaces: engine.side_stream)
-        self.side = side_stream(device, slot) if train else None
-        self.ev_fork = torch.cuda.Event() if train else None
-        self.ev_join = torch.cuda.Event() if train else None
-        self.ev_cnn_fwd = torch.cuda.Event() if train else None  # recorded after the ROI-CNN forward (Trainer's micro-batch stagger)
-        self.ev_zero = torch.cuda.Event() if train else None     # the cleared d layer_in destinations (side stream)
+        super().__init__(cfg, B, T, roi_hw, device, train, slot)
         N, H = B * T, cfg.hidden
         f32 = dict(device=device, dtype=torch.float32)
         u8 = dict(device=device, dtype=torch.uint8)
         i16 = dict(device=device, dtype=torch.int16)  # bf16 bit patterns
-        self.lengths = torch.empty(B, device=device, dtype=torch.int32)
-        self.Z = torch.empty(N, cfg.in_dim, **f32) if cfg.use_roi else None
-        self.gi = [torch.empty(2, N, 3 * H, **f32) for _ in range(cfg.gru_layers)]
-        self.out = [torch.empty(N, 2 * H, **f32) for _ in range(cfg.gru_layers)]
         # bf16 copies that feed MFMAs: the layer inputs (Z; the -- dropped-out -- output of the layer below, left by its recurrence
         # kernel), the layer outputs (h_prev operand of d W_hh), W_hh / W_hh^T / W_ih (once per step: ss_gru_bf16_prep)
         self.kin = [cfg.in_dim if l == 0 else 2 * H for l in range(cfg.gru_layers)]
         self.kp = [_pad8(k) for k in self.kin]
         self.lin_bf0 = torch.zeros(N, self.kp[0], **i16)
+        self.lin_bf = {}  # layer l >= 1 -> what the last forward multiplied its W_ih with (the output below, dropped out or not)
         self.out_bf = [torch.empty(N, 2 * H, **i16) for _ in range(cfg.gru_layers)]
         self.out_drop_bf = [torch.empty(N, 2 * H, **i16) for _ in range(cfg.gru_layers - 1)] if train else []
         self.whh = [torch.empty(2, 3 * H, H, **i16) for _ in range(cfg.gru_layers)]
@@ -163,11 +143,6 @@ class WorkspaceBf16:
         if L.load().ss_gru_bf16_sync_bytes(B, T, H, C.byref(nb)) != 0:
             raise RuntimeError("ss_gru_bf16_sync_bytes failed")
         self.gru_sync = torch.zeros(nb.value // 4, device=device, dtype=torch.int32) if nb.value else None
-        self.logits = torch.empty(B, cfg.num_classes, **f32)
-        self.attn = torch.empty(B, T, **f32)
-        self.mid_drop = torch.empty(B, cfg.head_mid, **f32)
-        self.ln = torch.empty(B, 2 * H, **f32)
-        self.mid = torch.empty(B, cfg.head_mid, **f32)
         if cfg.use_roi:
             c1, c2, c3, c4 = CNN_CHANNELS
             self.feat = torch.empty(N, c4, **f32)
@@ -177,23 +152,14 @@ class WorkspaceBf16:
             self.a3 = torch.empty(N, 12, 12, c3, **i16)
             self.i3 = torch.empty(N, 12, 12, c3, **u8)
         if train:
-            self.save = [torch.empty(2, N, 4, H, **f32) for _ in range(cfg.gru_layers)]
             # gate gradients: only the bf16 copy (the GEMMs' operand) when the persistent BPTT kernel makes the bias sums itself
             self.dG = [torch.empty(2, N, 4, H, **f32) if self.gru_sync is None else None for _ in range(cfg.gru_layers)]
             self.dG_bf = [torch.empty(2, N, 4, H, **i16) for _ in range(cfg.gru_layers)]
-            self.d_out = torch.empty(N, 2 * H, **f32)
             # scratch of the grouped weight-gradient launches: the largest group of the schedule backward() really runs (round 3
             # sized it for one layer or all layers; with three GRU layers the launches are {2, 1} and {0}, and {2, 1} was larger
             # than either -- 18.9 MB written past the end)
             groups = dw_group_schedule(cfg, B, T, self.kp)
             self.dw_ws = torch.empty(max(4, max(L.gemm_group_ws_floats(g, bf16=True) for g in groups)), **f32) if groups else None
-            self.d_lower = [None] + [torch.empty(N, 2 * H, **f32) for _ in range(1, cfg.gru_layers)]
-            self.xhat = torch.empty(B, 2 * H, **f32)
-            self.rstd = torch.empty(B, **f32)
-            self.d_logits = torch.empty(B, cfg.num_classes, **f32)
-            self.d_mid = torch.empty(B, cfg.head_mid, **f32)
-            self.tail_part = torch.empty(B, 3, 2 * H, **f32)
-            self.dZ = torch.empty(N, cfg.in_dim, **f32) if cfg.use_roi else None
             if cfg.use_roi:
                 c1, c2, c3, c4 = CNN_CHANNELS
                 self.st = torch.empty(N, 2, **f32)
@@ -255,21 +221,8 @@ def forward(P: Dict[str, torch.Tensor], cfg, ws: WorkspaceBf16, X: torch.Tensor,
                ws.save[l].data_ptr() if stash else None, ws.out_bf[l].data_ptr(), ws.out_drop_bf[l].data_ptr() if drop else None,
                cfg.gru_dropout if drop else 0.0, seed, (l + 1) << 40, ws.gru_ws.data_ptr(), L.ptr(ws.gru_sync), L.nbytes(ws.gru_sync), s)
         lin = ws.out_drop_bf[l] if drop else ws.out_bf[l]
-        ws.lin_bf = getattr(ws, "lin_bf", {})
         ws.lin_bf[l + 1] = lin
-    top = ws.out[cfg.gru_layers - 1]
-    p_drop = cfg.head_dropout if train else 0.0
-    y_ptr, ls, denom, loss_ptr, correct_ptr, cw_ptr, den_ptr = (tuple(ce) + (None, None))[:7] if ce is not None else (None, 0.0, 1.0, None, None, None, None)
-    # (class weights: the same launch with the weights and the device-side normaliser in place of the host denom)
-    tail_fwd, ce_norm = ("ss_tail_fwd_w", (cw_ptr, den_ptr)) if cw_ptr else ("ss_tail_fwd", (denom,))
-    L.call(tail_fwd, top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(), P["pool.score.bias"].data_ptr(),
-           P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(), P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(),
-           P["head.4.weight"].data_ptr(), P["head.4.bias"].data_ptr(), y_ptr, B, T, 2 * H, cfg.head_mid, cfg.num_classes, cfg.ln_eps,
-           p_drop, seed, 7 << 40, ls, *ce_norm, ws.attn.data_ptr() if stash else None, ws.xhat.data_ptr() if stash else None,
-           ws.rstd.data_ptr() if stash else None, ws.ln.data_ptr() if stash else None, ws.mid.data_ptr() if stash else None,
-           ws.mid_drop.data_ptr() if stash else None, ws.logits.data_ptr(), ws.d_logits.data_ptr() if ce is not None else None,
-           loss_ptr, correct_ptr, s)
-    return ws.logits
+    return tail_fwd(P, cfg, ws, ws.out[cfg.gru_layers - 1], train, stash, seed, ce)
 
 
 def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: WorkspaceBf16, X: torch.Tensor,
@@ -277,40 +230,10 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: Wo
              d_X: Optional[torch.Tensor] = None) -> None:
     B, T, H, N = ws.B, ws.T, cfg.hidden, ws.B * ws.T
     s = L.stream()
-    Cn, MID = cfg.num_classes, cfg.head_mid
-    p_drop = cfg.head_dropout if train else 0.0
-    top = ws.out[cfg.gru_layers - 1]
-    L.call("ss_tail_bwd", top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(), P["head.0.weight"].data_ptr(),
-           P["head.1.weight"].data_ptr(), P["head.4.weight"].data_ptr(), ws.attn.data_ptr(), ws.xhat.data_ptr(), ws.rstd.data_ptr(),
-           ws.mid.data_ptr(), d_logits.data_ptr(), B, T, 2 * H, MID, Cn, p_drop, seed, 7 << 40, ws.d_mid.data_ptr(),
-           ws.d_out.data_ptr(), G["head.0.weight"].data_ptr(), G["head.0.bias"].data_ptr(), G["pool.score.weight"].data_ptr(),
-           G["pool.score.bias"].data_ptr(), ws.tail_part.data_ptr(), s)
-    def head_grads():
-        # the atomically summed destinations of the d layer_in GEMMs first (the top layer's GEMM waits for them), then what only
-        # feeds parameter gradients of the head: column sums of the rows the tail kernel left per clip, the two Linear weight
-        # gradients (f32, K = B: latency-bound launches that leave the chip empty -- beside the top layer's BPTT kernel they are free)
-        zero_buffers(ws.d_lower[1:] + ([ws.dZ] if cfg.use_roi else []))
-        ws.ev_zero.record()
-        for k_, name_ in enumerate(("head.0.weight", "head.0.bias", "pool.score.weight")):
-            L.call("ss_colsum_f32", _addr(ws.tail_part, k_ * 2 * H), B, 2 * H, 3 * 2 * H, G[name_].data_ptr(), L.stream())
-        gemm_f32(0, 0, Cn, MID, B, d_logits.data_ptr(), Cn, ws.mid_drop.data_ptr(), MID, G["head.4.weight"].data_ptr(), MID,
-                 accumulate=True, atomic=True, a_colsum=G["head.4.bias"].data_ptr())
-        gemm_f32(0, 0, MID, 2 * H, B, ws.d_mid.data_ptr(), MID, ws.ln.data_ptr(), 2 * H, G["head.1.weight"].data_ptr(), 2 * H,
-                 accumulate=True, atomic=True, a_colsum=G["head.1.bias"].data_ptr())
-
-    # the fork event is recorded here, the side stream's launches are enqueued behind the top layer's BPTT launch (below): the host
-    # needs tens of microseconds for them and the main queue sat empty meanwhile (engine.backward, tools/step_gaps.py)
-    if USE_SIDE_STREAM:
-        ws.ev_fork.record()
-
-    def head_side_work():
-        if USE_SIDE_STREAM:
-            with torch.cuda.stream(ws.side):
-                ws.side.wait_event(ws.ev_fork)
-                head_grads()
-        else:
-            head_grads()
-
+    tail_bwd(P, G, cfg, ws, d_logits, train, seed)
+    # the fork event is recorded here, the side stream's launches (engine.head_grads) are enqueued behind the top layer's BPTT launch
+    # (below): the host needs tens of microseconds for them and the main queue sat empty meanwhile (engine.backward, tools/step_gaps.py)
+    fork(ws, USE_SIDE_STREAM)
     zero_waited = False
     dw_pending = []
     use_drop = train and cfg.gru_dropout > 0.0
@@ -325,7 +248,7 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: Wo
                G[f"gru.bias_ih_l{l}_reverse"].data_ptr(), G[f"gru.bias_hh_l{l}_reverse"].data_ptr(), ws.gru_ws.data_ptr(),
                L.ptr(ws.gru_sync), L.nbytes(ws.gru_sync), s)
         if top_layer:
-            head_side_work()
+            on_side(ws, USE_SIDE_STREAM, lambda: head_grads(G, cfg, ws, d_logits))
         Kp = ws.kp[l]
         lin = (ws.lin_bf0 if l == 0 else ws.lin_bf[l]).data_ptr()  # what the forward pass multiplied W_ih with (dropped out or not)
         dg = ws.dG_bf[l].data_ptr()
@@ -387,13 +310,8 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: Wo
             else:
                 gemm(1, 0, N, K - c0, 3 * H, dg, 4 * H, _addr(ws.wih[l], c0), Kp, dst, ld_dst, accumulate=True, atomic=True, batch=2,
                      splits=2 if K - c0 < 128 else 1, strides=(N * 4 * H, 3 * H * Kp, 0, 0), tag="gemm_bf16_dX")
-        if USE_SIDE_STREAM:
-            ws.ev_fork.record()
-            with torch.cuda.stream(ws.side):
-                ws.side.wait_event(ws.ev_fork)
-                param_grads()
-        else:
-            param_grads()
+        fork(ws, USE_SIDE_STREAM)
+        on_side(ws, USE_SIDE_STREAM, param_grads)
     assert not dw_pending, "a weight-gradient group was queued and never launched"  # (dw_flush_after flushes at l == 0)
     if cfg.use_roi:
         if d_X is not None:
@@ -410,13 +328,8 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: Wo
             gemm_f32(0, 0, E, c4, N, dz, cfg.in_dim, ws.feat.data_ptr(), c4, G["roi_cnn.fc.weight"].data_ptr(), c4, accumulate=True,
                      atomic=True, splits=split_k_f32(E, c4, N), a_colsum=G["roi_cnn.fc.bias"].data_ptr(), tag="gemm_fc")
 
-        if USE_SIDE_STREAM:
-            ws.ev_fork.record()
-            with torch.cuda.stream(ws.side):
-                ws.side.wait_event(ws.ev_fork)
-                fc_grads()
-        else:
-            fc_grads()
+        fork(ws, USE_SIDE_STREAM)
+        on_side(ws, USE_SIDE_STREAM, fc_grads)
         L.call("ss_c5_conv_last_wgrad_df", ws.a3.data_ptr(), ws.dfeat.data_ptr(), ws.m4.data_ptr(), N, gw[3], gb[3],
                ws.wg_part.data_ptr(), ws.wg_part.numel(), s, tag="ss_c5_conv_last_wgrad")
         L.call("ss_c5_conv_last_dgrad_df", ws.dfeat.data_ptr(), ws.m4.data_ptr(), N, w[3], ws.da3.data_ptr(), s,
@@ -433,6 +346,4 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg, ws: Wo
         # and conv1's weight gradient as two kernels
         L.call("ss_c5_conv2_dgrad_conv1_wgrad_i1", ws.da2.data_ptr(), ws.i2.data_ptr(), N, w[1], R.data_ptr(), ws.st.data_ptr(),
                int(cfg.roi_standardize), w[0], bb[0], None, gw[0], gb[0], L.ptr(ws.i1), s, tag="ss_c5_conv2_dgrad_conv1_wgrad")
-    if USE_SIDE_STREAM:  # the caller's next kernels (all-reduce, clip, Adam) read every gradient
-        ws.ev_join.record(ws.side)
-        torch.cuda.current_stream().wait_event(ws.ev_join)
+    join_side(ws, USE_SIDE_STREAM)  # the caller's next kernels (all-reduce, clip, Adam) read every gradient

@@ -287,8 +287,7 @@ class BiGRUClassifier(nn.Module):
         if out is None:
             out, ld_out = torch.empty(n, E_, device=frames.device), E_
         P = self._param_dict()
-        cw = [P[k].data_ptr() for k in ("roi_cnn.net.0.weight", "roi_cnn.net.0.bias", "roi_cnn.net.3.weight", "roi_cnn.net.3.bias",
-                                        "roi_cnn.net.6.weight", "roi_cnn.net.6.bias", "roi_cnn.fc.weight", "roi_cnn.fc.bias")]
+        cw = [P[k].data_ptr() for k in E.CNN_PARAMS]
         E.L.call("ss_roi_cnn_fwd", frames.contiguous().data_ptr(), n, Hh, Ww, int(self.cfg.roi_standardize), *cw, E_, out.data_ptr(),
                  int(ld_out), E.L.stream())
         return out
