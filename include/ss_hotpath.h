@@ -335,6 +335,21 @@ int ss_batch_gather_f32_aug(const float* src, int D, const int32_t* frame_map, l
                             ss_stream_t stream);
 int ss_batch_gather_u8_shift(const uint8_t* src, int H, int W, const int32_t* frame_map, long rows, const int32_t* row_shift,
                              int rows_per_clip, int shift_max_x, int shift_max_y, uint8_t* dst, ss_stream_t stream);
+/* Rows of a training batch for a model whose ROI CNN is frozen: the embeddings of the store's frames are constants of the run
+ * (emb (n_frames, E) f32, made once), so the batch carries E floats per frame instead of the pixels.  Row r of dst (rows rows,
+ * ld_dst >= D + E floats apart; columns behind D + E are not written):
+ *   [0, D)     bit for bit what ss_batch_gather_f32_aug writes to row r of a dense (rows, D) destination for the same feat, xmap,
+ *              noise_map, noise_std, seed, noise_first, row_scale and rows_per_clip -- element (r, c) draws element
+ *              noise_first + r * D + c of the noise stream (dense in D, not in ld_dst); row_scale NULL: no scale, i.e. what
+ *              ss_batch_gather_f32_at writes (rows_per_clip is then ignored); noise_map NULL: no noise; xmap[r] < 0: zeros.
+ *   [D, D + E) emb[rmap[r]] where rmap[r] >= 0, else emb_fill (E floats: the embedding of an all-zero frame, which a clip without
+ *              ROI frames gets), or zeros when emb_fill is NULL.  rmap NULL: every row takes the fill (emb may then be NULL).
+ * D, E and ld_dst multiples of 4 and feat, emb, emb_fill, dst 16-byte aligned: 16 bytes per lane; anything else goes element by
+ * element.  SS_ERR_ARG, nothing written: D <= 0, E <= 0, ld_dst < D + E, rows <= 0, noise_std < 0, row_scale with
+ * rows % rows_per_clip != 0, rmap without emb, a base pointer that is not 4-byte aligned. */
+int ss_batch_gather_z(const float* feat, int D, const int32_t* xmap, const float* emb, int E, const int32_t* rmap,
+                      const float* emb_fill, long rows, const int32_t* noise_map, float noise_std, uint64_t seed,
+                      uint64_t noise_first, const float* row_scale, int rows_per_clip, float* dst, int ld_dst, ss_stream_t stream);
 
 /* ---- sliding-window serving of many streams ---------------------------------------
  * per stream a ring of the last max_t frames (features (S,max_t,D) f32, optional ROI (S,max_t,frame_bytes) u8), a head

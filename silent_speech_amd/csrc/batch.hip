@@ -9,9 +9,10 @@
 // (rng "reference" / "device") or from the planning kernels below them: the epoch's class-balanced sample order
 // (:382-397) and the augmentation draws + maps of a batch, both on the Philox stream, nothing crossing PCIe.
 //
-// Five kernels behind the eight entry points:
+// Six kernels behind the nine entry points:
 //   batch_gather_f32_kernel<HOST_NOISE, SCALE>  ss_batch_gather_f32 (<true, false> with a noise table, else <false, false>),
 //                                               ss_batch_gather_f32_at (<false, false>), ss_batch_gather_f32_aug (<false, true>)
+//   batch_gather_z_kernel<W>                    ss_batch_gather_z (W = 4: 16 bytes per lane; W = 1: any row geometry)
 //   batch_gather_u8_kernel                      ss_batch_gather_u8
 //   batch_gather_u8_shift_kernel<WIDE>          ss_batch_gather_u8_shift (WIDE: W % 16 == 0)
 //   epoch_sample_kernel                         ss_epoch_sample
@@ -112,6 +113,82 @@ __global__ __launch_bounds__(256) void batch_gather_f32_kernel(const float* __re
 #pragma unroll
     for (int e = 0; e < 4; ++e)
       if (q + e < total) dst[q + e] = SCALE ? __fmul_rn(v[e], sc[e]) : v[e];
+  }
+}
+
+// component k (0..3) of a float4 by selects: nothing is indexed at run time, so nothing goes to scratch
+__device__ __forceinline__ float pick4(const float4 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
+
+// Rows of a frozen-CNN training batch (ss_batch_gather_z): dst[r] = feature row | embedding row, ld_dst >= D + E floats apart,
+// the columns behind D + E left alone.
+//   [0, D)      what batch_gather_f32_kernel<false, SCALE> writes to row r of a dense (rows, D) destination, bit for bit: element
+//               (r, c) is element n = noise_first + r * D + c of the noise stream -- component n & 3 of Philox block n >> 2, which is
+//               what that kernel's chunk walk hands the same element -- added as noise_std * N in the same expression form (one
+//               contracted multiply-add), then one rounded product with row_scale[r / rows_per_clip] (row_scale NULL: none).
+//   [D, D + E)  emb[rmap[r]] where rmap[r] >= 0, else emb_fill (NULL: zeros); rmap NULL: the fill on every row.
+// One lane per W consecutive elements of a row, W = 4 (one 16-byte load and store per lane; D, E, ld_dst multiples of 4 and every
+// base 16-byte aligned, so a chunk lies inside one half of the row and its noise inside two neighbouring blocks) or W = 1 (any
+// geometry: x_dim = 83 exists in the reference's lineage).
+template <int W>
+__global__ __launch_bounds__(256) void batch_gather_z_kernel(const float* __restrict__ feat, int D,
+                                                             const int32_t* __restrict__ xmap, const float* __restrict__ emb,
+                                                             int E, const int32_t* __restrict__ rmap,
+                                                             const float* __restrict__ emb_fill, long rows,
+                                                             const int32_t* __restrict__ noise_map, float noise_std,
+                                                             uint64_t seed, uint64_t noise_first,
+                                                             const float* __restrict__ row_scale, int rows_per_clip,
+                                                             float* __restrict__ dst, int ld_dst) {
+  static_assert(W == 1 || W == 4, "one element or one 16-byte chunk per lane");
+  const int units = (D + E) / W;  // per row
+  const long total = rows * units;
+  const bool philox = noise_map && noise_std > 0.f;
+  for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)gridDim.x * 256) {
+    const long r = u / units;  // one division per lane and 16-byte chunk, as in the f32 gather
+    const int c = (int)(u - r * units) * W;
+    float v[W];
+    if (c < D) {
+      const int m = xmap[r];
+      const float* s = feat + (long)(m < 0 ? 0 : m) * D + c;
+      if constexpr (W == 4) {
+        const float4 x = m >= 0 ? *reinterpret_cast<const float4*>(s) : float4{0.f, 0.f, 0.f, 0.f};
+        v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+      } else {
+        v[0] = m >= 0 ? *s : 0.f;
+      }
+      if (philox && m >= 0 && noise_map[r] >= 0) {
+        const uint64_t n0 = noise_first + (uint64_t)(r * D + c);
+        const int shift = (int)(n0 & 3);
+        const float4 a = gather_noise4(n0 >> 2, seed);
+#pragma unroll
+        for (int e = 0; e < W; ++e)
+          if (shift + e < 4) v[e] += noise_std * pick4(a, shift + e);
+        if (shift + W > 4) {  // (W == 4 and noise_first & 3 != 0: the same for every chunk)
+          const float4 b = gather_noise4((n0 >> 2) + 1, seed);
+#pragma unroll
+          for (int e = 0; e < W; ++e)
+            if (shift + e >= 4) v[e] += noise_std * pick4(b, shift + e - 4);
+        }
+      }
+      if (row_scale) {
+        const float sc = row_scale[r / rows_per_clip];
+#pragma unroll
+        for (int e = 0; e < W; ++e) v[e] = __fmul_rn(v[e], sc);
+      }
+    } else {
+      const int m = rmap ? rmap[r] : -1;
+      const float* s = m >= 0 ? emb + (long)m * E + (c - D) : emb_fill ? emb_fill + (c - D) : nullptr;
+      if constexpr (W == 4) {
+        const float4 x = s ? *reinterpret_cast<const float4*>(s) : float4{0.f, 0.f, 0.f, 0.f};
+        v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+      } else {
+        v[0] = s ? *s : 0.f;
+      }
+    }
+    float* d = dst + r * ld_dst + c;
+    if constexpr (W == 4)
+      *reinterpret_cast<float4*>(d) = float4{v[0], v[1], v[2], v[3]};
+    else
+      *d = v[0];
   }
 }
 
@@ -473,5 +550,33 @@ extern "C" int ss_batch_gather_u8_shift(const uint8_t* src, int H, int W, const 
   else
     hipLaunchKernelGGL(batch_gather_u8_shift_kernel<false>, dim3((unsigned)blocks), dim3(256), 0,
                        static_cast<hipStream_t>(stream), src, H, W, frame_map, rows, row_shift, rows_per_clip, dst);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_gather_z(const float* feat, int D, const int32_t* xmap, const float* emb, int E, const int32_t* rmap,
+                                 const float* emb_fill, long rows, const int32_t* noise_map, float noise_std, uint64_t seed,
+                                 uint64_t noise_first, const float* row_scale, int rows_per_clip, float* dst, int ld_dst,
+                                 ss_stream_t stream) {
+  SS_REQUIRE(feat && xmap && dst && (emb || !rmap) && rows > 0 && noise_std >= 0.f, SS_ERR_ARG);
+  SS_REQUIRE(D > 0 && E > 0 && (long)D + E <= 0x7fffffffL && ld_dst >= D + E, SS_ERR_ARG);
+  SS_REQUIRE(!row_scale || (rows_per_clip > 0 && rows % rows_per_clip == 0), SS_ERR_ARG);
+  const uintptr_t bases = reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(emb) |
+                          reinterpret_cast<uintptr_t>(emb_fill) | reinterpret_cast<uintptr_t>(dst);
+  SS_REQUIRE((bases & 3) == 0 && (reinterpret_cast<uintptr_t>(row_scale) & 3) == 0, SS_ERR_ARG);
+  SS_REQUIRE(((reinterpret_cast<uintptr_t>(xmap) | reinterpret_cast<uintptr_t>(rmap) | reinterpret_cast<uintptr_t>(noise_map)) & 3) == 0,
+             SS_ERR_ARG);
+  // 16 bytes per lane where every chunk of a row is one aligned float4 on both sides; else one element per lane
+  const bool wide = ((D | E | ld_dst) & 3) == 0 && (bases & 15) == 0;
+  const long lanes = rows * ((D + E) / (wide ? 4 : 1));
+  long blocks = (lanes + 255) / 256;
+  blocks = blocks > 4096 ? 4096 : blocks;
+  if (wide)
+    hipLaunchKernelGGL(batch_gather_z_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), feat, D,
+                       xmap, emb, E, rmap, emb_fill, rows, noise_map, noise_std, seed, noise_first, row_scale,
+                       row_scale ? rows_per_clip : 1, dst, ld_dst);
+  else
+    hipLaunchKernelGGL(batch_gather_z_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), feat, D,
+                       xmap, emb, E, rmap, emb_fill, rows, noise_map, noise_std, seed, noise_first, row_scale,
+                       row_scale ? rows_per_clip : 1, dst, ld_dst);
   return ss_launch_status();
 }

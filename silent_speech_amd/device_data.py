@@ -28,6 +28,12 @@ kernel (without / with the policy), ``ss_batch_gather_f32`` / ``_at`` / ``_aug``
 the latter from any element offset of the stream, with or without the per-clip scale).  Here ``_batch_philox`` is the one
 ``rng="philox"`` path -- only its choice of entry points depends on the policy -- and ``_gather`` the one place that allocates
 ``X`` and ``R`` and launches the two gathers, for every rng.
+
+Fine-tuning with the ROI CNN frozen (``Trainer(freeze_cnn=True)``): a frame's embedding depends on that frame and the CNN's weights
+alone, so ``embed(model)`` runs the CNN over the store ONCE and ``batch(rng="philox", embedded=True)`` returns ``Z``, the rows
+``features | embedding`` the GRU takes, from the unchanged plan kernel and one ``ss_batch_gather_z`` launch: 128 B of embedding per
+frame instead of 4 096 B of pixels.  ``check()`` compares the CNN's parameters with the copy ``embed`` kept, so embeddings that
+have gone stale are an error, not a silent one.
 """
 from __future__ import annotations
 
@@ -149,6 +155,9 @@ class DeviceClipStore:
         self.n_classes_present = len(present)
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)  # set by ss_batch_plan, read by check()
         self._plan_bufs = {}  # batch size -> (xmap, nmap, rmap, lens, y, row_scale, row_shift)
+        # embed(): the frozen CNN's embeddings of the ROI frames, of one all-zero frame, and what they were made from
+        self.E = self.E0 = None
+        self._embed_model = self._embed_params = self._embed_version = None
 
     def __len__(self):
         return len(self.x_len)
@@ -195,11 +204,51 @@ class DeviceClipStore:
         if bad:
             self._err.zero_()
             raise IndexError("DeviceClipStore.batch(rng='philox'): a device index was outside [0, %d)" % len(self))
+        if self._embed_model is not None:  # after embed(): the embeddings are those of the CNN as it is now
+            now = self._embed_model.flat_params[:self._embed_params.numel()]
+            if not torch.equal(now.to(self._embed_params.device), self._embed_params):
+                raise RuntimeError("DeviceClipStore.check(): the model's ROI-CNN parameters have changed since embed(); the "
+                                   "stored embeddings are stale (call embed(model) again, or train with freeze_cnn=True)")
 
-    def empty_batch(self):
+    def embed(self, model, chunk: int = 8192) -> None:
+        """Run ``model``'s ROI CNN over every ROI frame of the store, once: ``self.E`` (sum Tr, roi_emb) f32, ``self.E0``
+        (roi_emb,) f32 = the embedding of one all-zero frame (what a clip without ROI frames stands for inside a ROI store: the
+        pixel path hands the CNN zero frames, and the CNN of a zero frame is not zero).  ``model.embed_rois`` in chunks of ``chunk``
+        frames -- the inference kernel, which treats every frame on its own.  A device copy of the CNN's parameters (the leading
+        range of the flat bucket, ``model.cnn_param_range()``) and ``model._bucket_version`` are kept; ``check()`` raises once the
+        parameters differ from the copy.  ``RuntimeError``: not an f32 ``use_roi`` model, a store without ROI frames, a ROI size
+        outside the fused kernels' set."""
+        from . import cnn_generic
+
+        cfg = getattr(model, "cfg", None)
+        if cfg is None or not cfg.use_roi or cfg.precision != "f32":
+            raise RuntimeError("embed() needs an f32 use_roi model (the bf16 engine has no frozen-CNN path)")
+        if self.R is None:
+            raise RuntimeError("embed(): the store holds no ROI frames")
+        if not cnn_generic.fused_supported(*self.roi_hw):
+            raise RuntimeError("embed(): %dx%d ROI frames are outside the fused CNN kernels' set" % tuple(self.roi_hw))
+        if model.flat_params.device != self.X.device:
+            raise RuntimeError("embed(): the model and the store are on different devices")
+        n, H, W = self.R.shape
+        self.E = torch.empty(n, cfg.roi_emb, device=self.device, dtype=torch.float32)
+        for lo in range(0, n, int(chunk)):
+            hi = min(n, lo + int(chunk))
+            model.embed_rois(self.R[lo:hi], out=self.E[lo:hi], ld_out=cfg.roi_emb)
+        self.E0 = model.embed_rois(torch.zeros(1, H, W, device=self.device, dtype=torch.uint8)).reshape(-1)
+        self._embed_model = model
+        self._embed_params = model.flat_params[:model.cnn_param_range()].detach().clone()
+        self._embed_version = model._bucket_version
+
+    def empty_batch(self, embedded: bool = False):
         """A batch of no clips, shaped like ``batch()``'s: what a data-parallel rank hands ``Trainer.step`` when its shard of a
-        global batch is empty (it still takes the step: the gradient all-reduce is collective)."""
+        global batch is empty (it still takes the step: the gradient all-reduce is collective).  ``embedded``: shaped like
+        ``batch(embedded=True)``'s, for ``Trainer.step_embedded``."""
         dev, mt = self.device, self.max_t
+        if embedded:
+            if self.E is None:
+                raise RuntimeError("empty_batch(embedded=True) needs a prior embed(model)")
+            return (torch.empty(0, mt, self.D + self.E.shape[1], device=dev), torch.empty(0, dtype=torch.int64, device=dev), None,
+                    torch.empty(0, dtype=torch.int64, device=dev))
         R = torch.empty((0, mt) + tuple(self.roi_hw), device=dev, dtype=torch.uint8) if self.R is not None else None
         return (torch.empty(0, mt, self.D, device=dev), torch.empty(0, dtype=torch.int64, device=dev), R,
                 torch.empty(0, dtype=torch.int64, device=dev))
@@ -221,7 +270,16 @@ class DeviceClipStore:
                 L.call("ss_batch_gather_u8_shift", self.R.data_ptr(), H, W, rmap.data_ptr(), B * mt, *shift, R.data_ptr(), s)
         return X, R
 
-    def _batch_philox(self, indices, augment, seed, first_row, batch_first_row=None, policy=None):
+    def _gather_z(self, B, xmap, rmap, tail):
+        """Allocates ``Z`` (B, max_t, D + roi_emb) and fills it with ONE launch: features (noise and scale as the f32 gathers apply
+        them, ``tail`` = ss_batch_gather_z's arguments between ``rows`` and ``dst``) | stored embeddings through ``rmap``."""
+        mt, Eo = self.max_t, self.E.shape[1]
+        Z = torch.empty(B, mt, self.D + Eo, device=self.device)
+        L.call("ss_batch_gather_z", self.X.data_ptr(), self.D, xmap.data_ptr(), self.E.data_ptr(), Eo, rmap.data_ptr(),
+               self.E0.data_ptr(), B * mt, *tail, Z.data_ptr(), self.D + Eo, L.stream())
+        return Z
+
+    def _batch_philox(self, indices, augment, seed, first_row, batch_first_row=None, policy=None, embedded=False):
         mt, dev = self.max_t, self.device
         if isinstance(indices, torch.Tensor) and indices.is_cuda:
             if indices.dtype != torch.int32 or indices.dim() != 1 or not indices.is_contiguous():
@@ -276,13 +334,23 @@ class DeviceClipStore:
                    self._err.data_ptr(), s)
             f32 = ("ss_batch_gather_f32_aug", nmap.data_ptr(), float(NOISE_STD), noise_seed, noise_first, row_scale.data_ptr(), mt)
             shift = (row_shift.data_ptr(), mt, int(mx), int(my))
+        if embedded:  # the same plan, one gather: (noise_map, noise_std, seed, noise_first, row_scale, rows_per_clip)
+            if policy is not None:
+                tail = f32[1:]
+            elif augment:
+                tail = (nmap.data_ptr(), float(NOISE_STD), noise_seed, noise_first, None, 1)
+            else:
+                tail = (None, 0.0, noise_seed, 0, None, 1)
+            Z = self._gather_z(B, xmap, rmap, tail)
+            Z._ss_keep = (idx_d,)
+            return Z, lens, None, y
         X, R = self._gather(B, xmap, rmap, f32, shift)
         X._ss_keep = (idx_d,)
         return X, lens, R, y
 
     def batch(self, indices: Sequence[int], augment: bool = False, rng: str = "device",
               generator: Optional[np.random.Generator] = None, seed: int = 0, first_row: int = 0,
-              batch_first_row: Optional[int] = None, policy: Optional[AugmentPolicy] = None):
+              batch_first_row: Optional[int] = None, policy: Optional[AugmentPolicy] = None, embedded: bool = False):
         """-> X (B,max_t,D) f32, T (B,) i64, R (B,max_t,H,W) u8 or None, y (B,) i64 -- all on the device.
 
         ``rng="philox"``: the plan is made by ``ss_batch_plan`` on the device.  ``indices`` is a device int32 tensor (a
@@ -300,14 +368,28 @@ class DeviceClipStore:
         ``policy`` (``rng="philox"`` with ``augment=True`` only, ``ValueError`` otherwise): an ``AugmentPolicy``; the batch is
         then planned and gathered by ``ss_batch_plan_aug`` / ``ss_batch_gather_f32_aug`` / ``ss_batch_gather_u8_shift``.  The
         decisions are keyed by the row's draw index like the rest of the plan, so shards (``batch_first_row``) stay bit-equal
-        to the single-process batch.  ``None``: exactly the three launches described above."""
+        to the single-process batch.  ``None``: exactly the three launches described above.
+
+        ``embedded`` (``rng="philox"`` only, after ``embed(model)``): -> ``(Z, T, None, y)``, ``Z`` (B, max_t, D + roi_emb) f32 = the
+        rows ``X | CNN(R)`` of the batch the same call returns without it (``model.forward_embedded(Z, T)`` are the logits of
+        ``model(X, T, R)``), from the same plan kernel and ONE ``ss_batch_gather_z`` launch: the features take the same noise and
+        scale bits, the embeddings are read from ``self.E`` through the ROI map (``self.E0`` where a clip has no ROI frames).  Time
+        warp and scale jitter act through the maps and the per-clip scale and work; a policy with ``roi_shift_prob > 0`` is a
+        ``ValueError``, since a shift acts on pixels.  Without ``embedded`` the launches are exactly those described above."""
         if policy is not None:
             if not isinstance(policy, AugmentPolicy):
                 raise TypeError("policy must be an AugmentPolicy")
             if rng != "philox" or not augment:
                 raise ValueError("an AugmentPolicy needs rng='philox' and augment=True")
+        if embedded:
+            if rng != "philox":
+                raise ValueError("embedded=True needs rng='philox': the embedded batch is planned on the device")
+            if policy is not None and policy.roi_shift_prob > 0:
+                raise ValueError("embedded=True cannot apply roi_shift_prob > 0: the shift acts on pixels, the store holds embeddings")
+            if self.E is None:
+                raise RuntimeError("batch(embedded=True) needs a prior embed(model)")
         if rng == "philox":
-            return self._batch_philox(indices, augment, seed, first_row, batch_first_row, policy)
+            return self._batch_philox(indices, augment, seed, first_row, batch_first_row, policy, embedded)
         if batch_first_row is not None:
             raise ValueError("batch_first_row belongs to rng='philox'")
         indices = list(indices)

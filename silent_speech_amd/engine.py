@@ -239,7 +239,8 @@ class WorkspaceBase:
             self.d_logits = torch.empty(B, cfg.num_classes, **f32)
             self.d_mid = torch.empty(B, cfg.head_mid, **f32)
             self.tail_part = torch.empty(B, 3, 2 * H, **f32)  # per-clip terms of d gamma | d beta | d w_score (tail_bwd)
-            self.dZ = torch.empty(N, cfg.in_dim, **f32) if cfg.use_roi else None
+            # (a z_ready workspace, roi_hw None: the ROI CNN is frozen, nothing flows back behind the GRU input)
+            self.dZ = torch.empty(N, cfg.in_dim, **f32) if cfg.use_roi and roi_hw is not None else None
 
 
 class Workspace(WorkspaceBase):
@@ -269,7 +270,7 @@ class Workspace(WorkspaceBase):
             # scratch for the K slices of one layer's weight-gradient GEMMs (the layers follow each other on the side stream)
             self.splitk_ws = torch.empty(max(L.gemm_group_ws_floats(dw_records(cfg, B, T, l, 4, 0, 0, 0, 0, (0, 0), (0, 0)))
                                              for l in range(cfg.gru_layers)), **f32)
-            if cfg.use_roi and self.cnn_generic is None:
+            if cfg.use_roi and roi_hw is not None and self.cnn_generic is None:
                 Hh, Ww = roi_hw
                 # every size comes from the library (the kernels' own LDS images, kept as they are) and goes back to it with
                 # each launch, where the forward and the backward object compare it with the layout they were compiled with
@@ -372,7 +373,9 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
             train: bool, stash: bool = False, seed: int = 0, ce=None, x_in_place: bool = False, z_ready: bool = False) -> torch.Tensor:
     """Runs the forward kernels; returns ws.logits (B,C).  ``ws.lengths`` must already hold the int32 lengths.
     ``z_ready``: X (B,T,in_dim) already holds torch.cat((landmark features, ROI embeddings)) of train_model_official.py:297 -- the
-    embeddings were made when the frames arrived (sliding-window serving) -- and the ROI branch is skipped (inference only).
+    embeddings were made when the frames arrived (sliding-window serving) or once per run (a frozen ROI CNN:
+    ``DeviceClipStore.embed``) -- and the ROI branch, the frame list and the CNN stash are skipped; the layer input is X itself.
+    ``train`` / ``stash`` then need a workspace built with ``roi_hw=None`` (``backward(frozen_cnn=True)`` follows).
     ``train`` turns the two dropouts on (p from cfg); ``stash`` keeps what ``backward`` needs (needs a
     Workspace built with train=True).  ``ce = (y_ptr, label_smoothing, denom, loss_ptr, correct_ptr)`` makes the
     fused tail kernel also evaluate the loss and leave d(loss)/d(logits) in ``ws.d_logits``; two more entries,
@@ -381,6 +384,8 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
     if ws.bf16:
         from . import engine_bf16
 
+        if z_ready:
+            raise RuntimeError("z_ready: the bf16 engine has no path for rows that already hold the embeddings")
         return engine_bf16.forward(P, cfg, ws, X, R, train=train, stash=stash, seed=seed, ce=ce, x_in_place=x_in_place)
     B, T, H, N = ws.B, ws.T, cfg.hidden, ws.B * ws.T
     s = L.stream()
@@ -388,8 +393,10 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
         raise RuntimeError("stash=True needs a training workspace")
     # ---- ROI branch: normalise + CNN -> columns [x_dim, x_dim+E) of Z; X -> columns [0, x_dim)
     if z_ready:
-        if stash or train or not cfg.use_roi or X.shape[2] != cfg.in_dim:
-            raise RuntimeError("z_ready: inference on rows of width in_dim = x_dim + roi_emb of a use_roi model")
+        if not cfg.use_roi or X.shape[2] != cfg.in_dim:
+            raise RuntimeError("z_ready: rows of width in_dim = x_dim + roi_emb of a use_roi model")
+        if (stash or train) and ws.roi_hw is not None:
+            raise RuntimeError("z_ready: train / stash need a workspace built with roi_hw=None")
         layer_in, ld_in = X.data_ptr(), cfg.in_dim
     elif cfg.use_roi:
         Hh, Ww = ws.roi_hw
@@ -443,9 +450,14 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
 
 def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Tensor,
              R: Optional[torch.Tensor], d_logits: torch.Tensor, *, train: bool, seed: int = 0,
-             d_X: Optional[torch.Tensor] = None) -> None:
+             d_X: Optional[torch.Tensor] = None, frozen_cnn: bool = False) -> None:
     """Accumulates d(loss)/d(param) into ``G`` (same keys as ``P``) given d(loss)/d(logits).
-    Must follow a ``forward(..., train=<same>, seed=<same>)`` on the same workspace."""
+    Must follow a ``forward(..., train=<same>, seed=<same>)`` on the same workspace.
+    ``frozen_cnn`` (after ``forward(z_ready=True, stash=True)``; f32 engine only): X is the ``Z`` that forward took, layer 0's
+    weight-gradient group reads it, and the pass stops at the GRU input as it does for a landmark-only model: no layer-0
+    d layer_in GEMM, no ``dZ``, no ROI-CNN backward, and no CNN entry of ``G`` is written."""
+    if frozen_cnn and (ws.bf16 or not cfg.use_roi or ws.roi_hw is not None or d_X is not None):
+        raise RuntimeError("frozen_cnn: the f32 engine, a use_roi model, a workspace built with roi_hw=None, and no d_X")
     if ws.bf16:
         from . import engine_bf16
 
@@ -476,7 +488,9 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
         if top_layer:
             on_side(ws, USE_SIDE_STREAM, lambda: head_grads(G, cfg, ws, d_logits))
         if l == 0:
-            if cfg.use_roi:
+            if frozen_cnn:
+                lin, ld_in = X.data_ptr(), cfg.in_dim
+            elif cfg.use_roi:
                 lin, ld_in = ws.Z.data_ptr(), cfg.in_dim
             else:
                 lin, ld_in = X.data_ptr(), cfg.x_dim
@@ -496,7 +510,7 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
         if l == 0:
             side_work()
         # d layer_in = dGi_f . W_ih_f + dGi_r . W_ih_r
-        need_dx = (l > 0) or cfg.use_roi or (d_X is not None)
+        need_dx = (l > 0) or (cfg.use_roi and not frozen_cnn) or (d_X is not None)
         if need_dx:
             # both directions in ONE launch (twice the workgroups: the N=116 case alone leaves half the CUs idle),
             # summed with float atomics into a destination that was zeroed on the side stream.  (Measured alternative:
@@ -532,7 +546,7 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
     # stream at that point would only finish after it (measured: a 180 us tail), so let them drain first -- they run beside the
     # d layer_in GEMM above and cost the critical path a few tens of microseconds.  (Nothing is queued there behind the join.)
     join_side(ws, USE_SIDE_STREAM)
-    if cfg.use_roi:
+    if cfg.use_roi and not frozen_cnn:
         Hh, Ww = ws.roi_hw
         if ws.cnn_generic is not None:
             ws.cnn_generic.backward(P, G, cfg.roi_emb, _addr(ws.dZ, cfg.x_dim), cfg.in_dim)

@@ -25,6 +25,7 @@ import collections
 import contextlib
 import dataclasses
 import glob
+import hashlib
 import os
 import random
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
@@ -223,7 +224,7 @@ class EvalResult:
 @torch.no_grad()
 def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = BATCH_SIZE, label_smoothing: float = 0.05,
                     rank: int = 0, world_size: int = 1, process_group=None,
-                    extra_sums: Optional[torch.Tensor] = None, class_weights=None) -> EvalResult:
+                    extra_sums: Optional[torch.Tensor] = None, class_weights=None, embedded: bool = False) -> EvalResult:
     """``evaluate`` with the validation state kept on the device.  The rank evaluates the clips
     ``shard_range(len(store), rank, world_size)`` of the store, in order, eval mode, no augmentation: batches planned by
     ``store.batch(rng="philox")``, one ``ss_eval_accum`` launch per batch (``first_row`` = the clip's index in the store),
@@ -235,7 +236,10 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
     ``class_weights`` (one finite positive number per class): ``ss_eval_accum_w`` keeps two sums, the per-clip weighted losses
     and w[label]; both add over ranks (the second rides in the same ``sums`` vector: no new collective) and ``loss`` is their
     quotient over the whole store -- ``EvalResult.loss_sum / weight_sum``.  As in ``evaluate`` this is not the reference's
-    average of per-batch means, which would change with the batch size and the world size."""
+    average of per-batch means, which would change with the batch size and the world size.
+    ``embedded`` (after ``store.embed(model)``; a frozen ROI CNN): the batches are ``store.batch(embedded=True)`` and the logits
+    come from ``model.forward_embedded`` -- the ``z_ready`` forward, no CNN launch; the same logits while the embeddings are those
+    of the model's CNN (``store.check()`` tells)."""
     from . import _lib as L
 
     cw = None if class_weights is None else check_class_weights(class_weights, model.cfg.num_classes)
@@ -254,8 +258,12 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
     model.eval()
     for b0 in range(lo, hi, batch_size):
         b1 = min(hi, b0 + batch_size)
-        X, T, R, y = store.batch(every[b0:b1], augment=False, rng="philox")
-        logits = model(X, T, R if model.use_roi else None).contiguous()
+        if embedded:
+            Z, T, _, y = store.batch(every[b0:b1], augment=False, rng="philox", embedded=True)
+            logits = model.forward_embedded(Z, T).contiguous()
+        else:
+            X, T, R, y = store.batch(every[b0:b1], augment=False, rng="philox")
+            logits = model(X, T, R if model.use_roi else None).contiguous()
         if cw is None:
             L.call("ss_eval_accum", logits.data_ptr(), y.data_ptr(), b1 - b0, C, label_smoothing, b0, loss_sum.data_ptr(),
                    counts.data_ptr(), confusion.data_ptr(), first_seen.data_ptr(), y_true.data_ptr() + 4 * (b0 - lo),
@@ -285,23 +293,54 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
 
 
 def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_roi, n_train, n_val, class_weights,
-                    augment_policy, ema_decay) -> dict:
+                    augment_policy, ema_decay, init_from=None, freeze_cnn=False) -> dict:
     """What a resumable ``fit`` run depends on, as plain values (``checkpoint.FINGERPRINT_FIELDS``): a train-state file is
     resumed only by a call whose fingerprint equals the saved one.  ``epochs`` and ``patience`` are not part of it: a run may be
-    resumed to train longer."""
+    resumed to train longer.  ``init_from`` (the sha256 of the checkpoint file the run started from, a hex string) and
+    ``freeze_cnn`` are entries only when they are set: the fingerprint of a run without them is what it always was."""
+    extra = {}
+    if init_from is not None:
+        extra["init_from"] = str(init_from)
+    if freeze_cnn:
+        extra["freeze_cnn"] = True
     return dict(seed=int(seed), batch_size=int(batch_size), world_size=int(world_size), max_t=int(max_t), lr=float(lr),
                 labels=[str(lab) for lab in labels], x_dim=int(x_dim), use_roi=bool(use_roi), n_train=int(n_train),
                 n_val=int(n_val), class_weights=None if class_weights is None else [float(w) for w in class_weights],
                 augment_policy=None if augment_policy is None else {k: (list(v) if isinstance(v, tuple) else v) for k, v in
                                                                     dataclasses.asdict(augment_policy).items()},
-                ema_decay=None if ema_decay is None else float(ema_decay))
+                ema_decay=None if ema_decay is None else float(ema_decay), **extra)
+
+
+def file_sha256(path: str) -> str:
+    h = hashlib.sha256()
+    with open(path, "rb") as f:
+        for block in iter(lambda: f.read(1 << 20), b""):
+            h.update(block)
+    return h.hexdigest()
+
+
+def load_init_checkpoint(path: str, x_dim: int, use_roi: bool, roi_emb: int, hidden: int) -> dict:
+    """The checkpoint ``fit(init_from=)`` starts from (reference schema, read as ``load_classifier`` reads it), checked against the
+    scanned clips: ``ValueError`` naming the first of ``x_dim``, ``use_roi``, ``roi_emb``, ``hidden`` that does not match.
+    -> the checkpoint dict.  Host code only."""
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    sd = ckpt["model"]
+    have = dict(x_dim=int(ckpt["x_dim"]), use_roi=bool(ckpt.get("use_roi", False)),
+                roi_emb=int(sd["roi_cnn.fc.weight"].shape[0]) if "roi_cnn.fc.weight" in sd else roi_emb,
+                hidden=int(sd["gru.weight_hh_l0"].shape[1]))
+    want = dict(x_dim=int(x_dim), use_roi=bool(use_roi), roi_emb=int(roi_emb), hidden=int(hidden))
+    for field in ("x_dim", "use_roi", "roi_emb", "hidden"):
+        if have[field] != want[field]:
+            raise ValueError(f"init_from {path}: {field} is {have[field]!r}, the clips need {want[field]!r}")
+    return ckpt
 
 
 def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BATCH_SIZE, patience: int = PATIENCE,
         max_t: int = 90, lr: float = 3e-4, seed: int = SEED, use_roi_if_present: bool = True, device="cuda",
         log=print, plan: str = "host", rank: int = 0, world_size: int = 1, process_group=None,
         history: Optional[list] = None, class_weights=None, augment_policy=None, ema_decay: Optional[float] = None,
-        state_path: Optional[str] = None, resume: bool = False) -> float:
+        state_path: Optional[str] = None, resume: bool = False, init_from: Optional[str] = None,
+        freeze_cnn: bool = False) -> float:
     """The reference's ``main()``: scan, split, train with class-balanced sampling and on-device augmentation, evaluate
     every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement.
 
@@ -347,9 +386,32 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     call's raises ``ValueError`` naming the first differing field, model, trainer, ``best`` and ``bad`` are restored and the run
     continues at the next epoch -- up to the order of the float atomics it is the uninterrupted run.  A saved run that had
     reached ``epochs`` or had stopped early returns ``best`` without training.  ``resume=True`` without a file starts fresh.
-    ``history`` gets only the epochs this call ran."""
+    ``history`` gets only the epochs this call ran.
+
+    ``init_from`` (the reference trains from scratch only): a checkpoint in the reference schema, loaded as ``load_classifier``
+    reads it, to start from -- adapting a shipped model to a new speaker or word list.  Its ``x_dim``, ``use_roi``, ``roi_emb``
+    and ``hidden`` must match the scanned clips (``ValueError`` naming the field).  Every tensor is copied; if the label list
+    differs, ``head.4.weight`` and ``head.4.bias`` keep their fresh initialisation, which is logged.  Data parallel, the broadcast
+    from rank 0 follows the load.
+
+    ``freeze_cnn`` (needs ``plan="device"``, clips with ROI frames and ``init_from``: a frozen random CNN is a mistake): the ROI
+    CNN is not trained.  Both stores run it over their frames once (``store.embed(model)``), the training batches are
+    ``batch(embedded=True)`` into ``Trainer.step_embedded`` and validation is ``evaluate_device(embedded=True)``: no step and no
+    validation batch launches the CNN or moves a pixel.  ``store.check()`` (once per epoch) also verifies that the CNN still is
+    the one the embeddings were made with.  The checkpoint written is the full model in the reference schema.  ``ROI shift`` in
+    an ``augment_policy`` is refused (it acts on pixels).
+
+    ``state_path``: the fingerprint holds ``init_from`` (the file's sha256) and ``freeze_cnn`` only when they are set, so the
+    files of runs without them are unchanged."""
     if plan not in ("host", "device"):
         raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
+    if freeze_cnn:  # (before anything touches a device or the clips)
+        if plan != "device":
+            raise ValueError("freeze_cnn needs plan='device': the embedded batches are planned on the device")
+        if init_from is None:
+            raise ValueError("freeze_cnn needs init_from: a frozen, randomly initialised ROI CNN is a mistake")
+        if augment_policy is not None and isinstance(augment_policy, AugmentPolicy) and augment_policy.roi_shift_prob > 0:
+            raise ValueError("freeze_cnn cannot apply roi_shift_prob > 0: the shift acts on pixels")
     if augment_policy is not None:
         if not isinstance(augment_policy, AugmentPolicy):
             raise TypeError("augment_policy must be an AugmentPolicy")
@@ -378,10 +440,16 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     train_labels = [str(np.load(f, allow_pickle=True)["label"]) for f in train_files]
     if isinstance(class_weights, str):
         class_weights = check_class_weights(balanced_class_weights(train_labels, info["id_to_label"]), len(info["uniq"]))
+    if freeze_cnn and not use_roi:
+        raise ValueError("freeze_cnn needs clips with ROI frames (and use_roi_if_present)")
+    init_ckpt = None
+    if init_from is not None:  # (host code: the mismatches raise before anything is uploaded)
+        init_ckpt = load_init_checkpoint(init_from, info["x_dim"], use_roi, 32, 192)
     saved, fingerprint = None, None
     if state_path is not None:
         fingerprint = run_fingerprint(seed, batch_size, world_size, max_t, lr, info["uniq"], info["x_dim"], use_roi,
-                                      len(train_files), len(val_files), class_weights, augment_policy, ema_decay)
+                                      len(train_files), len(val_files), class_weights, augment_policy, ema_decay,
+                                      init_from=None if init_from is None else file_sha256(init_from), freeze_cnn=freeze_cnn)
         if resume and os.path.exists(state_path):
             saved = load_train_state(state_path)
             field = fingerprint_difference(saved["fingerprint"], fingerprint)
@@ -397,13 +465,23 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                 return float(saved["best"])
     train_store = DeviceClipStore(train_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
     val_store = DeviceClipStore(val_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
-    model = BiGRUClassifier(info["x_dim"], len(info["uniq"]), use_roi=use_roi, roi_emb=32, hidden=192).to(device).train()
+    model = BiGRUClassifier(info["x_dim"], len(info["uniq"]), use_roi=use_roi, roi_emb=32, hidden=192,
+                            gru_layers=2 if init_ckpt is None else int(init_ckpt.get("gru_layers", 2))).to(device).train()
+    if init_ckpt is not None:
+        sd = dict(init_ckpt["model"])
+        if list(init_ckpt["labels"]) != list(info["uniq"]):
+            log(f"init_from {init_from}: its {len(init_ckpt['labels'])} labels differ from the clips' {len(info['uniq'])}; "
+                "head.4.weight and head.4.bias keep their fresh initialisation")
+            fresh = model.state_dict()
+            sd["head.4.weight"], sd["head.4.bias"] = fresh["head.4.weight"], fresh["head.4.bias"]
+        model.load_state_dict(sd)
     if process_group is not None:
         import torch.distributed as dist
 
         dist.broadcast(model.flat_params, src=dist.get_global_rank(process_group, 0), group=process_group)
     trainer = Trainer(model, lr=lr, world_size=world_size, process_group=process_group,
-                      always_allreduce=process_group is not None, class_weights=class_weights, ema_decay=ema_decay)
+                      always_allreduce=process_group is not None, class_weights=class_weights, ema_decay=ema_decay,
+                      freeze_cnn=freeze_cnn)
     trainer.rank = rank
     # validation and the checkpoint see the averaged weights when there are any (two swap launches around each)
     averaged = trainer.ema_weights if ema_decay is not None else contextlib.nullcontext
@@ -415,6 +493,9 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
         trainer.load_state_dict(saved["trainer"])
         best, bad, first_epoch = float(saved["best"]), int(saved["bad"]), int(saved["epoch"]) + 1
         log(f"Resuming from {state_path} at epoch {first_epoch} (best val acc {best:.3f})")
+    if freeze_cnn:  # (behind the load, the broadcast and a resume: the CNN is final now, and the same on every rank)
+        train_store.embed(model)
+        val_store.embed(model)
     for ep in range(first_epoch, epochs + 1):
         epoch_base = (ep - 1) * len(train_store)
         if plan == "device":
@@ -430,17 +511,22 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                 if hi > lo:
                     X, T, R, y = train_store.batch(order[lo:hi], augment=True, rng="philox", seed=seed,
                                                    first_row=epoch_base + first_row,
-                                                   batch_first_row=epoch_base + lo - lo % batch_size, policy=augment_policy)
+                                                   batch_first_row=epoch_base + lo - lo % batch_size, policy=augment_policy,
+                                                   embedded=freeze_cnn)
                 else:
-                    X, T, R, y = train_store.empty_batch()
+                    X, T, R, y = train_store.empty_batch(embedded=freeze_cnn)
                 # (the loss is this rank's part of the global mean: the parts of all ranks sum to it)
-                loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch,
-                                             y_global=None if y_epoch is None else y_epoch[k * batch_size:k * batch_size + global_batch])
+                y_glob = None if y_epoch is None else y_epoch[k * batch_size:k * batch_size + global_batch]
+                if freeze_cnn:  # (X is Z: the rows features | embedding)
+                    loss, correct = trainer.step_embedded(X, T, y, global_batch=global_batch, y_global=y_glob)
+                else:
+                    loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch, y_global=y_glob)
                 tr_loss += loss * global_batch
                 tr_ok += correct
             with averaged():
                 res = evaluate_device(model, val_store, batch_size, rank=rank, world_size=world_size, process_group=process_group,
-                                      extra_sums=torch.stack([tr_loss.double(), tr_ok.double()]), class_weights=class_weights)
+                                      extra_sums=torch.stack([tr_loss.double(), tr_ok.double()]), class_weights=class_weights,
+                                      embedded=freeze_cnn)
             train_store.check()  # (the evaluation above has synchronised)
             val_store.check()
             va_loss, va_acc, tr_loss, tr_ok = res.loss, res.acc, res.extra[0], res.extra[1]

@@ -180,6 +180,18 @@ class BiGRUClassifier(nn.Module):
             off += (p.numel() + 3) // 4 * 4  # keep every tensor 16-byte aligned for the vector loads
         return lay, off
 
+    def cnn_param_range(self) -> int:
+        """``n_cnn``: the ROI CNN's parameters are elements ``[0, n_cnn)`` of the flat buckets.  ``roi_cnn`` is the first module
+        registered, so its tensors lead ``_layout``; every tensor starts 16-byte aligned, so ``n_cnn`` is a multiple of 4 and the
+        rest of the bucket, ``[n_cnn, n)``, starts aligned as well -- the optimiser's entry points run on it unchanged
+        (``Trainer(freeze_cnn=True)``).  0 without a ROI branch."""
+        lay, total = self._layout()
+        cnn = [k for k, (name, *_) in enumerate(lay) if name.startswith("roi_cnn.")]
+        assert cnn == list(range(len(cnn))), "the ROI CNN's parameters must lead the flat bucket"
+        n_cnn = lay[len(cnn)][1] if len(cnn) < len(lay) else total
+        assert n_cnn % 4 == 0
+        return n_cnn
+
     def _views_of(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         return {name: flat[off:off + n].view(shape) for name, off, n, shape in self._layout()[0]}
 
@@ -237,6 +249,16 @@ class BiGRUClassifier(nn.Module):
         if ws is None:
             ws = E.make_workspace(self.cfg, B, T, hw, X.device, train, slot)
             self._ws_cache[key] = ws
+        return ws
+
+    def _workspace_embedded(self, Z, train: bool, slot=0) -> E.Workspace:
+        """Buffers for rows that already hold the embeddings (``forward(z_ready=True)``): built with ``roi_hw=None``, so without
+        ``Z`` / ``dZ``, the frame list and the CNN stashes."""
+        B, T, _ = Z.shape
+        key = (B, T, "embedded", train, Z.device, slot)
+        ws = self._ws_cache.get(key)
+        if ws is None:
+            ws = self._ws_cache[key] = E.make_workspace(self.cfg, B, T, None, Z.device, train, slot)
         return ws
 
     def check_health(self) -> None:
@@ -298,11 +320,7 @@ class BiGRUClassifier(nn.Module):
         if not self.use_roi or self.cfg.precision != "f32" or Z.dim() != 3 or Z.shape[2] != self.cfg.in_dim or not Z.is_cuda:
             raise RuntimeError(f"Z must be (B,T,{self.cfg.in_dim}) on the HIP device of a use_roi model")
         Z = Z.contiguous().float()
-        B, T, _ = Z.shape
-        key = (B, T, "embedded", False, Z.device, 0)
-        ws = self._ws_cache.get(key)
-        if ws is None:
-            ws = self._ws_cache[key] = E.make_workspace(self.cfg, B, T, None, Z.device, False)
+        ws = self._workspace_embedded(Z, train=False)
         ws.lengths.copy_(lengths.to(torch.int32), non_blocking=True)
         with torch.no_grad():
             return E.forward(self._param_dict(), self.cfg, ws, Z, None, train=False, z_ready=True).clone()

@@ -91,7 +91,21 @@ class Trainer:
     the step.  An empty shard updates it like every other rank's, so the ranks' averages stay the same bits as their parameters
     do.  ``ema_weights()`` puts the average behind the module's parameters for a block of code; ``state_dict()`` /
     ``load_state_dict()`` carry the moments, the average and the step count (``harness.fit(state_path=)``).  Without
-    ``ema_decay`` a step issues exactly the launches it always has."""
+    ``ema_decay`` a step issues exactly the launches it always has.
+
+    ``freeze_cnn`` (an f32 ``use_roi`` model; fine-tuning a shipped checkpoint on a few clips): the ROI CNN is not trained, so its
+    embeddings of the clips are constants of the run (``DeviceClipStore.embed``) and the step is ``step_embedded(Z, lengths, y)``
+    on batches that already hold them (``store.batch(embedded=True)``): the ``z_ready`` forward, a backward that stops at the GRU
+    input -- no ``ss_roi_cnn_*`` launch, no layer-0 d layer_in GEMM -- and the optimiser on the rest of the bucket.  ``roi_cnn`` is
+    registered first, so its parameters are the leading range ``[0, n_cnn)`` of the flat bucket (``model.cnn_param_range()``, a
+    multiple of 4 elements), and the existing entry points -- the zeroing, ``ss_sumsq_f32``, the all-reduce, ``ss_adam_clip`` /
+    ``ss_adam_clip_ema``, ``ss_swap_f32`` -- simply run on ``[n_cnn, n)``.  Consequences: the frozen parameters and their average
+    keep their exact bits (no launch ever writes them: not an update with a zero gradient, which would still move ``m``, ``v`` and
+    the average); the clip norm is taken over the trainable parameters, as ``clip_grad_norm_`` sees a model whose CNN has
+    ``requires_grad=False``, and ``grad_norm()`` reports that norm.  ``step`` on such a trainer raises, and so does
+    ``step_embedded`` on any other: mixing the two would silently skip or apply CNN updates.  ``micro_batches`` > 1 is a
+    ``ValueError``.  Class weights, the weight average, ``state_dict`` / ``load_state_dict`` and empty shards work as in ``step``.
+    Without ``freeze_cnn`` a step issues exactly the launches it always has."""
 
     # CUs left to the other micro-batch's recurrence while a persistent ROI-CNN kernel runs (2 directions x 8 slices)
     CNN_RESERVED_CUS = 32
@@ -99,7 +113,12 @@ class Trainer:
     def __init__(self, model: BiGRUClassifier, lr: float = 3e-4, max_norm: float = 1.0,
                  label_smoothing: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  process_group=None, dropout: bool = True, micro_batches: int = 1, always_allreduce: bool = False,
-                 class_weights=None, ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 class_weights=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, freeze_cnn: bool = False):
+        if freeze_cnn:
+            if not model.cfg.use_roi or model.cfg.precision != "f32":
+                raise RuntimeError("freeze_cnn needs an f32 use_roi model (the bf16 engine has no frozen-CNN path)")
+            if int(micro_batches) > 1:
+                raise ValueError("freeze_cnn does not combine with micro_batches > 1")
         cw = None if class_weights is None else check_class_weights(class_weights, model.cfg.num_classes)
         if ema_decay is not None:
             ema_decay = float(ema_decay)
@@ -127,6 +146,9 @@ class Trainer:
         # class weights (uploaded once) and the step's normaliser, sum of w[y] over the global batch: both stay on the device
         self.cw = None if cw is None else torch.from_numpy(cw).to(dev)
         self.den = None if cw is None else torch.zeros(1, device=dev, dtype=torch.float32)
+        self.freeze_cnn = bool(freeze_cnn)
+        # the optimiser's range of the flat bucket is [n_frozen, n): everything, or everything behind the ROI CNN
+        self.n_frozen = model.cnn_param_range() if freeze_cnn else 0
         self.step_count = 0
         self.rank = 0
         if world_size > 1:
@@ -158,6 +180,8 @@ class Trainer:
                 self.cw, self.den = self.cw.to(flat.device), self.den.to(flat.device)
         self.G = model._views_of(model.flat_grads)
         model.attach_flat_grads()
+        if self.n_frozen:  # never written by a frozen step and never read by its optimiser: zero, whatever was there
+            model.flat_grads[:self.n_frozen].zero_()
         self._bucket_version = model._bucket_version
 
     def step(self, X: torch.Tensor, lengths: torch.Tensor, R: Optional[torch.Tensor], y: torch.Tensor,
@@ -175,6 +199,8 @@ class Trainer:
         instead of ``global_batch`` -- taken by one fixed-order launch, so every rank divides by the same bits -- and the returned
         loss is this rank's part of the global weighted mean.  Every micro-batch uses the same sum."""
         model, cfg = self.model, self.model.cfg
+        if self.freeze_cnn:
+            raise RuntimeError("Trainer.step on a freeze_cnn trainer: it would train the ROI CNN (use step_embedded)")
         if self._ema_swapped:
             raise RuntimeError("Trainer.step inside ema_weights(): the parameters are the averaged ones there")
         if model._bucket_version != self._bucket_version:
@@ -201,18 +227,7 @@ class Trainer:
             model.flat_grads.zero_()
             self.scal.zero_()
             self.correct.zero_()
-        ce_w = (None, None)
-        if self.cw is not None and B > 0:
-            yg = y if y_global is None else y_global
-            if not yg.is_cuda or yg.dim() != 1 or yg.numel() == 0:
-                raise ValueError("y_global must be a non-empty 1-D device tensor of labels")
-            if yg.dtype != torch.int64 or not yg.is_contiguous():
-                yg = yg.to(torch.int64).contiguous()
-            # (before the micro-batch streams fork: they wait for ev_start, recorded behind this launch)
-            L.call("ss_class_weight_sum", yg.data_ptr(), yg.numel(), self.cw.data_ptr(), cfg.num_classes, self.den.data_ptr(),
-                   L.stream())
-            ce_w = (self.cw.data_ptr(), self.den.data_ptr())
-        self._ce_w = ce_w
+        self._weight_sum(B, y, y_global)
         if B == 0:
             pass  # an empty shard: this rank's gradient is the zero bucket
         elif M == 1:
@@ -243,34 +258,99 @@ class Trainer:
             for ev in self.ev_done:
                 cur.wait_event(ev)
             L.call("ss_roi_cnn_set_max_workgroups", 0)
-        s = L.stream()
+        self._reduce_clip_adam()
+        return self.scal[0], self.correct[0]
+
+    def _weight_sum(self, B, y, y_global):
+        """Class weights: the step's normaliser, sum of w[label] over the global batch, by one launch; sets ``self._ce_w``."""
+        ce_w = (None, None)
+        if self.cw is not None and B > 0:
+            yg = y if y_global is None else y_global
+            if not yg.is_cuda or yg.dim() != 1 or yg.numel() == 0:
+                raise ValueError("y_global must be a non-empty 1-D device tensor of labels")
+            if yg.dtype != torch.int64 or not yg.is_contiguous():
+                yg = yg.to(torch.int64).contiguous()
+            # (before the micro-batch streams fork: they wait for ev_start, recorded behind this launch)
+            L.call("ss_class_weight_sum", yg.data_ptr(), yg.numel(), self.cw.data_ptr(), self.model.cfg.num_classes,
+                   self.den.data_ptr(), L.stream())
+            ce_w = (self.cw.data_ptr(), self.den.data_ptr())
+        self._ce_w = ce_w
+
+    def _reduce_clip_adam(self):
+        """Behind backward: the gradient all-reduce, the global norm, clip + Adam (+ the weight average), each on elements
+        ``[n_frozen, n)`` of the flat buckets -- all of them unless the ROI CNN is frozen."""
+        model, s, lo = self.model, L.stream(), self.n_frozen
+        grads = model.flat_grads if lo == 0 else model.flat_grads[lo:]
         if self.world > 1 or self.always_allreduce:
             if self.allreduce_events is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            allreduce_flat_grads(model.flat_grads, self.group, always=self.always_allreduce)
+            allreduce_flat_grads(grads, self.group, always=self.always_allreduce)
             if self.allreduce_events is not None:
                 e1.record()
                 self.allreduce_events.append((e0, e1))
-        n_el = model.flat_grads.numel()
-        L.call("ss_sumsq_f32", model.flat_grads.data_ptr(), n_el, self.scal.data_ptr() + 4, s)
+        n_el, at = model.flat_grads.numel() - lo, 4 * lo
+        L.call("ss_sumsq_f32", model.flat_grads.data_ptr() + at, n_el, self.scal.data_ptr() + 4, s)
         # d_logits already carries 1/(B*world), so the summed bucket IS the global-mean gradient
         if self.ema is None:
-            L.call("ss_adam_clip", model.flat_params.data_ptr(), model.flat_grads.data_ptr(), self.m.data_ptr(),
-                   self.v.data_ptr(), n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr, self.betas[0],
+            L.call("ss_adam_clip", model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at, self.m.data_ptr() + at,
+                   self.v.data_ptr() + at, n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr, self.betas[0],
                    self.betas[1], self.eps, self.step_count, s)
         else:  # the same update of p, m, v, and the weight average in the same pass over the bucket
-            L.call("ss_adam_clip_ema", model.flat_params.data_ptr(), model.flat_grads.data_ptr(), self.m.data_ptr(),
-                   self.v.data_ptr(), self.ema.data_ptr(), n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr,
+            L.call("ss_adam_clip_ema", model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at, self.m.data_ptr() + at,
+                   self.v.data_ptr() + at, self.ema.data_ptr() + at, n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr,
                    self.betas[0], self.betas[1], self.eps, self.step_count,
                    ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup), s)
+
+    def step_embedded(self, Z: torch.Tensor, lengths: torch.Tensor, y: torch.Tensor, global_batch: Optional[int] = None,
+                      y_global: Optional[torch.Tensor] = None):
+        """``step`` of a ``freeze_cnn`` trainer: ``Z`` (B, T, x_dim + roi_emb) f32 on the device already holds
+        torch.cat((features, ROI embeddings)) (``store.batch(embedded=True)``).  Same returns, ``global_batch``, ``y_global`` and
+        empty-shard rule as ``step``; the dropout seeds are the same function of the step count, so with embeddings of the
+        current CNN it is the step ``step`` takes, minus everything that belongs to the CNN (class docstring)."""
+        model, cfg = self.model, self.model.cfg
+        if not self.freeze_cnn:
+            raise RuntimeError("Trainer.step_embedded needs Trainer(freeze_cnn=True): this trainer updates the ROI CNN")
+        if self._ema_swapped:
+            raise RuntimeError("Trainer.step_embedded inside ema_weights(): the parameters are the averaged ones there")
+        if Z.dim() != 3 or Z.shape[2] != cfg.in_dim or not Z.is_cuda or Z.dtype != torch.float32:
+            raise RuntimeError(f"Z must be f32 (B,T,{cfg.in_dim}) on the HIP device")
+        if model._bucket_version != self._bucket_version:
+            self._bind_bucket()
+        Z = Z.contiguous()
+        B, T = Z.shape[:2]
+        self.step_count += 1
+        train = self.dropout and model.training
+        denom = float(global_batch if global_batch is not None else B * self.world)
+        seed = self.step_count * self.world + self.rank
+        lo, n = self.n_frozen, model.flat_grads.numel()
+        fused_prologue = B > 0 and lengths.dtype == torch.int64 and lengths.is_cuda and lengths.is_contiguous()
+        if fused_prologue:  # the prologue of a landmark-only step: nothing to place, no frame list -- on the trainable range
+            ws = model._workspace_embedded(Z, train=True)
+            L.call("ss_train_prologue", model.flat_grads.data_ptr() + 4 * lo, n - lo, self.scal.data_ptr(), 2,
+                   self.correct.data_ptr(), lengths.data_ptr(), ws.lengths.data_ptr(), B, None, cfg.x_dim, None, cfg.in_dim,
+                   B * T, cfg.x_dim, None, 0, L.stream())
+        else:
+            model.flat_grads[lo:].zero_()
+            self.scal.zero_()
+            self.correct.zero_()
+        self._weight_sum(B, y, y_global)
+        if B > 0:
+            ws = model._workspace_embedded(Z, train=True)
+            P = model._param_dict()
+            if not fused_prologue:
+                ws.lengths.copy_(lengths.to(torch.int32), non_blocking=True)
+            E.forward(P, cfg, ws, Z, None, train=train, stash=True, seed=seed, z_ready=True,
+                      ce=(y.data_ptr(), self.ls, denom, self.scal.data_ptr(), self.correct.data_ptr()) + self._ce_w)
+            E.backward(P, self.G, cfg, ws, Z, None, ws.d_logits, train=train, seed=seed, frozen_cnn=True)
+        self._reduce_clip_adam()
         return self.scal[0], self.correct[0]
 
     def _swap_ema(self):
         if self.model._bucket_version != self._bucket_version:
             self._bind_bucket()
-        flat = self.model.flat_params
-        L.call("ss_swap_f32", flat.data_ptr(), self.ema.data_ptr(), flat.numel(), L.stream())
+        flat, lo = self.model.flat_params, self.n_frozen  # (the frozen range of the average IS the weights: nothing to exchange)
+        L.call("ss_swap_f32", flat.data_ptr() + 4 * lo, self.ema.data_ptr() + 4 * lo, flat.numel() - lo, L.stream())
 
     @contextlib.contextmanager
     def ema_weights(self):
@@ -301,12 +381,12 @@ class Trainer:
         return dict(m=self.m.detach().clone(), v=self.v.detach().clone(), ema=None if self.ema is None else self.ema.detach().clone(),
                     step_count=int(self.step_count), ema_decay=self.ema_decay, ema_warmup=bool(self.ema_warmup),
                     betas=[float(b) for b in self.betas], eps=float(self.eps), lr=float(self.lr), max_norm=float(self.max_norm),
-                    numel=int(self.model.flat_params.numel()))
+                    numel=int(self.model.flat_params.numel()), **({"freeze_cnn": True} if self.freeze_cnn else {}))
 
     def load_state_dict(self, state: dict) -> None:
         """Take over a ``state_dict()``: the tensors are copied into this trainer's device buffers (nothing is re-allocated), the
-        step count and the hyperparameters are set.  ``ValueError`` when the bucket has another element count, or when one side
-        keeps a weight average and the other does not."""
+        step count and the hyperparameters are set.  ``ValueError`` when the bucket has another element count, when one side
+        keeps a weight average and the other does not, or when one side freezes the ROI CNN and the other does not."""
         if self._ema_swapped:
             raise RuntimeError("Trainer.load_state_dict inside ema_weights()")
         if self.model._bucket_version != self._bucket_version:
@@ -314,6 +394,9 @@ class Trainer:
         n = self.model.flat_params.numel()
         if int(state["numel"]) != n or any(state[k].numel() != n for k in ("m", "v")):
             raise ValueError(f"the saved trainer state is for a bucket of {int(state['numel'])} elements, this model's has {n}")
+        if bool(state.get("freeze_cnn", False)) != self.freeze_cnn:
+            raise ValueError("the saved trainer state and this Trainer disagree about freeze_cnn: "
+                             f"saved {bool(state.get('freeze_cnn', False))!r}, this one {self.freeze_cnn!r}")
         if (state["ema"] is None) != (self.ema is None):
             raise ValueError("the saved trainer state and this Trainer disagree about ema_decay: "
                              f"saved {state['ema_decay']!r}, this one {self.ema_decay!r}")
@@ -342,5 +425,5 @@ class Trainer:
             E.backward(P, self.G, cfg, ws, X, R, ws.d_logits, train=train, seed=seed)
 
     def grad_norm(self) -> torch.Tensor:
-        """Global L2 norm of the last step's (pre-clip) gradient."""
+        """Global L2 norm of the last step's (pre-clip) gradient (``freeze_cnn``: of the trainable parameters')."""
         return self.scal[1].sqrt()
