@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import flat_ref as FR
 import optim_ref as OR
 import weights as W
 
@@ -20,6 +21,10 @@ pytestmark = pytest.mark.gpu
 SPREAD = 9.781275e-08
 LOSS_BOUND = 10 * SPREAD
 NS = [1, 3, 4, 5, 1023, 1024, 1025, 256 * 4 * 3 + 2]  # tail alone, one vector, vector + tail, both sides of a workgroup's stride
+# one sweep of the capped grid of ss_adam_clip_ema and ss_swap_f32 is 2048 x 256 x 4 = 2 097 152 elements: both sides of it, a
+# second trip of one lane + a tail, a third trip
+NS_LARGE = [2097151, 2097152, 2097157, 4194311]
+NS_FLOAT64 = (2097157, 4194311)
 DECAYS = [0.0, 0.1, 0.999]
 ADAM = (1.0, 1.0, 3e-4, 0.9, 0.999, 1e-8)  # grad_scale, max_norm, lr, beta1, beta2, eps
 WORDS = ["aura", "no", "yes"]
@@ -50,19 +55,26 @@ def bits(t):
 # ---------------------------------------------------------------------------------------------------------------- kernels
 def optimiser_inputs(n, seed):
     g = torch.Generator().manual_seed(seed)
-    p, m, ema = torch.randn(n, generator=g), 0.01 * torch.randn(n, generator=g), torch.randn(n, generator=g)
+
+    def randn():  # (among millions of draws an exact 0.0 does turn up: that element gets 0.5)
+        t = torch.randn(n, generator=g)
+        return torch.where(t == 0, torch.full_like(t, 0.5), t)
+
+    p, m, ema = randn(), 0.01 * randn(), randn()
     v = 1e-4 * torch.rand(n, generator=g) + 1e-8
     grads = [0.05 * torch.randn(n, generator=g), 3.0 * torch.randn(n, generator=g)]  # (the second one is clipped for n > 1)
     assert all(bool((t != 0).all()) for t in (p, m, v, ema))
     return p, m, v, ema, grads
 
 
-@pytest.mark.parametrize("n", NS)
-def test_adam_clip_ema_against_adam_clip(L, n):
+def check_adam_clip_ema(L, n, decays, against_float64=False):
     """Two steps (step numbers 1 and 7) from nonzero moments: p, m, v of ``ss_adam_clip_ema`` are the bits of ``ss_adam_clip`` on
-    copies of the same inputs; the average is within 2 ulp of its float64 value; d = 0 makes it p_new exactly."""
-    for d in DECAYS:
-        p, m, v, ema, grads = optimiser_inputs(n, 100 + n)
+    copies of the same inputs; the average is within 2 ulp of its float64 value; d = 0 makes it p_new exactly.
+    ``against_float64``: p, m, v are also within ``flat_ref.adam_clip_expected``'s bounds of the float64 step from the values and
+    the sumsq word the kernel saw (first decay only) -> the largest error / bound ratios."""
+    p, m, v, ema, grads = optimiser_inputs(n, 100 + n)
+    worst = dict(p=0.0, m=0.0, v=0.0)
+    for d in decays:
         A = [t.cuda() for t in (p, m, v)]
         B = [t.cuda() for t in (p, m, v)]
         e_d, ssq = ema.cuda(), torch.zeros(1, device="cuda")
@@ -71,6 +83,7 @@ def test_adam_clip_ema_against_adam_clip(L, n):
             ssq.zero_()
             L.call("ss_sumsq_f32", g_d.data_ptr(), n, ssq.data_ptr(), L.stream())
             ema_old = e_d.cpu().numpy().copy()
+            before = [t.cpu().numpy() for t in B] if against_float64 and d == decays[0] else None
             L.call("ss_adam_clip", A[0].data_ptr(), g_d.data_ptr(), A[1].data_ptr(), A[2].data_ptr(), n, ssq.data_ptr(), *ADAM, step,
                    L.stream())
             L.call("ss_adam_clip_ema", B[0].data_ptr(), g_d.data_ptr(), B[1].data_ptr(), B[2].data_ptr(), e_d.data_ptr(), n,
@@ -87,6 +100,29 @@ def test_adam_clip_ema_against_adam_clip(L, n):
                 assert np.array_equal(ema_new, p_new)
             else:
                 assert not np.array_equal(ema_new, p_new) and not np.array_equal(ema_new, ema_old)
+            if before is not None:
+                want, bound = FR.adam_clip_expected(before[0], g.numpy(), before[1], before[2], np.float32(float(ssq[0])), step,
+                                                    lr=ADAM[2], max_norm=ADAM[1], beta1=ADAM[3], beta2=ADAM[4], eps=ADAM[5],
+                                                    grad_scale=ADAM[0])
+                for name, b in zip("pmv", B):
+                    err = np.abs(b.cpu().numpy().astype(np.float64) - want[name])
+                    worst[name] = max(worst[name], float((err / bound[name]).max()))
+                    assert (err <= bound[name]).all(), (name, n, step, worst[name])
+    return worst
+
+
+@pytest.mark.parametrize("n", NS)
+def test_adam_clip_ema_against_adam_clip(L, n):
+    check_adam_clip_ema(L, n, DECAYS)
+
+
+@pytest.mark.parametrize("n", NS_LARGE)
+def test_adam_clip_ema_past_one_sweep_of_the_capped_grid(L, n):
+    """The same checks where the 2048-workgroup grid strides a second and a third time (two decays; d = 0 still makes the
+    average p_new exactly), and at two of the sizes p, m, v against the float64 step as well, not only against ``ss_adam_clip``."""
+    worst = check_adam_clip_ema(L, n, [0.0, 0.999], against_float64=n in NS_FLOAT64)
+    if n in NS_FLOAT64:
+        print(f"adam_clip_ema n={n}: largest err / bound  m {worst['m']:.4f}  v {worst['v']:.4f}  p {worst['p']:.4f}")
 
 
 def test_adam_clip_ema_refuses_bad_arguments_and_writes_nothing(L):
@@ -131,7 +167,7 @@ def guarded(n, seed):
     return host.cuda().view(torch.float32), host
 
 
-@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("n", NS + NS_LARGE)
 def test_swap_exchanges_two_buffers_in_place(L, n):
     a, a0 = guarded(n, 2 * n)
     b, b0 = guarded(n, 2 * n + 1)

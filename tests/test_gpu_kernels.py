@@ -677,6 +677,12 @@ def test_dropout_mask_is_reproducible_and_unbiased(L):
     assert abs(keep - 0.8) < 3e-3
     assert abs(float(y1.mean()) - 1.0) < 5e-3
     assert set(torch.unique(y1).tolist()) == {0.0, 1.25}
+    # ... and it is the stream of an independent Philox4x32-10 (tests/flat_ref.py): every fused consumer above is compared
+    # with ss_dropout, this ties ss_dropout to the published generator
+    import flat_ref as FR
+
+    keep, want, bound = FR.dropout_expected(np.ones(n, np.float32), n, 0.2, 11, 5 << 40)
+    assert np.array_equal(y1.cpu().numpy() != 0, keep) and (np.abs(y1.cpu().numpy().astype(np.float64) - want) <= bound).all()
 
 
 # ------------------------------------------------------------------------------------- ROI CNN
