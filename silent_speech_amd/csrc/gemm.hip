@@ -16,6 +16,8 @@
 // buffer and a reduce pass; several split-K problems can share one launch (gemm_dma_group_kernel).
 #include <stdlib.h>
 
+#include <type_traits>
+
 // diagnostic build: rows of the stamp table in dispatch order over the 3-D grid
 #define SS_STAMP_ROW ((int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)))
 #include "ss_common.h"
@@ -360,7 +362,66 @@ __global__ __launch_bounds__(256, 5) void gemm_f32_kernel(GemmParams p) {  // 5 
 // through registers with zero fill.
 __device__ __forceinline__ constexpr int kc_swz(int r) { return (0 - (r >> 2)) & 3; }
 constexpr int DSTAGES = 4;
+constexpr int GEMM_GROUP_MAX = 4;  // problems of one grouped launch
 constexpr int D_A = BM * BK, D_B = BN * BK, D_STAGE = D_A + D_B;  // floats per stage: 12 KB
+
+// The two LDS images, each as a pair: where the 16-byte slot `sl` of the image comes from (DMA side), and at which float of the
+// image lane group g reads its four k-steps k = 4 g + kk of operand row `row` (MFMA side).  The kernels below hold no other copy
+// of a swizzle.
+template <int ROWS>
+struct KRowImage {  // [16 k][ROWS]
+  static constexpr int U = ROWS / 4;  // 16-byte units per k row
+  static __device__ __forceinline__ constexpr int rot(int k) { return 4 * ((k >> 2) & 1); }
+  static __device__ __forceinline__ int k(int sl) { return sl / U; }
+  static __device__ __forceinline__ int src_unit(int sl) {  // the row unit that slot sl holds: (u - rot(k)) mod U
+    const int ru = sl % U - rot(sl / U);
+    return (U & (U - 1)) == 0 ? (ru & (U - 1)) : ru + (ru < 0 ? U : 0);
+  }
+  static __device__ __forceinline__ int src_col(int sl, int row0, int nrows) { return min(row0 + 4 * src_unit(sl), nrows - 4); }
+  static __device__ __forceinline__ int frag(int row, int g) {  // + kk * ROWS for the k-step kk
+    const int u = (row >> 2) + rot(4 * g);
+    return 4 * g * ROWS + 4 * ((U & (U - 1)) == 0 ? (u & (U - 1)) : u % U) + (row & 3);
+  }
+  // ragged last tile (kvalid < 16 k rows left): the same image through registers, zeros past the end
+  static __device__ __forceinline__ void tail(float* slot, int sl, const float* src, int kvalid) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (k(sl) < kvalid) v = *reinterpret_cast<const f32x4*>(src);
+    *reinterpret_cast<f32x4*>(slot) = v;
+  }
+};
+struct KcImage {  // [ROWS][16 k]
+  static __device__ __forceinline__ int src_k(int sl) { return 4 * ((sl & 3) ^ kc_swz(sl >> 2)); }
+  static __device__ __forceinline__ int src_row(int sl, int row0, int nrows) { return min(row0 + (sl >> 2), nrows - 1); }
+  static __device__ __forceinline__ int frag(int row, int g) { return row * BK + 4 * (g ^ kc_swz(row)); }  // one ds_read_b128
+  static __device__ __forceinline__ void tail(float* slot, int sl, const float* src, int kvalid) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (src_k(sl) + e < kvalid) v[e] = src[e];
+    *reinterpret_cast<f32x4*>(slot) = v;
+  }
+};
+
+// Running source of one lane's slot of a [k][row] image.  linear (wave-uniform): the next tile is BK k rows further on in
+// memory, the caller steps `src`.  Otherwise (the (b,t) -> (b,t-1) pairing of d W_hh) the storage k row of the current tile
+// is q * rm.S + r (+ rm.off, folded into src), r < rm.G.
+struct KRowSlot {
+  const float* src;
+  int q, r;
+  template <int ROWS>
+  __device__ __forceinline__ void init(const float* P, int ld, const RowMap& rm, bool linear, int row0, int nrows, int kbeg, int sl) {
+    const int gk = kbeg + KRowImage<ROWS>::k(sl);
+    src = P + KRowImage<ROWS>::src_col(sl, row0, nrows) + (long)rm.off * ld;
+    q = linear ? 0 : gk / rm.G;
+    r = gk - q * rm.G;
+    if (linear) src += (long)gk * ld;
+  }
+  __device__ __forceinline__ const float* cur(int S, int ld, bool linear) const { return linear ? src : src + ((long)q * S + r) * ld; }
+  __device__ __forceinline__ void advance(int G) {
+    r += BK;
+    while (r >= G) { r -= G; ++q; }
+  }
+};
 
 template <int ROWS, bool KC>
 struct DmaOperand {
@@ -440,12 +501,44 @@ struct DmaOperand {
   }
 };
 
-template <int N>
-__device__ __forceinline__ void ss_vmcnt_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void ss_raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+// The k loop of the DMA-fed kernels, all waves in lockstep: DSTAGES - 1 tiles ahead; per tile wait for the own LPW DMA
+// instructions of tile t, barrier, step(stage, refill) -- refill is the buffer tile t - 1 left, for the step to start the next
+// DMA into (-1: none), then fragments and MFMAs of the stage.  A ragged last tile (rem k rows) goes through tail() into stage 0.
+// Both wide kernels call it.  gemm_dma_body keeps the same loop written out: through this function its eight instantiations
+// compile to other code (the hoisted nfull / rem compares change order and with them the register assignment).
+template <int LPW, class Issue, class Step, class Tail>
+__device__ __forceinline__ void ring_k_loop(int nfull, int rem, Issue&& issue, Step&& step, Tail&& tail) {
+#pragma unroll
+  for (int s_ = 0; s_ < DSTAGES - 1; ++s_)
+    if (s_ < nfull) issue(s_);
+  for (int t0 = 0; t0 < nfull; t0 += DSTAGES) {
+#pragma unroll
+    for (int s_ = 0; s_ < DSTAGES; ++s_) {
+      const int t = t0 + s_;
+      if (t < nfull) {
+        // tile t has landed once at most the DSTAGES - 2 younger tiles are still in flight (the pipeline tail just drains)
+        if (t + DSTAGES - 2 < nfull) ss_vmcnt_wait<(DSTAGES - 2) * LPW>();
+        else ss_vmcnt_wait<0>();
+        ss_raw_barrier();  // everybody's share of tile t is in LDS, and everybody is done reading tile t - 1 ...
+        step(s_, t + DSTAGES - 1 < nfull ? (s_ + DSTAGES - 1) % DSTAGES : -1);  // ... whose buffer the new tile takes
+      }
+    }
+  }
+  if (rem) {
+    __syncthreads();
+    tail(rem);
+    __syncthreads();
+    step(0, -1);
+  }
+}
+
+// Workgroup blockIdx.x of a grouped launch belongs to problem j: first[j] <= blockIdx.x < first[j + 1].
+__device__ __forceinline__ int group_index(const int* first, int n) {
+  int j = 0;
+#pragma unroll
+  for (int q = 1; q < GEMM_GROUP_MAX; ++q)
+    if (q < n && (int)blockIdx.x >= first[q]) j = q;
+  return j;
 }
 
 template <bool A_KC, bool B_KC>
@@ -469,13 +562,15 @@ __device__ __forceinline__ void gemm_dma_body(GemmParams p, const TileId id, flo
   // this lane's operand read offsets inside a stage (floats); the rest of every address is an immediate
   int offA[4], offB[2];
 #pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-    offA[mt] = A_KC ? (wm * 64 + mt * 16 + i) * BK + 4 * (g ^ kc_swz(i))
-                    : 4 * g * BM + (((16 * wm + 4 * mt + (i >> 2) + 4 * (g & 1)) & 31) << 2) + (i & 3);
+  for (int mt = 0; mt < 4; ++mt) {
+    const int m = wm * 64 + mt * 16 + i;
+    offA[mt] = A_KC ? KcImage::frag(m, g) : KRowImage<BM>::frag(m, g);
+  }
 #pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-    offB[nt] = D_A + (B_KC ? (wn * 32 + nt * 16 + i) * BK + 4 * (g ^ kc_swz(i))
-                           : 4 * g * BN + (((8 * wn + 4 * nt + (i >> 2) + 4 * (g & 1)) & 15) << 2) + (i & 3));
+  for (int nt = 0; nt < 2; ++nt) {
+    const int nn = wn * 32 + nt * 16 + i;
+    offB[nt] = D_A + (B_KC ? KcImage::frag(nn, g) : KRowImage<BN>::frag(nn, g));
+  }
 
   f32x4 acc[4][2];
 #pragma unroll
@@ -526,33 +621,33 @@ __device__ __forceinline__ void gemm_dma_body(GemmParams p, const TileId id, flo
   };
 
   for (int kc = 0; kc < p.kcat; ++kc) {
-  if (kc) ss_raw_barrier();  // the ring is about to be refilled: everybody is done with the previous pair's last tiles
-  da.init(p.A + kc * p.sA, p.lda, p.ra, m0, p.M, kbeg);
-  db.init(p.B + kc * p.sB, p.ldb, p.rb, n0, p.N, kbeg);
+    if (kc) ss_raw_barrier();  // the ring is about to be refilled: everybody is done with the previous pair's last tiles
+    da.init(p.A + kc * p.sA, p.lda, p.ra, m0, p.M, kbeg);
+    db.init(p.B + kc * p.sB, p.ldb, p.rb, n0, p.N, kbeg);
+    // ring_k_loop<LPW>, written out (see there)
 #pragma unroll
-  for (int s_ = 0; s_ < DSTAGES - 1; ++s_)
-    if (s_ < nfull) issue(s_);
-  for (int t0 = 0; t0 < nfull; t0 += DSTAGES) {
+    for (int s_ = 0; s_ < DSTAGES - 1; ++s_)
+      if (s_ < nfull) issue(s_);
+    for (int t0 = 0; t0 < nfull; t0 += DSTAGES) {
 #pragma unroll
-    for (int s_ = 0; s_ < DSTAGES; ++s_) {
-      const int t = t0 + s_;
-      if (t < nfull) {
-        // tile t has landed once at most the DSTAGES - 2 younger tiles are still in flight (the pipeline tail just drains)
-        if (t + DSTAGES - 2 < nfull) ss_vmcnt_wait<(DSTAGES - 2) * LPW>();
-        else ss_vmcnt_wait<0>();
-        ss_raw_barrier();  // everybody's share of tile t is in LDS, and everybody is done reading tile t - 1 ...
-        compute(dlds + s_ * D_STAGE, t + DSTAGES - 1 < nfull ? (s_ + DSTAGES - 1) % DSTAGES : -1);  // ... whose buffer the new tile takes
+      for (int s_ = 0; s_ < DSTAGES; ++s_) {
+        const int t = t0 + s_;
+        if (t < nfull) {
+          if (t + DSTAGES - 2 < nfull) ss_vmcnt_wait<(DSTAGES - 2) * LPW>();
+          else ss_vmcnt_wait<0>();
+          ss_raw_barrier();
+          compute(dlds + s_ * D_STAGE, t + DSTAGES - 1 < nfull ? (s_ + DSTAGES - 1) % DSTAGES : -1);
+        }
       }
     }
+    if (rem) {
+      __syncthreads();
+      da.tail(dlds, rem);
+      db.tail(dlds + D_A, rem);
+      __syncthreads();
+      compute(dlds, -1);
+    }
   }
-  if (rem) {
-    __syncthreads();
-    da.tail(dlds, rem);
-    db.tail(dlds + D_A, rem);
-    __syncthreads();
-    compute(dlds, -1);
-  }
-  }  // kcat
   static_assert(BM * (BN + 4) <= DSTAGES * D_STAGE, "the output tile is staged in the k-tile ring");
   gemm_epilogue(p, acc, m0, n0, zs, wm, wn, i, g, dlds, id);
 }
@@ -565,7 +660,6 @@ __global__ __launch_bounds__(256, 3) void gemm_dma_kernel(GemmParams p) {
 
 // Several split-K problems of one operand layout in ONE launch (the three weight-gradient GEMMs of a GRU layer): every launch
 // boundary on a stream costs the tail of one kernel and the ramp of the next, and these are 30 us kernels.
-constexpr int GEMM_GROUP_MAX = 4;
 struct GemmGroup {
   GemmParams p[GEMM_GROUP_MAX];
   int first[GEMM_GROUP_MAX + 1];  // workgroups [first[j], first[j+1]) belong to problem j
@@ -576,10 +670,7 @@ struct GemmGroup {
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(256, 3) void gemm_dma_group_kernel(GemmGroup gg) {
   extern __shared__ __attribute__((aligned(16))) float dlds[];
-  int j = 0;
-#pragma unroll
-  for (int q = 1; q < GEMM_GROUP_MAX; ++q)
-    if (q < gg.n && (int)blockIdx.x >= gg.first[q]) j = q;
+  const int j = group_index(gg.first, gg.n);
   const int local = blockIdx.x - gg.first[j], gx = gg.gx[j], gy = gg.gy[j];
   const int bx = local % gx, by = (local / gx) % gy, bz = local / (gx * gy);
   gemm_dma_body<A_KC, B_KC>(gg.p[j], TileId{bx, by, bz, gx, gy}, dlds);
@@ -593,13 +684,17 @@ struct ReduceGroup {
   int first[GEMM_GROUP_MAX + 1];
   int n;
 };
-__device__ __forceinline__ void splitk_reduce_body(const ReduceItem& r, int block) {
-  const int q = block & 7, tile = block >> 3;
+// The reduce of both tile geometries.  TM x TN output tiles, NT threads as waves of WM x WN laid out wave = 2 wm + wn; a workgroup
+// of the GEMM left Q = (WM / 16) (WN / 16) accumulator quads per thread, slab after slab in the order (bi, slice, by, bx).  This
+// workgroup sums quad q of tile (bi, by, bx) over the nz slices and adds it to C.  P: a record with nz, gx, gy, M, N, C, ldc, sC.
+template <int TM, int TN, int NT, int WM, int WN, class P>
+__device__ __forceinline__ void slab_reduce(const P& r, const f32x4* ws, int q, int tile) {
+  constexpr int NQ = WN / 16, Q = (WM / 16) * NQ;
   const int bx = tile % r.gx, by = (tile / r.gx) % r.gy, bi = tile / (r.gx * r.gy);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wm = wid >> 1, wn = wid & 1, i = lane & 15, g = lane >> 4;
-  const int mt = q >> 1, nt = q & 1;
-  const f32x4* src = r.ws + ((((long)bi * r.nz) * r.gy + by) * r.gx + bx) * (8 * 256) + q * 256 + tid;
-  const long zstride = (long)r.gy * r.gx * (8 * 256);
+  const int mt = q / NQ, nt = q % NQ;
+  const f32x4* src = ws + ((((long)bi * r.nz) * r.gy + by) * r.gx + bx) * (Q * NT) + q * NT + tid;
+  const long zstride = (long)r.gy * r.gx * (Q * NT);
   // eight slices in flight per thread: the loads are independent, the sum must not become a chain of memory latencies
   f32x4 s0 = {0.f, 0.f, 0.f, 0.f};
   int z = 0;
@@ -615,20 +710,20 @@ __device__ __forceinline__ void splitk_reduce_body(const ReduceItem& r, int bloc
     for (int u = 0; u < 8; ++u) v[u] = (z + u < r.nz) ? src[(z + u) * zstride] : f32x4{0.f, 0.f, 0.f, 0.f};
     s0 += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
   }
-  const int col = bx * BN + wn * 32 + nt * 16 + i;
+  const int col = bx * TN + wn * WN + nt * 16 + i;
   if (col >= r.N) return;
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
-    const int row = by * BM + wm * 64 + mt * 16 + 4 * g + rr;
+    const int row = by * TM + wm * WM + mt * 16 + 4 * g + rr;
     if (row < r.M) r.C[bi * r.sC + (long)row * r.ldc + col] += s0[rr];
   }
 }
+__device__ __forceinline__ void splitk_reduce_body(const ReduceItem& r, int block) {
+  slab_reduce<BM, BN, 256, 64, 32>(r, r.ws, block & 7, block >> 3);
+}
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(ReduceItem r) { splitk_reduce_body(r, blockIdx.x); }
 __global__ __launch_bounds__(256) void splitk_reduce_group_kernel(ReduceGroup rg) {
-  int j = 0;
-#pragma unroll
-  for (int q = 1; q < GEMM_GROUP_MAX; ++q)
-    if (q < rg.n && (int)blockIdx.x >= rg.first[q]) j = q;
+  const int j = group_index(rg.first, rg.n);
   splitk_reduce_body(rg.it[j], blockIdx.x - rg.first[j]);
 }
 
@@ -644,7 +739,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_group_kernel(ReduceGroup rg
 // u - 4 ((k >> 2) & 1) mod 48: the k rows of lane groups g and g + 1 land 16 banks apart).
 namespace wide {
 constexpr int WT = 192, WNT = 512, WNWV = 8;
-constexpr int W_U = WT / 4;                          // 16-byte units per k row
 constexpr int W_PIECES = WT * BK / 4 / 64;           // 1 KB DMA pieces per operand and k tile: 12
 constexpr int W_STAGE = 2 * WT * BK;                 // floats per stage (A image, B image): 24 KB
 constexpr int W_LPW = 2 * W_PIECES / WNWV;           // DMA instructions per wave and k tile: 3
@@ -669,95 +763,55 @@ struct WideGroup {
   int n;
 };
 
-// The k loop of both wide kernels: all eight waves in lockstep -- wait for the own DMA pieces of tile t, barrier, refill of the
-// buffer tile t - 1 left, fragments of tile t, 72 MFMAs.  MEASURED AND NOT USED: the bf16 ring kernel's ping-pong (waves 4..7 one
-// barrier behind waves 0..3, one half reading fragments / issuing DMA while the other multiplies; two barriers per tile, hazards
-// worked out and the tests green): layer 1's weight gradients 112.8 -> 130.7 us, layer 0's 82.8 -> 94.9, the input projections
-// 0.1045 -> 0.1082 ms per step.  With f32 MFMAs the half that reads is starved by the half that multiplies (a saturated
-// v_mfma_f32_16x16x4_f32 stream leaves the SIMD's other wave one vector instruction per ~180 cycles, docs/LAB_NOTES.md 8c-2 (6)), so its
-// "read phase" stretches over the partner's whole MFMA burst instead of hiding under it; in lockstep both halves read with
-// nothing to contend with and then share the pipe.
-#define WIDE_K_LOOP                                                                                                      \
-  {                                                                                                                      \
-    _Pragma("unroll") for (int s_ = 0; s_ < DSTAGES - 1; ++s_) if (s_ < nfull) issue(s_);                                \
-    for (int t0 = 0; t0 < nfull; t0 += DSTAGES) {                                                                        \
-      _Pragma("unroll") for (int s_ = 0; s_ < DSTAGES; ++s_) {                                                           \
-        const int t = t0 + s_;                                                                                           \
-        if (t < nfull) {                                                                                                 \
-          if (t + DSTAGES - 2 < nfull) ss_vmcnt_wait<(DSTAGES - 2) * W_LPW>(); else ss_vmcnt_wait<0>();                  \
-          ss_raw_barrier();                                                                                              \
-          if (t + DSTAGES - 1 < nfull) issue((s_ + DSTAGES - 1) % DSTAGES);                                              \
-          read(dlds + s_ * W_STAGE);                                                                                     \
-          mma();                                                                                                         \
-        }                                                                                                                \
-      }                                                                                                                  \
-    }                                                                                                                    \
-  }
-
-// one wave's three DMA pieces of a k tile: piece q = wave + 8 n of the 24 (A: 0..11, B: 12..23)
+// one wave's three DMA pieces of a k tile: piece = wave + 8 n of the 24 (A: 0..11, B: 12..23).  G / S / ld / lin per piece: a
+// wave's pieces can belong to different operands.
 struct WidePieces {
-  const float* src[W_LPW];
-  int q[W_LPW], r[W_LPW];   // k row = q * S + r for a remapped operand (see DmaOperand)
+  KRowSlot s[W_LPW];
   int G[W_LPW], S[W_LPW], ld[W_LPW];
   bool lin[W_LPW];
+  static __device__ __forceinline__ int piece(int n) { return (threadIdx.x >> 6) + WNWV * n; }
+  static __device__ __forceinline__ int slot(int n) { return (piece(n) % W_PIECES) * 64 + (threadIdx.x & 63); }  // of its operand's image
   __device__ __forceinline__ void init(const WideProblem& P, const float* A, const float* B, int m0, int n0, int kbeg) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int n = 0; n < W_LPW; ++n) {
-      const int piece = wave + WNWV * n;
-      const bool isb = piece >= W_PIECES;
-      const int sl = (piece - (isb ? W_PIECES : 0)) * 64 + lane;
-      const int k = sl / W_U, u = sl % W_U;
-      int ru = u - 4 * ((k >> 2) & 1);
-      ru += ru < 0 ? W_U : 0;
+      const bool isb = piece(n) >= W_PIECES;
       const RowMap& rm = isb ? P.rb : P.ra;
-      const int nrows = isb ? P.N : P.M, row0 = isb ? n0 : m0;
       ld[n] = isb ? P.ldb : P.lda;
       lin[n] = rm.G == 0x7fffffff;
       G[n] = rm.G; S[n] = rm.S;
-      const int gk = kbeg + k;
-      src[n] = (isb ? B : A) + min(row0 + 4 * ru, nrows - 4) + (long)rm.off * ld[n];
-      q[n] = lin[n] ? 0 : gk / rm.G;
-      r[n] = gk - q[n] * rm.G;
-      if (lin[n]) src[n] += (long)gk * ld[n];
+      s[n].init<WT>(isb ? B : A, ld[n], rm, lin[n], isb ? n0 : m0, isb ? P.N : P.M, kbeg, slot(n));
     }
   }
-  __device__ __forceinline__ const float* cur(int n) const { return lin[n] ? src[n] : src[n] + ((long)q[n] * S[n] + r[n]) * ld[n]; }
+  __device__ __forceinline__ const float* cur(int n) const { return s[n].cur(S[n], ld[n], lin[n]); }
   __device__ __forceinline__ void issue(unsigned stage_byte) const {
-    const int wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int n = 0; n < W_LPW; ++n) ss_dma16(cur(n), stage_byte + (wave + WNWV * n) * 1024);
+    for (int n = 0; n < W_LPW; ++n) ss_dma16(cur(n), stage_byte + piece(n) * 1024);
   }
   __device__ __forceinline__ void advance() {
 #pragma unroll
     for (int n = 0; n < W_LPW; ++n) {
-      if (lin[n]) src[n] += (long)BK * ld[n];
-      else {
-        r[n] += BK;
-        while (r[n] >= G[n]) { r[n] -= G[n]; ++q[n]; }
-      }
+      if (lin[n]) s[n].src += (long)BK * ld[n];
+      else s[n].advance(G[n]);
     }
   }
-  // ragged last tile (kvalid < 16 k rows left): the same image through registers, zeros past the end
   __device__ __forceinline__ void tail(float* img, int kvalid) const {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int n = 0; n < W_LPW; ++n) {
-      const int piece = wave + WNWV * n;
-      const int sl = (piece % W_PIECES) * 64 + lane;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (sl / W_U < kvalid) v = *reinterpret_cast<const f32x4*>(cur(n));
-      *reinterpret_cast<f32x4*>(img + piece * 256 + 4 * lane) = v;
-    }
+    for (int n = 0; n < W_LPW; ++n) KRowImage<WT>::tail(img + piece(n) * 256 + 4 * (threadIdx.x & 63), slot(n), cur(n), kvalid);
   }
 };
 
+// The k loop of both wide kernels is ring_k_loop<W_LPW> with the step each of them states: all eight waves in lockstep -- wait
+// for the own DMA pieces of tile t, barrier, refill of the buffer tile t - 1 left, fragments of tile t, 72 MFMAs.  MEASURED
+// AND NOT USED: the bf16 ring kernel's ping-pong (waves 4..7 one barrier behind waves 0..3, one half reading fragments /
+// issuing DMA while the other multiplies; two barriers per tile, hazards worked out and the tests green): layer 1's weight
+// gradients 112.8 -> 130.7 us, layer 0's 82.8 -> 94.9, the input projections 0.1045 -> 0.1082 ms per step.  With f32 MFMAs the
+// half that reads is starved by the half that multiplies (a saturated v_mfma_f32_16x16x4_f32 stream leaves the SIMD's other
+// wave one vector instruction per ~180 cycles, docs/LAB_NOTES.md 8c-2 (6)), so its "read phase" stretches over the partner's
+// whole MFMA burst instead of hiding under it; in lockstep both halves read with nothing to contend with and then share the
+// pipe.
 __global__ __launch_bounds__(WNT) void gemm_wide_group_kernel(WideGroup gg) {
   extern __shared__ __attribute__((aligned(16))) float dlds[];  // DSTAGES x (A image, B image), at LDS address 0
-  int j = 0;
-#pragma unroll
-  for (int q = 1; q < GEMM_GROUP_MAX; ++q)
-    if (q < gg.n && (int)blockIdx.x >= gg.first[q]) j = q;
+  const int j = group_index(gg.first, gg.n);
   const WideProblem& P = gg.p[j];
   const int local = blockIdx.x - gg.first[j];
   const int bx = local % P.gx, by = (local / P.gx) % P.gy, bz = local / (P.gx * P.gy);
@@ -772,15 +826,9 @@ __global__ __launch_bounds__(WNT) void gemm_wide_group_kernel(WideGroup gg) {
   dp.init(P, P.A + bi * P.sA, P.B + bi * P.sB, m0, n0, kbeg);
   int offA[3], offB[6];
 #pragma unroll
-  for (int mt = 0; mt < 3; ++mt) {
-    const int m = wm * 48 + mt * 16 + i;
-    offA[mt] = 4 * g * WT + 4 * (((m >> 2) + 4 * (g & 1)) % W_U) + (m & 3);
-  }
+  for (int mt = 0; mt < 3; ++mt) offA[mt] = KRowImage<WT>::frag(wm * 48 + mt * 16 + i, g);
 #pragma unroll
-  for (int nt = 0; nt < 6; ++nt) {
-    const int nn = wn * 96 + nt * 16 + i;
-    offB[nt] = WT * BK + 4 * g * WT + 4 * (((nn >> 2) + 4 * (g & 1)) % W_U) + (nn & 3);
-  }
+  for (int nt = 0; nt < 6; ++nt) offB[nt] = WT * BK + KRowImage<WT>::frag(wn * 96 + nt * 16 + i, g);
   f32x4 acc[3][6];
 #pragma unroll
   for (int mt = 0; mt < 3; ++mt)
@@ -809,14 +857,14 @@ __global__ __launch_bounds__(WNT) void gemm_wide_group_kernel(WideGroup gg) {
 #pragma unroll
         for (int nt = 0; nt < 6; ++nt) acc[mt][nt] = mfma16(a[mt][kk], b[nt][kk], acc[mt][nt]);
   };
-  WIDE_K_LOOP
-  if (rem) {
-    __syncthreads();
-    dp.tail(dlds, rem);
-    __syncthreads();
-    read(dlds);
-    mma();
-  }
+  ring_k_loop<W_LPW>(
+      nfull, rem, issue,
+      [&](int stage, int refill) {
+        if (refill >= 0) issue(refill);
+        read(dlds + stage * W_STAGE);
+        mma();
+      },
+      [&](int kvalid) { dp.tail(dlds, kvalid); });
   // raw accumulators as they lie in the registers: 18 coalesced 16-byte stores per thread
   f32x4* w = reinterpret_cast<f32x4*>(gg.ws + P.ws_off) + (long)local * (W_Q * WNT) + threadIdx.x;
 #pragma unroll
@@ -827,40 +875,10 @@ __global__ __launch_bounds__(WNT) void gemm_wide_group_kernel(WideGroup gg) {
 
 // C[bi][row][col] += sum over the nz slices: one workgroup per (problem, batch entry, tile, accumulator quad)
 __global__ __launch_bounds__(WNT) void gemm_wide_reduce_kernel(WideGroup gg) {
-  int j = 0;
-#pragma unroll
-  for (int q = 1; q < GEMM_GROUP_MAX; ++q)
-    if (q < gg.n && (int)blockIdx.x >= gg.rfirst[q]) j = q;
+  const int j = group_index(gg.rfirst, gg.n);
   const WideProblem& P = gg.p[j];
   const int blk = blockIdx.x - gg.rfirst[j];
-  const int q = blk % W_Q, tile = blk / W_Q;  // tile = (bi * gy + by) * gx + bx
-  const int bx = tile % P.gx, by = (tile / P.gx) % P.gy, bi = tile / (P.gx * P.gy);
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wm = wid >> 1, wn = wid & 1, i = lane & 15, g = lane >> 4;
-  const int mt = q / 6, nt = q % 6;
-  const long tiles = (long)P.gx * P.gy;
-  const f32x4* src = reinterpret_cast<const f32x4*>(gg.ws + P.ws_off) + (((long)bi * P.nz * tiles + by * P.gx + bx) * W_Q + q) * WNT + tid;
-  const long zstride = tiles * W_Q * WNT;
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f};
-  int z = 0;
-  for (; z + 8 <= P.nz; z += 8) {
-    f32x4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = src[(z + u) * zstride];
-    s0 += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-  }
-  {
-    f32x4 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = (z + u < P.nz) ? src[(z + u) * zstride] : f32x4{0.f, 0.f, 0.f, 0.f};
-    s0 += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-  }
-  const int col = bx * WT + wn * 96 + nt * 16 + i;
-  if (col >= P.N) return;
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
-    const int row = by * WT + wm * 48 + mt * 16 + 4 * g + rr;
-    if (row < P.M) P.C[bi * P.sC + (long)row * P.ldc + col] += s0[rr];
-  }
+  slab_reduce<WT, WT, WNT, 48, 96>(P, reinterpret_cast<const f32x4*>(gg.ws + P.ws_off), blk % W_Q, blk / W_Q);
 }
 
 // ---- the same tile for the GRU input projections: C[M][N] = A[M][K] B[N][K]^T + bias, both operands [row][k] (k contiguous), M = B T
@@ -875,43 +893,29 @@ struct WideKcParams {
   int M, N, K, lda, ldb, ldc, gx, gy;
   long sA, sB, sC, sBias;
 };
-struct WidePiecesKc {
+struct WidePiecesKc {  // pieces and slots as WidePieces, [row][16 k] images, plain operands
   const float* src[W_LPW];
   __device__ __forceinline__ void init(const WideKcParams& P, const float* A, const float* B, int m0, int n0) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int n = 0; n < W_LPW; ++n) {
-      const int piece = wave + WNWV * n;
-      const bool isb = piece >= W_PIECES;
-      const int sl = (piece - (isb ? W_PIECES : 0)) * 64 + lane;  // 16-byte slot of the [row][16 k] image
-      const int rr = sl >> 2, ku = (sl & 3) ^ kc_swz(rr);
-      const int nrows = isb ? P.N : P.M, row0 = isb ? n0 : m0;
-      const int gr = min(row0 + rr, nrows - 1);  // rows past the end feed accumulators nobody stores
-      src[n] = (isb ? B + (long)gr * P.ldb : A + (long)gr * P.lda) + 4 * ku;
+      const bool isb = WidePieces::piece(n) >= W_PIECES;
+      const int sl = WidePieces::slot(n);
+      const int gr = KcImage::src_row(sl, isb ? n0 : m0, isb ? P.N : P.M);  // rows past the end feed accumulators nobody stores
+      src[n] = (isb ? B + (long)gr * P.ldb : A + (long)gr * P.lda) + KcImage::src_k(sl);
     }
   }
   __device__ __forceinline__ void issue(unsigned stage_byte) const {
-    const int wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int n = 0; n < W_LPW; ++n) ss_dma16(src[n], stage_byte + (wave + WNWV * n) * 1024);
+    for (int n = 0; n < W_LPW; ++n) ss_dma16(src[n], stage_byte + WidePieces::piece(n) * 1024);
   }
   __device__ __forceinline__ void advance() {
 #pragma unroll
     for (int n = 0; n < W_LPW; ++n) src[n] += BK;
   }
-  __device__ __forceinline__ void tail(float* img, int kvalid) const {  // ragged last tile through registers, zeros past K
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __device__ __forceinline__ void tail(float* img, int kvalid) const {
 #pragma unroll
-    for (int n = 0; n < W_LPW; ++n) {
-      const int piece = wave + WNWV * n;
-      const int sl = (piece % W_PIECES) * 64 + lane;
-      const int ku = (sl & 3) ^ kc_swz(sl >> 2);
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (4 * ku + e < kvalid) v[e] = src[n][e];
-      *reinterpret_cast<f32x4*>(img + piece * 256 + 4 * lane) = v;
-    }
+    for (int n = 0; n < W_LPW; ++n)
+      KcImage::tail(img + WidePieces::piece(n) * 256 + 4 * (threadIdx.x & 63), WidePieces::slot(n), src[n], kvalid);
   }
 };
 
@@ -926,9 +930,9 @@ __global__ __launch_bounds__(WNT) void gemm_wide_kc_kernel(WideKcParams P) {
   dp.init(P, P.A + bi * P.sA, P.B + bi * P.sB, m0, n0);
   int offA[3], offB[6];
 #pragma unroll
-  for (int mt = 0; mt < 3; ++mt) offA[mt] = (wm * 48 + mt * 16 + i) * BK + 4 * (g ^ kc_swz(i));
+  for (int mt = 0; mt < 3; ++mt) offA[mt] = KcImage::frag(wm * 48 + mt * 16 + i, g);
 #pragma unroll
-  for (int nt = 0; nt < 6; ++nt) offB[nt] = WT * BK + (wn * 96 + nt * 16 + i) * BK + 4 * (g ^ kc_swz(i));
+  for (int nt = 0; nt < 6; ++nt) offB[nt] = WT * BK + KcImage::frag(wn * 96 + nt * 16 + i, g);
   f32x4 acc[3][6];
 #pragma unroll
   for (int mt = 0; mt < 3; ++mt)
@@ -953,14 +957,14 @@ __global__ __launch_bounds__(WNT) void gemm_wide_kc_kernel(WideKcParams P) {
 #pragma unroll
         for (int nt = 0; nt < 6; ++nt) acc[mt][nt] = mfma16(a[mt][kk], b[nt][kk], acc[mt][nt]);
   };
-  WIDE_K_LOOP
-  if (rem) {
-    __syncthreads();
-    dp.tail(dlds, rem);
-    __syncthreads();
-    read(dlds);
-    mma();
-  }
+  ring_k_loop<W_LPW>(
+      nfull, rem, issue,
+      [&](int stage, int refill) {
+        if (refill >= 0) issue(refill);
+        read(dlds + stage * W_STAGE);
+        mma();
+      },
+      [&](int kvalid) { dp.tail(dlds, kvalid); });
   // output tile through LDS, one 96-column half (the waves with wn == h) at a time: rows leave as 24 x 16-byte stores
   constexpr int LDS_C = 96 + 4;
   static_assert(WT * LDS_C <= DSTAGES * W_STAGE, "half an output tile is staged in the k-tile ring");
@@ -1004,12 +1008,33 @@ int splitk_slices(int K, int splits, int* per_out) {
   return ceil_div(K, per);
 }
 
+// floats of the slabs the 128 x 64 split-K kernels leave for one problem (flags bit3)
+long splitk_slab_floats(int M, int N, int K, int splits, int batch) {
+  return (long)batch * splitk_slices(K, splits, nullptr) * ceil_div(M, BM) * ceil_div(N, BN) * BM * BN;
+}
+
+bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+constexpr size_t dma_lds = (size_t)DSTAGES * D_STAGE * sizeof(float);
+constexpr size_t wide_lds = (size_t)DSTAGES * wide::W_STAGE * sizeof(float);
+
+// f(a, b) with the two layout flags as compile-time constants: launch(K<decltype(a)::value, decltype(b)::value>)
+template <class F>
+void by_layout(bool a_kcontig, bool b_kcontig, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  if (a_kcontig && b_kcontig) f(T{}, T{});
+  else if (a_kcontig && !b_kcontig) f(T{}, N{});
+  else if (!a_kcontig && b_kcontig) f(N{}, T{});
+  else f(N{}, N{});
+}
+
 }  // namespace
 
 // Floats a split-K workspace needs for ss_gemm_f32_batched(flags bit3) + ss_gemm_splitk_reduce on this problem.
 extern "C" int ss_gemm_splitk_ws_floats(int M, int N, int K, int splits, int batch, long* floats) {
   SS_REQUIRE(M > 0 && N > 0 && K > 0 && splits >= 1 && batch >= 1 && floats, SS_ERR_ARG);
-  *floats = (long)batch * splitk_slices(K, splits, nullptr) * ceil_div(M, BM) * ceil_div(N, BN) * BM * BN;
+  *floats = splitk_slab_floats(M, N, K, splits, batch);
   return SS_OK;
 }
 
@@ -1025,53 +1050,53 @@ extern "C" int ss_gemm_splitk_reduce(const float* ws, int M, int N, int K, int s
   return ss_launch_status();
 }
 
+// What a GEMM call says beyond an ss_gemm_problem record.
+struct GemmExtras {
+  const float* bias;
+  float* a_colsum;
+  int flags;
+  long stride_bias, stride_colsum;
+};
 // Argument checks and kernel parameters shared by the plain and the grouped entry points.
 struct GemmLaunch {
   GemmParams p;
   dim3 grid;
   bool dma_ok;
 };
-static int gemm_prepare(int a_kcontig, int b_kcontig, int M, int N, int K, const float* A, int lda, int a_group, int a_gstride,
-                        int a_off, const float* B, int ldb, int b_group, int b_gstride, int b_off, float* C, int ldc,
-                        const float* bias, float* a_colsum, int flags, int splits, int batch, long stride_a, long stride_b,
-                        long stride_c, long stride_bias, long stride_colsum, GemmLaunch* out) {
-  SS_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C && batch >= 1, SS_ERR_ARG);
-  SS_REQUIRE(!a_colsum || !a_kcontig, SS_ERR_ARG);
-  SS_REQUIRE(splits >= 1 && a_group > 0 && b_group > 0, SS_ERR_ARG);
+static int gemm_prepare(const ss_gemm_problem& q, const GemmExtras& x, GemmLaunch* out) {
+  const int flags = x.flags;
+  SS_REQUIRE(q.M > 0 && q.N > 0 && q.K > 0 && q.A && q.B && q.C && q.batch >= 1, SS_ERR_ARG);
+  SS_REQUIRE(!x.a_colsum || !q.a_kcontig, SS_ERR_ARG);
+  SS_REQUIRE(q.splits >= 1 && q.a_group > 0 && q.b_group > 0, SS_ERR_ARG);
   // split-K accumulates with atomics: C must already hold the value to add to, and ReLU cannot apply
-  SS_REQUIRE((flags & 8) || (splits == 1 && !(flags & 4)) || ((flags & 1) && !(flags & 2)), SS_ERR_ARG);
+  SS_REQUIRE((flags & 8) || (q.splits == 1 && !(flags & 4)) || ((flags & 1) && !(flags & 2)), SS_ERR_ARG);
   // workspace mode: raw accumulators only -- bias, ReLU and accumulation belong to the reduce pass
-  SS_REQUIRE(!(flags & 8) || (!(flags & 7) && !bias && (reinterpret_cast<uintptr_t>(C) & 15) == 0), SS_ERR_ARG);
+  SS_REQUIRE(!(flags & 8) || (!(flags & 7) && !x.bias && al16(q.C)), SS_ERR_ARG);
   GemmParams& p = out->p;
-  p.A = A; p.B = B; p.C = C; p.bias = bias; p.asum = a_colsum;
-  p.M = M; p.N = N; p.K = K;
-  p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  p.ra = RowMap{a_group, a_gstride, a_off};
-  p.rb = RowMap{b_group, b_gstride, b_off};
-  p.nz = splitk_slices(K, splits, &p.ksplit);
-  p.sA = stride_a; p.sB = stride_b; p.sC = stride_c; p.sBias = stride_bias; p.sAsum = stride_colsum;
+  p.A = q.A; p.B = q.B; p.C = q.C; p.bias = x.bias; p.asum = x.a_colsum;
+  p.M = q.M; p.N = q.N; p.K = q.K;
+  p.lda = q.lda; p.ldb = q.ldb; p.ldc = q.ldc;
+  p.ra = RowMap{q.a_group, q.a_gstride, q.a_off};
+  p.rb = RowMap{q.b_group, q.b_gstride, q.b_off};
+  p.nz = splitk_slices(q.K, q.splits, &p.ksplit);
+  p.sA = q.stride_a; p.sB = q.stride_b; p.sC = q.stride_c; p.sBias = x.stride_bias; p.sAsum = x.stride_colsum;
   p.flags = flags & 15;
   p.kcat = 1;
-  out->grid = dim3(ceil_div(N, BN), ceil_div(M, BM), p.nz * batch);
+  out->grid = dim3(ceil_div(q.N, BN), ceil_div(q.M, BM), p.nz * q.batch);
   SS_REQUIRE(out->grid.z <= 65535, SS_ERR_UNSUPPORTED);
   // the DMA-fed kernel wants 16-byte aligned operands whose [k][row] row counts are multiples of 4; the rest (the head's
   // tiny GEMMs, column sums riding along) stays on the register-staged kernel
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  out->dma_ok = !a_colsum && al16(A) && al16(B) && (lda & 3) == 0 && (ldb & 3) == 0 && (stride_a & 3) == 0 &&
-                (stride_b & 3) == 0 && (a_kcontig || (M >= 4 && (M & 3) == 0)) && (b_kcontig || (N >= 4 && (N & 3) == 0)) &&
-                p.ksplit >= 4 * BK;
+  out->dma_ok = !x.a_colsum && al16(q.A) && al16(q.B) && (q.lda & 3) == 0 && (q.ldb & 3) == 0 && (q.stride_a & 3) == 0 &&
+                (q.stride_b & 3) == 0 && (q.a_kcontig || (q.M >= 4 && (q.M & 3) == 0)) &&
+                (q.b_kcontig || (q.N >= 4 && (q.N & 3) == 0)) && p.ksplit >= 4 * BK;
   return SS_OK;
 }
 
-extern "C" int ss_gemm_f32_batched(int a_kcontig, int b_kcontig, int M, int N, int K, const float* A, int lda,
-                                   int a_group, int a_gstride, int a_off, const float* B, int ldb, int b_group,
-                                   int b_gstride, int b_off, float* C, int ldc, const float* bias, float* a_colsum,
-                                   int flags, int splits, int batch, long stride_a, long stride_b, long stride_c,
-                                   long stride_bias, long stride_colsum, ss_stream_t stream) {
+// ss_gemm_f32_batched on a record
+static int gemm_batched(const ss_gemm_problem& q, const GemmExtras& x, ss_stream_t stream) {
+  const int flags = x.flags;
   GemmLaunch gl;
-  const int st = gemm_prepare(a_kcontig, b_kcontig, M, N, K, A, lda, a_group, a_gstride, a_off, B, ldb, b_group, b_gstride, b_off,
-                              C, ldc, bias, a_colsum, flags, splits, batch, stride_a, stride_b, stride_c, stride_bias,
-                              stride_colsum, &gl);
+  const int st = gemm_prepare(q, x, &gl);
   if (st != SS_OK) return st;
   GemmParams& p = gl.p;
   dim3 grid = gl.grid, block(256);
@@ -1079,61 +1104,72 @@ extern "C" int ss_gemm_f32_batched(int a_kcontig, int b_kcontig, int M, int N, i
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (flags & 16) {
     // the batch is summed into one C
-    SS_REQUIRE(!(flags & 8) && !a_colsum, SS_ERR_ARG);
+    SS_REQUIRE(!(flags & 8) && !x.a_colsum, SS_ERR_ARG);
     if (!dma_ok) {  // register-staged kernel: one launch per pair, the later ones accumulate (stream order)
-      for (int b = 0; b < batch; ++b) {
-        const int st2 = ss_gemm_f32_batched(a_kcontig, b_kcontig, M, N, K, A + b * stride_a, lda, a_group, a_gstride, a_off,
-                                            B + b * stride_b, ldb, b_group, b_gstride, b_off, C, ldc, b ? nullptr : bias, nullptr,
-                                            (flags & 15) | (b ? 1 : 0), splits, 1, 0, 0, 0, 0, 0, stream);
+      for (int b = 0; b < q.batch; ++b) {
+        ss_gemm_problem one = q;
+        one.A += b * q.stride_a; one.B += b * q.stride_b;
+        one.batch = 1;
+        one.stride_a = one.stride_b = one.stride_c = 0;
+        const int st2 = gemm_batched(one, GemmExtras{b ? nullptr : x.bias, nullptr, (flags & 15) | (b ? 1 : 0), 0, 0}, stream);
         if (st2 != SS_OK) return st2;
       }
       return SS_OK;
     }
-    p.kcat = batch;
+    p.kcat = q.batch;
     grid.z = p.nz;
   }
   // [row][k] x [row][k] with enough 192 x 192 output tiles to fill most of the chip in one round, plain store (+ bias): the
   // wide-tile kernel (the GRU input projections)
-  if (dma_ok && a_kcontig && b_kcontig && !(flags & 31) && splits == 1 && p.ra.G == 0x7fffffff && p.ra.off == 0 &&
-      p.rb.G == 0x7fffffff && p.rb.off == 0 && (K & 3) == 0) {
-    const long tiles = (long)ceil_div(M, wide::WT) * ceil_div(N, wide::WT) * batch;
+  if (dma_ok && q.a_kcontig && q.b_kcontig && !(flags & 31) && q.splits == 1 && p.ra.G == 0x7fffffff && p.ra.off == 0 &&
+      p.rb.G == 0x7fffffff && p.rb.off == 0 && (q.K & 3) == 0) {
+    const long tiles = (long)ceil_div(q.M, wide::WT) * ceil_div(q.N, wide::WT) * q.batch;
     const int cus = ss_device_cus();
     // ONE round of the chip, at least 80 % full: that is where the gain is (config 2: 240 tiles against 1.4 rounds of 128 x 64
     // ones).  Over several rounds the wide kernel measured 3.5 % SLOWER than the narrow one (shipped shape, 720 tiles = 2.8
     // rounds: gemm_gru_ih 0.335 against 0.323 ms) -- per tile it is no more efficient, it only quantises better.
-    if (tiles <= cus && tiles * 10 >= (long)cus * 8 && N >= 96) {
+    if (tiles <= cus && tiles * 10 >= (long)cus * 8 && q.N >= 96) {
       wide::WideKcParams w;
-      w.A = A; w.B = B; w.bias = bias; w.C = C; w.M = M; w.N = N; w.K = K; w.lda = lda; w.ldb = ldb; w.ldc = ldc;
-      w.gx = ceil_div(N, wide::WT); w.gy = ceil_div(M, wide::WT);
-      w.sA = stride_a; w.sB = stride_b; w.sC = stride_c; w.sBias = stride_bias;
-      constexpr size_t wide_lds = (size_t)DSTAGES * wide::W_STAGE * sizeof(float);
+      w.A = q.A; w.B = q.B; w.bias = x.bias; w.C = q.C; w.M = q.M; w.N = q.N; w.K = q.K; w.lda = q.lda; w.ldb = q.ldb; w.ldc = q.ldc;
+      w.gx = ceil_div(q.N, wide::WT); w.gy = ceil_div(q.M, wide::WT);
+      w.sA = q.stride_a; w.sB = q.stride_b; w.sC = q.stride_c; w.sBias = x.stride_bias;
       SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(wide::gemm_wide_kc_kernel), (int)wide_lds) == SS_OK, SS_ERR_LAUNCH);
-      hipLaunchKernelGGL(wide::gemm_wide_kc_kernel, dim3((unsigned)(w.gx * w.gy), (unsigned)batch), dim3(wide::WNT), wide_lds, s, w);
+      hipLaunchKernelGGL(wide::gemm_wide_kc_kernel, dim3((unsigned)(w.gx * w.gy), (unsigned)q.batch), dim3(wide::WNT), wide_lds, s, w);
       return ss_launch_status();
     }
   }
-  if (dma_ok) {
-    constexpr size_t lds_bytes = (size_t)DSTAGES * D_STAGE * sizeof(float);
-    if (a_kcontig && b_kcontig) hipLaunchKernelGGL((gemm_dma_kernel<true, true>), grid, block, lds_bytes, s, p);
-    else if (a_kcontig && !b_kcontig) hipLaunchKernelGGL((gemm_dma_kernel<true, false>), grid, block, lds_bytes, s, p);
-    else if (!a_kcontig && b_kcontig) hipLaunchKernelGGL((gemm_dma_kernel<false, true>), grid, block, lds_bytes, s, p);
-    else hipLaunchKernelGGL((gemm_dma_kernel<false, false>), grid, block, lds_bytes, s, p);
-    return ss_launch_status();
-  }
-  if (a_kcontig && b_kcontig) hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, 0, s, p);
-  else if (a_kcontig && !b_kcontig) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, block, 0, s, p);
-  else if (!a_kcontig && b_kcontig) hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, 0, s, p);
+  by_layout(q.a_kcontig, q.b_kcontig, [&](auto a, auto b) {
+    if (dma_ok) hipLaunchKernelGGL((gemm_dma_kernel<decltype(a)::value, decltype(b)::value>), grid, block, dma_lds, s, p);
+    else hipLaunchKernelGGL((gemm_f32_kernel<decltype(a)::value, decltype(b)::value>), grid, block, 0, s, p);
+  });
   return ss_launch_status();
+}
+
+extern "C" int ss_gemm_f32_batched(int a_kcontig, int b_kcontig, int M, int N, int K, const float* A, int lda,
+                                   int a_group, int a_gstride, int a_off, const float* B, int ldb, int b_group,
+                                   int b_gstride, int b_off, float* C, int ldc, const float* bias, float* a_colsum,
+                                   int flags, int splits, int batch, long stride_a, long stride_b, long stride_c,
+                                   long stride_bias, long stride_colsum, ss_stream_t stream) {
+  const ss_gemm_problem q{a_kcontig, b_kcontig, M, N, K, A, lda, a_group, a_gstride, a_off, B, ldb, b_group, b_gstride, b_off,
+                          C, ldc, splits, batch, stride_a, stride_b, stride_c};
+  return gemm_batched(q, GemmExtras{bias, a_colsum, flags, stride_bias, stride_colsum}, stream);
 }
 
 // ---- grouped split-K: C_j += A_j^T-ish . B_j for up to GEMM_GROUP_MAX problems, one GEMM launch + one reduce launch
 static long group_ws_offset(const ss_gemm_problem* pr, int j) {  // floats in front of problem j's slices
   long off = 0;
-  for (int q = 0; q < j; ++q)
-    off += (long)pr[q].batch * splitk_slices(pr[q].K, pr[q].splits, nullptr) * ceil_div(pr[q].M, BM) * ceil_div(pr[q].N, BN) * BM * BN;
+  for (int q = 0; q < j; ++q) off += splitk_slab_floats(pr[q].M, pr[q].N, pr[q].K, pr[q].splits, pr[q].batch);
   return off;
 }
+// Problem j of a group as the GEMM that leaves its slabs in the workspace (flags bit3): C = its slabs, the rest as recorded.
+static ss_gemm_problem group_slab_gemm(const ss_gemm_problem* pr, int j, float* ws) {
+  ss_gemm_problem q = pr[j];
+  q.C = ws + group_ws_offset(pr, j);
+  q.ldc = q.N;
+  q.stride_c = 0;
+  return q;
+}
+static const GemmExtras kSlabGemm{nullptr, nullptr, 8, 0, 0};
 
 // The wide-tile form (namespace wide) of a group: K slices chosen here, from the shapes and the chip's CU count alone, so that the
 // workgroups of all problems together fill the chip once (one 512-thread workgroup per CU); `splits` of the records is ignored.
@@ -1188,7 +1224,6 @@ static bool wide_plan(const ss_gemm_problem* pr, int n, wide::WideGroup* out, lo
   }
   if (floats) *floats = off;
   // what the DMA ring and the row clamps need: k-major operands, 16-byte aligned, row counts that are multiples of 4
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   bool ok = true;
   for (int j = 0; j < n; ++j) {
     const ss_gemm_problem& q = pr[j];
@@ -1225,7 +1260,6 @@ extern "C" int ss_gemm_f32_splitk_group(const ss_gemm_problem* problems, int n, 
     if ((flags & 1) && wide_plan(problems, n, &wg, nullptr)) {
       for (int j = 0; j < n; ++j) SS_REQUIRE(problems[j].C && problems[j].ldc >= problems[j].N, SS_ERR_ARG);
       wg.ws = ws;
-      constexpr size_t wide_lds = (size_t)DSTAGES * wide::W_STAGE * sizeof(float);
       SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(wide::gemm_wide_group_kernel), (int)wide_lds) == SS_OK, SS_ERR_LAUNCH);
       hipStream_t s = static_cast<hipStream_t>(stream);
       hipLaunchKernelGGL(wide::gemm_wide_group_kernel, dim3((unsigned)wg.first[n]), dim3(wide::WNT), wide_lds, s, wg);
@@ -1241,18 +1275,16 @@ extern "C" int ss_gemm_f32_splitk_group(const ss_gemm_problem* problems, int n, 
   bool grouped = true;
   for (int j = 0; j < n; ++j) {
     const ss_gemm_problem& q = problems[j];
+    const ss_gemm_problem slab = group_slab_gemm(problems, j, ws);
     GemmLaunch gl;
-    float* wsj = ws + group_ws_offset(problems, j);
-    const int st = gemm_prepare(q.a_kcontig, q.b_kcontig, q.M, q.N, q.K, q.A, q.lda, q.a_group, q.a_gstride, q.a_off, q.B, q.ldb,
-                                q.b_group, q.b_gstride, q.b_off, wsj, q.N, nullptr, nullptr, 8, q.splits, q.batch, q.stride_a,
-                                q.stride_b, 0, 0, 0, &gl);
+    const int st = gemm_prepare(slab, kSlabGemm, &gl);
     if (st != SS_OK) return st;
     SS_REQUIRE(q.C && q.ldc >= q.N, SS_ERR_ARG);
     grouped = grouped && gl.dma_ok && q.a_kcontig == problems[0].a_kcontig && q.b_kcontig == problems[0].b_kcontig;
     gg.p[j] = gl.p;
     gg.gx[j] = gl.grid.x; gg.gy[j] = gl.grid.y;
     gg.first[j + 1] = gg.first[j] + (int)(gl.grid.x * gl.grid.y * gl.grid.z);
-    rg.it[j] = ReduceItem{reinterpret_cast<const f32x4*>(wsj), gl.p.nz, (int)gl.grid.x, (int)gl.grid.y, q.M, q.N, q.C, q.ldc, q.stride_c};
+    rg.it[j] = ReduceItem{reinterpret_cast<const f32x4*>(slab.C), gl.p.nz, (int)gl.grid.x, (int)gl.grid.y, q.M, q.N, q.C, q.ldc, q.stride_c};
     rg.first[j + 1] = rg.first[j] + (int)(q.batch * gl.grid.x * gl.grid.y * 8);
   }
   for (int j = n; j < GEMM_GROUP_MAX; ++j) {
@@ -1263,23 +1295,18 @@ extern "C" int ss_gemm_f32_splitk_group(const ss_gemm_problem* problems, int n, 
   if (!grouped) {  // an operand the DMA-fed kernel cannot take: the same work, problem by problem
     for (int j = 0; j < n; ++j) {
       const ss_gemm_problem& q = problems[j];
-      float* wsj = ws + group_ws_offset(problems, j);
-      int st = ss_gemm_f32_batched(q.a_kcontig, q.b_kcontig, q.M, q.N, q.K, q.A, q.lda, q.a_group, q.a_gstride, q.a_off, q.B,
-                                   q.ldb, q.b_group, q.b_gstride, q.b_off, wsj, q.N, nullptr, nullptr, 8, q.splits, q.batch,
-                                   q.stride_a, q.stride_b, 0, 0, 0, stream);
+      const ss_gemm_problem slab = group_slab_gemm(problems, j, ws);
+      int st = gemm_batched(slab, kSlabGemm, stream);
       if (st != SS_OK) return st;
-      st = ss_gemm_splitk_reduce(wsj, q.M, q.N, q.K, q.splits, q.batch, q.C, q.ldc, q.stride_c, stream);
+      st = ss_gemm_splitk_reduce(slab.C, q.M, q.N, q.K, q.splits, q.batch, q.C, q.ldc, q.stride_c, stream);
       if (st != SS_OK) return st;
     }
     return SS_OK;
   }
-  constexpr size_t lds_bytes = (size_t)DSTAGES * D_STAGE * sizeof(float);
   const dim3 ggrid((unsigned)gg.first[n]), block(256);
-  const bool akc = problems[0].a_kcontig, bkc = problems[0].b_kcontig;
-  if (akc && bkc) hipLaunchKernelGGL((gemm_dma_group_kernel<true, true>), ggrid, block, lds_bytes, s, gg);
-  else if (akc && !bkc) hipLaunchKernelGGL((gemm_dma_group_kernel<true, false>), ggrid, block, lds_bytes, s, gg);
-  else if (!akc && bkc) hipLaunchKernelGGL((gemm_dma_group_kernel<false, true>), ggrid, block, lds_bytes, s, gg);
-  else hipLaunchKernelGGL((gemm_dma_group_kernel<false, false>), ggrid, block, lds_bytes, s, gg);
+  by_layout(problems[0].a_kcontig, problems[0].b_kcontig, [&](auto a, auto b) {
+    hipLaunchKernelGGL((gemm_dma_group_kernel<decltype(a)::value, decltype(b)::value>), ggrid, block, dma_lds, s, gg);
+  });
   if (ss_launch_status() != SS_OK) return SS_ERR_LAUNCH;
   hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3((unsigned)rg.first[n]), dim3(256), 0, s, rg);
   return ss_launch_status();

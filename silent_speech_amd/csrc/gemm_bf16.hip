@@ -351,13 +351,6 @@ __device__ __forceinline__ void buf_dma16(i32x4 rs, unsigned voff, int soff, uns
                : "v"(voff), "s"(rs), "s"(soff), "s"(lds_addr)
                : "memory");
 }
-template <int N>
-__device__ __forceinline__ void vmcnt_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // One operand's share of a k tile for one wave: NL pieces of 1 KB (piece j = wave + 8 n of the tile's ROWS / 8).
 //   KC = 1: piece j = rows 8 j .. 8 j + 7 (128 bytes each); lane l -> row 8 j + (l >> 3), position l & 7.
@@ -525,7 +518,7 @@ __device__ __forceinline__ void ring_mainloop(const GemmBfParams& p, long ea, in
   };
   auto phase_barrier = [&]() {  // (register-only MFMAs would move across a bare barrier)
     __builtin_amdgcn_sched_barrier(0);
-    raw_barrier();
+    ss_raw_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
 
@@ -534,9 +527,9 @@ __device__ __forceinline__ void ring_mainloop(const GemmBfParams& p, long ea, in
   if (nk > 0) issue(0);
   if (nk > 1) {
     issue(1);
-    vmcnt_wait<LPW>();
+    ss_vmcnt_wait<LPW>();
   } else {
-    vmcnt_wait<0>();
+    ss_vmcnt_wait<0>();
   }
   phase_barrier();  // tile 0 is in LDS
   if (late) phase_barrier();
@@ -546,8 +539,8 @@ __device__ __forceinline__ void ring_mainloop(const GemmBfParams& p, long ea, in
       const int t = t0 + s_;
       if (t < nk) {
         load(rlds + s_ * STAGE_BYTES, t + 2 < nk ? (s_ + 2) % RST : -1);
-        if (t + 2 < nk) vmcnt_wait<LPW>();  // tile t + 1: at most tile t + 2's LPW instructions of this wave stay in flight
-        else vmcnt_wait<0>();
+        if (t + 2 < nk) ss_vmcnt_wait<LPW>();  // tile t + 1: at most tile t + 2's LPW instructions of this wave stay in flight
+        else ss_vmcnt_wait<0>();
         phase_barrier();
         mult();
         phase_barrier();

@@ -51,6 +51,15 @@ __device__ __forceinline__ void ss_dma4(const void* gsrc_lane, unsigned lds_byte
                : "memory");
 }
 __device__ __forceinline__ void ss_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// counted form for a ring of DMA stages (at most N of this wave's DMA instructions stay in flight), and the bare barrier that
+// goes with it: no waitcnt of the compiler's in front, fenced against reordering of memory accesses on both sides
+template <int N>
+__device__ __forceinline__ void ss_vmcnt_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ __forceinline__ void ss_raw_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
 
 // Wave-wide reductions on the DPP crossbar instead of __shfl_xor (which lowers to ds_bpermute_b32: one LDS round
 // trip, ~100 cycles, per butterfly level).  Four DPP levels leave every lane of a 16-lane row with its row's result,
