@@ -13,6 +13,7 @@
 // unit, D cols = clip.  The three gate accumulators of one (unit, clip) land in the same lane, so
 // sigmoid/tanh/blend run in registers and each step costs one workgroup barrier.
 #include "ss_common.h"
+#include "gru_cell.h"
 
 namespace {
 
@@ -137,10 +138,8 @@ __global__ __launch_bounds__(H * 4) void gru_fwd_kernel(GruFwdParams p) {
     f32x4 r, z, n, hn;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      r[e] = sigmoid_f(gr[e] + ar[e]);
-      z[e] = sigmoid_f(gz[e] + az[e]);
-      n[e] = tanh_f(gn[e] + r[e] * an[e]);
-      hn[e] = (1.0f - z[e]) * n[e] + z[e] * hp[e];
+      GRU_GATES(r[e], z[e], n[e], gr[e] + ar[e], gz[e] + az[e], gn[e], an[e]);
+      hn[e] = GRU_BLEND(z[e], n[e], hp[e]);
     }
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (valid) {
@@ -149,13 +148,7 @@ __global__ __launch_bounds__(H * 4) void gru_fwd_kernel(GruFwdParams p) {
     }
     if (clip_ok) {
       *reinterpret_cast<f32x4*>(p.out + frame * (2 * H) + dir * H + j0) = o;
-      if (p.save && valid) {
-        float* sp = p.save + (dir_off + frame) * (4 * H) + j0;
-        *reinterpret_cast<f32x4*>(sp) = r;
-        *reinterpret_cast<f32x4*>(sp + H) = z;
-        *reinterpret_cast<f32x4*>(sp + 2 * H) = n;
-        *reinterpret_cast<f32x4*>(sp + 3 * H) = an;
-      }
+      if (p.save && valid) store_rows4(p.save + (dir_off + frame) * (4 * H) + j0, H, r, z, n, an);
     }
     float* hnx = hbuf + (cur ^ 1) * H * SLICE;
 #pragma unroll
@@ -177,37 +170,9 @@ struct GruBwdParams {
   // (ss_dropout stream (seed, offset) over the (B*T, 2H) tensor) is re-drawn while d_out is read
   float drop_p;
   uint64_t drop_seed, drop_off;
-  // bias gradients (each [3H], accumulated; all NULL = not wanted): d b_ih += sum over (clip, t) of (d a_r, d a_z, d a_n),
-  // d b_hh += the same with d a_n * r in the n block.  They ride on the BPTT: a pass over d_g afterwards costs as much HBM
-  // traffic as the weight-gradient GEMM that follows it.
+  // bias gradients (each [3H], accumulated; all NULL = not wanted), see GruBiasAcc
   float* g_bih[2];
   float* g_bhh[2];
-};
-
-// Per-lane running sums of the four gate gradients of hidden units j0..j0+3 (lane row = 16 clips); flush() adds the rows up on
-// the DPP crossbar and lets one lane per row add them to the gradient vectors.  Every lane of the wave must call flush().
-struct GruBiasAcc {
-  f32x4 r = {0.f, 0.f, 0.f, 0.f}, z = r, n = r, q = r;
-  __device__ __forceinline__ void add(const f32x4& dar, const f32x4& daz, const f32x4& dan, const f32x4& dqn) {
-    r += dar; z += daz; n += dan; q += dqn;
-  }
-  __device__ __forceinline__ void flush(const GruBwdParams& p, int dir, int H, int j0, int i) {
-    if (!p.g_bih[dir]) return;
-    float* gi = p.g_bih[dir];
-    float* gh = p.g_bhh[dir];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float sr = row_sum(r[e]), sz = row_sum(z[e]), sn = row_sum(n[e]), sq = row_sum(q[e]);
-      if (i == 0) {
-        atomicAdd(&gi[j0 + e], sr);
-        atomicAdd(&gh[j0 + e], sr);
-        atomicAdd(&gi[H + j0 + e], sz);
-        atomicAdd(&gh[H + j0 + e], sz);
-        atomicAdd(&gi[2 * H + j0 + e], sn);
-        atomicAdd(&gh[2 * H + j0 + e], sq);
-      }
-    }
-  }
 };
 
 template <int H>
@@ -252,6 +217,7 @@ __global__ __launch_bounds__(H * 4) void gru_bwd_kernel(GruBwdParams p) {
     if (valid) {
       f32x4 go = *reinterpret_cast<const f32x4*>(p.d_out + frame * (2 * H) + dir * H + j0);
       if (p.drop_p > 0.f) go *= drop_scale4((frame * (2 * H) + dir * H + j0) >> 2, p.drop_p, p.drop_seed, p.drop_off);
+      // (load_rows4 would do; its reference outputs reorder this kernel's loop-carried registers at H = 192, so the text stays)
       const float* sp = p.save + (dir_off + frame) * (4 * H) + j0;
       f32x4 r = *reinterpret_cast<const f32x4*>(sp);
       f32x4 z = *reinterpret_cast<const f32x4*>(sp + H);
@@ -261,24 +227,11 @@ __global__ __launch_bounds__(H * 4) void gru_bwd_kernel(GruBwdParams p) {
       if (tp >= 0 && tp < len) hprev = *reinterpret_cast<const f32x4*>(p.out + ((long)clip * T + tp) * (2 * H) + dir * H + j0);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        float d = go[e] + dh[e];
-        float dn = d * (1.0f - z[e]);
-        float dz = d * (hprev[e] - n[e]);
-        dan[e] = dn * (1.0f - n[e] * n[e]);
-        dar[e] = dan[e] * q[e] * r[e] * (1.0f - r[e]);
-        daz[e] = dz * z[e] * (1.0f - z[e]);
-        dqn[e] = dan[e] * r[e];
-        dcarry[e] = d * z[e];
+        GRU_GATE_GRADS(dar[e], daz[e], dan[e], dqn[e], dcarry[e], go[e] + dh[e], r[e], z[e], n[e], q[e], hprev[e]);
       }
     }
     bacc.add(dar, daz, dan, dqn);
-    if (clip_ok) {
-      float* gp = p.d_g + (dir_off + frame) * (4 * H) + j0;
-      *reinterpret_cast<f32x4*>(gp) = dar;
-      *reinterpret_cast<f32x4*>(gp + H) = daz;
-      *reinterpret_cast<f32x4*>(gp + 2 * H) = dan;
-      *reinterpret_cast<f32x4*>(gp + 3 * H) = dqn;
-    }
+    if (clip_ok) store_rows4(p.d_g + (dir_off + frame) * (4 * H) + j0, H, dar, daz, dan, dqn);
     __syncthreads();  // previous step's MFMA reads of db are done (also orders the wlds fill)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -309,7 +262,7 @@ __global__ __launch_bounds__(H * 4) void gru_bwd_kernel(GruBwdParams p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) dh[e] = dcarry[e] + (a0[e] + a1[e]) + a2[e];
   }
-  bacc.flush(p, dir, H, j0, i);
+  bacc.flush(p.g_bih, p.g_bhh, dir, H, j0, i);
 }
 
 }  // namespace
@@ -321,7 +274,7 @@ STAMP_TABLE(ss_debug_stamps_gru)
 extern "C" int ss_gru_sync_bytes(int B, int T, int H, long* bytes) {
   SS_REQUIRE(bytes && B > 0 && T > 0 && H > 0, SS_ERR_ARG);
   const int P = gru_split_small_parts(B, gru_split_parts(B, T, H));
-  *bytes = P ? SYNC_HDR_WORDS * 4L + (gru_xid_granules(B) + gru_fwd_granules(B, H) + gru_bwd_granules(B, H, P)) * 8 : 0;
+  *bytes = P ? split_sync(B, H, P).bytes() : 0;
   return SS_OK;
 }
 
@@ -341,16 +294,14 @@ extern "C" int ss_gru_fwd_drop(const float* gi, const float* w_hh_f, const float
   p.out_drop = out_drop; p.drop_p = drop_p; p.drop_seed = drop_seed; p.drop_off = drop_offset;
   dim3 grid(ceil_div(B, SLICE), 2);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int P = sync_ws ? gru_split_parts(B, T, H) : 0;
-  SS_REQUIRE(P || !out_drop, SS_ERR_UNSUPPORTED);
-  if (P) {
-    // (while a CU cap is set on the persistent CNN kernels -- Trainer(micro_batches > 1) -- the slices keep six parts: the CUs the cap
-    // reserves hold 96 recurrence workgroups, what two 8-slice micro-batches of six parts need)
-    const int PF = ss_cnn_max_wgs ? P : gru_split_small_parts(B, P);
-    dim3 sgrid(gru_split_grid_pairs(B, PF) * PF);
-    unsigned* sy = static_cast<unsigned*>(sync_ws);
-    u64* xid = reinterpret_cast<u64*>(sy + SYNC_HDR_WORDS);
-    u64* hx = xid + gru_xid_granules(B);
+  int wgs;
+  const int PF = gru_split_launch(sync_ws, B, T, H, &wgs);
+  SS_REQUIRE(PF || !out_drop, SS_ERR_UNSUPPORTED);
+  if (PF) {
+    dim3 sgrid(wgs);
+    const SyncSections ws = split_sync(B, H, PF);
+    unsigned* sy = ws.hdr(sync_ws);
+    u64 *xid = ws.xid(sync_ws), *hx = ws.fwd(sync_ws);
     if (H == 192 && PF == 12) hipLaunchKernelGGL((gru_split_fwd_kernel<192, 12>), sgrid, dim3(256), 0, s, p, sy, xid, hx);
     else if (H == 192) hipLaunchKernelGGL((gru_split_fwd_kernel<192, 6>), sgrid, dim3(256), 0, s, p, sy, xid, hx);
     else hipLaunchKernelGGL((gru_split_fwd_kernel<64, 2>), sgrid, dim3(256), 0, s, p, sy, xid, hx);
@@ -383,13 +334,13 @@ extern "C" int ss_gru_bwd(const float* d_out, const float* out, const float* sav
   p.drop_p = drop_p; p.drop_seed = drop_seed; p.drop_off = drop_offset;
   dim3 grid(ceil_div(B, SLICE), 2);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int P = sync_ws ? gru_split_parts(B, T, H) : 0;
-  if (P) {
-    const int PB = ss_cnn_max_wgs ? P : gru_split_small_parts(B, P);
-    dim3 sgrid(gru_split_grid_pairs(B, PB) * PB);
-    unsigned* sy = static_cast<unsigned*>(sync_ws);
-    u64* xid = reinterpret_cast<u64*>(sy + SYNC_HDR_WORDS);
-    u64* xg = xid + gru_xid_granules(B) + gru_fwd_granules(B, H);
+  int wgs;
+  const int PB = gru_split_launch(sync_ws, B, T, H, &wgs);
+  if (PB) {
+    dim3 sgrid(wgs);
+    const SyncSections ws = split_sync(B, H, PB);
+    unsigned* sy = ws.hdr(sync_ws);
+    u64 *xid = ws.xid(sync_ws), *xg = ws.bwd(sync_ws);
     if (H == 192 && PB == 12) hipLaunchKernelGGL((gru_split_bwd_kernel<192, 12>), sgrid, dim3(256), 0, s, p, sy, xid, xg);
     else if (H == 192) hipLaunchKernelGGL((gru_split_bwd_kernel<192, 6>), sgrid, dim3(256), 0, s, p, sy, xid, xg);
     else hipLaunchKernelGGL((gru_split_bwd_kernel<64, 2>), sgrid, dim3(256), 0, s, p, sy, xid, xg);

@@ -12,6 +12,8 @@
 //
 // Packed-sequence semantics by masking, exactly as gru.hip: forward direction t = s, reverse direction t = T-1-s at step
 // s; a step with t >= len[b] leaves the state (and emits zeros); the reverse direction therefore starts at len-1.
+#include <type_traits>
+
 #include "bf16_common.h"
 namespace {
 STAMP_TABLE(ss_debug_stamps_gru_bf16)
@@ -148,20 +150,12 @@ __global__ __launch_bounds__(256) void gru_step_fwd_kernel(StepFwdParams p) {
     f32x4 rr, zz, nn, hh;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float r = sigmoid_f(gir[e] + gh[0][e] + br[e]);
-      const float z = sigmoid_f(giz[e] + gh[1][e] + bz[e]);
-      const float hpre = gh[2][e] + bn[e];
-      const float n = tanh_f(gin[e] + r * hpre);
-      rr[e] = r; zz[e] = z; nn[e] = n; hh[e] = hpre;
-      hn[e] = (1.0f - z) * n + z * hp[e];
+      float r, z, n;  // (q is formed, and kept for `save`, where the n gate uses it: behind z, as this kernel always did)
+      GRU_GATES(r, z, n, gir[e] + gh[0][e] + br[e], giz[e] + gh[1][e] + bz[e], gin[e], hh[e] = gh[2][e] + bn[e]);
+      rr[e] = r; zz[e] = z; nn[e] = n;
+      hn[e] = GRU_BLEND(z, n, hp[e]);
     }
-    if (p.save) {
-      float* sv = p.save + ((long)dir * N + row) * 4 * H;
-      *reinterpret_cast<f32x4*>(sv + u) = rr;
-      *reinterpret_cast<f32x4*>(sv + H + u) = zz;
-      *reinterpret_cast<f32x4*>(sv + 2 * H + u) = nn;
-      *reinterpret_cast<f32x4*>(sv + 3 * H + u) = hh;
-    }
+    if (p.save) store_rows4(p.save + ((long)dir * N + row) * 4 * H + u, H, rr, zz, nn, hh);
   }
   *reinterpret_cast<f32x4*>(p.out + row * 2 * H + dir * H + u) = hn;
   *reinterpret_cast<uint2*>(p.hb_out + ((long)dir * B + bq) * H + u) = pack_bf16x4(hn[0], hn[1], hn[2], hn[3]);
@@ -257,6 +251,8 @@ __global__ __launch_bounds__(256) void gru_step_bwd_kernel(StepBwdParams p) {
     dh += carry;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
+      // GRU_GATE_GRADS(drp, dzp, dnp, dhn, keep, dh, r, z, n, hpre, hp) and the row helpers of gru_cell.h, in this kernel's own
+      // statement and address order: the shared text costs it one to three instructions and another schedule
       const float dn = dh[e] * (1.0f - z[e]);
       const float dz = dh[e] * (hp[e] - n[e]);
       keep[e] = dh[e] * z[e];
@@ -329,32 +325,34 @@ void cvt_rows(const float* x, int ld_x, bf16_t* y, int ld_y, long rows, int cols
   hipLaunchKernelGGL(cvt_bf16_rows_kernel, dim3((int)blocks), dim3(256), 0, st, x, ld_x, y, ld_y, rows, cols, drop_p, seed, offset);
 }
 
-template <int H>
-void launch_pers_fwd(PersFwdParams p, void* sync_ws, int chunk, hipStream_t st) {
-  constexpr int P = H / PUNITS;
-  unsigned* sy = static_cast<unsigned*>(sync_ws);
-  const int gmax = 2 * ceil_div(chunk, PSLICE);
-  u64* xid = reinterpret_cast<u64*>(sy + SYNC_HDR_WORDS);
-  u64* hx = xid + pers_xid_granules(gmax, P);
+// One persistent launch per chunk of clips: `gran` = the forward resp. backward granules of the sync workspace
+template <typename Params, typename Kernel>
+void launch_pers_chunks(Kernel kernel, Params p, int P, int chunk, const SyncSections& ws, void* sync_ws, unsigned long long* gran,
+                        hipStream_t st) {
   for (int c0 = 0; c0 < p.B; c0 += chunk) {
     p.c0 = c0;
     p.nc = p.B - c0 < chunk ? p.B - c0 : chunk;
-    hipLaunchKernelGGL(gru_pers_fwd_kernel<H>, dim3(2 * ceil_div(p.nc, PSLICE) * P), dim3(256), 0, st, p, sy, xid, hx);
+    hipLaunchKernelGGL(kernel, dim3(2 * ceil_div(p.nc, PSLICE) * P), dim3(256), 0, st, p, ws.hdr(sync_ws), ws.xid(sync_ws), gran);
   }
 }
 
-template <int H>
-void launch_pers_bwd(PersBwdParams p, void* sync_ws, int chunk, hipStream_t st) {
-  constexpr int P = H / PUNITS;
-  unsigned* sy = static_cast<unsigned*>(sync_ws);
-  const int gmax = 2 * ceil_div(chunk, PSLICE);
-  u64* xid = reinterpret_cast<u64*>(sy + SYNC_HDR_WORDS);
-  u64* xg = xid + pers_xid_granules(gmax, P) + pers_fwd_granules(gmax, H);
-  for (int c0 = 0; c0 < p.B; c0 += chunk) {
-    p.c0 = c0;
-    p.nc = p.B - c0 < chunk ? p.B - c0 : chunk;
-    hipLaunchKernelGGL(gru_pers_bwd_kernel<H>, dim3(2 * ceil_div(p.nc, PSLICE) * P), dim3(256), 0, st, p, sy, xid, xg);
+// The built hidden sizes: f(std::integral_constant<int, H>) for the H asked for.  1024 exists for the step kernels only.
+template <bool STEP, typename F>
+int dispatch_h(int H, F&& f) {
+  switch (H) {
+    case 128: f(std::integral_constant<int, 128>()); break;
+    case 256: f(std::integral_constant<int, 256>()); break;
+    case 384: f(std::integral_constant<int, 384>()); break;
+    case 512: f(std::integral_constant<int, 512>()); break;
+    case 1024:
+      if constexpr (STEP) {
+        f(std::integral_constant<int, 1024>());
+        break;
+      }
+      [[fallthrough]];
+    default: return SS_ERR_UNSUPPORTED;
   }
+  return SS_OK;
 }
 
 }  // namespace
@@ -379,12 +377,8 @@ extern "C" int ss_gru_bf16_ws_bytes(int B, int H, long* bytes) {
 
 extern "C" int ss_gru_bf16_sync_bytes(int B, int T, int H, long* bytes) {
   SS_REQUIRE(bytes && B > 0 && T > 0 && H > 0, SS_ERR_ARG);
-  *bytes = 0;
-  if (!pers_supported(H) || T > 1022) return SS_OK;  // step tags are 10 bits
-  const int chunk = pers_chunk_clips(B, H, ss_device_cus());
-  if (chunk <= 0) return SS_OK;
-  const int gmax = 2 * ceil_div(chunk, PSLICE);
-  *bytes = SYNC_HDR_WORDS * 4L + (pers_xid_granules(gmax, H / PUNITS) + pers_fwd_granules(gmax, H) + pers_bwd_granules(gmax, H)) * 8;
+  const int chunk = pers_launch_chunk(B, T, H);
+  *bytes = chunk > 0 ? pers_sync(chunk, H).bytes() : 0;
   return SS_OK;
 }
 
@@ -407,35 +401,24 @@ extern "C" int ss_gru_bf16_fwd(const float* gi, const uint16_t* whh_bf16, const 
   SS_REQUIRE(B > 0 && T > 0 && drop_p >= 0.f && drop_p < 1.f, SS_ERR_ARG);
   SS_REQUIRE(H >= 128 && H % 128 == 0, SS_ERR_UNSUPPORTED);  // (step kernels: four waves x whole 32-deep k steps; built: 128..512, 1024)
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int chunk = (sync_ws && pers_supported(H) && T <= 1022) ? pers_chunk_clips(B, H, ss_device_cus()) : 0;
+  const int chunk = sync_ws ? pers_launch_chunk(B, T, H) : 0;
   if (chunk > 0) {
-    long need = 0;
-    if (ss_gru_bf16_sync_bytes(B, T, H, &need) != SS_OK) return SS_ERR_ARG;
-    SS_REQUIRE(sync_bytes >= need, SS_ERR_ARG);  // the section offsets below are derived from B: an area sized for another batch may be short
+    const SyncSections ws = pers_sync(chunk, H);
+    SS_REQUIRE(sync_bytes >= ws.bytes(), SS_ERR_ARG);  // the sections are derived from B: an area sized for another batch may be short
     PersFwdParams q;
     q.gi = gi; q.whh = whh_bf16; q.bhh_f = b_hh_f; q.bhh_r = b_hh_r; q.lengths = lengths; q.B = B; q.T = T;
     q.out = out; q.save = save; q.out_bf = out_bf16; q.out_drop_bf = out_drop_bf16; q.drop_p = drop_p; q.seed = seed; q.offset = offset;
-    switch (H) {
-      case 128: launch_pers_fwd<128>(q, sync_ws, chunk, st); break;
-      case 256: launch_pers_fwd<256>(q, sync_ws, chunk, st); break;
-      case 384: launch_pers_fwd<384>(q, sync_ws, chunk, st); break;
-      case 512: launch_pers_fwd<512>(q, sync_ws, chunk, st); break;
-      default: return SS_ERR_UNSUPPORTED;
-    }
-    return ss_launch_status();
+    const int rc = dispatch_h<false>(H, [&](auto h) {
+      launch_pers_chunks(gru_pers_fwd_kernel<h()>, q, h() / PUNITS, chunk, ws, sync_ws, ws.fwd(sync_ws), st);
+    });
+    return rc == SS_OK ? ss_launch_status() : rc;
   }
   StepFwdParams p;
   p.gi = gi; p.whh = whh_bf16; p.bhh_f = b_hh_f; p.bhh_r = b_hh_r; p.lengths = lengths;
   p.B = B; p.T = T; p.H = H; p.out = out; p.save = save;
   bf16_t* hb = static_cast<bf16_t*>(ws);
-  switch (H) {
-    case 128: launch_fwd_steps<128>(p, hb, T, st); break;
-    case 256: launch_fwd_steps<256>(p, hb, T, st); break;
-    case 384: launch_fwd_steps<384>(p, hb, T, st); break;
-    case 512: launch_fwd_steps<512>(p, hb, T, st); break;
-    case 1024: launch_fwd_steps<1024>(p, hb, T, st); break;
-    default: return SS_ERR_UNSUPPORTED;
-  }
+  const int rc = dispatch_h<true>(H, [&](auto h) { launch_fwd_steps<h()>(p, hb, T, st); });
+  if (rc != SS_OK) return rc;
   const long N = (long)B * T;
   if (out_bf16) cvt_rows(out, 2 * H, out_bf16, 2 * H, N, 2 * H, 0.f, 0, 0, st);
   if (out_drop_bf16) cvt_rows(out, 2 * H, out_drop_bf16, 2 * H, N, 2 * H, drop_p, seed, offset, st);
@@ -452,23 +435,18 @@ extern "C" int ss_gru_bf16_bwd(const float* d_out, const float* out, const float
   const bool want_bias = g_bih_f || g_bhh_f || g_bih_r || g_bhh_r;
   SS_REQUIRE(!want_bias || (g_bih_f && g_bhh_f && g_bih_r && g_bhh_r), SS_ERR_ARG);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int chunk = (sync_ws && pers_supported(H) && T <= 1022) ? pers_chunk_clips(B, H, ss_device_cus()) : 0;
+  const int chunk = sync_ws ? pers_launch_chunk(B, T, H) : 0;
   if (chunk > 0) {
-    long need = 0;
-    if (ss_gru_bf16_sync_bytes(B, T, H, &need) != SS_OK) return SS_ERR_ARG;
-    SS_REQUIRE(sync_bytes >= need, SS_ERR_ARG);  // the section offsets below are derived from B: an area sized for another batch may be short
+    const SyncSections ws = pers_sync(chunk, H);
+    SS_REQUIRE(sync_bytes >= ws.bytes(), SS_ERR_ARG);  // the sections are derived from B: an area sized for another batch may be short
     PersBwdParams q;
     q.d_out = d_out; q.out = out; q.save = save; q.whht = whh_t_bf16; q.lengths = lengths; q.B = B; q.T = T;
     q.dG = d_g; q.dG_bf = d_g_bf16; q.drop_p = drop_p; q.seed = seed; q.offset = offset;
     q.g_bih[0] = g_bih_f; q.g_bih[1] = g_bih_r; q.g_bhh[0] = g_bhh_f; q.g_bhh[1] = g_bhh_r;
-    switch (H) {
-      case 128: launch_pers_bwd<128>(q, sync_ws, chunk, st); break;
-      case 256: launch_pers_bwd<256>(q, sync_ws, chunk, st); break;
-      case 384: launch_pers_bwd<384>(q, sync_ws, chunk, st); break;
-      case 512: launch_pers_bwd<512>(q, sync_ws, chunk, st); break;
-      default: return SS_ERR_UNSUPPORTED;
-    }
-    return ss_launch_status();
+    const int rc = dispatch_h<false>(H, [&](auto h) {
+      launch_pers_chunks(gru_pers_bwd_kernel<h()>, q, h() / PUNITS, chunk, ws, sync_ws, ws.bwd(sync_ws), st);
+    });
+    return rc == SS_OK ? ss_launch_status() : rc;
   }
   SS_REQUIRE(d_g, SS_ERR_ARG);  // the step kernels hand the gate gradients on through d_g
   StepBwdParams p;
@@ -477,14 +455,8 @@ extern "C" int ss_gru_bf16_bwd(const float* d_out, const float* out, const float
   bf16_t* base = static_cast<bf16_t*>(ws) + 2L * 2 * B * H;  // behind the two forward state slots
   const long slot = 2L * B * 3 * H;
   p.dhz = reinterpret_cast<float*>(base + 2 * slot);
-  switch (H) {
-    case 128: launch_bwd_steps<128>(p, base, T, st); break;
-    case 256: launch_bwd_steps<256>(p, base, T, st); break;
-    case 384: launch_bwd_steps<384>(p, base, T, st); break;
-    case 512: launch_bwd_steps<512>(p, base, T, st); break;
-    case 1024: launch_bwd_steps<1024>(p, base, T, st); break;
-    default: return SS_ERR_UNSUPPORTED;
-  }
+  const int rc = dispatch_h<true>(H, [&](auto h) { launch_bwd_steps<h()>(p, base, T, st); });
+  if (rc != SS_OK) return rc;
   const long N = (long)B * T;
   if (d_g_bf16) cvt_rows(d_g, 4 * H, d_g_bf16, 4 * H, 2 * N, 4 * H, 0.f, 0, 0, st);
   if (want_bias) {

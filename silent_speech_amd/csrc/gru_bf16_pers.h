@@ -21,58 +21,12 @@
 // run as several launches over clip chunks) and H is 128 ... 512 in steps of 64; anything else stays on the step kernels.
 #pragma once
 #include "granule_xchg.h"
+#include "gru_cell.h"
 
 namespace {
 
 constexpr int PSLICE = 16;   // clips per group = MFMA N
 constexpr int PUNITS = 64;   // hidden units per part = 4 waves x 16
-
-// generic sweep: thread re-reads N 16-byte granule pairs (stride `stride` pairs) until every tag matches; payloads raw
-template <int N>
-__device__ __forceinline__ bool sweep_pairs(rsrc_t rs, int pair0, int stride, unsigned tag, unsigned (&v)[2 * N], unsigned* errors,
-                                            int lane) {
-  for (int spins = 0;;) {
-    bool ok = true;
-    asm volatile("" ::: "memory");  // every pass really loads again
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-      const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs, (pair0 + stride * k) * 16, 0, AUX_SC1);
-      v[2 * k] = x[0];
-      v[2 * k + 1] = x[2];
-      ok &= x[1] == tag && x[3] == tag;
-    }
-    if (__all(ok)) return true;
-    if (++spins > (1 << 20)) {
-      if (lane == 0) atomicAdd(errors, 1u);
-      return false;
-    }
-  }
-}
-
-// A sweep in two halves: issue the first pass, do something else while its loads fly, then look at the tags (and fall back to the
-// spinning form when a partner has not published yet)
-template <int N>
-__device__ __forceinline__ void sweep_issue(rsrc_t rs, int pair0, int stride, u32x4 (&raw)[N]) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) raw[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, (pair0 + stride * k) * 16, 0, AUX_SC1);
-}
-template <int N>
-__device__ __forceinline__ bool sweep_check(const u32x4 (&raw)[N], unsigned tag, unsigned (&v)[2 * N]) {
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    v[2 * k] = raw[k][0];
-    v[2 * k + 1] = raw[k][2];
-    ok &= raw[k][1] == tag && raw[k][3] == tag;
-  }
-  return __all(ok);
-}
-
-__device__ __forceinline__ void store_pair_raw(rsrc_t rs, int pair, unsigned tag, unsigned p0, unsigned p1, bool same_xcd) {
-  const u32x4 d = {p0, tag, p1, tag};
-  if (same_xcd) __builtin_amdgcn_raw_buffer_store_b128(d, rs, pair * 16, 0, 0);
-  else __builtin_amdgcn_raw_buffer_store_b128(d, rs, pair * 16, 0, AUX_SC1);
-}
 
 struct PersFwdParams {
   const float* gi;        // (2, N, 3H) f32
@@ -88,14 +42,6 @@ struct PersFwdParams {
   uint64_t seed, offset;
 };
 
-// blockIdx -> (group = slice * 2 + direction, part); part-major when the group count is a multiple of 8 (partners share an XCD)
-__device__ __forceinline__ void pers_ids(int P, int& groups, int& group, int& part) {
-  groups = gridDim.x / P;
-  const bool part_major = (groups & 7) == 0;
-  part = part_major ? blockIdx.x / groups : blockIdx.x % P;
-  group = part_major ? blockIdx.x % groups : blockIdx.x / P;
-}
-
 template <int H>
 __global__ __launch_bounds__(256) void gru_pers_fwd_kernel(PersFwdParams p, unsigned* sync, u64* xid, u64* hx) {
   constexpr int P = H / PUNITS, KS = H / 32;
@@ -109,7 +55,7 @@ __global__ __launch_bounds__(256) void gru_pers_fwd_kernel(PersFwdParams p, unsi
   __shared__ __attribute__((aligned(16))) bf16_t hpan2[2][PSLICE * LDH];
   __shared__ unsigned s_gen;
   int groups, group, part;
-  pers_ids(P, groups, group, part);
+  xchg_ids(P, groups, group, part);
   const int dir = group & 1, b0 = p.c0 + (group >> 1) * PSLICE;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, g = lane >> 4;
   const int u0 = part * PUNITS + 16 * w + 4 * g;  // first of this lane's 4 hidden units (D rows 4g .. 4g+3 of unit tile w)
@@ -117,12 +63,7 @@ __global__ __launch_bounds__(256) void gru_pers_fwd_kernel(PersFwdParams p, unsi
   const bool clip_ok = clip < p.c0 + p.nc;
   const int len = clip_ok ? p.lengths[clip] : 0;
   const int T = p.T;
-  if (tid == 0) s_gen = __hip_atomic_load(&sync[0], __ATOMIC_RELAXED, SS_AGENT);
-  if (plays_dead(sync)) {  // wave-uniform; tests only
-    __syncthreads();
-    finish_launch(sync, s_gen);
-    return;
-  }
+  if (!xchg_begin(sync, s_gen, 0, 1)) return;
   __builtin_amdgcn_s_setprio(3);
 
   // A fragments: rows = this wave's 16 units of gate G, k = 32 ks + 8 g + j
@@ -139,11 +80,9 @@ __global__ __launch_bounds__(256) void gru_pers_fwd_kernel(PersFwdParams p, unsi
   const f32x4 br = *reinterpret_cast<const f32x4*>(bhh + u0), bz = *reinterpret_cast<const f32x4*>(bhh + H + u0),
               bn = *reinterpret_cast<const f32x4*>(bhh + 2 * H + u0);
   __syncthreads();
-  const unsigned gen = s_gen;
-  const unsigned base = (gen & 0x3FFFFFu) << 10;
-  bool dead = false;
-  const bool same_xcd = partners_share_xcd(xid, group, part, P, base, &sync[2], lane, &dead);
-  if (tid == 0 && same_xcd) atomicAdd(&sync[3], 1u);
+  unsigned gen, base;
+  bool dead;
+  const bool same_xcd = xchg_open(sync, s_gen, xid, group, part, P, lane, gen, base, dead);
 
   const long N = (long)p.B * T;
   const rsrc_t hrs = granule_rsrc(hx, 2L * groups * PSLICE * (H / 2));
@@ -166,13 +105,7 @@ __global__ __launch_bounds__(256) void gru_pers_fwd_kernel(PersFwdParams p, unsi
       if (p.drop_p > 0.f) od *= drop_scale4((st_row * (2 * H) + dir * H + u0) >> 2, p.drop_p, p.seed, p.offset);
       *reinterpret_cast<uint2*>(p.out_drop_bf + st_row * (2 * H) + dir * H + u0) = pack_bf16x4(od[0], od[1], od[2], od[3]);
     }
-    if (p.save && st_valid) {
-      float* sv = p.save + ((long)dir * N + st_row) * (4 * H) + u0;
-      *reinterpret_cast<f32x4*>(sv) = st_r;
-      *reinterpret_cast<f32x4*>(sv + H) = st_z;
-      *reinterpret_cast<f32x4*>(sv + 2 * H) = st_n;
-      *reinterpret_cast<f32x4*>(sv + 3 * H) = st_q;
-    }
+    if (p.save && st_valid) store_rows4(p.save + ((long)dir * N + st_row) * (4 * H) + u0, H, st_r, st_z, st_n, st_q);
   };
   f32x4 ngr, ngz, ngn;  // input-projection gates of the NEXT step
   auto load_gi = [&](int s) {
@@ -191,12 +124,7 @@ __global__ __launch_bounds__(256) void gru_pers_fwd_kernel(PersFwdParams p, unsi
     const int t = dir ? (T - 1 - s) : s;
     const long row = (long)clip * T + t;
     const bool valid = t < len;
-    // In flight during the sweep -- and UNCONDITIONAL (a lane past its clip's end reads a row of a valid clip and never uses it):
-    // behind `if (valid)` the registers were cleared first, and a write to the destination of an older load makes hipcc wait for
-    // that load by COUNT -- it cannot count the younger stores issued under divergent branches, so it waited for (nearly) all of
-    // them, write-through granule stores included.  In the BPTT kernel below that wait was 3.3 k of 11.6 k cycles per step.
-    // ... and requested a step AHEAD, behind the previous step's sweep: loads return in order, so requested at the top of their own
-    // step (the first version) the sweep's L2 hits queued behind these three HBM misses.
+    // the input-projection gates: UNCONDITIONAL LOADS, A STEP AHEAD behind the previous step's sweep (gru_cell.h)
     const f32x4 gr = ngr, gz = ngz, gn = ngn;
     if (s == 0 && T > 1) load_gi(1);
     f32x4 ar = br, az = bz, an = bn;
@@ -234,13 +162,11 @@ __global__ __launch_bounds__(256) void gru_pers_fwd_kernel(PersFwdParams p, unsi
     f32x4 r, z, n, o = z4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      r[e] = sigmoid_f(gr[e] + ar[e]);
-      z[e] = sigmoid_f(gz[e] + az[e]);
-      n[e] = tanh_f(gn[e] + r[e] * an[e]);
+      GRU_GATES(r[e], z[e], n[e], gr[e] + ar[e], gz[e] + az[e], gn[e], an[e]);
     }
     if (valid) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) hp[e] = (1.0f - z[e]) * n[e] + z[e] * hp[e];
+      for (int e = 0; e < 4; ++e) hp[e] = GRU_BLEND(z[e], n[e], hp[e]);
       o = hp;
     }
     if (dead) o = f32x4{NAN_F, NAN_F, NAN_F, NAN_F};
@@ -285,7 +211,7 @@ __global__ __launch_bounds__(256) void gru_pers_bwd_kernel(PersBwdParams p, unsi
   __shared__ __attribute__((aligned(16))) float dsum[PSLICE * LDS_];
   __shared__ unsigned s_gen;
   int groups, group, part;
-  pers_ids(P, groups, group, part);
+  xchg_ids(P, groups, group, part);
   const int dir = group & 1, b0 = p.c0 + (group >> 1) * PSLICE;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, g = lane >> 4;
   const int ul = 16 * w + 4 * g;                 // local index of this lane's 4 units inside the part
@@ -294,12 +220,7 @@ __global__ __launch_bounds__(256) void gru_pers_bwd_kernel(PersBwdParams p, unsi
   const bool clip_ok = clip < p.c0 + p.nc;
   const int len = clip_ok ? p.lengths[clip] : 0;
   const int T = p.T;
-  if (tid == 0) s_gen = __hip_atomic_load(&sync[0], __ATOMIC_RELAXED, SS_AGENT);
-  if (plays_dead(sync)) {  // wave-uniform; tests only
-    __syncthreads();
-    finish_launch(sync, s_gen);
-    return;
-  }
+  if (!xchg_begin(sync, s_gen, 0, 1)) return;
   __builtin_amdgcn_s_setprio(3);
 
   // A fragments: rows = output units 16 (MT w + mt) + li, k = local row 32 ks + 8 g + j = (gate, unit of this part)
@@ -316,11 +237,9 @@ __global__ __launch_bounds__(256) void gru_pers_bwd_kernel(PersBwdParams p, unsi
       }
   }
   __syncthreads();
-  const unsigned gen = s_gen;
-  const unsigned base = (gen & 0x3FFFFFu) << 10;
-  bool dead = false;
-  const bool same_xcd = partners_share_xcd(xid, group, part, P, base, &sync[2], lane, &dead);
-  if (tid == 0 && same_xcd) atomicAdd(&sync[3], 1u);
+  unsigned gen, base;
+  bool dead;
+  const bool same_xcd = xchg_open(sync, s_gen, xid, group, part, P, lane, gen, base, dead);
 
   const long N = (long)p.B * T;
   const rsrc_t xrs = granule_rsrc(xg, 2L * groups * P * P * PSLICE * (PUNITS / 2));
@@ -328,9 +247,8 @@ __global__ __launch_bounds__(256) void gru_pers_bwd_kernel(PersBwdParams p, unsi
   f32x4 dh = z4;
   f32x4 sb_r = z4, sb_z = z4, sb_n = z4, sb_q = z4;  // bias-gradient sums of this lane's (clip, 4 units)
   f32x4 go, gsc, sr, sz, sn, sq, hprev;
-  // The loads of a step's inputs are UNCONDITIONAL (a lane past its clip's end, or without a previous state, reads a row of a valid
-  // clip; the step tests `valid` / `hp_ok` where it uses the values): see the forward kernel -- behind `if (t < len)` the registers
-  // were cleared first and hipcc waited for the step's granule stores before it touched them (3.3 k of 11.6 k cycles per step).
+  // UNCONDITIONAL LOADS (gru_cell.h); behind `if (t < len)` the wait for the step's granule stores was 3.3 k of 11.6 k cycles per
+  // step in this kernel's stage timers
   auto load_inputs = [&](int s) {
     const int t = dir ? s : (T - 1 - s);
     const int tp = dir ? t + 1 : t - 1;
@@ -338,15 +256,10 @@ __global__ __launch_bounds__(256) void gru_pers_bwd_kernel(PersBwdParams p, unsi
     const long cl = clip_ok ? clip : p.c0;
     const long row = cl * T + (in ? t : 0), rowp = cl * T + ((in && tp >= 0 && tp < len) ? tp : 0);
     go = *reinterpret_cast<const f32x4*>(p.d_out + row * (2 * H) + dir * H + u0);
-    // the dropout scale stays beside the raw load: multiplying here made the wave sit through the load's whole latency in
-    // every step of a layer with dropout (2 700 of 12 200 cycles, stage timers)
+    // THE DROPOUT SCALE STAYS BESIDE THE RAW LOAD (gru_cell.h): multiplied here it cost 2 700 of 12 200 cycles (stage timers)
     gsc = f32x4{1.f, 1.f, 1.f, 1.f};
     if (p.drop_p > 0.f) gsc = drop_scale4((row * (2 * H) + dir * H + u0) >> 2, p.drop_p, p.seed, p.offset);  // (wave-uniform branch)
-    const float* sv = p.save + ((long)dir * N + row) * (4 * H) + u0;
-    sr = *reinterpret_cast<const f32x4*>(sv);
-    sz = *reinterpret_cast<const f32x4*>(sv + H);
-    sn = *reinterpret_cast<const f32x4*>(sv + 2 * H);
-    sq = *reinterpret_cast<const f32x4*>(sv + 3 * H);
+    load_rows4(p.save + ((long)dir * N + row) * (4 * H) + u0, H, sr, sz, sn, sq);
     hprev = *reinterpret_cast<const f32x4*>(p.out + rowp * (2 * H) + dir * H + u0);
   };
   load_inputs(0);
@@ -365,20 +278,13 @@ __global__ __launch_bounds__(256) void gru_pers_bwd_kernel(PersBwdParams p, unsi
     if (valid) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float d = go[e] * gsc[e] + dh[e];
-        const float dn = d * (1.0f - sz[e]);
-        const float dz = d * ((hp_ok ? hprev[e] : 0.f) - sn[e]);
-        dan[e] = dn * (1.0f - sn[e] * sn[e]);
-        dar[e] = dan[e] * sq[e] * sr[e] * (1.0f - sr[e]);
-        daz[e] = dz * sz[e] * (1.0f - sz[e]);
-        dqn[e] = dan[e] * sr[e];
-        dcarry[e] = d * sz[e];
+        GRU_GATE_GRADS(dar[e], daz[e], dan[e], dqn[e], dcarry[e], go[e] * gsc[e] + dh[e], sr[e], sz[e], sn[e], sq[e],
+                       hp_ok ? hprev[e] : 0.f);
       }
     }
     if (dead) dar = daz = dan = dqn = f32x4{NAN_F, NAN_F, NAN_F, NAN_F};
-    // The next step's inputs are requested HERE, into the registers the gate gradients above have just finished with: loads return
-    // in order, so requested behind the publish (as the first version did) the sweep's L2 hits queued behind six HBM misses and
-    // every step paid max(miss, exchange) -- "next step's inputs" 3.3 k of 11.6 k cycles in the stage timers.
+    // A STEP AHEAD (gru_cell.h), into the registers the gate gradients above have just finished with: requested behind the publish
+    // every step paid max(miss, exchange) -- "next step's inputs" 3.3 k of 11.6 k cycles in the stage timers
     if (!last) load_inputs(s + 1);
     const uint2 br_ = pack_bf16x4(dar[0], dar[1], dar[2], dar[3]), bz_ = pack_bf16x4(daz[0], daz[1], daz[2], daz[3]),
                 bq_ = pack_bf16x4(dqn[0], dqn[1], dqn[2], dqn[3]);
@@ -454,6 +360,8 @@ __global__ __launch_bounds__(256) void gru_pers_bwd_kernel(PersBwdParams p, unsi
     STAMP(11);
   }
   STAMP_FLUSH();
+  // (GruBiasAcc::flush with its atomics in another order, and the row stores above not through store_rows3 / store_rows4: the
+  // shared text gives this kernel six to eleven instructions more and another schedule)
   if (p.g_bih[0]) {  // sum over the 16 clips of the slice (the lanes of a row), one atomic per unit and workgroup
     float* gbi = p.g_bih[dir];
     float* gbh = p.g_bhh[dir];
@@ -469,10 +377,11 @@ __global__ __launch_bounds__(256) void gru_pers_bwd_kernel(PersBwdParams p, unsi
   finish_launch(sync, gen);
 }
 
-// sync workspace sections (granules of 8 bytes) for up to `groups` groups
-inline long pers_xid_granules(int groups, int P) { return ((long)groups * P + 7) / 8 * 8; }
-inline long pers_fwd_granules(int groups, int H) { return 2L * groups * PSLICE * (H / 2); }
-inline long pers_bwd_granules(int groups, int H) { return 2L * groups * (H / PUNITS) * (H / PUNITS) * PSLICE * (PUNITS / 2); }
+// sync workspace sections for launches of up to `chunk` clips
+inline SyncSections pers_sync(int chunk, int H) {
+  const long groups = 2 * ceil_div(chunk, PSLICE), P = H / PUNITS;
+  return SyncSections{(groups * P + 7) / 8 * 8, 2 * groups * PSLICE * (H / 2), 2 * groups * P * P * PSLICE * (PUNITS / 2)};
+}
 
 inline bool pers_supported(int H) { return H >= 128 && H <= 512 && H % 64 == 0; }
 
@@ -489,6 +398,12 @@ inline int pers_chunk_clips(int B, int H, int cus) {
   int per = ceil_div(need, launches);
   if ((per + 3) / 4 * 4 <= slices) per = (per + 3) / 4 * 4;
   return per * PSLICE;
+}
+
+
+// clips per persistent launch of a shape, 0 = the step kernels run it
+inline int pers_launch_chunk(int B, int T, int H) {
+  return pers_supported(H) && T <= XCHG_MAX_T ? pers_chunk_clips(B, H, ss_device_cus()) : 0;
 }
 
 }  // namespace

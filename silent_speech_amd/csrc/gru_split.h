@@ -45,7 +45,6 @@ namespace {
 
 // co-residency bound of the multi-CU recurrence: one 4-wave workgroup per CU, 16 CUs of slack (240 on MI355X's 256 CUs)
 inline int split_max_wgs() { return ss_device_cus() - 16; }
-constexpr int SPLIT_MAX_T = 1022;
 
 template <int H, int P>
 struct SplitCfg {
@@ -71,13 +70,9 @@ __global__ __launch_bounds__(256) void gru_split_fwd_kernel(GruFwdParams p, unsi
   __shared__ __attribute__((aligned(16))) float red[C::RED];
   __shared__ __attribute__((aligned(16))) float hpan[SLICE * LDH];  // previous state of the slice, [clip][unit]
   __shared__ unsigned s_gen;
-  // part-major when the pair count is a multiple of 8: workgroups b and b + 8k share an XCD, so do the partners then
-  // (the launch pads the pair count to a multiple of 8 where the padded grid still fits -- gru_split_grid_pairs: workgroups of the
-  // pad pairs leave at once -- so small batches, the reference's own 16 clips among them, get the same-XCD exchange too)
-  const int pairs = 2 * ((p.B + SLICE - 1) / SLICE), grid_pairs = gridDim.x / P;
-  const bool part_major = (grid_pairs & 7) == 0;
-  const int part = part_major ? blockIdx.x / grid_pairs : blockIdx.x % P;
-  const int pair = part_major ? blockIdx.x % grid_pairs : blockIdx.x / P;
+  const int pairs = 2 * ((p.B + SLICE - 1) / SLICE);
+  int grid_pairs, pair, part;
+  xchg_ids(P, grid_pairs, pair, part);
   const int dir = pair & 1, b0 = (pair >> 1) * SLICE;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int ut = w % C::UT, kh = w / C::UT;
@@ -88,14 +83,13 @@ __global__ __launch_bounds__(256) void gru_split_fwd_kernel(GruFwdParams p, unsi
   const bool clip_ok = clip < p.B;
   const int len = clip_ok ? p.lengths[clip] : 0;
   const int T = p.T;
+  // (xchg_begin's text: as a call, the pad test joins the branch with its operands swapped)
   if (threadIdx.x == 0) s_gen = __hip_atomic_load(&sync[0], __ATOMIC_RELAXED, SS_AGENT);
-  if (plays_dead(sync) || pair >= pairs) {  // wave-uniform; tests only, resp. a workgroup of the grid's pad
+  if (plays_dead(sync) || pair >= pairs) {
     __syncthreads();
     finish_launch(sync, s_gen);
     return;
   }
-  // every cycle of this chain is on the step's critical path: issue ahead of the weight-gradient GEMM waves that
-  // share the SIMDs
   __builtin_amdgcn_s_setprio(3);
 
   // A fragments: rows = this tile's units of gate G, slots (q, e) carry k = 16*(kh*QF + q) + 4g + e
@@ -119,22 +113,15 @@ __global__ __launch_bounds__(256) void gru_split_fwd_kernel(GruFwdParams p, unsi
     bn = *reinterpret_cast<const f32x4*>(p.b_hh[dir] + 2 * H + j0);
   }
   __syncthreads();
-  const unsigned gen = s_gen;
-  const unsigned base = (gen & 0x3FFFFFu) << 10;
-  bool dead = false;  // a partner never arrived: everything this workgroup emits from then on is NaN
-  const bool same_xcd = partners_share_xcd(xid, pair, part, P, base, &sync[2], lane, &dead);
-  if (threadIdx.x == 0 && same_xcd) atomicAdd(&sync[3], 1u);  // observability: workgroup-launches on the fast path
+  unsigned gen, base;
+  bool dead;
+  const bool same_xcd = xchg_open(sync, s_gen, xid, pair, part, P, lane, gen, base, dead);
 
   f32x4 hp = {0.f, 0.f, 0.f, 0.f};
   const long dir_off = (long)dir * p.B * T;
   const rsrc_t hrs = granule_rsrc(hx, 2L * pairs * SLICE * H);
-  // (unconditional for the owner waves: a lane past its clip's end reads its clip's first row and never uses the values -- behind
-  // `valid` the registers were cleared first, and hipcc waits for a step's younger stores before it overwrites the destination
-  // of an older load)
-  // input-projection gates of a step: independent of the recurrence, requested a step AHEAD behind the previous step's sweep into
-  // the other of two register sets (the step loop runs two steps per turn).  The first version requested them at the top of their
-  // own step, "in flight during the sweep": loads return in order, so the sweep's L2 hits queued behind these three HBM misses
-  // (found in the bf16 kernels' stage timers); one set copied at the top of the step made the copy wait for them there.
+  // input-projection gates of a step (owner waves): UNCONDITIONAL LOADS, A STEP AHEAD (gru_cell.h), into the other of two register
+  // sets -- the step loop runs two steps per turn; one set copied at the top of the step made the copy wait for the loads there
   struct Gi { f32x4 r, z, n; };
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   Gi gA{zero4, zero4, zero4}, gB{zero4, zero4, zero4};
@@ -205,10 +192,8 @@ __global__ __launch_bounds__(256) void gru_split_fwd_kernel(GruFwdParams p, unsi
       f32x4 r, z, n, hn;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        r[e] = sigmoid_f(gc.r[e] + ar[e]);
-        z[e] = sigmoid_f(gc.z[e] + az[e]);
-        n[e] = tanh_f(gc.n[e] + r[e] * an[e]);
-        hn[e] = (1.0f - z[e]) * n[e] + z[e] * hp[e];
+        GRU_GATES(r[e], z[e], n[e], gc.r[e] + ar[e], gc.z[e] + az[e], gc.n[e], an[e]);
+        hn[e] = GRU_BLEND(z[e], n[e], hp[e]);
       }
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
       if (valid) {
@@ -230,13 +215,7 @@ __global__ __launch_bounds__(256) void gru_split_fwd_kernel(GruFwdParams p, unsi
           if (p.drop_p > 0.f) od *= drop_scale4(e0 >> 2, p.drop_p, p.drop_seed, p.drop_off);
           *reinterpret_cast<f32x4*>(p.out_drop + e0) = od;
         }
-        if (p.save && valid) {
-          float* sp = p.save + (dir_off + frame) * (4 * H) + j0;
-          *reinterpret_cast<f32x4*>(sp) = r;
-          *reinterpret_cast<f32x4*>(sp + H) = z;
-          *reinterpret_cast<f32x4*>(sp + 2 * H) = n;
-          *reinterpret_cast<f32x4*>(sp + 3 * H) = an;
-        }
+        if (p.save && valid) store_rows4(p.save + (dir_off + frame) * (4 * H) + j0, H, r, z, n, an);
       }
     }
   };
@@ -263,9 +242,7 @@ __global__ __launch_bounds__(256) void gru_split_bwd_kernel(GruBwdParams p, unsi
   __shared__ __attribute__((aligned(16))) float dpan[SLICE * LDP];     // this part's d_pre, [clip][local row]
   __shared__ __attribute__((aligned(16))) float dsum[SLICE * 32];      // summed dh_prev of this part's units (UP = 16: two halves)
   __shared__ unsigned s_gen;
-  // part-major when the pair count is a multiple of 8: workgroups b and b + 8k share an XCD, so do the partners then
-  // (the launch pads the pair count to a multiple of 8 where the padded grid still fits -- gru_split_grid_pairs: workgroups of the
-  // pad pairs leave at once -- so small batches, the reference's own 16 clips among them, get the same-XCD exchange too)
+  // (xchg_ids' text: through the call this kernel computes its clip index another way, ten instructions more at UP = 32)
   const int pairs = 2 * ((p.B + SLICE - 1) / SLICE), grid_pairs = gridDim.x / P;
   const bool part_major = (grid_pairs & 7) == 0;
   const int part = part_major ? blockIdx.x / grid_pairs : blockIdx.x % P;
@@ -280,13 +257,14 @@ __global__ __launch_bounds__(256) void gru_split_bwd_kernel(GruBwdParams p, unsi
   const bool clip_ok = clip < p.B;
   const int len = clip_ok ? p.lengths[clip] : 0;
   const int T = p.T;
+  // (xchg_begin's text: as a call, the pad test joins the branch with its operands swapped)
   if (threadIdx.x == 0) s_gen = __hip_atomic_load(&sync[0], __ATOMIC_RELAXED, SS_AGENT);
-  if (plays_dead(sync) || pair >= pairs) {  // wave-uniform; tests only, resp. a workgroup of the grid's pad
+  if (plays_dead(sync) || pair >= pairs) {
     __syncthreads();
     finish_launch(sync, s_gen);
     return;
   }
-  __builtin_amdgcn_s_setprio(3);  // as in the forward kernel
+  __builtin_amdgcn_s_setprio(3);
 
   // A fragments: A[i = output unit 16*(NT*w + nt) + i][slot (q, e)] = W[row(16q + 4g + e)][unit], local row
   // kk = G * UP + u  <->  W row G*H + part*UP + u
@@ -304,11 +282,9 @@ __global__ __launch_bounds__(256) void gru_split_bwd_kernel(GruBwdParams p, unsi
         }
   }
   __syncthreads();
-  const unsigned gen = s_gen;
-  const unsigned base = (gen & 0x3FFFFFu) << 10;
-  bool dead = false;  // a partner never arrived: every gate gradient this workgroup emits from then on is NaN
-  const bool same_xcd = partners_share_xcd(xid, pair, part, P, base, &sync[2], lane, &dead);
-  if (threadIdx.x == 0 && same_xcd) atomicAdd(&sync[3], 1u);  // observability: workgroup-launches on the fast path
+  unsigned gen, base;
+  bool dead;
+  const bool same_xcd = xchg_open(sync, s_gen, xid, pair, part, P, lane, gen, base, dead);
 
   f32x4 dh = {0.f, 0.f, 0.f, 0.f};
   GruBiasAcc bacc;
@@ -319,26 +295,16 @@ __global__ __launch_bounds__(256) void gru_split_bwd_kernel(GruBwdParams p, unsi
   auto load_inputs = [&](int s) {
     const int t = dir ? s : (T - 1 - s);
     const int tp = dir ? t + 1 : t - 1;
-    // UNCONDITIONAL loads (an owner lane past its clip's end, or without a previous state, reads a row of its clip's first step
-    // and the step tests `valid` / `hp_ok` where it uses the values): behind `if (t < len)` the registers were cleared first, and a
-    // write to the destination of an older load makes hipcc wait for that load by COUNT -- it cannot count the younger stores issued
-    // under divergent branches, so it waited for the step's granule stores as well (found in the bf16 kernel's stage timers:
-    // 3.3 k of 11.6 k cycles per step)
+    // UNCONDITIONAL LOADS (gru_cell.h): an owner lane past its clip's end, or without a previous state, reads its clip's first row
     gsc = f32x4{1.f, 1.f, 1.f, 1.f};
     if (owner) {  // (the non-owner lanes of a wave hold no units: wave-uniform by construction of the lane map)
       const bool in = t < len;
       const long cl = clip_ok ? clip : b0;
       const long frame = cl * T + (in ? t : 0), framep = cl * T + ((in && tp >= 0 && tp < len) ? tp : 0);
       go = *reinterpret_cast<const f32x4*>(p.d_out + frame * (2 * H) + dir * H + j0);
-      // the dropout scale stays beside the raw load and is applied where the gradient is used, a step later: multiplying here
-      // made the wave wait for the load it had just issued -- a memory latency in front of every sweep of a layer with dropout
-      // (found with the stage timers of the bf16 kernel, which had inherited the line)
+      // THE DROPOUT SCALE STAYS BESIDE THE RAW LOAD (gru_cell.h)
       if (p.drop_p > 0.f) gsc = drop_scale4((frame * (2 * H) + dir * H + j0) >> 2, p.drop_p, p.drop_seed, p.drop_off);
-      const float* sp = p.save + (dir_off + frame) * (4 * H) + j0;
-      sr = *reinterpret_cast<const f32x4*>(sp);
-      sz = *reinterpret_cast<const f32x4*>(sp + H);
-      sn = *reinterpret_cast<const f32x4*>(sp + 2 * H);
-      sq = *reinterpret_cast<const f32x4*>(sp + 3 * H);
+      load_rows4(p.save + (dir_off + frame) * (4 * H) + j0, H, sr, sz, sn, sq);
       hprev = *reinterpret_cast<const f32x4*>(p.out + framep * (2 * H) + dir * H + j0);
     }
   };
@@ -359,27 +325,14 @@ __global__ __launch_bounds__(256) void gru_split_bwd_kernel(GruBwdParams p, unsi
       if (valid) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float d = go[e] * gsc[e] + dh[e];
-          const float dn = d * (1.0f - sz[e]);
-          const float dz = d * ((hp_ok ? hprev[e] : 0.f) - sn[e]);
-          dan[e] = dn * (1.0f - sn[e] * sn[e]);
-          dar[e] = dan[e] * sq[e] * sr[e] * (1.0f - sr[e]);
-          daz[e] = dz * sz[e] * (1.0f - sz[e]);
-          dqn[e] = dan[e] * sr[e];
-          dcarry[e] = d * sz[e];
+          GRU_GATE_GRADS(dar[e], daz[e], dan[e], dqn[e], dcarry[e], go[e] * gsc[e] + dh[e], sr[e], sz[e], sn[e], sq[e],
+                         hp_ok ? hprev[e] : 0.f);
         }
       }
       if (dead) dar = daz = dan = dqn = f32x4{NAN_F, NAN_F, NAN_F, NAN_F};
-      if (!last) {
-        float* dp = &dpan[i * LDP + 16 * ut + 4 * g];
-        *reinterpret_cast<f32x4*>(dp) = dar;
-        *reinterpret_cast<f32x4*>(dp + C::UP) = daz;
-        *reinterpret_cast<f32x4*>(dp + 2 * C::UP) = dqn;
-      }
+      if (!last) store_rows3(&dpan[i * LDP + 16 * ut + 4 * g], C::UP, dar, daz, dqn);
     }
-    // The next step's inputs are requested here, into the registers the gate gradients above have just finished with: loads return
-    // in order, so requested behind the publish (the first version) the sweep's L2 hits queued behind six HBM misses
-    // (found in the bf16 kernel's stage timers: 3.3 k of 11.6 k cycles per step)
+    // A STEP AHEAD (gru_cell.h): into the registers the gate gradients above have just finished with
     if (!last) load_inputs(s + 1);
     if (!last) {
       __syncthreads();
@@ -408,13 +361,7 @@ __global__ __launch_bounds__(256) void gru_split_bwd_kernel(GruBwdParams p, unsi
       STAMP(2);
     }
     if (owner) bacc.add(dar, daz, dan, dqn);
-    if (owner && clip_ok) {
-      float* gp = p.d_g + (dir_off + frame) * (4 * H) + j0;
-      *reinterpret_cast<f32x4*>(gp) = dar;
-      *reinterpret_cast<f32x4*>(gp + H) = daz;
-      *reinterpret_cast<f32x4*>(gp + 2 * H) = dan;
-      *reinterpret_cast<f32x4*>(gp + 3 * H) = dqn;
-    }
+    if (owner && clip_ok) store_rows4(p.d_g + (dir_off + frame) * (4 * H) + j0, H, dar, daz, dan, dqn);
     if (last) break;
     // sum the P partials of this part's units: thread -> positions 2 tid, 2 tid + 1 of the [clip][UP] tile
     float xv[2 * NGP];
@@ -435,16 +382,17 @@ __global__ __launch_bounds__(256) void gru_split_bwd_kernel(GruBwdParams p, unsi
     }
     STAMP(1);
   }
-  if (owner) bacc.flush(p, dir, H, j0, i);  // owner is wave-uniform
+  if (owner) bacc.flush(p.g_bih, p.g_bhh, dir, H, j0, i);  // owner is wave-uniform
   STAMP_FLUSH();
   finish_launch(sync, gen);
 }
 
-// sync_ws sections, in granules
+// sync_ws sections of a batch whose backward pass runs P parts per pair
 constexpr int SPLIT_MAX_PARTS = 12;  // the XCD-id rows of the workspace are laid out for the widest split (forward, small batches)
-inline long gru_xid_granules(int B) { return ((2L * ceil_div(B, SLICE) * SPLIT_MAX_PARTS) + 7) / 8 * 8; }
-inline long gru_fwd_granules(int B, int H) { return 2L * (2 * ceil_div(B, SLICE)) * SLICE * H; }
-inline long gru_bwd_granules(int B, int H, int P) { return 2L * (2 * ceil_div(B, SLICE)) * P * SLICE * H; }
+inline SyncSections split_sync(int B, int H, int P) {
+  const long pairs = 2 * ceil_div(B, SLICE);
+  return SyncSections{(pairs * SPLIT_MAX_PARTS + 7) / 8 * 8, 2 * pairs * SLICE * H, 2 * pairs * P * SLICE * H};
+}
 
 // pairs the grid is launched with: the next multiple of 8 when that still fits the co-residency bound.  Workgroup b runs on XCD
 // b % 8 (round-robin dispatch), so with a multiple of 8 pairs and part-major numbering the P partners of a pair share an XCD and
@@ -471,9 +419,19 @@ inline int gru_split_small_parts(int B, int P) {
 // parts per (slice, direction) for a shape, or 0 when the single-workgroup form is the right one
 inline int gru_split_parts(int B, int T, int H) {
   const int pairs = 2 * ceil_div(B, SLICE);
-  if (T > SPLIT_MAX_T) return 0;
+  if (T > XCHG_MAX_T) return 0;
   const int P = H == 192 ? 6 : (H == 64 ? 2 : 0);
   return (P && pairs * P <= split_max_wgs()) ? P : 0;
+}
+
+// What ss_gru_fwd_drop and ss_gru_bwd launch for a shape: parts per (slice, direction) -- 0 = the single-workgroup form -- and the
+// workgroups of the padded grid.  (While a CU cap is set on the persistent CNN kernels -- Trainer(micro_batches > 1) -- the slices
+// keep six parts: the CUs the cap reserves hold 96 recurrence workgroups, what two 8-slice micro-batches of six parts need.)
+inline int gru_split_launch(const void* sync_ws, int B, int T, int H, int* wgs) {
+  int P = sync_ws ? gru_split_parts(B, T, H) : 0;
+  if (P && !ss_cnn_max_wgs) P = gru_split_small_parts(B, P);
+  *wgs = P ? gru_split_grid_pairs(B, P) * P : 0;
+  return P;
 }
 
 }  // namespace

@@ -104,6 +104,18 @@ def test_host_side_size_queries_need_no_gpu():
     assert lib.ss_gru_bf16_sync_bytes(256, 2000, 512, C.byref(n)) == 0 and n.value == 0        # step tags are 10 bits
     assert lib.ss_gru_bf16_sync_bytes(0, 30, 512, C.byref(n)) != 0
     assert _lib.gru_sync_bytes(256, 30, 192) > 0 and _lib.gru_sync_bytes(4096, 60, 192) == 0   # f32: one CU per slice for big batches
+    # Exact sizes: header + XCD ids + forward granules + backward granules, as the launchers carve them.  They follow the CU count,
+    # which is 256 without a device (the target chip's) and on an unpartitioned MI355X; a device of another size is not pinned.
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        return
+    f32 = {(16, 30, 192): 1278400, (128, 30, 192): 10225408, (129, 30, 192): 6195136, (256, 30, 192): 11013376,
+           (3, 1022, 192): 1278400, (3, 1023, 192): 0, (250, 9, 64): 1576192}
+    for (B, T, H), want in f32.items():
+        assert _lib.gru_sync_bytes(B, T, H) == want, (B, T, H)
+    bf16 = {(16, 30, 128): 98624, (256, 30, 512): 18876672, (2048, 30, 512): 18876672, (256, 1022, 512): 18876672,
+            (256, 1023, 512): 0}
+    for (B, T, H), want in bf16.items():
+        assert lib.ss_gru_bf16_sync_bytes(B, T, H, C.byref(n)) == 0 and n.value == want, (B, T, H)
 
 
 def test_bf16_weight_gradient_group_size_query_needs_no_gpu():

@@ -399,7 +399,7 @@ def test_gru_fwd_bwd_padded_past_the_longest_clip(L, H, B, T, lengths, split):
 
 @pytest.mark.parametrize("T", [1022, 1023])
 def test_gru_fwd_bwd_at_the_step_tag_limit(L, T):
-    """Step tags are 10 bits (gru_split.h, SPLIT_MAX_T = 1022): T = 1022 is the longest clip the multi-CU recurrence takes, at
+    """Step tags are 10 bits (granule_xchg.h, XCHG_MAX_T = 1022): T = 1022 is the longest clip the multi-CU recurrence takes, at
     T = 1023 gru_sync_bytes says 0 and the one-CU kernels run.  Both sides against the reference, ragged, max(len) < T on one side."""
     H, B = 192, 3
     nb = L.gru_sync_bytes(B, T, H)
@@ -410,7 +410,7 @@ def test_gru_fwd_bwd_at_the_step_tag_limit(L, T):
 
 @pytest.mark.parametrize("gen0", [2**22 - 2, -2], ids=["gen_2^22-2", "gen_2^32-2"])
 def test_gru_split_generation_wrap(L, gen0):
-    """The launch generation is masked to 22 bits in the step tags ((gen & 0x3FFFFF) << 10, gru_split.h) and is a 32-bit
+    """The launch generation is masked to 22 bits in the step tags ((gen & 0x3FFFFF) << 10, xchg_tag_base in granule_xchg.h) and is a 32-bit
     counter in the header: a graph replayed for every served window reaches both wraps.  The six launches of test_gru_fwd_bwd
     across each wrap give the bits a fresh workspace gives, and no bounded wait gives up (a wrong tag shows as NaN plus a
     time-out count in sync[2], not as a hang)."""
