@@ -350,6 +350,38 @@ int ss_batch_gather_u8_shift(const uint8_t* src, int H, int W, const int32_t* fr
 int ss_batch_gather_z(const float* feat, int D, const int32_t* xmap, const float* emb, int E, const int32_t* rmap,
                       const float* emb_fill, long rows, const int32_t* noise_map, float noise_std, uint64_t seed,
                       uint64_t noise_first, const float* row_scale, int rows_per_clip, float* dst, int ld_dst, ss_stream_t stream);
+/* The masking augmentations of the policy: one masked run of frames, one zeroed band of feature columns, one filled rectangle of
+ * the ROI frames, each per clip.  Two launches beside the ones above, which do not change: the masks are planned into the maps a
+ * planner has written, the band and the rectangle are written over what the gathers have written.
+ * ss_batch_plan_mask: behind ss_batch_plan or ss_batch_plan_aug on the same stream; one wave per batch row.  xmap, nmap, rmap
+ *   (may be NULL) (B, max_t) are edited in place, lens (B) is read.  Row b draws the planner's own counter (draw index
+ *   first_row + b, tag "plan", key = seed), sub-draws 4 (m0..m3), 5 (c0..c3) and 6 (q0..q3); sub-draws 0 - 3 keep their use.
+ *   n = lens[b]; has_roi = rmap && n > 0 && rmap[b][0] >= 0.
+ *     time  : augment && n >= 8 && m0 < thr(time_mask_prob): cap = min(time_mask_max, n / 4), tw = 1 + mulhi(m1, cap),
+ *             t0 = 1 + mulhi(m2, n - tw): the run [t0, t0 + tw) lies in [1, n), frame 0 is never masked, lens never changes.
+ *             time_mask_streams 0 (both), 1 (features: xmap and nmap), 2 (roi: rmap) selects the maps the run is written into;
+ *             time_mask_fill 0 (zero): their entries become -1, the gathers write zero rows (ss_batch_gather_z: emb_fill);
+ *             1 (hold): xmap[t] = xmap[t0 - 1], rmap[t] = rmap[t0 - 1], nmap untouched -- a repeated row takes fresh noise.
+ *     band  : augment && c0 < thr(feat_mask_prob): cw = 1 + mulhi(c1, min(feat_mask_max, D)), col0 = mulhi(c2, D - cw + 1).
+ *     cutout: augment && has_roi && c3 < thr(cutout_prob): rw = 1 + mulhi(q0, min(cut_max_w, W)),
+ *             rh = 1 + mulhi(q1, min(cut_max_h, H)), x0 = mulhi(q2, W - rw + 1), y0 = mulhi(q3, H - rh + 1).
+ *   A maximum of 0 switches its mask off (the cutout: either of its two).  row_mask (B, 8) int32 = {t0, tw, col0, cw, x0, y0, rw,
+ *   rh}; an inactive mask writes width 0 and position 0, an empty row (n = 0, the planner's invalid-index rows among them) eight
+ *   zeros and edits nothing.  SS_ERR_ARG, nothing written: a probability outside [0, 1], a negative maximum, streams outside
+ *   0..2, fill outside 0..1, cutout_fill outside [0, 255] (only checked here), a cutout that is on with rmap NULL or H, W <= 0.
+ * ss_batch_mask_apply: behind the gathers, in place.  Row r of the batch belongs to clip r / rows_per_clip:
+ *     X[r][col0, col0 + cw) = 0.0f; X rows are ld_x >= D floats apart, so the call serves the dense X (ld_x = D) and the Z of
+ *     ss_batch_gather_z (ld_x = D + E) alike;  R[r][y0, y0 + rh)[x0, x0 + rw) = fill where rmap[r] >= 0 (zero-padding frames and
+ *     the frames of clips without ROI stay zero).  X or R may be NULL (its half is skipped).  Nothing else is read or written:
+ *   the launch's traffic is the masked bytes and the two tables.  Whatever row_mask holds, positions and widths are clamped into
+ *   the row and the frame first.  SS_ERR_ARG: both X and R NULL, rows % rows_per_clip != 0, fill outside [0, 255], ld_x < D,
+ *   R without rmap. */
+int ss_batch_plan_mask(int32_t* xmap, int32_t* nmap, int32_t* rmap, const int64_t* lens, int B, int max_t, int D, int H, int W,
+                       int augment, uint64_t first_row, uint64_t seed, double time_mask_prob, int time_mask_max,
+                       int time_mask_streams, int time_mask_fill, double feat_mask_prob, int feat_mask_max, double cutout_prob,
+                       int cut_max_w, int cut_max_h, int cutout_fill, int32_t* row_mask, ss_stream_t stream);
+int ss_batch_mask_apply(float* X, int ld_x, int D, uint8_t* R, int H, int W, const int32_t* rmap, const int32_t* row_mask,
+                        long rows, int rows_per_clip, int fill, ss_stream_t stream);
 
 /* ---- sliding-window serving of many streams ---------------------------------------
  * per stream a ring of the last max_t frames (features (S,max_t,D) f32, optional ROI (S,max_t,frame_bytes) u8), a head

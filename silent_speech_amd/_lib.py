@@ -91,6 +91,8 @@ SIGNATURES = {
     "ss_batch_gather_f32_aug": [_vp, _i, _vp, _l, _vp, _f, _u64, _u64, _vp, _i, _vp, _vp],
     "ss_batch_gather_u8_shift": [_vp, _i, _i, _vp, _l, _vp, _i, _i, _i, _vp, _vp],
     "ss_batch_gather_z": [_vp, _i, _vp, _vp, _i, _vp, _vp, _l, _vp, _f, _u64, _u64, _vp, _i, _vp, _i, _vp],
+    "ss_batch_plan_mask": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _u64, _u64, _d, _i, _i, _i, _d, _i, _d, _i, _i, _i, _vp, _vp],
+    "ss_batch_mask_apply": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _l, _i, _i, _vp],
     "ss_crop_gray_resize": [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp],
     "ss_ring_tick": [_vp, _i, _vp, _vp],
     "ss_ring_push": [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],

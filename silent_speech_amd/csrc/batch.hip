@@ -9,7 +9,7 @@
 // (rng "reference" / "device") or from the planning kernels below them: the epoch's class-balanced sample order
 // (:382-397) and the augmentation draws + maps of a batch, both on the Philox stream, nothing crossing PCIe.
 //
-// Six kernels behind the nine entry points:
+// Eight kernels behind the eleven entry points:
 //   batch_gather_f32_kernel<HOST_NOISE, SCALE>  ss_batch_gather_f32 (<true, false> with a noise table, else <false, false>),
 //                                               ss_batch_gather_f32_at (<false, false>), ss_batch_gather_f32_aug (<false, true>)
 //   batch_gather_z_kernel<W>                    ss_batch_gather_z (W = 4: 16 bytes per lane; W = 1: any row geometry)
@@ -17,6 +17,8 @@
 //   batch_gather_u8_shift_kernel<WIDE>          ss_batch_gather_u8_shift (WIDE: W % 16 == 0)
 //   epoch_sample_kernel                         ss_epoch_sample
 //   batch_plan_kernel<POLICY>                   ss_batch_plan (<false>), ss_batch_plan_aug (<true>)
+//   batch_plan_mask_kernel                      ss_batch_plan_mask (behind either planner: edits its maps in place)
+//   batch_mask_apply_kernel                     ss_batch_mask_apply (behind the gathers: writes the masked bytes only)
 #include "ss_common.h"
 
 namespace {
@@ -418,6 +420,134 @@ __global__ __launch_bounds__(SS_WAVE) void batch_plan_kernel(
   }
 }
 
+// ---- the masking augmentations (AugmentPolicy: time mask, feature band, ROI cutout).  Two launches beside the kernels above,
+// none of which changes: the plan of the masks edits the maps a planner has written, the apply step overwrites the masked
+// columns and rectangles of what the gathers have written.
+struct MaskPolicy {
+  uint64_t time_thr;
+  int time_max, streams /* 0 both, 1 features, 2 roi */, hold;
+  uint64_t band_thr;
+  int band_max;
+  uint64_t cut_thr;
+  int cut_max_w, cut_max_h;
+};
+
+// One wave per batch row, lanes over t, as the planner; row b draws the planner's own counter (first_row + b, "plan", seed),
+// sub-draws 4 (m: time mask), 5 (c: feature band, cutout decision) and 6 (q: cutout rectangle).  n = lens[b] is what the
+// planner left; the run [t0, t0 + tw) lies in [1, n), so frame 0 stays and lens is only read.  "zero": the entries of the run
+// become -1 (features: xmap and nmap); "hold": they become entry t0 - 1, which lies before the run and is written by nobody here
+// (nmap stays: a repeated row takes fresh noise).  A maximum of 0 switches its mask off; an inactive mask is width 0 at position
+// 0, an empty row eight zeros.  row_mask[b] = {t0, tw, col0, cw, x0, y0, rw, rh}.
+__global__ __launch_bounds__(SS_WAVE) void batch_plan_mask_kernel(int32_t* xmap, int32_t* nmap, int32_t* rmap,
+                                                                  const int64_t* __restrict__ lens, int max_t, int D, int H, int W,
+                                                                  int augment, uint64_t first_row, uint64_t seed, MaskPolicy pol,
+                                                                  int32_t* __restrict__ row_mask) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long base = (long)b * max_t;
+  const int64_t len = lens[b];
+  const int n = len < 0 ? 0 : len > max_t ? max_t : (int)len;
+  int t0 = 0, tw = 0, col0 = 0, cw = 0, x0 = 0, y0 = 0, rw = 0, rh = 0;
+  if (augment && n > 0) {
+    const bool has_roi = rmap && rmap[base] >= 0;  // (entry 0 is never masked)
+    const uint64_t row = first_row + (uint64_t)b;
+    const uint32_t r0 = (uint32_t)row, r1 = (uint32_t)(row >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    if (pol.time_thr && pol.time_max >= 1 && n >= 8) {
+      uint32_t m[4];
+      philox4(r0, r1, TAG_PLANNER, 4u, k0, k1, m);
+      if ((uint64_t)m[0] < pol.time_thr) {
+        const int cap = pol.time_max < n / 4 ? pol.time_max : n / 4;
+        tw = 1 + (int)mulhi_u32(m[1], (uint32_t)cap);
+        t0 = 1 + (int)mulhi_u32(m[2], (uint32_t)(n - tw));
+      }
+    }
+    const bool band_on = pol.band_thr && pol.band_max >= 1;
+    const bool cut_on = pol.cut_thr && pol.cut_max_w >= 1 && pol.cut_max_h >= 1 && has_roi;
+    if (band_on || cut_on) {
+      uint32_t c[4];
+      philox4(r0, r1, TAG_PLANNER, 5u, k0, k1, c);
+      if (band_on && (uint64_t)c[0] < pol.band_thr) {
+        cw = 1 + (int)mulhi_u32(c[1], (uint32_t)(pol.band_max < D ? pol.band_max : D));
+        col0 = (int)mulhi_u32(c[2], (uint32_t)(D - cw + 1));
+      }
+      if (cut_on && (uint64_t)c[3] < pol.cut_thr) {
+        uint32_t q[4];
+        philox4(r0, r1, TAG_PLANNER, 6u, k0, k1, q);
+        rw = 1 + (int)mulhi_u32(q[0], (uint32_t)(pol.cut_max_w < W ? pol.cut_max_w : W));
+        rh = 1 + (int)mulhi_u32(q[1], (uint32_t)(pol.cut_max_h < H ? pol.cut_max_h : H));
+        x0 = (int)mulhi_u32(q[2], (uint32_t)(W - rw + 1));
+        y0 = (int)mulhi_u32(q[3], (uint32_t)(H - rh + 1));
+      }
+    }
+    if (tw) {
+      const bool feat = pol.streams != 2, roi = pol.streams != 1 && rmap;
+      int hx = -1, hr = -1;
+      if (pol.hold) {
+        if (feat) hx = xmap[base + t0 - 1];
+        if (roi) hr = rmap[base + t0 - 1];
+      }
+      for (int t = t0 + lane; t < t0 + tw; t += SS_WAVE) {
+        if (feat) {
+          xmap[base + t] = hx;
+          if (!pol.hold) nmap[base + t] = -1;
+        }
+        if (roi) rmap[base + t] = hr;
+      }
+    }
+  }
+  if (lane < 8) {
+    const int v = lane == 0 ? t0 : lane == 1 ? tw : lane == 2 ? col0 : lane == 3 ? cw : lane == 4 ? x0 : lane == 5 ? y0
+                : lane == 6 ? rw : rh;
+    row_mask[(long)b * 8 + lane] = v;
+  }
+}
+
+// The band and the rectangle of row_mask written over what the gathers left, in place: one wave per row r of the batch (clip
+// r / rows_per_clip), so the launch reads the two tables and writes the masked bytes -- it is not a pass over X or R.
+//   X[r][col0, col0 + cw) = 0.0f (X NULL: skipped);  R[r][y0, y0 + rh)[x0, x0 + rw) = fill where rmap[r] >= 0 (R NULL: skipped).
+// Position and width are clamped into the row and the frame before any address is formed, whatever the table holds.  A run of
+// the rectangle inside one image row goes as the bytes up to the next 4-byte address, whole dwords, and the bytes left over:
+// chunk 0 is the head, chunk k >= 1 the k-th dword behind it; a power-of-two group of lanes takes the chunks of one image row,
+// the groups of the wave take the image rows.  No byte outside the rectangle is read or written.
+__global__ __launch_bounds__(256) void batch_mask_apply_kernel(float* __restrict__ X, int ld_x, int D, uint8_t* __restrict__ R,
+                                                               int H, int W, const int32_t* __restrict__ rmap,
+                                                               const int32_t* __restrict__ row_mask, long rows, int rows_per_clip,
+                                                               int fill) {
+  const int lane = threadIdx.x & (SS_WAVE - 1), wave = threadIdx.x / SS_WAVE;
+  const uint32_t fill4 = 0x01010101u * (uint32_t)fill;
+  for (long r = (long)blockIdx.x * 4 + wave; r < rows; r += (long)gridDim.x * 4) {
+    const int32_t* m = row_mask + 8 * (r / rows_per_clip);
+    if (X) {
+      const int col0 = clampi(m[2], 0, D), cw = clampi(m[3], 0, D - col0);
+      float* x = X + r * ld_x + col0;
+      for (int c = lane; c < cw; c += SS_WAVE) x[c] = 0.f;
+    }
+    if (R) {
+      const int x0 = clampi(m[4], 0, W), y0 = clampi(m[5], 0, H);
+      const int rw = clampi(m[6], 0, W - x0), rh = clampi(m[7], 0, H - y0);
+      if (rw == 0 || rh == 0 || rmap[r] < 0) continue;
+      uint8_t* frame = R + r * ((long)H * W);
+      const int chunks = (rw + 3) / 4 + 1;
+      int shift = 0;  // lanes per image row: the power of two that holds the chunks, at most the wave
+      while ((1 << shift) < chunks && shift < 6) ++shift;
+      const int sub = 1 << shift, lx = lane & (sub - 1), ly = lane >> shift;
+      for (int y = ly; y < rh; y += SS_WAVE >> shift) {
+        uint8_t* s = frame + (long)(y0 + y) * W + x0;
+        const int head = (int)((4 - (reinterpret_cast<uintptr_t>(s) & 3)) & 3);
+        for (int k = lx; k < chunks; k += sub) {
+          const int lo = k == 0 ? 0 : head + 4 * (k - 1);
+          int hi = k == 0 ? head : lo + 4;
+          hi = hi < rw ? hi : rw;
+          if (hi - lo == 4) {
+            *reinterpret_cast<uint32_t*>(s + lo) = fill4;  // (k >= 1: s + lo is a 4-byte address)
+          } else {
+            for (int i = lo; i < hi; ++i) s[i] = (uint8_t)fill;
+          }
+        }
+      }
+    }
+  }
+}
+
 // the launch of the f32 gather shared by its three entry points: one lane per 16-byte chunk of dst, at most 4096 workgroups
 template <bool HOST_NOISE, bool SCALE>
 int launch_gather_f32(const float* src, int D, const int32_t* frame_map, long rows, const float* noise, const int32_t* noise_map,
@@ -578,5 +708,39 @@ extern "C" int ss_batch_gather_z(const float* feat, int D, const int32_t* xmap, 
     hipLaunchKernelGGL(batch_gather_z_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), feat, D,
                        xmap, emb, E, rmap, emb_fill, rows, noise_map, noise_std, seed, noise_first, row_scale,
                        row_scale ? rows_per_clip : 1, dst, ld_dst);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_plan_mask(int32_t* xmap, int32_t* nmap, int32_t* rmap, const int64_t* lens, int B, int max_t, int D, int H,
+                                  int W, int augment, uint64_t first_row, uint64_t seed, double time_mask_prob, int time_mask_max,
+                                  int time_mask_streams, int time_mask_fill, double feat_mask_prob, int feat_mask_max,
+                                  double cutout_prob, int cut_max_w, int cut_max_h, int cutout_fill, int32_t* row_mask,
+                                  ss_stream_t stream) {
+  SS_REQUIRE(xmap && nmap && lens && row_mask && B > 0 && max_t > 0 && D > 0 && H >= 0 && W >= 0, SS_ERR_ARG);
+  SS_REQUIRE(time_mask_prob >= 0.0 && time_mask_prob <= 1.0 && feat_mask_prob >= 0.0 && feat_mask_prob <= 1.0, SS_ERR_ARG);
+  SS_REQUIRE(cutout_prob >= 0.0 && cutout_prob <= 1.0, SS_ERR_ARG);  // (a NaN fails every one of these)
+  SS_REQUIRE(time_mask_max >= 0 && feat_mask_max >= 0 && cut_max_w >= 0 && cut_max_h >= 0, SS_ERR_ARG);
+  SS_REQUIRE(time_mask_streams >= 0 && time_mask_streams <= 2 && time_mask_fill >= 0 && time_mask_fill <= 1, SS_ERR_ARG);
+  SS_REQUIRE(cutout_fill >= 0 && cutout_fill <= 255, SS_ERR_ARG);
+  const bool cut_on = cutout_prob > 0.0 && cut_max_w >= 1 && cut_max_h >= 1;
+  SS_REQUIRE(!cut_on || (rmap && H > 0 && W > 0), SS_ERR_ARG);
+  const MaskPolicy pol{prob_threshold(time_mask_prob), time_mask_max, time_mask_streams, time_mask_fill,
+                       prob_threshold(feat_mask_prob), feat_mask_max, prob_threshold(cutout_prob), cut_max_w, cut_max_h};
+  hipLaunchKernelGGL(batch_plan_mask_kernel, dim3((unsigned)B), dim3(SS_WAVE), 0, static_cast<hipStream_t>(stream), xmap, nmap,
+                     rmap, lens, max_t, D, H, W, augment, first_row, seed, pol, row_mask);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_mask_apply(float* X, int ld_x, int D, uint8_t* R, int H, int W, const int32_t* rmap,
+                                   const int32_t* row_mask, long rows, int rows_per_clip, int fill, ss_stream_t stream) {
+  SS_REQUIRE((X || R) && row_mask && rows > 0 && rows_per_clip > 0 && rows % rows_per_clip == 0, SS_ERR_ARG);
+  SS_REQUIRE(fill >= 0 && fill <= 255, SS_ERR_ARG);
+  SS_REQUIRE(!X || (D > 0 && ld_x >= D && (reinterpret_cast<uintptr_t>(X) & 3) == 0), SS_ERR_ARG);
+  SS_REQUIRE(!R || (rmap && H > 0 && W > 0), SS_ERR_ARG);
+  SS_REQUIRE(!R || (long)H * W <= 0x7fffffffL, SS_ERR_UNSUPPORTED);
+  long blocks = (rows + 3) / 4;
+  blocks = blocks > 8192 ? 8192 : blocks;
+  hipLaunchKernelGGL(batch_mask_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), X, ld_x, D, R,
+                     H, W, rmap, row_mask, rows, rows_per_clip, fill);
   return ss_launch_status();
 }

@@ -21,7 +21,10 @@ Three sources of randomness:
 ``AugmentPolicy`` (``batch(rng="philox", augment=True, policy=)``) adds what the reference's lineage had and its official
 script dropped (inactive/train_reduced.py:103-123: time warp, scale jitter) and a per-clip shift of the ROI frames, planned and
 applied on the device as well (``ss_batch_plan_aug``, ``ss_batch_gather_f32_aug``, ``ss_batch_gather_u8_shift``;
-tests/aug_plan_ref.py restates them).  Without a policy the launches are the three above, unchanged.
+tests/aug_plan_ref.py restates them).  Without a policy the launches are the three above, unchanged.  The policy's masks (a masked
+run of frames, a zeroed band of feature columns, a filled rectangle of the ROI frames) are two more launches when one of them is
+on: ``ss_batch_plan_mask`` edits the maps behind either planner, ``ss_batch_mask_apply`` writes the band and the rectangle behind the
+gathers.
 
 In ``csrc/batch.hip`` the entry points are instantiations of a few kernels: ``ss_batch_plan`` / ``ss_batch_plan_aug`` of one plan
 kernel (without / with the policy), ``ss_batch_gather_f32`` / ``_at`` / ``_aug`` of one feature gather (host-drawn or Philox noise,
@@ -68,20 +71,42 @@ class AugmentPolicy:
     ``j * (T - 1) // (L - 1)``); the reference's frame drop then acts on the warped clip.  ``scale_prob`` / ``scale_range``: the
     features (after the noise) times one factor uniform in the range.  ``roi_shift_prob`` / ``roi_shift_max`` = (dx, dy): the
     ROI frames of a clip moved by an integer offset uniform in [-dx, dx] x [-dy, dy], edges replicated (a crop box that
-    jitters with the landmarks)."""
+    jitters with the landmarks).
+
+    The masks remove data where the three above move it (``ss_batch_plan_mask`` behind the planner, ``ss_batch_mask_apply`` behind the
+    gathers; tests/mask_plan_ref.py restates both).  ``time_mask_prob`` / ``time_mask_max``: a clip of at least 8 planned frames gets
+    one masked run of 1 .. ``min(time_mask_max, n // 4)`` frames inside ``[1, n)``; ``time_mask_streams`` = ``"both"``, ``"features"``
+    or ``"roi"`` names the maps the run is written into, ``time_mask_fill`` = ``"zero"`` (zero rows; on the embedded path the
+    embedding of a zero frame) or ``"hold"`` (the last frame before the run, repeated; the features still take fresh noise).
+    ``feat_mask_prob`` / ``feat_mask_max``: one band of 1 .. ``min(feat_mask_max, D)`` feature columns set to 0.0 in every row of the
+    clip.  ``cutout_prob`` / ``cutout_max`` = (w, h) / ``cutout_fill``: a clip with ROI frames gets one rectangle of at most w x h pixels
+    filled with the grey level in all its frames (padding frames stay zero).  A mask is on when its probability is > 0 and its
+    maximum >= 1; with all three off ``batch()`` issues the launches it issues without them."""
     time_warp_prob: float = 0.0
     time_warp_range: Tuple[float, float] = (0.8, 1.2)
     scale_prob: float = 0.0
     scale_range: Tuple[float, float] = (0.95, 1.05)
     roi_shift_prob: float = 0.0
     roi_shift_max: Tuple[int, int] = (0, 0)
+    time_mask_prob: float = 0.0
+    time_mask_max: int = 0
+    time_mask_streams: str = "both"
+    time_mask_fill: str = "zero"
+    feat_mask_prob: float = 0.0
+    feat_mask_max: int = 0
+    cutout_prob: float = 0.0
+    cutout_max: Tuple[int, int] = (0, 0)
+    cutout_fill: int = 128
+
+    _STREAMS = ("both", "features", "roi")  # (the codes ss_batch_plan_mask takes: the position in the tuple)
+    _FILLS = ("zero", "hold")
 
     def __post_init__(self):
-        for name in ("time_warp_prob", "scale_prob", "roi_shift_prob"):
+        for name in ("time_warp_prob", "scale_prob", "roi_shift_prob", "time_mask_prob", "feat_mask_prob", "cutout_prob"):
             p = getattr(self, name)
             if not (isinstance(p, (int, float)) and 0.0 <= p <= 1.0):
                 raise ValueError(f"{name} must lie in [0, 1], not {p!r}")
-        for name in ("time_warp_range", "scale_range", "roi_shift_max"):
+        for name in ("time_warp_range", "scale_range", "roi_shift_max", "cutout_max"):
             v = getattr(self, name)
             if not (isinstance(v, (tuple, list)) and len(v) == 2):
                 raise ValueError(f"{name} must be a pair, not {v!r}")
@@ -95,11 +120,52 @@ class AugmentPolicy:
         mx, my = self.roi_shift_max
         if not all(isinstance(m, (int, np.integer)) and 0 <= m < 2 ** 30 for m in (mx, my)):
             raise ValueError(f"roi_shift_max must be two integers >= 0, not {self.roi_shift_max!r}")
+        is_count = lambda m: isinstance(m, (int, np.integer)) and not isinstance(m, bool) and 0 <= m < 2 ** 31  # noqa: E731
+        for name in ("time_mask_max", "feat_mask_max"):
+            if not is_count(getattr(self, name)):
+                raise ValueError(f"{name} must be an integer >= 0, not {getattr(self, name)!r}")
+        if not all(is_count(m) for m in self.cutout_max):
+            raise ValueError(f"cutout_max must be two integers >= 0, not {self.cutout_max!r}")
+        if not (is_count(self.cutout_fill) and self.cutout_fill <= 255):
+            raise ValueError(f"cutout_fill must be an integer in [0, 255], not {self.cutout_fill!r}")
+        if self.time_mask_streams not in self._STREAMS:
+            raise ValueError(f"time_mask_streams must be one of {self._STREAMS!r}, not {self.time_mask_streams!r}")
+        if self.time_mask_fill not in self._FILLS:
+            raise ValueError(f"time_mask_fill must be one of {self._FILLS!r}, not {self.time_mask_fill!r}")
 
     @classmethod
     def lineage(cls, **overrides) -> "AugmentPolicy":
         """The values of inactive/train_reduced.py:103-123 (warp 0.5 / 0.8-1.2, scale 0.3 / 0.95-1.05), no ROI shift."""
         return replace(cls(time_warp_prob=0.5, time_warp_range=(0.8, 1.2), scale_prob=0.3, scale_range=(0.95, 1.05)), **overrides)
+
+    @property
+    def time_mask_on(self) -> bool:
+        return self.time_mask_prob > 0 and self.time_mask_max >= 1
+
+    @property
+    def feat_mask_on(self) -> bool:
+        return self.feat_mask_prob > 0 and self.feat_mask_max >= 1
+
+    @property
+    def cutout_on(self) -> bool:
+        return self.cutout_prob > 0 and min(self.cutout_max) >= 1
+
+    def mask_fields(self) -> dict:
+        """The mask fields that differ from their defaults (tuples as lists): what ``harness.run_fingerprint`` adds for them, so
+        the fingerprint of a policy that leaves the masks alone is what it was before they existed."""
+        out = {}
+        for name in MASK_FIELDS:
+            v, default = getattr(self, name), type(self).__dataclass_fields__[name].default
+            if v != default:
+                out[name] = list(v) if isinstance(v, tuple) else v
+        return out
+
+    def mask_args(self, cutout: bool = True) -> tuple:
+        """The policy's scalars as ``ss_batch_plan_mask`` takes them between ``seed`` and ``row_mask``.  ``cutout=False``: the cutout
+        switched off (a store without ROI frames has no clip it could apply to)."""
+        return (float(self.time_mask_prob), int(self.time_mask_max), self._STREAMS.index(self.time_mask_streams),
+                self._FILLS.index(self.time_mask_fill), float(self.feat_mask_prob), int(self.feat_mask_max),
+                float(self.cutout_prob) if cutout else 0.0, int(self.cutout_max[0]), int(self.cutout_max[1]), int(self.cutout_fill))
 
     def warp_permille(self) -> Tuple[int, int]:
         """The warp range as the planner takes it: integers, permille."""
@@ -110,6 +176,10 @@ class AugmentPolicy:
         """The scale range as the planner takes it: low end and hi - lo, each rounded to f32 once."""
         lo, hi = self.scale_range
         return float(np.float32(lo)), float(np.float32(float(hi) - float(lo)))
+
+
+MASK_FIELDS = ("time_mask_prob", "time_mask_max", "time_mask_streams", "time_mask_fill", "feat_mask_prob", "feat_mask_max",
+               "cutout_prob", "cutout_max", "cutout_fill")
 
 
 class DeviceClipStore:
@@ -155,6 +225,7 @@ class DeviceClipStore:
         self.n_classes_present = len(present)
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)  # set by ss_batch_plan, read by check()
         self._plan_bufs = {}  # batch size -> (xmap, nmap, rmap, lens, y, row_scale, row_shift)
+        self._mask_bufs = {}  # batch size -> row_mask (B, 8), for the batch sizes a policy with a mask on has planned
         # embed(): the frozen CNN's embeddings of the ROI frames, of one all-zero frame, and what they were made from
         self.E = self.E0 = None
         self._embed_model = self._embed_params = self._embed_version = None
@@ -334,6 +405,18 @@ class DeviceClipStore:
                    self._err.data_ptr(), s)
             f32 = ("ss_batch_gather_f32_aug", nmap.data_ptr(), float(NOISE_STD), noise_seed, noise_first, row_scale.data_ptr(), mt)
             shift = (row_shift.data_ptr(), mt, int(mx), int(my))
+        # the masks: planned into the maps behind the planner, band and rectangle written behind the gathers (a policy whose masks
+        # are all off adds no launch).  row_mask joins the per-batch-size buffers, reused in stream order like them.
+        cutout = policy is not None and policy.cutout_on and rmap is not None
+        band = policy is not None and policy.feat_mask_on
+        row_mask = None
+        if policy is not None and (policy.time_mask_on or band or cutout):
+            row_mask = self._mask_bufs.get(B)
+            if row_mask is None:
+                row_mask = self._mask_bufs[B] = torch.empty(B, 8, dtype=torch.int32, device=dev)
+            H, W = self.roi_hw if rmap is not None else (0, 0)
+            L.call("ss_batch_plan_mask", xmap.data_ptr(), nmap.data_ptr(), L.ptr(rmap), lens.data_ptr(), B, mt, self.D, H, W,
+                   int(bool(augment)), int(first_row) & _MASK64, int(seed) & _MASK64, *policy.mask_args(cutout), row_mask.data_ptr(), s)
         if embedded:  # the same plan, one gather: (noise_map, noise_std, seed, noise_first, row_scale, rows_per_clip)
             if policy is not None:
                 tail = f32[1:]
@@ -342,9 +425,15 @@ class DeviceClipStore:
             else:
                 tail = (None, 0.0, noise_seed, 0, None, 1)
             Z = self._gather_z(B, xmap, rmap, tail)
+            if band:
+                L.call("ss_batch_mask_apply", Z.data_ptr(), Z.shape[2], self.D, None, 0, 0, None, row_mask.data_ptr(), B * mt, mt, 0, s)
             Z._ss_keep = (idx_d,)
             return Z, lens, None, y
         X, R = self._gather(B, xmap, rmap, f32, shift)
+        if band or cutout:
+            H, W = self.roi_hw if cutout else (0, 0)
+            L.call("ss_batch_mask_apply", X.data_ptr() if band else None, self.D, self.D, R.data_ptr() if cutout else None, H, W,
+                   rmap.data_ptr() if cutout else None, row_mask.data_ptr(), B * mt, mt, int(policy.cutout_fill), s)
         X._ss_keep = (idx_d,)
         return X, lens, R, y
 
@@ -368,14 +457,17 @@ class DeviceClipStore:
         ``policy`` (``rng="philox"`` with ``augment=True`` only, ``ValueError`` otherwise): an ``AugmentPolicy``; the batch is
         then planned and gathered by ``ss_batch_plan_aug`` / ``ss_batch_gather_f32_aug`` / ``ss_batch_gather_u8_shift``.  The
         decisions are keyed by the row's draw index like the rest of the plan, so shards (``batch_first_row``) stay bit-equal
-        to the single-process batch.  ``None``: exactly the three launches described above.
+        to the single-process batch.  ``None``: exactly the three launches described above.  A policy with a mask switched on (time
+        mask, feature band, ROI cutout) adds ``ss_batch_plan_mask`` behind the planner and, for the band and the cutout,
+        ``ss_batch_mask_apply`` behind the gathers; with all masks off neither is launched.
 
         ``embedded`` (``rng="philox"`` only, after ``embed(model)``): -> ``(Z, T, None, y)``, ``Z`` (B, max_t, D + roi_emb) f32 = the
         rows ``X | CNN(R)`` of the batch the same call returns without it (``model.forward_embedded(Z, T)`` are the logits of
         ``model(X, T, R)``), from the same plan kernel and ONE ``ss_batch_gather_z`` launch: the features take the same noise and
         scale bits, the embeddings are read from ``self.E`` through the ROI map (``self.E0`` where a clip has no ROI frames).  Time
-        warp and scale jitter act through the maps and the per-clip scale and work; a policy with ``roi_shift_prob > 0`` is a
-        ``ValueError``, since a shift acts on pixels.  Without ``embedded`` the launches are exactly those described above."""
+        warp, scale jitter and the time mask act through the maps and the per-clip scale and work, and so does the feature band (on the
+        first ``D`` columns of ``Z``; a zero-masked ROI row holds ``self.E0``); a policy with ``roi_shift_prob > 0`` or
+        ``cutout_prob > 0`` is a ``ValueError``, since both act on pixels.  Without ``embedded`` the launches are exactly those described above."""
         if policy is not None:
             if not isinstance(policy, AugmentPolicy):
                 raise TypeError("policy must be an AugmentPolicy")
@@ -386,6 +478,8 @@ class DeviceClipStore:
                 raise ValueError("embedded=True needs rng='philox': the embedded batch is planned on the device")
             if policy is not None and policy.roi_shift_prob > 0:
                 raise ValueError("embedded=True cannot apply roi_shift_prob > 0: the shift acts on pixels, the store holds embeddings")
+            if policy is not None and policy.cutout_prob > 0:
+                raise ValueError("embedded=True cannot apply cutout_prob > 0: the cutout acts on pixels, the store holds embeddings")
             if self.E is None:
                 raise RuntimeError("batch(embedded=True) needs a prior embed(model)")
         if rng == "philox":

@@ -35,7 +35,7 @@ import torch
 
 from .checkpoint import (TRAIN_STATE_FORMAT, fingerprint_difference, load_train_state, save_checkpoint,
                          save_train_state)
-from .device_data import AugmentPolicy, DeviceClipStore
+from .device_data import MASK_FIELDS, AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier
 from .train import Trainer, check_class_weights, shard_range
 
@@ -297,7 +297,8 @@ def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_
     """What a resumable ``fit`` run depends on, as plain values (``checkpoint.FINGERPRINT_FIELDS``): a train-state file is
     resumed only by a call whose fingerprint equals the saved one.  ``epochs`` and ``patience`` are not part of it: a run may be
     resumed to train longer.  ``init_from`` (the sha256 of the checkpoint file the run started from, a hex string) and
-    ``freeze_cnn`` are entries only when they are set: the fingerprint of a run without them is what it always was."""
+    ``freeze_cnn`` are entries only when they are set: the fingerprint of a run without them is what it always was.  The same holds
+    for the policy's mask fields (``AugmentPolicy.mask_fields``): each is an entry only where it differs from its default."""
     extra = {}
     if init_from is not None:
         extra["init_from"] = str(init_from)
@@ -306,8 +307,9 @@ def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_
     return dict(seed=int(seed), batch_size=int(batch_size), world_size=int(world_size), max_t=int(max_t), lr=float(lr),
                 labels=[str(lab) for lab in labels], x_dim=int(x_dim), use_roi=bool(use_roi), n_train=int(n_train),
                 n_val=int(n_val), class_weights=None if class_weights is None else [float(w) for w in class_weights],
-                augment_policy=None if augment_policy is None else {k: (list(v) if isinstance(v, tuple) else v) for k, v in
-                                                                    dataclasses.asdict(augment_policy).items()},
+                augment_policy=None if augment_policy is None else {
+                    **{k: (list(v) if isinstance(v, tuple) else v) for k, v in dataclasses.asdict(augment_policy).items()
+                       if k not in MASK_FIELDS}, **augment_policy.mask_fields()},
                 ema_decay=None if ema_decay is None else float(ema_decay), **extra)
 
 
@@ -370,8 +372,8 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     train loss stays the sum of loss x batch over the clip count, as the reference logs it (:441); the validation loss is
     the weighted mean over the whole validation set (``evaluate``).
 
-    ``augment_policy``: an ``AugmentPolicy`` for the training batches (time warp, scale jitter, ROI shift, planned on the
-    device); needs ``plan="device"``.  Validation batches are never augmented.  None: the reference's two augmentations only.
+    ``augment_policy``: an ``AugmentPolicy`` for the training batches (time warp, scale jitter, ROI shift, and the masks: time
+    mask, feature band, ROI cutout; all planned on the device); needs ``plan="device"``.  Validation batches are never augmented.  None: the reference's two augmentations only.
 
     ``ema_decay`` (``d`` in [0, 1); the reference has no averaged model): ``Trainer(ema_decay=d)`` keeps an exponential moving
     average of the weights inside the Adam launch.  Every epoch's validation, under both plans, runs on the AVERAGED weights
@@ -412,6 +414,8 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
             raise ValueError("freeze_cnn needs init_from: a frozen, randomly initialised ROI CNN is a mistake")
         if augment_policy is not None and isinstance(augment_policy, AugmentPolicy) and augment_policy.roi_shift_prob > 0:
             raise ValueError("freeze_cnn cannot apply roi_shift_prob > 0: the shift acts on pixels")
+        if augment_policy is not None and isinstance(augment_policy, AugmentPolicy) and augment_policy.cutout_prob > 0:
+            raise ValueError("freeze_cnn cannot apply cutout_prob > 0: the cutout acts on pixels")
     if augment_policy is not None:
         if not isinstance(augment_policy, AugmentPolicy):
             raise TypeError("augment_policy must be an AugmentPolicy")

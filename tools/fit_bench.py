@@ -4,24 +4,29 @@ batches planned by the kernel (``rng="philox"``), with ``Trainer.step`` on a res
     python tools/fit_bench.py [--steps 200] [--windows 5] [--warmup 20]
 
 One JSON line.  Per shape (config 2: B=256, T=30, D=84, 64x64 ROI; shipped: B=16, T=90, D=180, 48x96 ROI):
-  clips_per_s.{resident, host_plan, device_plan, device_plan_policy}
-                                                  median (min, max) over the windows; the four loops alternate window by window
+  clips_per_s.{resident, host_plan, device_plan, device_plan_policy, device_plan_policy_masks}
+                                                  median (min, max) over the windows; the five loops alternate window by window
                                                   inside this one process, every window ends in a device synchronise.
                                                   device_plan_policy: ``batch(policy=AugmentPolicy.lineage(roi_shift_prob=0.5,
                                                   roi_shift_max=(4, 2)))`` -- time warp, scale jitter and ROI shift
+                                                  device_plan_policy_masks: the same policy with the three masks on (time mask 0.5 / 8
+                                                  frames, feature band 0.5 / 16 columns, ROI cutout 0.5 / 16 x 16 pixels)
   policy_of_device_plan                           median device_plan_policy / median device_plan of this run, and device_plan's own
                                                   (max - min) / median beside it: the yardstick is this run's device_plan loop
+  masks_of_policy                                 median device_plan_policy_masks / median device_plan_policy of this run, and
+                                                  device_plan_policy's own (max - min) / median beside it
   clips_per_s.resident_weighted, class_weight_us  (--class-weights) the resident loop through ``Trainer(class_weights=)``, a fourth loop
                                                   in the same alternation, and what its step costs more than the unweighted one
                                                   (the one ``ss_class_weight_sum`` launch): median over the windows of the difference
                                                   in us per step between neighbouring windows
-  assemble_ms.{host_plan, device_plan, device_plan_policy}
+  assemble_ms.{host_plan, device_plan, device_plan_policy, device_plan_policy_masks}
                                                   the batch() calls alone (no step), same alternation: ms per batch
   enqueue_ms.{host_plan, device_plan}             host wall time of one batch() call while the GPU is idle (no synchronise
                                                   inside the timed region: what the call costs the Python thread)
-  kernels_ms.{host_plan, device_plan, device_plan_policy}
+  kernels_ms.{host_plan, device_plan, device_plan_policy, device_plan_policy_masks}
                                                   HIP-event time per launch of the kernels batch() enqueues (L.PROFILE); the policy's
-                                                  are ss_batch_plan_aug, ss_batch_gather_f32_aug and ss_batch_gather_u8_shift
+                                                  are ss_batch_plan_aug, ss_batch_gather_f32_aug and ss_batch_gather_u8_shift, the
+                                                  masks add ss_batch_plan_mask and ss_batch_mask_apply
   validation_ms.{evaluate, evaluate_device}       (config2 only, --eval-clips N, 0 = skip) one validation pass over N clips in batches of
                                                   B: ``harness.evaluate`` (two read-backs per batch, confusions counted on the host)
                                                   against ``harness.evaluate_device`` (``ss_eval_accum``, one read at the end);
@@ -111,6 +116,13 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         row[0] += B
         return store.batch(dev_order[i * B:(i + 1) * B], augment=True, rng="philox", seed=SEED, first_row=row[0], policy=policy)
 
+    masks = ss.AugmentPolicy.lineage(roi_shift_prob=0.5, roi_shift_max=(4, 2), time_mask_prob=0.5, time_mask_max=8, feat_mask_prob=0.5,
+                                     feat_mask_max=16, cutout_prob=0.5, cutout_max=(16, 16))
+
+    def masks_batch(i):
+        row[0] += B
+        return store.batch(dev_order[i * B:(i + 1) * B], augment=True, rng="philox", seed=SEED, first_row=row[0], policy=masks)
+
     def window(make_batch, step, n):
         tr = weighted if step == "weighted" else trainer
         torch.cuda.synchronize()
@@ -123,10 +135,11 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         return time.perf_counter() - t0
 
     loops = {"resident": (None, True), "host_plan": (host_batch, True), "device_plan": (dev_batch, True),
-             "device_plan_policy": (policy_batch, True)}
+             "device_plan_policy": (policy_batch, True), "device_plan_policy_masks": (masks_batch, True)}
     if weighted is not None:
         loops = {"resident": (None, True), "resident_weighted": (None, "weighted"), **loops}
-    asm = {"host_plan": (host_batch, False), "device_plan": (dev_batch, False), "device_plan_policy": (policy_batch, False)}
+    asm = {"host_plan": (host_batch, False), "device_plan": (dev_batch, False), "device_plan_policy": (policy_batch, False),
+           "device_plan_policy_masks": (masks_batch, False)}
     for mk, st in list(loops.values()) + list(asm.values()):  # every shape and code path of the timed windows, warmed up
         window(mk, st, warmup)
     rate = {k: [] for k in loops}
@@ -162,9 +175,13 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         extra["class_weight_us"] = summary(extra_us, 2)
     return {**extra, "shape": dict(B=B, T=T, D=D, roi="%dx%d" % tuple(roi), classes=C),
             "clips_per_s": {k: summary(v) for k, v in rate.items()},
-            "of_resident": {k: round(med[k] / med["resident"], 4) for k in ("host_plan", "device_plan", "device_plan_policy")},
+            "of_resident": {k: round(med[k] / med["resident"], 4) for k in ("host_plan", "device_plan", "device_plan_policy",
+                                                                            "device_plan_policy_masks")},
             "policy_of_device_plan": {"ratio": round(med["device_plan_policy"] / med["device_plan"], 4),
                                       "device_plan_spread": round((max(rate["device_plan"]) - min(rate["device_plan"])) / med["device_plan"], 4)},
+            "masks_of_policy": {"ratio": round(med["device_plan_policy_masks"] / med["device_plan_policy"], 4),
+                                "device_plan_policy_spread": round((max(rate["device_plan_policy"]) - min(rate["device_plan_policy"]))
+                                                                   / med["device_plan_policy"], 4)},
             "assemble_ms": {k: summary(v, 4) for k, v in asm_ms.items()},
             "enqueue_ms": enq, "kernels_ms": kern}
 
@@ -181,7 +198,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("fit_bench.py measures on the GPU: no device found")
     dev = torch.device("cuda")
-    out = {"metric": "clips/s of the training loop: resident batch, host-planned batches, device-planned batches, device-planned with an AugmentPolicy",
+    out = {"metric": "clips/s of the training loop: resident batch, host-planned batches, device-planned batches, device-planned with an AugmentPolicy, the same with its masks on",
            "steps_per_window": args.steps, "windows": args.windows, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     for name in args.shapes.split(","):
         out[name] = run_shape(name, steps=args.steps, windows=args.windows, warmup=args.warmup, dev=dev, eval_clips=args.eval_clips, class_weights=args.class_weights,
