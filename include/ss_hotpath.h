@@ -249,8 +249,20 @@ int ss_gemm_f32_splitk_group(const ss_gemm_problem* problems, int n, float* ws, 
 int ss_gemm_bf16_splitk_group_ws_floats(const ss_gemm_problem* problems, int n, long* floats);
 int ss_gemm_bf16_splitk_group(const ss_gemm_problem* problems, int n, float* ws, long ws_floats, ss_stream_t stream);
 
-/* a[0..na) = 0 and b[0..nb) = 0 in one launch (either may be empty; 16-byte aligned): the destinations the d layer_in GEMMs
- * sum into with float atomics are cleared by this, off the critical path, instead of two library fills */
+/* d layer_in of a GRU layer, both directions as one contraction:
+ *   C[M][N] = A0[M][K] B0[K][N] + A1[M][K] B1[K][N],  A1 = A + stride_a, B1 = B + stride_b (element strides)
+ * A: [row][k] with lda >= K (the gate gradients dG of one direction, lda = 4H, K = 3H); B: [k][col] with ldb, the wanted columns
+ * are b_col0 .. b_col0 + N (W_ih as nn.GRU keeps it; b_col0 = x_dim asks for the ROI-embedding columns of layer 0 only); C with
+ * ldc >= N.  Every element of C[0..M)[0..N) is written once with a plain store -- C needs no clearing, nothing outside it is
+ * written, nothing outside the operands is read -- and the sum runs through A0 B0 with k ascending, then through A1 B1, in one
+ * accumulator: the same operands give the same bits.  64 x 192 tiles (N > 32) or 32 x 32 tiles on the LDS-DMA ring; operands
+ * that are not 16-byte aligned in every address, leading dimension and stride, or N not a multiple of 4, are staged through
+ * registers instead (slow, same result).  SS_ERR_ARG: a null pointer, a size <= 0, lda < K, ldb < b_col0 + N, ldc < N. */
+int ss_gru_dx_f32(int M, int N, int K, const float* A, int lda, long stride_a, const float* B, int ldb, int b_col0,
+                  long stride_b, float* C, int ldc, ss_stream_t stream);
+
+/* a[0..na) = 0 and b[0..nb) = 0 in one launch (either may be empty; 16-byte aligned): destinations that are summed into with float
+ * atomics (the bf16 engine's d layer_in GEMMs) are cleared by this, off the critical path, instead of two library fills */
 int ss_zero_f32x2(float* a, long na, float* b, long nb, ss_stream_t stream);
 
 /* column sums: out[n] += sum_r A[r*lda + n]  (bias gradients) */

@@ -78,6 +78,7 @@ SIGNATURES = {
     "ss_gemm_f32_splitk_group": [_vp, _i, _vp, _l, _i, _vp],
     "ss_gemm_bf16_splitk_group_ws_floats": [_vp, _i, _vp],
     "ss_gemm_bf16_splitk_group": [_vp, _i, _vp, _l, _vp],
+    "ss_gru_dx_f32": [_i, _i, _i, _vp, _i, _l, _vp, _i, _i, _l, _vp, _i, _vp],
     "ss_colsum_f32": [_vp, _i, _i, _i, _vp, _vp],
     "ss_zero_f32x2": [_vp, _l, _vp, _l, _vp],
     "ss_train_prologue": [_vp, _l, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp],

@@ -1002,6 +1002,218 @@ __global__ __launch_bounds__(WNT) void gemm_wide_kc_kernel(WideKcParams P) {
 }
 }  // namespace wide
 
+// ---------------------------------------------------------------------------------------------------------------------
+// d layer_in of a GRU layer: C[M][N] = A0[M][K] B0[K][N] + A1[M][K] B1[K][N] -- the two directions' gate gradients ([row][k], rows
+// of dG) against the two directions' W_ih ([k][col]) -- as ONE contraction over 2 K.  The k loop runs through A0 B0 with k
+// ascending and then through A1 B1 into the same accumulators, and every element of C is written once with a plain store: no
+// atomics, no cleared destination, and the result is a pure function of the operands.  (Through ss_gemm_f32_batched this product
+// was two problems summed into a zeroed C with float atomics, 720 workgroups of 128 x 64 at config 2.)
+//
+// Wide form, 64 x 192 output tiles, 512 threads = 8 waves as 2 (M) x 4 (N), wave tile 32 x 48 = 2 x 3 MFMA tiles:
+//   workgroups   M = 7 680, N = 384 (config 2): 120 x 2 = 240 on 256 CUs, one round at one per CU (0.94 of the chip); the shipped
+//                M = 23 040: 360 x 2 = 720 = 2.8 rounds.  (128 x 96 gives the same 240 / 720 but 8 + 6 = 14 DMA pieces per k tile
+//                for 8 waves; 4 + 12 = 16 deal two to every wave, so one counted wait serves all of them, and dG is fetched
+//                N / 192 = 2 times instead of 4.)
+//   LDS          stage = (64 + 192) x 16 floats = 16 KB, ring of DSTAGES = 4: 64 KB; the output tile (64 x 196 floats, 49 KB) leaves
+//                through the ring so that a row is written as one 768-byte run
+//   LDS reads    per wave and k tile 2 ds_read_b128 (A, [row][16 k] image) + 12 ds_read_b32 (B, [16 k][192] image) for 24 MFMAs
+//                (the 128 x 64 kernel: 4 + 8 for 32)
+//   registers    24 accumulator + 8 + 12 operand + 5 offsets + 2 x (pointer, step) per lane: 92 in all, of the 128 a 512-thread
+//                workgroup may use
+// Narrow form for N <= 32 (layer 0 when only the ROI-embedding columns are wanted), 32 x 32 tiles, 256 threads = 4 waves as 2 x 2,
+// one MFMA tile each: no MFMA is issued for a column tile without columns, 2 + 2 DMA pieces per k tile (one per wave), 16 KB of
+// LDS and 34 registers -- it fits on a CU beside a 512-thread, 96 KB workgroup of the wide weight-gradient group, with which
+// layer 0 runs it; 240 workgroups at M = 7 680.
+// Operands the DMA ring cannot take (an address, a leading dimension or a stride that is no multiple of 16 bytes, N no multiple
+// of 4) run the same tiles with every k tile staged through registers, element by element: slow and never wrong.
+namespace dx {
+constexpr int XCDS = 8;  // workgroup b is dispatched to XCD b % 8: the tiles of one row panel are numbered 8 apart, so that they
+                         // share the panel of dG in one L2 (a wrong guess about the chip is slower, not different)
+struct DxParams {
+  const float *A, *B;  // B: column 0 of the wanted columns
+  float* C;
+  int M, N, K, lda, ldb, ldc, gx, gy;
+  long sA, sB;  // element strides from (A0, B0) to (A1, B1)
+  int dma;      // the operands can feed the LDS-DMA ring
+};
+
+template <int TM_, int TN_, int WGM_, int WGN_>
+struct Tile {
+  static constexpr int TM = TM_, TN = TN_, WGM = WGM_, WGN = WGN_;
+  static constexpr int NW = WGM * WGN, NT = 64 * NW;
+  static constexpr int WTM = TM / WGM, WTN = TN / WGN, MT = WTM / 16, NTL = WTN / 16;
+  static constexpr int PA = TM / 16, PB = TN / 16;  // 1 KB DMA pieces of the A and the B image of a k tile
+  static constexpr int LPW = (PA + PB) / NW;        // DMA instructions per wave and k tile
+  static constexpr int STAGE = (TM + TN) * BK;      // floats
+  static constexpr size_t LDS = (size_t)DSTAGES * STAGE * sizeof(float);
+  static_assert((PA + PB) % NW == 0, "pieces deal evenly over the waves");
+  static_assert(TM * (TN + 4) <= DSTAGES * STAGE, "the output tile is staged in the k-tile ring");
+  static_assert(WTM % 16 == 0 && WTN % 16 == 0 && TN % 4 == 0, "whole MFMA tiles per wave");
+};
+using Wide = Tile<64, 192, 2, 4>;
+using Narrow = Tile<32, 32, 2, 2>;
+
+// one wave's DMA pieces of a k tile: piece = wave + NW n of the PA + PB (A first); A image [TM][16 k], B image [16 k][TN]
+template <class T>
+struct Pieces {
+  const float* src[T::LPW];
+  long step[T::LPW];
+  static __device__ __forceinline__ int piece(int n) { return (threadIdx.x >> 6) + T::NW * n; }
+  static __device__ __forceinline__ bool isb(int n) { return piece(n) >= T::PA; }
+  static __device__ __forceinline__ int slot(int n) { return (piece(n) - (isb(n) ? T::PA : 0)) * 64 + (threadIdx.x & 63); }
+  __device__ __forceinline__ void init(const DxParams& P, int dir, int m0, int n0) {
+#pragma unroll
+    for (int n = 0; n < T::LPW; ++n) {
+      const int sl = slot(n);
+      if (isb(n)) {  // columns past N are clamped to the last four (they feed accumulators nobody stores)
+        src[n] = P.B + dir * P.sB + (long)KRowImage<T::TN>::k(sl) * P.ldb + KRowImage<T::TN>::src_col(sl, n0, P.N);
+        step[n] = (long)BK * P.ldb;
+      } else {
+        src[n] = P.A + dir * P.sA + (long)KcImage::src_row(sl, m0, P.M) * P.lda + KcImage::src_k(sl);
+        step[n] = BK;
+      }
+    }
+  }
+  __device__ __forceinline__ void issue(unsigned stage_byte) const {
+#pragma unroll
+    for (int n = 0; n < T::LPW; ++n) ss_dma16(src[n], stage_byte + piece(n) * 1024);
+  }
+  __device__ __forceinline__ void advance() {
+#pragma unroll
+    for (int n = 0; n < T::LPW; ++n) src[n] += step[n];
+  }
+  // the k tile that starts at k0 of direction dir through registers, element by element: zeros past K and past column N, rows
+  // past M clamped -- a ragged last tile, and every tile of operands the DMA cannot take
+  static __device__ __forceinline__ void stage(float* img, const DxParams& P, int dir, int m0, int n0, int k0) {
+#pragma unroll
+    for (int n = 0; n < T::LPW; ++n) {
+      const int sl = slot(n);
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (isb(n)) {
+        const int k = k0 + KRowImage<T::TN>::k(sl), col = n0 + 4 * KRowImage<T::TN>::src_unit(sl);
+        if (k < P.K) {
+          const float* s = P.B + dir * P.sB + (long)k * P.ldb + col;
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (col + e < P.N) v[e] = s[e];
+        }
+      } else {
+        const int kq = k0 + KcImage::src_k(sl);
+        const float* s = P.A + dir * P.sA + (long)KcImage::src_row(sl, m0, P.M) * P.lda + kq;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (kq + e < P.K) v[e] = s[e];
+      }
+      *reinterpret_cast<f32x4*>(img + piece(n) * 256 + 4 * (threadIdx.x & 63)) = v;
+    }
+  }
+};
+
+template <class T>
+__global__ __launch_bounds__(T::NT) void gru_dx_kernel(DxParams P) {
+  extern __shared__ __attribute__((aligned(16))) float dlds[];  // DSTAGES x (A image, B image), at LDS address 0
+  const int per = XCDS * P.gx, grp = blockIdx.x / per, r = blockIdx.x - grp * per;
+  const int by = grp * XCDS + r % XCDS, bx = r / XCDS;
+  if (by >= P.gy) return;  // (the grid is rounded up to whole groups of eight row panels)
+  const int m0 = by * T::TM, n0 = bx * T::TN;
+  const int nfull = P.K / BK, rem = P.K - nfull * BK;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wm = wid / T::WGN, wn = wid % T::WGN, i = lane & 15, g = lane >> 4;
+  int offA[T::MT], offB[T::NTL];
+#pragma unroll
+  for (int mt = 0; mt < T::MT; ++mt) offA[mt] = KcImage::frag(wm * T::WTM + mt * 16 + i, g);
+#pragma unroll
+  for (int nt = 0; nt < T::NTL; ++nt) offB[nt] = T::TM * BK + KRowImage<T::TN>::frag(wn * T::WTN + nt * 16 + i, g);
+  f32x4 acc[T::MT][T::NTL];
+#pragma unroll
+  for (int mt = 0; mt < T::MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < T::NTL; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto multiply = [&](const float* st) {
+    f32x4 a[T::MT];
+    float b[T::NTL][4];
+#pragma unroll
+    for (int mt = 0; mt < T::MT; ++mt) a[mt] = *reinterpret_cast<const f32x4*>(st + offA[mt]);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int nt = 0; nt < T::NTL; ++nt) b[nt][kk] = st[offB[nt] + kk * T::TN];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int mt = 0; mt < T::MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < T::NTL; ++nt) acc[mt][nt] = mfma16(a[mt][kk], b[nt][kk], acc[mt][nt]);
+  };
+  if (P.dma) {
+    // K a multiple of 16: one ring loop over the 2 K / 16 tiles, the sources move to (A1, B1) behind tile K / 16 - 1.  Otherwise
+    // one loop per direction, each with its ragged tile, so that the order of the sum stays A0 B0 first.
+    Pieces<T> dp;
+    const int passes = rem ? 2 : 1;
+    for (int pass = 0; pass < passes; ++pass) {
+      if (pass) __syncthreads();  // the ring is refilled: everybody is done with the first direction's ragged tile
+      dp.init(P, pass, m0, n0);
+      int issued = 0;
+      auto issue = [&](int buf) {
+        dp.issue((unsigned)(buf * T::STAGE * 4));
+        dp.advance();
+        if (++issued == nfull && !rem) dp.init(P, 1, m0, n0);
+      };
+      ring_k_loop<T::LPW>(
+          rem ? nfull : 2 * nfull, rem, issue,
+          [&](int stage, int refill) {
+            if (refill >= 0) issue(refill);
+            multiply(dlds + stage * T::STAGE);
+          },
+          [&](int) { Pieces<T>::stage(dlds, P, pass, m0, n0, nfull * BK); });
+    }
+  } else {
+    for (int dir = 0; dir < 2; ++dir)
+      for (int k0 = 0; k0 < P.K; k0 += BK) {
+        __syncthreads();
+        Pieces<T>::stage(dlds, P, dir, m0, n0, k0);
+        __syncthreads();
+        multiply(dlds);
+      }
+  }
+  // the output tile through LDS: a row leaves as one run of 16-byte stores
+  constexpr int LDS_C = T::TN + 4, Q = T::TN / 4;
+  __syncthreads();  // the last k tile has been read by everybody
+#pragma unroll
+  for (int mt = 0; mt < T::MT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < T::NTL; ++nt)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr)
+        dlds[(wm * T::WTM + mt * 16 + 4 * g + rr) * LDS_C + wn * T::WTN + nt * 16 + i] = acc[mt][nt][rr];
+  __syncthreads();
+  const bool vec_ok = (P.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(P.C) & 15) == 0;
+  for (int q = threadIdx.x; q < T::TM * Q; q += T::NT) {
+    const int row = q / Q, c4 = 4 * (q % Q);
+    const int gr = m0 + row, gc = n0 + c4;
+    if (gr < P.M && gc < P.N) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(&dlds[row * LDS_C + c4]);
+      float* dst = P.C + (long)gr * P.ldc + gc;
+      if (vec_ok && gc + 4 <= P.N) *reinterpret_cast<f32x4*>(dst) = v;
+      else
+        for (int e = 0; e < 4; ++e)
+          if (gc + e < P.N) dst[e] = v[e];
+    }
+  }
+}
+
+template <class T>
+int launch(DxParams P, hipStream_t s) {
+  P.gx = ceil_div(P.N, T::TN);
+  P.gy = ceil_div(P.M, T::TM);
+  const long grid = (long)ceil_div(P.gy, XCDS) * XCDS * P.gx;
+  SS_REQUIRE(grid <= 0x7fffffff, SS_ERR_UNSUPPORTED);
+  SS_REQUIRE(ss_dynamic_lds(reinterpret_cast<const void*>(gru_dx_kernel<T>), (int)T::LDS) == SS_OK, SS_ERR_LAUNCH);
+  hipLaunchKernelGGL(gru_dx_kernel<T>, dim3((unsigned)grid), dim3(T::NT), T::LDS, s, P);
+  return ss_launch_status();
+}
+}  // namespace dx
+
 int splitk_slices(int K, int splits, int* per_out) {
   const int per = ceil_div(ceil_div(K, splits), BK * KSUB) * BK * KSUB;
   if (per_out) *per_out = per;
@@ -1318,4 +1530,19 @@ extern "C" int ss_gemm_f32(int a_kcontig, int b_kcontig, int M, int N, int K, co
                            ss_stream_t stream) {
   return ss_gemm_f32_batched(a_kcontig, b_kcontig, M, N, K, A, lda, a_group, a_gstride, a_off, B, ldb, b_group,
                              b_gstride, b_off, C, ldc, bias, a_colsum, flags, splits, 1, 0, 0, 0, 0, 0, stream);
+}
+
+// d layer_in of a GRU layer (namespace dx above): C = A0 B0 + A1 B1 with plain stores, (A1, B1) = (A0 + stride_a, B0 + stride_b).
+extern "C" int ss_gru_dx_f32(int M, int N, int K, const float* A, int lda, long stride_a, const float* B, int ldb, int b_col0,
+                             long stride_b, float* C, int ldc, ss_stream_t stream) {
+  SS_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C, SS_ERR_ARG);
+  SS_REQUIRE(lda >= K && b_col0 >= 0 && (long)b_col0 + N <= ldb && ldc >= N, SS_ERR_ARG);
+  dx::DxParams P;
+  P.A = A; P.B = B + b_col0; P.C = C;
+  P.M = M; P.N = N; P.K = K; P.lda = lda; P.ldb = ldb; P.ldc = ldc;
+  P.sA = stride_a; P.sB = stride_b;
+  P.dma = al16(P.A) && al16(P.B) && (lda & 3) == 0 && (ldb & 3) == 0 && (stride_a & 3) == 0 && (stride_b & 3) == 0 && N >= 4 &&
+          (N & 3) == 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return N <= dx::Narrow::TN ? dx::launch<dx::Narrow>(P, s) : dx::launch<dx::Wide>(P, s);
 }

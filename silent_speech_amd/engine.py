@@ -90,7 +90,19 @@ DW_WIDE_ALONE = 1
 # recurrence and carry no gradient): a batch that is 40 % padding costs 40 % less CNN time.  0 = every frame, as the reference does.
 SKIP_PADDED_FRAMES = os.environ.get("SS_CNN_SKIP_PADDING", "1") != "0"
 
-_DX_SPLIT_CAP = 2  # K slices of a d layer_in GEMM with few output tiles
+_DX_SPLIT_CAP = 2  # K slices of a summed-with-atomics d layer_in GEMM with few output tiles
+# The d layer_in product of a GRU layer, dG_f W_ih_f + dG_r W_ih_r, runs as ONE launch with plain stores (ss_gru_dx_f32: 64 x 192
+# tiles, one 512-thread workgroup per CU, both directions in one k loop) when those tiles number at least this share of the
+# chip's CUs -- the kernel's design point is one full round.  Measured, parent against this form, alternating on one MI355X:
+# config 2 (7 680 rows, 240 workgroups on 256 CUs) 1.921 -> 1.897 ms per step, the shipped shape at B = 256 (23 040 rows, 720
+# workgroups) 6.54 -> 6.45 ms; at B = 16 (1 440 rows, 46 workgroups) 1.360 -> 1.381 ms: with a fifth of the chip in use the
+# 128 x 64 form's several workgroups per CU win, so fewer rows keep that form, its cleared destinations and their event.
+DX_ONE_LAUNCH_MIN_FILL = 0.8
+
+
+def dx_one_launch(cfg, rows: int, device) -> bool:
+    cus = torch.cuda.get_device_properties(device).multi_processor_count
+    return -(-rows // 64) * -(-2 * cfg.hidden // 192) >= DX_ONE_LAUNCH_MIN_FILL * cus
 
 
 def split_k(M, N, K, batch=1, target_wgs=_SPLITK_TARGET):
@@ -217,6 +229,7 @@ class WorkspaceBase:
         self.ev_join = torch.cuda.Event() if train else None
         self.ev_cnn_fwd = torch.cuda.Event() if train else None  # recorded after the ROI-CNN forward (micro-batch stagger)
         self.ev_zero = torch.cuda.Event() if train else None     # the cleared d layer_in destinations (side stream)
+        self.dx_one_launch = False  # the f32 engine's d layer_in GEMMs as ss_gru_dx_f32: plain stores, nothing to clear (Workspace)
         self.stagger = False  # set by the trainer when another micro-batch waits for ev_cnn_fwd
         # roi_hw None with use_roi: a workspace for forward(..., z_ready=True) -- rows that already hold the embeddings (serving.py)
         self.Z = torch.empty(N, cfg.in_dim, **f32) if cfg.use_roi and roi_hw is not None else None
@@ -231,8 +244,9 @@ class WorkspaceBase:
         if train:
             self.save = [torch.empty(2, N, 4, H, **f32) for _ in range(cfg.gru_layers)]
             self.d_out = torch.empty(N, 2 * H, **f32)
-            # gradient w.r.t. the output of layer l-1 (destination of layer l's d layer_in GEMM, l >= 1): zeroed on the side
-            # stream while the top of the backward pass runs, summed into with atomics by both directions
+            # gradient w.r.t. the output of layer l-1 (destination of layer l's d layer_in GEMM, l >= 1): written once, with
+            # plain stores, by ss_gru_dx_f32 (dx_one_launch); otherwise zeroed on the side stream while the top of the backward
+            # pass runs and summed into with atomics by both directions
             self.d_lower = [None] + [torch.empty(N, 2 * H, **f32) for _ in range(1, cfg.gru_layers)]
             self.xhat = torch.empty(B, 2 * H, **f32)
             self.rstd = torch.empty(B, **f32)
@@ -256,6 +270,7 @@ class Workspace(WorkspaceBase):
         # step counters of the multi-CU recurrence (zeroed once; the kernels keep them consistent): only shapes small
         # enough to leave most of the chip idle under the one-CU-per-slice kernels get one
         nb = L.gru_sync_bytes(B, T, H)
+        self.dx_one_launch = train and dx_one_launch(cfg, N, device)
         self.gru_sync = torch.zeros(nb // 4, device=device, dtype=torch.int32) if nb else None
         # ROI sizes the fused, LDS-resident CNN kernels are not built for run layer by layer (cnn_generic.py)
         self.cnn_generic = None
@@ -330,10 +345,12 @@ def tail_bwd(P, G, cfg: Config, ws, d_logits, train, seed):
 def head_grads(G, cfg: Config, ws, d_logits):
     """What both engines run on the side stream behind the top layer's BPTT launch."""
     B, H, C, MID = ws.B, cfg.hidden, cfg.num_classes, cfg.head_mid
-    # the atomically summed destinations of the d layer_in GEMMs: cleared here, off the critical path, and first --
-    # the top layer's d layer_in GEMM waits for them
-    zero_buffers(ws.d_lower[1:] + ([ws.dZ] if cfg.use_roi else []))
-    ws.ev_zero.record()
+    if not ws.dx_one_launch:
+        # the atomically summed destinations of the d layer_in GEMMs: cleared here, off the critical path, and first -- the top
+        # layer's d layer_in GEMM waits for them.  (The f32 engine's one-launch form writes them with plain stores: no clear, no
+        # event.)
+        zero_buffers(ws.d_lower[1:] + ([ws.dZ] if cfg.use_roi else []))
+        ws.ev_zero.record()
     if ws.frames_seen is not None:  # how many frames of this batch lay inside a clip: read by a later step's forward
         ws.frames_seen.copy_(ws.frames[:1], non_blocking=True)
     # LayerNorm gamma / beta and score-weight gradients: column sums of the rows the tail kernel left per clip
@@ -512,30 +529,36 @@ def backward(P: Dict[str, torch.Tensor], G: Dict[str, torch.Tensor], cfg: Config
         # d layer_in = dGi_f . W_ih_f + dGi_r . W_ih_r
         need_dx = (l > 0) or (cfg.use_roi and not frozen_cnn) or (d_X is not None)
         if need_dx:
-            # both directions in ONE launch (twice the workgroups: the N=116 case alone leaves half the CUs idle),
-            # summed with float atomics into a destination that was zeroed on the side stream.  (Measured alternative:
-            # sum_batch=True -- one workgroup per tile running its K loop through both directions, plain stores, nothing
-            # to clear -- is 0.8 % slower on the step: half the workgroups, and layer 0 has only 60 tiles.)
             if l > 0:
                 dst, ld_dst = ws.d_lower[l].data_ptr(), 2 * H
             elif cfg.use_roi:
                 dst, ld_dst = ws.dZ.data_ptr(), cfg.in_dim
             else:
                 dst, ld_dst = d_X.data_ptr(), cfg.x_dim
-                zero_buffers([d_X])
-            if USE_SIDE_STREAM and not zero_waited:  # once per backward pass: every cleared buffer is behind the same event
-                torch.cuda.current_stream().wait_event(ws.ev_zero)
-                zero_waited = True
             wi, wir = f"gru.weight_ih_l{l}", f"gru.weight_ih_l{l}_reverse"
-            # nobody asked for d X: only the ROI-embedding columns of d Z feed the CNN backward
+            # nobody asked for d X: only the ROI-embedding columns of d Z feed the CNN backward, the columns [0, x_dim) of d Z
+            # are then not read by anybody (and not written by the one-launch form).  With d X asked for, all in_dim columns are.
             c0 = cfg.x_dim if (l == 0 and cfg.use_roi and d_X is None) else 0
-            # few output tiles (layer 0 with only the ROI columns wanted: 120 workgroups for 256 CUs): slice K as well --
-            # the destination is summed atomically anyway
-            tiles = -(-N // 128) * -(-(K - c0) // 64) * 2
-            dx_splits = max(1, min(_DX_SPLIT_CAP, 768 // tiles, (3 * H) // 96))
-            gemm(1, 0, N, K - c0, 3 * H, ws.dG[l].data_ptr(), 4 * H, _addr(P[wi], c0), K, dst + 4 * c0, ld_dst,
-                 accumulate=True, atomic=True, tag="gemm_gru_dX", batch=2, splits=dx_splits,
-                 strides=(N * 4 * H, _pstride(P, wi, wir), 0, 0, 0))
+            if ws.dx_one_launch:
+                # both directions as ONE contraction over 2 * 3H in a kernel of its own: every element of the destination is
+                # written once with a plain store, so nothing is cleared, no event is waited for, and the same inputs give
+                # the same bits
+                L.call("ss_gru_dx_f32", N, K - c0, 3 * H, ws.dG[l].data_ptr(), 4 * H, N * 4 * H, P[wi].data_ptr(), K, c0,
+                       _pstride(P, wi, wir), dst + 4 * c0, ld_dst, s, tag="gemm_gru_dX")
+            else:
+                # few rows (see DX_ONE_LAUNCH_MIN_FILL): both directions as two problems of ONE launch of 128 x 64 tiles, K
+                # sliced as well when the tiles are few, summed with float atomics into a destination that was zeroed on the
+                # side stream (head_grads; d X here)
+                if l == 0 and not cfg.use_roi:
+                    zero_buffers([d_X])
+                if USE_SIDE_STREAM and not zero_waited:  # once per backward pass: every cleared buffer is behind the same event
+                    torch.cuda.current_stream().wait_event(ws.ev_zero)
+                    zero_waited = True
+                tiles = -(-N // 128) * -(-(K - c0) // 64) * 2
+                dx_splits = max(1, min(_DX_SPLIT_CAP, 768 // tiles, (3 * H) // 96))
+                gemm(1, 0, N, K - c0, 3 * H, ws.dG[l].data_ptr(), 4 * H, _addr(P[wi], c0), K, dst + 4 * c0, ld_dst,
+                     accumulate=True, atomic=True, tag="gemm_gru_dX", batch=2, splits=dx_splits,
+                     strides=(N * 4 * H, _pstride(P, wi, wir), 0, 0, 0))
         if l > 0:
             side_work()
     # ---- ROI CNN
