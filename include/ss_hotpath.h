@@ -395,6 +395,29 @@ int ss_batch_plan_mask(int32_t* xmap, int32_t* nmap, int32_t* rmap, const int64_
 int ss_batch_mask_apply(float* X, int ld_x, int D, uint8_t* R, int H, int W, const int32_t* rmap, const int32_t* row_mask,
                         long rows, int rows_per_clip, int fill, ss_stream_t stream);
 
+/* Mixup of a planned batch (AugmentPolicy: mixup_prob, mixup_alpha; inactive/train_reduced.py:36-53 mixes the collated batch): one
+ * factor lam = k / 256 per batch, k an integer in [0, 256], and one partner row per row.  Two launches behind everything above:
+ * ss_batch_plan_mixup: one workgroup; lens (B) and y (B) int64 as a planner wrote them.  Draws of the planners' scheme under the
+ *   domain tag "mixp" (0x6d697870), so they meet no other stream: counter (batch_first_row, "mixp", 0) gives u0, u1; the batch is
+ *   mixed iff augment && u0 < thr(mixup_prob), and then k = table[mulhi(u1, N)] -- table (N) device uint16 with entries in
+ *   [0, 256] (quantiles of Beta(alpha, alpha) times 256; larger entries count as 256), N a power of two.  Counter
+ *   (batch_first_row + b, "mixp", 1) gives row b its 32-bit key; perm[b] = the rank of (key_b, b) among the rows (a stable
+ *   argsort: a uniform permutation).  Not mixed: perm = identity, k = 256.  Written, all on the device: perm (B) int32,
+ *   y_b (B) int64 = y[perm], lens_m (B) int64 = max(lens, lens[perm]) (the shorter clip adds its zero padding), k_out (1) int32,
+ *   lam_out (1) float = k / 256.  SS_ERR_ARG, nothing written: B outside [1, 1024], N not a power of two, mixup_prob outside [0, 1].
+ * ss_batch_mixup: the blended batch, out of place (rows are read through perm), one launch, two HBM streams:
+ *     Xm[b] = fmaf(lam, X[b], (1 - lam) * X[perm[b]])                 X, Xm (B, T, D) f32, rows ld_x >= D floats apart in both
+ *     Rm[b] = (k R[b] + (256 - k) R[perm[b]] + 128) >> 8 per byte     R, Rm (B, T, frame_bytes) u8, frame_bytes % 16 == 0
+ *   with k (1) int32 read from the DEVICE.  X / Xm or R / Rm may be NULL as a pair.  A clip with perm[b] == b, and every clip
+ *   when k == 256, is copied byte for byte.  Any D (16 bytes per lane where D and ld_x are multiples of 4 and X, Xm 16-byte
+ *   aligned).  SS_ERR_ARG: both pairs NULL, half a pair, X == Xm or R == Rm, ld_x < D, R or Rm not 16-byte aligned;
+ *   SS_ERR_UNSUPPORTED: frame_bytes % 16 != 0. */
+int ss_batch_plan_mixup(const int64_t* lens, const int64_t* y, int B, int augment, uint64_t batch_first_row, uint64_t seed,
+                        double mixup_prob, const uint16_t* table, int N, int32_t* perm, int64_t* y_b, int64_t* lens_m,
+                        int32_t* k_out, float* lam_out, ss_stream_t stream);
+int ss_batch_mixup(const float* X, int ld_x, int D, float* Xm, const uint8_t* R, uint8_t* Rm, int frame_bytes,
+                   const int32_t* perm, const int32_t* k, int B, int T, ss_stream_t stream);
+
 /* ---- sliding-window serving of many streams ---------------------------------------
  * per stream a ring of the last max_t frames (features (S,max_t,D) f32, optional ROI (S,max_t,frame_bytes) u8), a head
  * and a count: the deque(maxlen=max_t) of inactive/live_feed.py:155.  A push appends one frame for each of n DISTINCT
@@ -642,6 +665,20 @@ int ss_tail_fwd_w(const float* h, const int32_t* lengths, const float* w_score, 
                   float label_smoothing, const float* cw, const float* den, float* attn, float* xhat, float* rstd, float* ln,
                   float* mid, float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct,
                   ss_stream_t stream);
+/* ss_tail_fwd / ss_tail_fwd_w with the two-label loss of a mixup batch: y_b (B) the partners' labels, lam (1) a DEVICE float in
+ * [0, 1] (ss_batch_plan_mixup writes both).  cw and den both NULL: the unweighted loss divided by `denom`; both given: the
+ * class-weighted one divided by *den (`denom` unused) -- sum_i cw[y_b[i]] is the sum over the same labels as sum_i cw[y[i]], so
+ * the one normaliser serves both terms.  Per row
+ *   l = lam * l(y) + (1 - lam) * l(y_b),    d_logits[c] = [ p_c A_mix - (lam tgt(y)_c + (1 - lam) tgt(y_b)_c) ] / normaliser,
+ * l, tgt and A as above and A_mix the same blend of the two As (1 without weights).  correct counts argmax == y.  A row with
+ * either label outside [0, C) gets a zero d_logits row and adds nothing.  *lam == 1: the bits of ss_tail_fwd / ss_tail_fwd_w.
+ * ss_tail_bwd serves this one too. */
+int ss_tail_fwd_mix(const float* h, const int32_t* lengths, const float* w_score, const float* b_score, const float* gamma,
+                    const float* beta, const float* w1, const float* b1, const float* w4, const float* b4, const int64_t* y,
+                    const int64_t* y_b, const float* lam, int B, int T, int D, int MID, int C, float ln_eps, float drop_p,
+                    uint64_t seed, uint64_t offset, float label_smoothing, float denom, const float* cw, const float* den,
+                    float* attn, float* xhat, float* rstd, float* ln, float* mid, float* mid_d, float* logits, float* d_logits,
+                    float* loss_sum, int32_t* correct, ss_stream_t stream);
 /* Backward of the tail from d_logits (B,C) down to d_h (B,T,D) (written) and d_mid (B,MID) (written: the input of the
  * first Linear's weight-gradient GEMM); g_gamma, g_beta (D), g_wscore (D), g_bscore (1) are accumulated -- unless
  * col_part (B,3,D) is given: then every clip STORES its terms of g_gamma | g_beta | g_wscore there and the caller adds the
@@ -668,6 +705,13 @@ int ss_ce_ls_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float 
  * outside [0, C) gets a zero gradient row and adds nothing.  Every w[c] == 1 and *den == denom: the bits of ss_ce_ls_fwd_bwd. */
 int ss_ce_ls_w_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float label_smoothing, const float* w,
                        const float* den, float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream);
+/* The two-label loss of a mixup batch, lam * CE(logits, y) + (1 - lam) * CE(logits, y_b): y_b (B) int64, lam (1) a DEVICE float.
+ * w and den both NULL: the unweighted loss over `denom`; both given: the weighted one over *den (see ss_tail_fwd_mix).  d_logits,
+ * loss_sum and correct (argmax == y) may each be NULL.  A row with either label outside [0, C) gets a zero gradient row and adds
+ * nothing.  *lam == 1: the bits of ss_ce_ls_fwd_bwd / ss_ce_ls_w_fwd_bwd. */
+int ss_ce_ls_mix_fwd_bwd(const float* logits, const int64_t* y, const int64_t* y_b, const float* lam, int B, int C,
+                         float label_smoothing, float denom, const float* w, const float* den, float* d_logits, float* loss_sum,
+                         int32_t* correct, ss_stream_t stream);
 /* out[0] = sum of w[y_i] over the n int64 labels y (device), written (not accumulated).  One workgroup, a fixed reduction
  * order: the result is a pure function of (the labels in order, w), so ranks that hold the same labels get the same bits.
  * A label outside [0, C) adds nothing. */

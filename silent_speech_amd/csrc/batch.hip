@@ -9,7 +9,7 @@
 // (rng "reference" / "device") or from the planning kernels below them: the epoch's class-balanced sample order
 // (:382-397) and the augmentation draws + maps of a batch, both on the Philox stream, nothing crossing PCIe.
 //
-// Eight kernels behind the eleven entry points:
+// Ten kernels behind the thirteen entry points:
 //   batch_gather_f32_kernel<HOST_NOISE, SCALE>  ss_batch_gather_f32 (<true, false> with a noise table, else <false, false>),
 //                                               ss_batch_gather_f32_at (<false, false>), ss_batch_gather_f32_aug (<false, true>)
 //   batch_gather_z_kernel<W>                    ss_batch_gather_z (W = 4: 16 bytes per lane; W = 1: any row geometry)
@@ -19,6 +19,8 @@
 //   batch_plan_kernel<POLICY>                   ss_batch_plan (<false>), ss_batch_plan_aug (<true>)
 //   batch_plan_mask_kernel                      ss_batch_plan_mask (behind either planner: edits its maps in place)
 //   batch_mask_apply_kernel                     ss_batch_mask_apply (behind the gathers: writes the masked bytes only)
+//   batch_plan_mixup_kernel                     ss_batch_plan_mixup (behind the planners: the batch's factor, partners, second labels)
+//   batch_mixup_kernel<W>                       ss_batch_mixup (behind everything else: the blended batch, out of place)
 #include "ss_common.h"
 
 namespace {
@@ -548,6 +550,135 @@ __global__ __launch_bounds__(256) void batch_mask_apply_kernel(float* __restrict
   }
 }
 
+// ---- mixup (AugmentPolicy: mixup_prob, mixup_alpha; inactive/train_reduced.py:36-53 mixes the collated batch).  One factor per
+// batch, lam = k / 256 with k an integer in [0, 256] from a table of Beta(alpha, alpha) quantiles, one partner row per row.
+constexpr uint32_t TAG_MIXUP = 0x6d697870u;  // "mixp"
+constexpr int MIXUP_MAX_B = 1024;
+
+// One workgroup plans the batch.  Counter (first_row, "mixp", 0) decides the batch: mixed iff augment && u0 < thr, then
+// k = table[mulhi(u1, N)]; counter (first_row + b, "mixp", 1) gives row b one 32-bit key, and perm[b] is the rank of (key_b, b)
+// among the rows -- a stable argsort, every thread counting the keys in LDS that order before its own (B <= 1024: at most 4 x 1024
+// compares per thread).  Not mixed: the identity, k = 256.  y_b = y[perm], lens_m = max(lens, lens[perm]).
+__global__ __launch_bounds__(256) void batch_plan_mixup_kernel(const int64_t* __restrict__ lens, const int64_t* __restrict__ y, int B,
+                                                               int augment, uint64_t first_row, uint64_t seed, uint64_t mix_thr,
+                                                               const uint16_t* __restrict__ table, int N,
+                                                               int32_t* __restrict__ perm, int64_t* __restrict__ y_b,
+                                                               int64_t* __restrict__ lens_m, int32_t* __restrict__ k_out,
+                                                               float* __restrict__ lam_out) {
+  __shared__ uint32_t keys[MIXUP_MAX_B];
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  uint32_t u[4];
+  philox4((uint32_t)first_row, (uint32_t)(first_row >> 32), TAG_MIXUP, 0u, k0, k1, u);
+  const bool mixed = augment && (uint64_t)u[0] < mix_thr;
+  int k = 256;
+  if (mixed) {
+    k = table[mulhi_u32(u[1], (uint32_t)N)];
+    k = k > 256 ? 256 : k;
+  }
+  for (int b = threadIdx.x; b < B; b += 256) {
+    const uint64_t row = first_row + (uint64_t)b;
+    uint32_t r[4];
+    philox4((uint32_t)row, (uint32_t)(row >> 32), TAG_MIXUP, 1u, k0, k1, r);
+    keys[b] = r[0];
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += 256) {
+    int p = b;
+    if (mixed) {
+      const uint32_t mine = keys[b];
+      p = 0;
+      for (int j = 0; j < B; ++j) {
+        const uint32_t other = keys[j];
+        p += (other < mine || (other == mine && j < b));
+      }
+    }
+    perm[b] = p;
+    y_b[b] = y[p];
+    const int64_t la = lens[b], lb = lens[p];
+    lens_m[b] = la > lb ? la : lb;
+  }
+  if (threadIdx.x == 0) {
+    k_out[0] = k;
+    lam_out[0] = (float)k * 0.00390625f;  // k / 256: exact
+  }
+}
+
+// bytes a and b blended by k / 256, four at a time: (k a + (256 - k) b + 128) >> 8 per byte.  Even and odd bytes each sit in
+// their own 16-bit lane of a dword, where the sum is at most 255 * 256 + 128 < 2^16: no carry leaves a lane.
+__device__ __forceinline__ uint32_t mix_bytes4(uint32_t a, uint32_t b, uint32_t k) {
+  const uint32_t m = 0x00ff00ffu, half = 0x00800080u, nk = 256u - k;
+  const uint32_t even = ((a & m) * k + (b & m) * nk + half) >> 8 & m;
+  const uint32_t odd = (((a >> 8) & m) * k + ((b >> 8) & m) * nk + half) & ~m;
+  return even | odd;
+}
+
+__device__ __forceinline__ float mix_f32(float lam, float oml, float a, float b) { return __fmaf_rn(lam, a, __fmul_rn(oml, b)); }
+
+// The blended batch, out of place (row b reads row perm[b], which an in-place pass may already have overwritten):
+//   Xm[b] = fmaf(lam, X[b], (1 - lam) * X[perm[b]]),   Rm[b] = (k R[b] + (256 - k) R[perm[b]] + 128) >> 8 per byte,
+// k read from the device, lam = k / 256 and 1 - lam both exact.  A clip whose partner is itself, and every clip when k == 256,
+// is copied: the input bytes, whatever they are (a -0.0, a NaN in a partner the factor gives no weight).  One launch, two
+// ranges of workgroups, both pure HBM streams of two reads and one write.  [0, r_blocks): the ROI frames, 16 bytes per lane as the
+// u8 gathers move them; the T frames of a clip are one run of T * chunks 16-byte chunks, and a lane takes chunk u of the batch,
+// clip u / (T * chunks), whatever the frame size (a 32 x 32 frame is 64 chunks: no lane idles on it).  Behind them: the features, one lane per W consecutive
+// elements of a row of D -- W = 4 (16 bytes per lane: D and ld_x multiples of 4, bases 16-byte aligned) or W = 1 (any D and
+// ld_x: 83 exists); rows are ld_x floats apart in X and in Xm.  An entry of perm outside [0, B) is never an index: the row is
+// copied.
+template <int W>
+__global__ __launch_bounds__(256) void batch_mixup_kernel(const float* __restrict__ X, int ld_x, int D, float* __restrict__ Xm,
+                                                          const uint8_t* __restrict__ R, uint8_t* __restrict__ Rm, int chunks,
+                                                          const int32_t* __restrict__ perm, const int32_t* __restrict__ k_dev,
+                                                          int B, int T, int r_blocks) {
+  static_assert(W == 1 || W == 4, "one element or one 16-byte chunk per lane");
+  const int kk = k_dev[0];
+  const uint32_t k = (uint32_t)(kk < 0 ? 0 : kk > 256 ? 256 : kk);
+  const long rows = (long)B * T;
+  if ((int)blockIdx.x < r_blocks) {
+    const uint4* src = reinterpret_cast<const uint4*>(R);
+    uint4* dst = reinterpret_cast<uint4*>(Rm);
+    const long per_clip = (long)T * chunks, total = rows * chunks;
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < total; u += (long)r_blocks * 256) {
+      const int b = (int)(u / per_clip);  // one division per lane and chunk, as in the gathers
+      const int pb = perm[b];
+      const uint4 a = src[u];
+      uint4 o = a;
+      if (!(k == 256u || pb == b || (unsigned)pb >= (unsigned)B)) {
+        const uint4 q = src[u + (long)(pb - b) * per_clip];
+        o = uint4{mix_bytes4(a.x, q.x, k), mix_bytes4(a.y, q.y, k), mix_bytes4(a.z, q.z, k), mix_bytes4(a.w, q.w, k)};
+      }
+      dst[u] = o;
+    }
+    return;
+  }
+  const float lam = (float)k * 0.00390625f, oml = (float)(256u - k) * 0.00390625f;
+  const int units = D / W;  // per row
+  const long total = rows * units;
+  const long x_blocks = (long)gridDim.x - r_blocks;
+  for (long u = ((long)blockIdx.x - r_blocks) * 256 + threadIdx.x; u < total; u += x_blocks * 256) {
+    const long r = u / units;  // one division per lane and chunk, as in the gathers
+    const int c = (int)(u - r * units) * W;
+    const int b = (int)(r / T);
+    const int pb = perm[b];
+    const bool copy = k == 256u || pb == b || (unsigned)pb >= (unsigned)B;
+    const float* xa = X + r * ld_x + c;
+    const float* xb = X + (r + (long)((copy ? b : pb) - b) * T) * ld_x + c;
+    float* d = Xm + r * ld_x + c;
+    if constexpr (W == 4) {
+      const float4 a = *reinterpret_cast<const float4*>(xa);
+      float4 o = a;
+      if (!copy) {
+        const float4 p = *reinterpret_cast<const float4*>(xb);
+        o = float4{mix_f32(lam, oml, a.x, p.x), mix_f32(lam, oml, a.y, p.y), mix_f32(lam, oml, a.z, p.z),
+                   mix_f32(lam, oml, a.w, p.w)};
+      }
+      *reinterpret_cast<float4*>(d) = o;
+    } else {
+      const float a = *xa;
+      *d = copy ? a : mix_f32(lam, oml, a, *xb);
+    }
+  }
+}
+
 // the launch of the f32 gather shared by its three entry points: one lane per 16-byte chunk of dst, at most 4096 workgroups
 template <bool HOST_NOISE, bool SCALE>
 int launch_gather_f32(const float* src, int D, const int32_t* frame_map, long rows, const float* noise, const int32_t* noise_map,
@@ -742,5 +873,42 @@ extern "C" int ss_batch_mask_apply(float* X, int ld_x, int D, uint8_t* R, int H,
   blocks = blocks > 8192 ? 8192 : blocks;
   hipLaunchKernelGGL(batch_mask_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), X, ld_x, D, R,
                      H, W, rmap, row_mask, rows, rows_per_clip, fill);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_plan_mixup(const int64_t* lens, const int64_t* y, int B, int augment, uint64_t batch_first_row,
+                                   uint64_t seed, double mixup_prob, const uint16_t* table, int N, int32_t* perm, int64_t* y_b,
+                                   int64_t* lens_m, int32_t* k_out, float* lam_out, ss_stream_t stream) {
+  SS_REQUIRE(lens && y && table && perm && y_b && lens_m && k_out && lam_out, SS_ERR_ARG);
+  SS_REQUIRE(B >= 1 && B <= MIXUP_MAX_B && N > 0 && (N & (N - 1)) == 0, SS_ERR_ARG);
+  SS_REQUIRE(mixup_prob >= 0.0 && mixup_prob <= 1.0, SS_ERR_ARG);  // (a NaN fails it)
+  hipLaunchKernelGGL(batch_plan_mixup_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), lens, y, B, augment,
+                     batch_first_row, seed, prob_threshold(mixup_prob), table, N, perm, y_b, lens_m, k_out, lam_out);
+  return ss_launch_status();
+}
+
+extern "C" int ss_batch_mixup(const float* X, int ld_x, int D, float* Xm, const uint8_t* R, uint8_t* Rm, int frame_bytes,
+                              const int32_t* perm, const int32_t* k, int B, int T, ss_stream_t stream) {
+  SS_REQUIRE((X == nullptr) == (Xm == nullptr) && (R == nullptr) == (Rm == nullptr) && (X || R), SS_ERR_ARG);
+  SS_REQUIRE(perm && k && B > 0 && T > 0, SS_ERR_ARG);
+  SS_REQUIRE(!X || (D > 0 && ld_x >= D && X != Xm), SS_ERR_ARG);
+  SS_REQUIRE(!X || ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Xm)) & 3) == 0, SS_ERR_ARG);
+  SS_REQUIRE(!R || (frame_bytes > 0 && R != Rm), SS_ERR_ARG);
+  SS_REQUIRE(!R || (frame_bytes & 15) == 0, SS_ERR_UNSUPPORTED);
+  SS_REQUIRE(!R || ((reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(Rm)) & 15) == 0, SS_ERR_ARG);
+  const long rows = (long)B * T;
+  // at most 2048 workgroups per stream: eight of 256 lanes on each of 256 CUs is all the chip holds at once
+  long r_blocks = !R ? 0 : (rows * (frame_bytes / 16) + 255) / 256;
+  r_blocks = r_blocks > 2048 ? 2048 : r_blocks;
+  const bool wide = X && ((D | ld_x) & 3) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Xm)) & 15) == 0;
+  long x_blocks = !X ? 0 : (rows * (D / (wide ? 4 : 1)) + 255) / 256;
+  x_blocks = x_blocks > 2048 ? 2048 : x_blocks;
+  const dim3 grid((unsigned)(r_blocks + x_blocks));
+  if (wide)
+    hipLaunchKernelGGL(batch_mixup_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), X, ld_x, D, Xm, R, Rm,
+                       frame_bytes / 16, perm, k, B, T, (int)r_blocks);
+  else
+    hipLaunchKernelGGL(batch_mixup_kernel<1>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), X, ld_x, D, Xm, R, Rm,
+                       frame_bytes / 16, perm, k, B, T, (int)r_blocks);
   return ss_launch_status();
 }

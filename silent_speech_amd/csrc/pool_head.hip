@@ -201,11 +201,15 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
 // one thread per clip (C is a handful of words); the row arithmetic is ce_row (ce_row.h).  WEIGHTED: class weights w (C) and the
 // normaliser read from the device (*den = sum of w[y] over the normalising set, ss_class_weight_sum); a row whose label is
 // outside [0, C) is never an index there: zero gradient, nothing added.
-template <bool WEIGHTED>
+// MIX (ss_ce_ls_mix_fwd_bwd): the two-label loss of a mixup batch, second labels y_b and the factor *lam read from the device; a row
+// with either label outside [0, C) is such a row too, weighted or not.  Without MIX neither pointer is read.
+template <bool WEIGHTED, bool MIX = false>
 __global__ __launch_bounds__(256) void ce_ls_kernel(const float* __restrict__ logits, const int64_t* __restrict__ y, int B,
                                                     int C, float eps, float denom, const float* __restrict__ w,
                                                     const float* __restrict__ den, float* __restrict__ d_logits,
-                                                    float* __restrict__ loss_sum, int* __restrict__ correct) {
+                                                    float* __restrict__ loss_sum, int* __restrict__ correct,
+                                                    const int64_t* __restrict__ y_b = nullptr,
+                                                    const float* __restrict__ lam = nullptr) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if constexpr (WEIGHTED) denom = den[0];
   float loss = 0.f;
@@ -214,10 +218,14 @@ __global__ __launch_bounds__(256) void ce_ls_kernel(const float* __restrict__ lo
     float* d_row = d_logits ? d_logits + (long)b * C : nullptr;
     bool valid = true;
     if constexpr (WEIGHTED) valid = y[b] >= 0 && y[b] < (int64_t)C;
+    if constexpr (MIX) valid = y[b] >= 0 && y[b] < (int64_t)C && y_b[b] >= 0 && y_b[b] < (int64_t)C;
     if (valid) {
       const int yy = (int)y[b];
       int am;
-      loss = ce_row<WEIGHTED>(logits + (long)b * C, yy, C, eps, w, denom, d_row, &am);
+      if constexpr (MIX)
+        loss = ce_row<WEIGHTED, true>(logits + (long)b * C, yy, C, eps, w, denom, d_row, &am, (int)y_b[b], lam[0]);
+      else
+        loss = ce_row<WEIGHTED>(logits + (long)b * C, yy, C, eps, w, denom, d_row, &am);
       ok = (am == yy);
     } else if (d_row) {
       for (int c = 0; c < C; ++c) d_row[c] = 0.f;
@@ -345,7 +353,7 @@ extern "C" int ss_ce_ls_fwd_bwd(const float* logits, const int64_t* y, int B, in
                                 ss_stream_t stream) {
   SS_REQUIRE(logits && y && B > 0 && C > 0 && denom > 0.f, SS_ERR_ARG);
   hipLaunchKernelGGL(ce_ls_kernel<false>, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, y,
-                     B, C, label_smoothing, denom, nullptr, nullptr, d_logits, loss_sum, correct);
+                     B, C, label_smoothing, denom, nullptr, nullptr, d_logits, loss_sum, correct, nullptr, nullptr);
   return ss_launch_status();
 }
 
@@ -354,7 +362,21 @@ extern "C" int ss_ce_ls_w_fwd_bwd(const float* logits, const int64_t* y, int B, 
                                   ss_stream_t stream) {
   SS_REQUIRE(logits && y && w && den && B > 0 && C > 0, SS_ERR_ARG);
   hipLaunchKernelGGL(ce_ls_kernel<true>, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, y,
-                     B, C, label_smoothing, 1.0f, w, den, d_logits, loss_sum, correct);
+                     B, C, label_smoothing, 1.0f, w, den, d_logits, loss_sum, correct, nullptr, nullptr);
+  return ss_launch_status();
+}
+
+extern "C" int ss_ce_ls_mix_fwd_bwd(const float* logits, const int64_t* y, const int64_t* y_b, const float* lam, int B, int C,
+                                    float label_smoothing, float denom, const float* w, const float* den, float* d_logits,
+                                    float* loss_sum, int32_t* correct, ss_stream_t stream) {
+  SS_REQUIRE(logits && y && y_b && lam && B > 0 && C > 0, SS_ERR_ARG);
+  SS_REQUIRE((w == nullptr) == (den == nullptr) && (w || denom > 0.f), SS_ERR_ARG);
+  if (w)
+    hipLaunchKernelGGL((ce_ls_kernel<true, true>), dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+                       y, B, C, label_smoothing, 1.0f, w, den, d_logits, loss_sum, correct, y_b, lam);
+  else
+    hipLaunchKernelGGL((ce_ls_kernel<false, true>), dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+                       y, B, C, label_smoothing, denom, nullptr, nullptr, d_logits, loss_sum, correct, y_b, lam);
   return ss_launch_status();
 }
 

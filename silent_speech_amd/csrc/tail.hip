@@ -47,12 +47,23 @@ struct TailFwdParams {
   float *attn, *xhat, *rstd, *ln, *mid, *mid_d, *logits, *d_logits, *loss_sum;
   int* correct;
   static constexpr bool weighted = false;
+  static constexpr bool mix = false;
 };
 
 // the class-weighted loss (ss_tail_fwd_w): class weights cw (C) and the normaliser on the device (*den) instead of `denom`
 struct TailFwdParamsW : TailFwdParams {
   const float *cw, *den;
   static constexpr bool weighted = true;
+};
+
+// the two-label loss of a mixup batch (ss_tail_fwd_mix), weighted (cw, den) or not (denom): second labels y_b and the factor *lam,
+// read from the device
+template <bool WEIGHTED>
+struct TailFwdParamsMix : TailFwdParamsW {
+  const int64_t* y_b;
+  const float* lam;
+  static constexpr bool weighted = WEIGHTED;
+  static constexpr bool mix = true;
 };
 
 // dynamic LDS: sc[T] | pooled[D] | lnv[D] | midv[MID] | lg[C]
@@ -232,10 +243,17 @@ __global__ __launch_bounds__(TNT) void tail_fwd_kernel(Params p) {
       cw = p.cw;
       valid = p.y[b] >= 0 && p.y[b] < (int64_t)C;  // a label outside the classes is never an index here: the row adds nothing
     }
+    int yb = 0;
+    float lam = 1.0f;
+    if constexpr (Params::mix) {  // either label outside the classes: the row adds nothing, weighted or not
+      valid = p.y[b] >= 0 && p.y[b] < (int64_t)C && p.y_b[b] >= 0 && p.y_b[b] < (int64_t)C;
+      yb = valid ? (int)p.y_b[b] : 0;
+      lam = p.lam[0];
+    }
     if (valid) {
       const int yy = (int)p.y[b];
       int am;
-      const float loss = ce_row_wave<Params::weighted>(lg, yy, C, lane, p.ls, cw, denom, d_row, &am);
+      const float loss = ce_row_wave<Params::weighted, Params::mix>(lg, yy, C, lane, p.ls, cw, denom, d_row, &am, yb, lam);
       if (lane == 0) {
         if (p.loss_sum) atomicAdd(p.loss_sum, loss / denom);
         if (p.correct && am == yy) atomicAdd(p.correct, 1);
@@ -347,29 +365,38 @@ __global__ __launch_bounds__(TNT) void tail_bwd_kernel(TailBwdParams p) {
 
 }  // namespace
 
-// cw == NULL: the unweighted loss divided by `denom`; else the class-weighted one divided by *den
+// cw == NULL: the unweighted loss divided by `denom`; else the class-weighted one divided by *den.  y_b != NULL: the two-label
+// loss of a mixup batch (lam then too)
 static int tail_fwd_launch(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
                            const float* gamma, const float* beta, const float* w1, const float* b1, const float* w4,
                            const float* b4, const int64_t* y, int B, int T, int D, int MID, int C, float ln_eps,
                            float drop_p, uint64_t seed, uint64_t offset, float label_smoothing, float denom,
                            const float* cw, const float* den, float* attn, float* xhat, float* rstd, float* ln, float* mid,
                            float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct,
-                           ss_stream_t stream) {
+                           ss_stream_t stream, const int64_t* y_b = nullptr, const float* lam = nullptr) {
   SS_REQUIRE(h && lengths && w_score && b_score && gamma && beta && w1 && b1 && w4 && b4 && logits, SS_ERR_ARG);
   SS_REQUIRE(B > 0 && T > 0 && D > 0 && MID > 0 && C > 0 && drop_p >= 0.f && drop_p < 1.f, SS_ERR_ARG);
   SS_REQUIRE(!y || (d_logits && denom > 0.f), SS_ERR_ARG);
   const size_t lds = (size_t)(T + 2 * D + MID + C) * sizeof(float);
   SS_REQUIRE(lds <= 60 * 1024, SS_ERR_UNSUPPORTED);
-  TailFwdParamsW p;
-  p.cw = cw; p.den = den;
+  TailFwdParamsMix<true> p;
+  p.cw = cw; p.den = den; p.y_b = y_b; p.lam = lam;
   p.h = h; p.lengths = lengths; p.w_score = w_score; p.b_score = b_score; p.gamma = gamma; p.beta = beta;
   p.w1 = w1; p.b1 = b1; p.w4 = w4; p.b4 = b4; p.y = y;
   p.B = B; p.T = T; p.D = D; p.MID = MID; p.C = C;
   p.eps = ln_eps; p.drop_p = drop_p; p.ls = label_smoothing; p.denom = denom; p.seed = seed; p.offset = offset;
   p.attn = attn; p.xhat = xhat; p.rstd = rstd; p.ln = ln; p.mid = mid; p.mid_d = mid_d; p.logits = logits;
   p.d_logits = d_logits; p.loss_sum = loss_sum; p.correct = correct;
-  if (cw)
-    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParamsW>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream), p);
+  if (y_b && cw) {
+    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParamsMix<true>>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream), p);
+  } else if (y_b) {
+    TailFwdParamsMix<false> q;
+    static_cast<TailFwdParamsW&>(q) = p;
+    q.y_b = y_b; q.lam = lam;
+    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParamsMix<false>>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream), q);
+  } else if (cw)
+    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParamsW>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream),
+                       static_cast<const TailFwdParamsW&>(p));
   else
     hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParams>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream),
                        static_cast<const TailFwdParams&>(p));
@@ -397,6 +424,19 @@ extern "C" int ss_tail_fwd_w(const float* h, const int32_t* lengths, const float
   return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4, y, B, T, D, MID, C, ln_eps, drop_p, seed,
                          offset, label_smoothing, 1.0f, cw, den, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits, loss_sum,
                          correct, stream);
+}
+
+extern "C" int ss_tail_fwd_mix(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
+                               const float* gamma, const float* beta, const float* w1, const float* b1, const float* w4,
+                               const float* b4, const int64_t* y, const int64_t* y_b, const float* lam, int B, int T, int D,
+                               int MID, int C, float ln_eps, float drop_p, uint64_t seed, uint64_t offset, float label_smoothing,
+                               float denom, const float* cw, const float* den, float* attn, float* xhat, float* rstd, float* ln,
+                               float* mid, float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct,
+                               ss_stream_t stream) {
+  SS_REQUIRE(y && y_b && lam && (cw == nullptr) == (den == nullptr), SS_ERR_ARG);
+  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4, y, B, T, D, MID, C, ln_eps, drop_p, seed,
+                         offset, label_smoothing, cw ? 1.0f : denom, cw, den, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits,
+                         loss_sum, correct, stream, y_b, lam);
 }
 
 extern "C" int ss_tail_bwd(const float* h, const int32_t* lengths, const float* w_score, const float* gamma,

@@ -24,7 +24,8 @@ applied on the device as well (``ss_batch_plan_aug``, ``ss_batch_gather_f32_aug`
 tests/aug_plan_ref.py restates them).  Without a policy the launches are the three above, unchanged.  The policy's masks (a masked
 run of frames, a zeroed band of feature columns, a filled rectangle of the ROI frames) are two more launches when one of them is
 on: ``ss_batch_plan_mask`` edits the maps behind either planner, ``ss_batch_mask_apply`` writes the band and the rectangle behind the
-gathers.
+gathers.  Mixup (``mixup_prob`` > 0; inactive/train_reduced.py:36-53) is two more behind all of them: ``ss_batch_plan_mixup`` draws the
+batch's factor and its partner rows, ``ss_batch_mixup`` writes the blended batch; tests/mixup_ref.py restates both.
 
 In ``csrc/batch.hip`` the entry points are instantiations of a few kernels: ``ss_batch_plan`` / ``ss_batch_plan_aug`` of one plan
 kernel (without / with the policy), ``ss_batch_gather_f32`` / ``_at`` / ``_aug`` of one feature gather (host-drawn or Philox noise,
@@ -81,7 +82,14 @@ class AugmentPolicy:
     ``feat_mask_prob`` / ``feat_mask_max``: one band of 1 .. ``min(feat_mask_max, D)`` feature columns set to 0.0 in every row of the
     clip.  ``cutout_prob`` / ``cutout_max`` = (w, h) / ``cutout_fill``: a clip with ROI frames gets one rectangle of at most w x h pixels
     filled with the grey level in all its frames (padding frames stay zero).  A mask is on when its probability is > 0 and its
-    maximum >= 1; with all three off ``batch()`` issues the launches it issues without them."""
+    maximum >= 1; with all three off ``batch()`` issues the launches it issues without them.
+
+    ``mixup_prob`` / ``mixup_alpha`` (the reference's lineage trains with it: inactive/train_reduced.py:36-53, 214-217): with
+    probability ``mixup_prob`` a training batch, after everything above, is blended with a permutation of its own rows by one
+    factor ``lam = k / 256`` per batch, ``k`` drawn from ``mixup_table(mixup_alpha)`` -- 1024 quantiles of Beta(alpha, alpha) in
+    steps of 1 / 256.  Features ``fmaf(lam, X[b], (1 - lam) * X[perm[b]])``, ROI bytes ``(k R[b] + (256 - k) R[perm[b]] + 128) >> 8``,
+    lengths the longer of the two; the partner labels and ``lam`` go to ``Trainer.step(mix=)``, whose loss is
+    ``lam * CE(y) + (1 - lam) * CE(y[perm])``.  Off (``mixup_prob`` == 0) no launch is added."""
     time_warp_prob: float = 0.0
     time_warp_range: Tuple[float, float] = (0.8, 1.2)
     scale_prob: float = 0.0
@@ -97,12 +105,14 @@ class AugmentPolicy:
     cutout_prob: float = 0.0
     cutout_max: Tuple[int, int] = (0, 0)
     cutout_fill: int = 128
+    mixup_prob: float = 0.0
+    mixup_alpha: float = 0.2
 
     _STREAMS = ("both", "features", "roi")  # (the codes ss_batch_plan_mask takes: the position in the tuple)
     _FILLS = ("zero", "hold")
 
     def __post_init__(self):
-        for name in ("time_warp_prob", "scale_prob", "roi_shift_prob", "time_mask_prob", "feat_mask_prob", "cutout_prob"):
+        for name in ("time_warp_prob", "scale_prob", "roi_shift_prob", "time_mask_prob", "feat_mask_prob", "cutout_prob", "mixup_prob"):
             p = getattr(self, name)
             if not (isinstance(p, (int, float)) and 0.0 <= p <= 1.0):
                 raise ValueError(f"{name} must lie in [0, 1], not {p!r}")
@@ -132,6 +142,9 @@ class AugmentPolicy:
             raise ValueError(f"time_mask_streams must be one of {self._STREAMS!r}, not {self.time_mask_streams!r}")
         if self.time_mask_fill not in self._FILLS:
             raise ValueError(f"time_mask_fill must be one of {self._FILLS!r}, not {self.time_mask_fill!r}")
+        a = self.mixup_alpha
+        if not (isinstance(a, (int, float)) and not isinstance(a, bool) and np.isfinite(a) and a > 0):
+            raise ValueError(f"mixup_alpha must be a finite number > 0, not {a!r}")
 
     @classmethod
     def lineage(cls, **overrides) -> "AugmentPolicy":
@@ -149,6 +162,14 @@ class AugmentPolicy:
     @property
     def cutout_on(self) -> bool:
         return self.cutout_prob > 0 and min(self.cutout_max) >= 1
+
+    @property
+    def mixup_on(self) -> bool:
+        return self.mixup_prob > 0
+
+    def mixup_fields(self) -> dict:
+        """``mixup_prob`` and ``mixup_alpha`` when mixup is on, else nothing: what ``harness.run_fingerprint`` adds for them."""
+        return {name: float(getattr(self, name)) for name in MIXUP_FIELDS} if self.mixup_on else {}
 
     def mask_fields(self) -> dict:
         """The mask fields that differ from their defaults (tuples as lists): what ``harness.run_fingerprint`` adds for them, so
@@ -180,6 +201,46 @@ class AugmentPolicy:
 
 MASK_FIELDS = ("time_mask_prob", "time_mask_max", "time_mask_streams", "time_mask_fill", "feat_mask_prob", "feat_mask_max",
                "cutout_prob", "cutout_max", "cutout_fill")
+MIXUP_FIELDS = ("mixup_prob", "mixup_alpha")
+
+
+def mixup_table(alpha: float, N: int = 1024) -> np.ndarray:
+    """-> (N,) uint16, ``k_i = round(256 * Q((i + 0.5) / N))`` with ``Q`` the quantile function of Beta(alpha, alpha): the table
+    ``ss_batch_plan_mixup`` draws the batch's ``k`` from (``lam = k / 256``).  float64, NumPy alone.
+
+    Beta(a, a) is symmetric about 1/2, so only ``x <= 1/2`` is computed: there the CDF is ``I(x) = B(x) / (2 B(1/2))``,
+    ``B(x) = int_0^x t^(a-1) (1-t)^(a-1) dt``.  For ``a < 1``, with ``u = t^a`` the integrand becomes ``(1/a) (1 - u^(1/a))^(a-1)``
+    on ``[0, (1/2)^a]``: bounded and smooth where the original has its ``t^(a-1)`` singularity.  For ``a >= 1`` there is no
+    singularity, and a grid uniform in ``u`` would crowd into the last step before 1/2 as ``a`` grows (``(1/2)^a`` underflows in the
+    end), so the grid is uniform in ``t`` and the integrand is ``(4 t (1-t))^(a-1)``, at most 1 for any ``a`` (the constant factor
+    cancels in ``I``).  Composite Simpson gives ``B`` at the grid points, ``Q(p)`` for ``p <= 1/2`` is the linear inverse of that
+    monotone table (the grid is fine enough that its error is far below the 1/512 that decides a rounding), and the upper half
+    is the mirror image: ``k_i + k_(N-1-i) = 256``.  ``ValueError`` if the integral is not a positive finite number (an ``alpha``
+    so small that ``1 / alpha`` overflows)."""
+    a = float(alpha)
+    if not (np.isfinite(a) and a > 0):
+        raise ValueError(f"alpha must be a finite number > 0, not {alpha!r}")
+    N = int(N)
+    if N < 2 or N & (N - 1):
+        raise ValueError(f"N must be a power of two >= 2, not {N!r}")
+    M = 1 << 18  # Simpson panels (each of two half-steps)
+    with np.errstate(all="ignore"):
+        if a < 1.0:
+            u = np.linspace(0.0, 0.5 ** a, 2 * M + 1)
+            t = u ** (1.0 / a)
+            f = (1.0 - t) ** (a - 1.0) / a
+        else:
+            u = t = np.linspace(0.0, 0.5, 2 * M + 1)
+            f = (4.0 * t * (1.0 - t)) ** (a - 1.0)
+        panels = (f[0:-1:2] + 4.0 * f[1::2] + f[2::2]) * ((u[2] - u[0]) / 6.0)
+        cum = np.concatenate([[0.0], np.cumsum(panels)])  # B at t[0::2]
+    if not (np.isfinite(cum[-1]) and cum[-1] > 0):
+        raise ValueError(f"alpha {alpha!r}: the float64 integral of the Beta density is {cum[-1]!r}")
+    cdf = cum / (2.0 * cum[-1])                       # 0 .. 1/2
+    p = (np.arange(N // 2) + 0.5) / N
+    x = np.interp(p, cdf, t[0::2])
+    lo = np.floor(256.0 * x + 0.5).astype(np.int64)
+    return np.concatenate([lo, 256 - lo[::-1]]).astype(np.uint16)
 
 
 class DeviceClipStore:
@@ -226,6 +287,9 @@ class DeviceClipStore:
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)  # set by ss_batch_plan, read by check()
         self._plan_bufs = {}  # batch size -> (xmap, nmap, rmap, lens, y, row_scale, row_shift)
         self._mask_bufs = {}  # batch size -> row_mask (B, 8), for the batch sizes a policy with a mask on has planned
+        self._mix_bufs = {}   # batch size -> (perm, y_b, lens_m, k, lam), for the batch sizes a policy with mixup on has planned
+        self._mix_tables = {}  # mixup_alpha -> mixup_table(alpha) on the device, uploaded once
+        self.mix = None  # (y_b, lam, perm, k) of the last batch a policy with mixup on has planned
         # embed(): the frozen CNN's embeddings of the ROI frames, of one all-zero frame, and what they were made from
         self.E = self.E0 = None
         self._embed_model = self._embed_params = self._embed_version = None
@@ -369,6 +433,8 @@ class DeviceClipStore:
         ahead = int(first_row) - int(first)
         if ahead < 0:
             raise ValueError("batch_first_row lies behind first_row")
+        if policy is not None and policy.mixup_on and (ahead or B > 1024):
+            raise ValueError("mixup needs the whole batch (no shard of a larger one) and at most 1024 clips")
         noise_seed, noise_first = philox_noise_seed(seed, first), ahead * mt * self.D
         # One set of map / length / label buffers (and the policy's per-clip scale and shift) per batch size, reused by every
         # batch: the plan kernel, the two gathers and whatever consumes T and y afterwards are enqueued on L.stream() in order,
@@ -435,7 +501,36 @@ class DeviceClipStore:
             L.call("ss_batch_mask_apply", X.data_ptr() if band else None, self.D, self.D, R.data_ptr() if cutout else None, H, W,
                    rmap.data_ptr() if cutout else None, row_mask.data_ptr(), B * mt, mt, int(policy.cutout_fill), s)
         X._ss_keep = (idx_d,)
+        if policy is not None and policy.mixup_on:
+            return self._mixup(X, lens, R, y, B, augment, first, seed, policy)
         return X, lens, R, y
+
+    def _mixup(self, X, lens, R, y, B, augment, batch_first_row, seed, policy):
+        """Behind the gathers and the masks, on the same stream: ``ss_batch_plan_mixup`` (the batch's ``k``, ``perm``, the partners'
+        labels, the longer lengths) and ``ss_batch_mixup`` (the blended ``X`` and ``R``, out of place).  The draw is keyed by the
+        first row of the whole batch, so it is one per batch."""
+        mt, dev, s = self.max_t, self.device, L.stream()
+        table = self._mix_tables.get(float(policy.mixup_alpha))
+        if table is None:
+            host = mixup_table(policy.mixup_alpha).astype(np.int16)  # (entries <= 256: the same bits as uint16)
+            table = self._mix_tables[float(policy.mixup_alpha)] = torch.from_numpy(host).to(dev)
+        bufs = self._mix_bufs.get(B)
+        if bufs is None:
+            bufs = self._mix_bufs[B] = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int64, device=dev),
+                                        torch.empty(B, dtype=torch.int64, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+                                        torch.empty(1, dtype=torch.float32, device=dev))
+        perm, y_b, lens_m, k, lam = bufs
+        L.call("ss_batch_plan_mixup", lens.data_ptr(), y.data_ptr(), B, int(bool(augment)), int(batch_first_row) & _MASK64,
+               int(seed) & _MASK64, float(policy.mixup_prob), table.data_ptr(), table.numel(), perm.data_ptr(), y_b.data_ptr(),
+               lens_m.data_ptr(), k.data_ptr(), lam.data_ptr(), s)
+        Xm = torch.empty_like(X)
+        Rm = None if R is None else torch.empty_like(R)
+        fb = 0 if R is None else self.roi_hw[0] * self.roi_hw[1]
+        L.call("ss_batch_mixup", X.data_ptr(), self.D, self.D, Xm.data_ptr(), L.ptr(R), L.ptr(Rm), fb, perm.data_ptr(),
+               k.data_ptr(), B, mt, s)
+        Xm._ss_keep = getattr(X, "_ss_keep", ())
+        self.mix = (y_b, lam, perm, k)
+        return Xm, lens_m, Rm, y
 
     def batch(self, indices: Sequence[int], augment: bool = False, rng: str = "device",
               generator: Optional[np.random.Generator] = None, seed: int = 0, first_row: int = 0,
@@ -459,7 +554,13 @@ class DeviceClipStore:
         decisions are keyed by the row's draw index like the rest of the plan, so shards (``batch_first_row``) stay bit-equal
         to the single-process batch.  ``None``: exactly the three launches described above.  A policy with a mask switched on (time
         mask, feature band, ROI cutout) adds ``ss_batch_plan_mask`` behind the planner and, for the band and the cutout,
-        ``ss_batch_mask_apply`` behind the gathers; with all masks off neither is launched.
+        ``ss_batch_mask_apply`` behind the gathers; with all masks off neither is launched.  A policy with ``mixup_prob`` > 0 adds
+        ``ss_batch_plan_mixup`` and ``ss_batch_mixup`` behind all of these: ``X``, ``T`` and ``R`` are then those of the blended batch
+        (``T`` the longer of a row's and its partner's), ``y`` stays the rows' own labels, and ``self.mix`` = ``(y_b, lam, perm, k)``
+        -- the partners' labels (B,) int64, the factor (1,) f32, the permutation (B,) int32 and ``k`` (1,) int32, all on the device and
+        valid until the next ``batch`` call of that batch size -- is what ``Trainer.step(mix=(y_b, lam))`` takes.  The draw is keyed
+        by the first row of the whole batch (``batch_first_row``); a shard of a larger batch would need its partners from other
+        ranks, which is not built.  With ``mixup_prob`` == 0 the launches are those without the fields.
 
         ``embedded`` (``rng="philox"`` only, after ``embed(model)``): -> ``(Z, T, None, y)``, ``Z`` (B, max_t, D + roi_emb) f32 = the
         rows ``X | CNN(R)`` of the batch the same call returns without it (``model.forward_embedded(Z, T)`` are the logits of
@@ -473,6 +574,8 @@ class DeviceClipStore:
                 raise TypeError("policy must be an AugmentPolicy")
             if rng != "philox" or not augment:
                 raise ValueError("an AugmentPolicy needs rng='philox' and augment=True")
+        if policy is not None and policy.mixup_on and embedded:
+            raise ValueError("embedded=True cannot apply mixup_prob > 0: mixup of embedded batches is not built")
         if embedded:
             if rng != "philox":
                 raise ValueError("embedded=True needs rng='philox': the embedded batch is planned on the device")

@@ -318,13 +318,18 @@ CNN_PARAMS = ("roi_cnn.net.0.weight", "roi_cnn.net.0.bias", "roi_cnn.net.3.weigh
 def tail_fwd(P, cfg: Config, ws, top, train, stash, seed, ce):
     """AttnPool + head (+ loss) of both engines: one fused launch, a workgroup per clip; ``ce`` as ``forward`` takes it."""
     p_drop = cfg.head_dropout if train else 0.0
-    y_ptr, ls, denom, loss_ptr, correct_ptr, cw_ptr, den_ptr = (tuple(ce) + (None, None))[:7] if ce is not None else (None, 0.0, 1.0, None, None, None, None)
-    # (class weights: the same launch with the weights and the device-side normaliser in place of the host denom)
-    name, ce_norm = ("ss_tail_fwd_w", (cw_ptr, den_ptr)) if cw_ptr else ("ss_tail_fwd", (denom,))
+    y_ptr, ls, denom, loss_ptr, correct_ptr, cw_ptr, den_ptr, yb_ptr, lam_ptr = (
+        (tuple(ce) + (None,) * 4)[:9] if ce is not None else (None, 0.0, 1.0, None, None, None, None, None, None))
+    # (class weights: the same launch with the weights and the device-side normaliser in place of the host denom; mixup: the
+    # two-label loss, which takes the partners' labels and the device-side factor and serves both normalisers)
+    if yb_ptr:
+        name, y_mix, ce_norm = "ss_tail_fwd_mix", (yb_ptr, lam_ptr), (denom, cw_ptr, den_ptr)
+    else:
+        name, y_mix, ce_norm = ("ss_tail_fwd_w", (), (cw_ptr, den_ptr)) if cw_ptr else ("ss_tail_fwd", (), (denom,))
     L.call(name, top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
            P["pool.score.bias"].data_ptr(), P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(),
            P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(), P["head.4.weight"].data_ptr(),
-           P["head.4.bias"].data_ptr(), y_ptr, ws.B, ws.T, 2 * cfg.hidden, cfg.head_mid, cfg.num_classes, cfg.ln_eps, p_drop, seed,
+           P["head.4.bias"].data_ptr(), y_ptr, *y_mix, ws.B, ws.T, 2 * cfg.hidden, cfg.head_mid, cfg.num_classes, cfg.ln_eps, p_drop, seed,
            7 << 40, ls, *ce_norm, ws.attn.data_ptr() if stash else None, ws.xhat.data_ptr() if stash else None,
            ws.rstd.data_ptr() if stash else None, ws.ln.data_ptr() if stash else None,
            ws.mid.data_ptr() if stash else None, ws.mid_drop.data_ptr() if stash else None, ws.logits.data_ptr(),
@@ -397,7 +402,8 @@ def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Ten
     Workspace built with train=True).  ``ce = (y_ptr, label_smoothing, denom, loss_ptr, correct_ptr)`` makes the
     fused tail kernel also evaluate the loss and leave d(loss)/d(logits) in ``ws.d_logits``; two more entries,
     ``(..., class_weights_ptr, den_ptr)``, make it the class-weighted loss divided by the device float ``*den_ptr``
-    (``ss_tail_fwd_w``; ``denom`` is then unused)."""
+    (``ss_tail_fwd_w``; ``denom`` is then unused); two more again, ``(..., y_b_ptr, lam_ptr)`` -- the class-weight pair ``None, None``
+    without weights -- make it the two-label loss of a mixup batch (``ss_tail_fwd_mix``)."""
     if ws.bf16:
         from . import engine_bf16
 

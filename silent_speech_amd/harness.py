@@ -35,7 +35,7 @@ import torch
 
 from .checkpoint import (TRAIN_STATE_FORMAT, fingerprint_difference, load_train_state, save_checkpoint,
                          save_train_state)
-from .device_data import MASK_FIELDS, AugmentPolicy, DeviceClipStore
+from .device_data import MASK_FIELDS, MIXUP_FIELDS, AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier
 from .train import Trainer, check_class_weights, shard_range
 
@@ -298,7 +298,8 @@ def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_
     resumed only by a call whose fingerprint equals the saved one.  ``epochs`` and ``patience`` are not part of it: a run may be
     resumed to train longer.  ``init_from`` (the sha256 of the checkpoint file the run started from, a hex string) and
     ``freeze_cnn`` are entries only when they are set: the fingerprint of a run without them is what it always was.  The same holds
-    for the policy's mask fields (``AugmentPolicy.mask_fields``): each is an entry only where it differs from its default."""
+    for the policy's mask fields (``AugmentPolicy.mask_fields``): each is an entry only where it differs from its default; and for
+    its two mixup fields (``AugmentPolicy.mixup_fields``), which are entries only when mixup is on."""
     extra = {}
     if init_from is not None:
         extra["init_from"] = str(init_from)
@@ -309,7 +310,7 @@ def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_
                 n_val=int(n_val), class_weights=None if class_weights is None else [float(w) for w in class_weights],
                 augment_policy=None if augment_policy is None else {
                     **{k: (list(v) if isinstance(v, tuple) else v) for k, v in dataclasses.asdict(augment_policy).items()
-                       if k not in MASK_FIELDS}, **augment_policy.mask_fields()},
+                       if k not in MASK_FIELDS + MIXUP_FIELDS}, **augment_policy.mask_fields(), **augment_policy.mixup_fields()},
                 ema_decay=None if ema_decay is None else float(ema_decay), **extra)
 
 
@@ -374,6 +375,11 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
 
     ``augment_policy``: an ``AugmentPolicy`` for the training batches (time warp, scale jitter, ROI shift, and the masks: time
     mask, feature band, ROI cutout; all planned on the device); needs ``plan="device"``.  Validation batches are never augmented.  None: the reference's two augmentations only.
+    With ``mixup_prob`` > 0 every training batch is planned with mixup (``store.mix`` goes to ``Trainer.step(mix=)``; the logged train
+    accuracy counts ``argmax == y``, the rows' own labels, as inactive/train_reduced.py logs it) and validation is never mixed.  The
+    plan is a pure function of (seed, the batch's first row), so a resumed run draws the partners and factors of the uninterrupted
+    one.  Mixup with ``world_size`` > 1 or a ``process_group`` is a ``ValueError``: a row's partner may lie in another rank's shard,
+    and exchanging partners across ranks is a later piece of work.  So is mixup with ``freeze_cnn`` (embedded batches are not mixed).
 
     ``ema_decay`` (``d`` in [0, 1); the reference has no averaged model): ``Trainer(ema_decay=d)`` keeps an exponential moving
     average of the weights inside the Adam launch.  Every epoch's validation, under both plans, runs on the AVERAGED weights
@@ -421,6 +427,13 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
             raise TypeError("augment_policy must be an AugmentPolicy")
         if plan != "device":
             raise ValueError("augment_policy needs plan='device': the policy is drawn by the planning kernel")
+        if augment_policy.mixup_on:
+            if world_size > 1 or process_group is not None:
+                raise ValueError("mixup_prob > 0 does not combine with data-parallel fit: a row's partner may lie in another rank's shard")
+            if freeze_cnn:
+                raise ValueError("mixup_prob > 0 does not combine with freeze_cnn: embedded batches are not mixed")
+            if batch_size > 1024:
+                raise ValueError("mixup_prob > 0 plans batches of at most 1024 clips")
     if world_size < 1 or not 0 <= rank < world_size:
         raise ValueError(f"rank {rank} is outside world_size {world_size}")
     parallel = world_size > 1 or process_group is not None
@@ -500,6 +513,7 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     if freeze_cnn:  # (behind the load, the broadcast and a resume: the CNN is final now, and the same on every rank)
         train_store.embed(model)
         val_store.embed(model)
+    mixup = augment_policy is not None and augment_policy.mixup_on
     for ep in range(first_epoch, epochs + 1):
         epoch_base = (ep - 1) * len(train_store)
         if plan == "device":
@@ -524,7 +538,8 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                 if freeze_cnn:  # (X is Z: the rows features | embedding)
                     loss, correct = trainer.step_embedded(X, T, y, global_batch=global_batch, y_global=y_glob)
                 else:
-                    loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch, y_global=y_glob)
+                    mix = train_store.mix[:2] if mixup and hi > lo else None
+                    loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch, y_global=y_glob, mix=mix)
                 tr_loss += loss * global_batch
                 tr_ok += correct
             with averaged():

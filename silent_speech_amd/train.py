@@ -147,6 +147,8 @@ class Trainer:
         self.cw = None if cw is None else torch.from_numpy(cw).to(dev)
         self.den = None if cw is None else torch.zeros(1, device=dev, dtype=torch.float32)
         self.freeze_cnn = bool(freeze_cnn)
+        self._ce_mix = ()  # step(mix=): the partners' labels and the factor, as engine.tail_fwd takes them
+        self._mix_keep = None  # (the two tensors behind those pointers, held until the next step)
         # the optimiser's range of the flat bucket is [n_frozen, n): everything, or everything behind the ROI CNN
         self.n_frozen = model.cnn_param_range() if freeze_cnn else 0
         self.step_count = 0
@@ -185,7 +187,7 @@ class Trainer:
         self._bucket_version = model._bucket_version
 
     def step(self, X: torch.Tensor, lengths: torch.Tensor, R: Optional[torch.Tensor], y: torch.Tensor,
-             global_batch: Optional[int] = None, y_global: Optional[torch.Tensor] = None):
+             global_batch: Optional[int] = None, y_global: Optional[torch.Tensor] = None, mix=None):
         """One optimiser step on this rank's shard.  Returns (loss, correct) device tensors:
         loss = this shard's contribution to the global mean loss (sum over ranks = global loss).
         ``global_batch`` = clips of ALL ranks in this step; needed only when the shards are unequal (``shard_range``
@@ -197,10 +199,15 @@ class Trainer:
         ``y_global`` (class weights only): the int64 device labels of ALL ranks' clips of this step, in any one order that is the
         same on every rank; default ``y``, which is right for one process.  The loss is divided by the sum of w[label] over them
         instead of ``global_batch`` -- taken by one fixed-order launch, so every rank divides by the same bits -- and the returned
-        loss is this rank's part of the global weighted mean.  Every micro-batch uses the same sum."""
+        loss is this rank's part of the global weighted mean.  Every micro-batch uses the same sum.
+        ``mix`` = ``(y_b, lam)`` (a mixup batch: ``DeviceClipStore.mix[:2]``): the partners' labels (B,) int64 and the batch's factor
+        (1,) f32, both on the device.  The loss is ``lam * CE(y) + (1 - lam) * CE(y_b)`` (``ss_tail_fwd_mix``), with class weights
+        both terms over the one normaliser of ``y`` (``y_b`` is a permutation of it); ``correct`` counts ``argmax == y``.  Not with
+        ``micro_batches`` > 1 (``ValueError``)."""
         model, cfg = self.model, self.model.cfg
         if self.freeze_cnn:
             raise RuntimeError("Trainer.step on a freeze_cnn trainer: it would train the ROI CNN (use step_embedded)")
+        self._ce_mix = self._check_mix(mix, X.shape[0], y)
         if self._ema_swapped:
             raise RuntimeError("Trainer.step inside ema_weights(): the parameters are the averaged ones there")
         if model._bucket_version != self._bucket_version:
@@ -261,6 +268,24 @@ class Trainer:
         self._reduce_clip_adam()
         return self.scal[0], self.correct[0]
 
+    def _check_mix(self, mix, B, y):
+        """``step(mix=)`` -> the two pointers ``engine.tail_fwd`` takes behind the class-weight pair (``()`` without mixup)."""
+        self._mix_keep = None
+        if mix is None:
+            return ()
+        if self.micro_batches > 1:
+            raise ValueError("Trainer.step(mix=) does not combine with micro_batches > 1")
+        y_b, lam = mix
+        if not (isinstance(y_b, torch.Tensor) and y_b.is_cuda and y_b.dtype == torch.int64 and y_b.is_contiguous()
+                and y_b.shape == (B,)):
+            raise ValueError("mix[0] must be a contiguous int64 device tensor of one partner label per clip")
+        if not (isinstance(lam, torch.Tensor) and lam.is_cuda and lam.dtype == torch.float32 and lam.numel() == 1):
+            raise ValueError("mix[1] must be a float32 device tensor of one element")
+        if y.dtype != torch.int64:
+            raise ValueError("Trainer.step(mix=) needs int64 labels")
+        self._mix_keep = (y_b, lam)
+        return (y_b.data_ptr(), lam.data_ptr())
+
     def _weight_sum(self, B, y, y_global):
         """Class weights: the step's normaliser, sum of w[label] over the global batch, by one launch; sets ``self._ce_w``."""
         ce_w = (None, None)
@@ -303,12 +328,14 @@ class Trainer:
                    ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup), s)
 
     def step_embedded(self, Z: torch.Tensor, lengths: torch.Tensor, y: torch.Tensor, global_batch: Optional[int] = None,
-                      y_global: Optional[torch.Tensor] = None):
+                      y_global: Optional[torch.Tensor] = None, mix=None):
         """``step`` of a ``freeze_cnn`` trainer: ``Z`` (B, T, x_dim + roi_emb) f32 on the device already holds
         torch.cat((features, ROI embeddings)) (``store.batch(embedded=True)``).  Same returns, ``global_batch``, ``y_global`` and
         empty-shard rule as ``step``; the dropout seeds are the same function of the step count, so with embeddings of the
         current CNN it is the step ``step`` takes, minus everything that belongs to the CNN (class docstring)."""
         model, cfg = self.model, self.model.cfg
+        if mix is not None:
+            raise ValueError("Trainer.step_embedded(mix=): mixup of embedded batches is not built")
         if not self.freeze_cnn:
             raise RuntimeError("Trainer.step_embedded needs Trainer(freeze_cnn=True): this trainer updates the ROI CNN")
         if self._ema_swapped:
@@ -420,7 +447,7 @@ class Trainer:
             if not prologue_done:
                 ws.lengths.copy_(lengths.to(torch.int32), non_blocking=True)
             E.forward(P, cfg, ws, X, R, train=train, stash=True, seed=seed, x_in_place=prologue_done,
-                      ce=(y.data_ptr(), self.ls, denom, self.scal.data_ptr(), self.correct.data_ptr()) + self._ce_w)
+                      ce=(y.data_ptr(), self.ls, denom, self.scal.data_ptr(), self.correct.data_ptr()) + self._ce_w + self._ce_mix)
         if phase in ("bwd", "both"):
             E.backward(P, self.G, cfg, ws, X, R, ws.d_logits, train=train, seed=seed)
 

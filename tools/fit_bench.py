@@ -1,7 +1,7 @@
 """What the training loop of ``harness.fit`` costs around the step: batches planned on the host (``rng="device"``) against
 batches planned by the kernel (``rng="philox"``), with ``Trainer.step`` on a resident batch as the yardstick.
 
-    python tools/fit_bench.py [--steps 200] [--windows 5] [--warmup 20]
+    python tools/fit_bench.py [--steps 200] [--windows 5] [--warmup 20] [--mixup]
 
 One JSON line.  Per shape (config 2: B=256, T=30, D=84, 64x64 ROI; shipped: B=16, T=90, D=180, 48x96 ROI):
   clips_per_s.{resident, host_plan, device_plan, device_plan_policy, device_plan_policy_masks}
@@ -15,6 +15,12 @@ One JSON line.  Per shape (config 2: B=256, T=30, D=84, 64x64 ROI; shipped: B=16
                                                   (max - min) / median beside it: the yardstick is this run's device_plan loop
   masks_of_policy                                 median device_plan_policy_masks / median device_plan_policy of this run, and
                                                   device_plan_policy's own (max - min) / median beside it
+  clips_per_s.device_plan_policy_mixup, mixup_of_policy, mixup_blend
+                                                  (--mixup) one more loop in the same alternation: device_plan_policy's policy with
+                                                  ``mixup_prob=1.0`` and ``Trainer.step(mix=store.mix[:2])``; its median over
+                                                  device_plan_policy's of this run with that loop's spread beside it; and what the
+                                                  blend launch moves -- two reads and one write of X and R -- over its kernels_ms, in
+                                                  bytes per second
   clips_per_s.resident_weighted, class_weight_us  (--class-weights) the resident loop through ``Trainer(class_weights=)``, a fourth loop
                                                   in the same alternation, and what its step costs more than the unweighted one
                                                   (the one ``ss_class_weight_sum`` launch): median over the windows of the difference
@@ -91,7 +97,7 @@ def time_validation(model, B, T, D, roi, C, n_clips, windows, dev):
     return {"clips": n_clips, "batches": -(-n_clips // B), **{k: summary(v, 3) for k, v in ms.items()}}
 
 
-def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, class_weights=False):
+def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, class_weights=False, mixup=False):
     store = make_store(T, D, roi, C, dev)
     model = ss.BiGRUClassifier(D, C, use_roi=True, roi_emb=32, hidden=192).to(dev).train()
     trainer = ss.Trainer(model)
@@ -123,6 +129,12 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         row[0] += B
         return store.batch(dev_order[i * B:(i + 1) * B], augment=True, rng="philox", seed=SEED, first_row=row[0], policy=masks)
 
+    mixed = ss.AugmentPolicy.lineage(roi_shift_prob=0.5, roi_shift_max=(4, 2), mixup_prob=1.0)
+
+    def mixup_batch(i):
+        row[0] += B
+        return store.batch(dev_order[i * B:(i + 1) * B], augment=True, rng="philox", seed=SEED, first_row=row[0], policy=mixed)
+
     def window(make_batch, step, n):
         tr = weighted if step == "weighted" else trainer
         torch.cuda.synchronize()
@@ -130,7 +142,7 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         for i in range(n):
             Xb, Tb, Rb, yb = make_batch(i % steps) if make_batch else resident
             if step:
-                tr.step(Xb, Tb, Rb, yb)
+                tr.step(Xb, Tb, Rb, yb, mix=store.mix[:2] if make_batch is mixup_batch else None)
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
@@ -140,6 +152,9 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
         loops = {"resident": (None, True), "resident_weighted": (None, "weighted"), **loops}
     asm = {"host_plan": (host_batch, False), "device_plan": (dev_batch, False), "device_plan_policy": (policy_batch, False),
            "device_plan_policy_masks": (masks_batch, False)}
+    if mixup:
+        loops["device_plan_policy_mixup"] = (mixup_batch, True)
+        asm["device_plan_policy_mixup"] = (mixup_batch, False)
     for mk, st in list(loops.values()) + list(asm.values()):  # every shape and code path of the timed windows, warmed up
         window(mk, st, warmup)
     rate = {k: [] for k in loops}
@@ -173,6 +188,13 @@ def run_shape(name, B, T, D, roi, C, steps, windows, warmup, dev, eval_clips=0, 
     extra = {} if not (eval_clips and name == "config2") else {"validation_ms": time_validation(model, B, T, D, roi, C, eval_clips, windows, dev)}
     if weighted is not None:
         extra["class_weight_us"] = summary(extra_us, 2)
+    if mixup:
+        moved = 3 * B * store.max_t * (4 * D + roi[0] * roi[1])
+        blend_ms = kern["device_plan_policy_mixup"]["ss_batch_mixup"]
+        extra["mixup_of_policy"] = {"ratio": round(med["device_plan_policy_mixup"] / med["device_plan_policy"], 4),
+                                    "device_plan_policy_spread": round((max(rate["device_plan_policy"]) - min(rate["device_plan_policy"]))
+                                                                       / med["device_plan_policy"], 4)}
+        extra["mixup_blend"] = {"bytes": moved, "ms": blend_ms, "bytes_per_s": round(moved / (1e-3 * blend_ms), 0)}
     return {**extra, "shape": dict(B=B, T=T, D=D, roi="%dx%d" % tuple(roi), classes=C),
             "clips_per_s": {k: summary(v) for k, v in rate.items()},
             "of_resident": {k: round(med[k] / med["resident"], 4) for k in ("host_plan", "device_plan", "device_plan_policy",
@@ -193,6 +215,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shapes", default="config2,shipped")
     ap.add_argument("--class-weights", action="store_true", help="also time the resident loop with class weights")
+    ap.add_argument("--mixup", action="store_true", help="also time the device-planned policy loop with mixup on")
     ap.add_argument("--eval-clips", type=int, default=1024, help="clips of the timed validation pass (config2; 0 = skip)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -202,6 +225,7 @@ def main():
            "steps_per_window": args.steps, "windows": args.windows, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
     for name in args.shapes.split(","):
         out[name] = run_shape(name, steps=args.steps, windows=args.windows, warmup=args.warmup, dev=dev, eval_clips=args.eval_clips, class_weights=args.class_weights,
+                              mixup=args.mixup,
                               **SHAPES[name])
     print(json.dumps(out))
 
