@@ -1,36 +1,90 @@
 // CrossEntropyLoss(weight=, label_smoothing=) of ONE logit row (train_model_official.py:405 and the class-weighted form of
 // :406-414): the loss, d(loss)/d(logits) and the arg-max, shared by ce_ls_kernel (pool_head.hip), eval_accum_kernel (eval.hip)
-// and the CE block of tail_fwd_kernel (tail.hip) and by their class-weighted entry points.
+// and the CE block of tail_fwd_kernel (tail.hip) and by their class-weighted and mixup entry points.
 //
 // Row with label y, log-softmax lp, p = exp(lp), smoothing eps, C classes, class weights w:
-//   loss      = (1 - eps) * (-w[y] * lp[y]) + (eps / C) * (-sum_c w[c] * lp[c])                      (un-normalised)
-//   d logit_c = [ p_c * A - ((c == y) * (1 - eps) * w[y] + (eps / C) * w[c]) ] / denom,  A = w[y] + eps * (sum_k w[k] / C - w[y])
+//   loss      = (1 - eps) * (-w[y] * lp[y]) + (eps / C) * (-sum_c w[c] * lp[c])                      (un-normalised)   ce_label_loss
+//   d logit_c = [ p_c * A - tgt_c ] / denom,  tgt_c = (c == y) * (1 - eps) * w[y] + (eps / C) * w[c]                   ce_tgt
+//               A = w[y] + eps * (sum_k w[k] / C - w[y])                                                               ce_a
 // (A is (1 - eps) * w[y] + (eps / C) * sum_k w[k], written so that w == 1 gives exactly 1).
+// Each of the three is written once, below, as a function of one label; the row functions call it for y and, under MIX, for yb.
 //
 // WEIGHTED = false is the arithmetic the three kernels have always done -- the same operations in the same order, so their
-// results keep their bits -- and never touches w.  WEIGHTED = true with every w[c] == 1.0f gives the same bits again: each
-// weight enters as a factor of a product whose other factor is the unweighted term (x * 1 and fma(x, 1, s) round like x and
-// s + x), sum_k w[k] = C exactly, A = 1 exactly.
+// results keep their bits -- and never touches w (A is the constant 1).  WEIGHTED = true with every w[c] == 1.0f gives the same
+// bits again: each weight enters as a factor of a product whose other factor is the unweighted term (x * 1 and fma(x, 1, s)
+// round like x and s + x), sum_k w[k] = C exactly, A = 1 exactly.
 //
 // MIX = true is the two-label loss of a mixup batch (ss_ce_ls_mix_fwd_bwd, ss_tail_fwd_mix): labels y and yb, one factor lam,
 //   loss      = lam * loss(y) + (1 - lam) * loss(yb),
 //   d logit_c = [ p_c * A_mix - tgt_mix_c ] / denom,  tgt_mix = lam * tgt(y) + (1 - lam) * tgt(yb),  A_mix the same blend of the As
-// (unweighted: A = 1 for both labels, so A_mix = 1 and never enters).  The formulas above still exist once: MIX adds the second
-// label's terms and the blend behind them.  MIX = false (the default) is every operation the row has always had, in its order;
-// MIX = true with lam == 1 gives those bits again (1 * x + 0 * z is x, fused or not, for finite z).
+// (unweighted: A = 1 for both labels, so A_mix = 1 and is not blended).  MIX = false is every operation the row has always had, in
+// its order; MIX = true with lam == 1 gives those bits again (1 * x + 0 * z is x, fused or not, for finite z).
 //
 // Two forms, because the callers spread a row differently: ce_row (one thread walks the row) and ce_row_wave (the 64 lanes of a
 // wave share it, classes lane, lane + 64, ...).  They differ in the order of their C-term sums, as the kernels always have.
+//
+// A launch's loss is one CeLoss, what it means for row b one CeRow (ce_row_of); ce_dispatch picks <WEIGHTED, MIX> on the host.
 #pragma once
+#include <type_traits>
+
 #include "ss_common.h"
 
-// One thread per row.  lr = the row's C logits, 0 <= yy < C (the caller checks).  d_row (may be NULL) gets the gradient row
-// divided by denom; *am_out the lowest index among the equal maxima (torch.argmax).  Returns the row's loss, not divided.
-// MIX: 0 <= yb < C too, and lam in [0, 1]; without MIX neither is read.
+// The loss of a launch.  cw / den (both or neither): class weights, and the device float *den divides instead of `denom`;
+// y_b / lam (both or neither): the two-label loss, the factor read from the device.  y == NULL: no loss (tail).
+struct CeLoss { const int64_t *y, *y_b; const float *lam, *cw, *den; float denom, ls; };
+// Row b of a CeLoss: does it count, its labels as indices, the mixing factor and the normaliser.
+struct CeRow { bool counts; int yy, yb; float lam, denom; };
+
+__device__ __forceinline__ bool ce_label_ok(int64_t label, int C) { return label >= 0 && label < (int64_t)C; }
+
+template <bool WEIGHTED>
+__device__ __forceinline__ float ce_denom(const CeLoss& l) { if constexpr (WEIGHTED) return l.den[0]; else return l.denom; }
+
+// THE label rule.  plain (neither weights nor mixup): the label is not looked at -- the caller vouches for 0 <= y < C, as it
+// always has;  WEIGHTED: the row counts iff 0 <= y < C;  MIX (weighted or not): iff 0 <= y < C and 0 <= y_b < C.
+// A row that does not count gets a zero gradient row and adds nothing to the loss or the hit count (its labels come back as 0:
+// not to be used).  `denom` = ce_denom of the loss: *den with weights, its `denom` without; lam is *lam under MIX, 1 otherwise.
+// (eval_accum_kernel applies ce_label_ok to every row, weighted or not, and raises its flag: it has no caller to vouch.)
+template <bool WEIGHTED, bool MIX>
+__device__ __forceinline__ CeRow ce_row_of(const int64_t* __restrict__ y, const int64_t* __restrict__ y_b,
+                                           const float* __restrict__ lam, float denom, int b, int C) {
+  CeRow r = {true, 0, 0, 1.0f, denom};
+  if constexpr (MIX) {
+    r.counts = ce_label_ok(y[b], C) && ce_label_ok(y_b[b], C);
+    r.yb = r.counts ? (int)y_b[b] : 0;
+    r.lam = lam[0];
+  } else if constexpr (WEIGHTED) {
+    r.counts = ce_label_ok(y[b], C);
+  }
+  r.yy = r.counts ? (int)y[b] : 0;
+  return r;
+}
+
+// ---- the three formulas, each for ONE label `l` with weight wl = w[l] (unweighted: w is not read, wl is ignored);
+// lse - logit_l = -lp[l], slp = sum_c w[c] * lp[c], sw = sum_k w[k]
+template <bool WEIGHTED>
+__device__ __forceinline__ float ce_tgt(int c, int l, float wl, const float* __restrict__ w, float eps, int C) {
+  if constexpr (WEIGHTED) return (c == l ? (1.0f - eps) * wl : 0.f) + (eps / C) * w[c];
+  else return (c == l ? (1.0f - eps) : 0.f) + eps / C;
+}
+template <bool WEIGHTED>
+__device__ __forceinline__ float ce_label_loss(float lse, float logit_l, float wl, float slp, float eps, int C) {
+  if constexpr (WEIGHTED) return (1.0f - eps) * (wl * (lse - logit_l)) + eps * (-slp / C);
+  else return (1.0f - eps) * (lse - logit_l) + eps * (-slp / C);
+}
+template <bool WEIGHTED>
+__device__ __forceinline__ float ce_a(float wl, float sw, float eps, int C) {
+  if constexpr (WEIGHTED) return wl + eps * (sw / C - wl);
+  else return 1.0f;
+}
+
+// One thread per row.  lr = the row's C logits, r = ce_row_of a row that counts (without MIX r.yb and r.lam are not read).
+// d_row (may be NULL): the gradient row / r.denom; *am_out: the lowest index among equal maxima (torch.argmax).  Returns the loss, undivided.
 template <bool WEIGHTED, bool MIX = false>
-__device__ __forceinline__ float ce_row(const float* __restrict__ lr, int yy, int C, float eps, const float* __restrict__ w,
-                                        float denom, float* __restrict__ d_row, int* am_out, int yb = 0, float lam = 1.0f) {
-  const float oml = 1.0f - lam;  // (MIX only)
+__device__ __forceinline__ float ce_row(const float* __restrict__ lr, int C, float eps, const float* __restrict__ w,
+                                        const CeRow& r, float* __restrict__ d_row, int* am_out) {
+  const int yy = r.yy, yb = r.yb;
+  const float lam = r.lam, oml = 1.0f - r.lam;  // (MIX only)
   float m = lr[0];
   int am = 0;
   for (int c = 1; c < C; ++c)
@@ -38,57 +92,40 @@ __device__ __forceinline__ float ce_row(const float* __restrict__ lr, int yy, in
   float se = 0.f;
   for (int c = 0; c < C; ++c) se += expf(lr[c] - m);
   const float lse = m + logf(se);
-  float slp = 0.f, sw = 0.f, wy = 1.f, wyb = 1.f, loss;
+  float slp = 0.f, sw = 0.f, wy = 1.f, wyb = 1.f;
   if constexpr (WEIGHTED) {
     wy = w[yy];
     for (int c = 0; c < C; ++c) {
       slp += w[c] * (lr[c] - lse);
       sw += w[c];
     }
-    loss = (1.0f - eps) * (wy * (lse - lr[yy])) + eps * (-slp / C);
-    if constexpr (MIX) {
-      wyb = w[yb];
-      const float loss_b = (1.0f - eps) * (wyb * (lse - lr[yb])) + eps * (-slp / C);
-      loss = lam * loss + oml * loss_b;
-    }
   } else {
     for (int c = 0; c < C; ++c) slp += lr[c] - lse;
-    loss = (1.0f - eps) * (lse - lr[yy]) + eps * (-slp / C);
-    if constexpr (MIX) {
-      const float loss_b = (1.0f - eps) * (lse - lr[yb]) + eps * (-slp / C);
-      loss = lam * loss + oml * loss_b;
-    }
   }
+  if constexpr (WEIGHTED && MIX) wyb = w[yb];
+  float loss = ce_label_loss<WEIGHTED>(lse, lr[yy], wy, slp, eps, C);
+  if constexpr (MIX) loss = lam * loss + oml * ce_label_loss<WEIGHTED>(lse, lr[yb], wyb, slp, eps, C);
   if (d_row) {
-    if constexpr (WEIGHTED) {
-      float a = wy + eps * (sw / C - wy);
-      if constexpr (MIX) a = lam * a + oml * (wyb + eps * (sw / C - wyb));
-      for (int c = 0; c < C; ++c) {
-        float pr = expf(lr[c] - lse);
-        float tgt = (c == yy ? (1.0f - eps) * wy : 0.f) + (eps / C) * w[c];
-        if constexpr (MIX) tgt = lam * tgt + oml * ((c == yb ? (1.0f - eps) * wyb : 0.f) + (eps / C) * w[c]);
-        d_row[c] = (pr * a - tgt) / denom;
-      }
-    } else {
-      for (int c = 0; c < C; ++c) {
-        float pr = expf(lr[c] - lse);
-        float tgt = (c == yy ? (1.0f - eps) : 0.f) + eps / C;
-        if constexpr (MIX) tgt = lam * tgt + oml * ((c == yb ? (1.0f - eps) : 0.f) + eps / C);
-        d_row[c] = (pr - tgt) / denom;
-      }
+    float a = ce_a<WEIGHTED>(wy, sw, eps, C);
+    if constexpr (WEIGHTED && MIX) a = lam * a + oml * ce_a<WEIGHTED>(wyb, sw, eps, C);
+    for (int c = 0; c < C; ++c) {
+      const float pr = expf(lr[c] - lse);
+      float tgt = ce_tgt<WEIGHTED>(c, yy, wy, w, eps, C);
+      if constexpr (MIX) tgt = lam * tgt + oml * ce_tgt<WEIGHTED>(c, yb, wyb, w, eps, C);
+      d_row[c] = (pr * a - tgt) / r.denom;
     }
   }
   *am_out = am;
   return loss;
 }
 
-// One wave per row; every lane of the wave calls it.  lg = the row's C logits (LDS or global), lane = 0..63.  d_row (not NULL)
-// gets the gradient row divided by denom.  Returns the row's loss, not divided, and leaves the arg-max in *am_out (both in
-// every lane).  MIX as in ce_row.
+// One wave per row; every lane of the wave calls it.  lg = the row's C logits (LDS or global), lane = 0..63, r as in ce_row.
+// d_row (not NULL) gets the gradient row / r.denom.  Returns the row's loss, not divided, and the arg-max in *am_out (every lane).
 template <bool WEIGHTED, bool MIX = false>
-__device__ __forceinline__ float ce_row_wave(const float* lg, int yy, int C, int lane, float eps, const float* __restrict__ w,
-                                             float denom, float* __restrict__ d_row, int* am_out, int yb = 0, float lam = 1.0f) {
-  const float oml = 1.0f - lam;  // (MIX only)
+__device__ __forceinline__ float ce_row_wave(const float* lg, int C, int lane, float eps, const float* __restrict__ w,
+                                             const CeRow& r, float* __restrict__ d_row, int* am_out) {
+  const int yy = r.yy, yb = r.yb;
+  const float lam = r.lam, oml = 1.0f - r.lam;  // (MIX only)
   float mx = -3.4e38f;
   int am = 0;
   for (int c = lane; c < C; c += 64)
@@ -100,52 +137,43 @@ __device__ __forceinline__ float ce_row_wave(const float* lg, int yy, int C, int
     const int oa = __shfl_xor(am, o, 64);
     if (om > mx || (om == mx && oa < am)) { mx = om; am = oa; }
   }
-  float se = 0.f, sl = 0.f;
+  float se = 0.f, sl = 0.f, sw = 0.f, wy = 1.f, wyb = 1.f;
   for (int c = lane; c < C; c += 64) se += expf(lg[c] - mx);
   se = wave_sum(se);
   const float lse = mx + logf(se);
-  float loss;
   if constexpr (WEIGHTED) {
-    float sw = 0.f;
     for (int c = lane; c < C; c += 64) {
       sl += w[c] * (lg[c] - lse);
       sw += w[c];
     }
     sl = wave_sum(sl);
     sw = wave_sum(sw);
-    const float wy = w[yy];
-    float wyb = 1.f;
-    float a = wy + eps * (sw / C - wy);
-    if constexpr (MIX) {
-      wyb = w[yb];
-      a = lam * a + oml * (wyb + eps * (sw / C - wyb));
-    }
-    for (int c = lane; c < C; c += 64) {
-      const float pr = expf(lg[c] - lse);
-      float tgt = (c == yy ? (1.0f - eps) * wy : 0.f) + (eps / C) * w[c];
-      if constexpr (MIX) tgt = lam * tgt + oml * ((c == yb ? (1.0f - eps) * wyb : 0.f) + (eps / C) * w[c]);
-      d_row[c] = (pr * a - tgt) / denom;
-    }
-    loss = (1.0f - eps) * (wy * (lse - lg[yy])) + eps * (-sl / C);
-    if constexpr (MIX) {
-      const float loss_b = (1.0f - eps) * (wyb * (lse - lg[yb])) + eps * (-sl / C);
-      loss = lam * loss + oml * loss_b;
-    }
+    wy = w[yy];
+    if constexpr (MIX) wyb = w[yb];
   } else {
     for (int c = lane; c < C; c += 64) sl += lg[c] - lse;
     sl = wave_sum(sl);
-    for (int c = lane; c < C; c += 64) {
-      const float pr = expf(lg[c] - lse);
-      float tgt = (c == yy ? (1.0f - eps) : 0.f) + eps / C;
-      if constexpr (MIX) tgt = lam * tgt + oml * ((c == yb ? (1.0f - eps) : 0.f) + eps / C);
-      d_row[c] = (pr - tgt) / denom;
-    }
-    loss = (1.0f - eps) * (lse - lg[yy]) + eps * (-sl / C);
-    if constexpr (MIX) {
-      const float loss_b = (1.0f - eps) * (lse - lg[yb]) + eps * (-sl / C);
-      loss = lam * loss + oml * loss_b;
-    }
   }
+  float a = ce_a<WEIGHTED>(wy, sw, eps, C);
+  if constexpr (WEIGHTED && MIX) a = lam * a + oml * ce_a<WEIGHTED>(wyb, sw, eps, C);
+  for (int c = lane; c < C; c += 64) {
+    const float pr = expf(lg[c] - lse);
+    float tgt = ce_tgt<WEIGHTED>(c, yy, wy, w, eps, C);
+    if constexpr (MIX) tgt = lam * tgt + oml * ce_tgt<WEIGHTED>(c, yb, wyb, w, eps, C);
+    d_row[c] = (pr * a - tgt) / r.denom;
+  }
+  float loss = ce_label_loss<WEIGHTED>(lse, lg[yy], wy, sl, eps, C);
+  if constexpr (MIX) loss = lam * loss + oml * ce_label_loss<WEIGHTED>(lse, lg[yb], wyb, sl, eps, C);
   *am_out = am;
   return loss;
+}
+
+// Host: f(std::bool_constant<WEIGHTED>, std::bool_constant<MIX>) for a loss with class weights (cw != NULL) and / or second
+// labels (y_b != NULL): the one if-ladder over the instantiations of the three kernels.
+template <class F>
+static inline void ce_dispatch(const void* cw, const void* y_b, F&& f) {
+  if (cw && y_b) f(std::true_type{}, std::true_type{});
+  else if (y_b) f(std::false_type{}, std::true_type{});
+  else if (cw) f(std::true_type{}, std::false_type{});
+  else f(std::false_type{}, std::false_type{});
 }

@@ -198,35 +198,26 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------- cross entropy
-// one thread per clip (C is a handful of words); the row arithmetic is ce_row (ce_row.h).  WEIGHTED: class weights w (C) and the
-// normaliser read from the device (*den = sum of w[y] over the normalising set, ss_class_weight_sum); a row whose label is
-// outside [0, C) is never an index there: zero gradient, nothing added.
-// MIX (ss_ce_ls_mix_fwd_bwd): the two-label loss of a mixup batch, second labels y_b and the factor *lam read from the device; a row
-// with either label outside [0, C) is such a row too, weighted or not.  Without MIX neither pointer is read.
-template <bool WEIGHTED, bool MIX = false>
+// one thread per clip (C is a handful of words); the row arithmetic is ce_row, the label rule ce_row_of (both ce_row.h).  The
+// launch's CeLoss arrives field by field: only a `const T* __restrict__` kernel ARGUMENT has its uniform reads (w[c] in the class
+// loops, lam[0]) done by scalar loads; as struct members they were vector loads and cost 1 to 3 VGPRs.
+template <bool WEIGHTED, bool MIX>
 __global__ __launch_bounds__(256) void ce_ls_kernel(const float* __restrict__ logits, const int64_t* __restrict__ y, int B,
                                                     int C, float eps, float denom, const float* __restrict__ w,
                                                     const float* __restrict__ den, float* __restrict__ d_logits,
                                                     float* __restrict__ loss_sum, int* __restrict__ correct,
-                                                    const int64_t* __restrict__ y_b = nullptr,
-                                                    const float* __restrict__ lam = nullptr) {
+                                                    const int64_t* __restrict__ y_b, const float* __restrict__ lam) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if constexpr (WEIGHTED) denom = den[0];
   float loss = 0.f;
   int ok = 0;
   if (b < B) {
     float* d_row = d_logits ? d_logits + (long)b * C : nullptr;
-    bool valid = true;
-    if constexpr (WEIGHTED) valid = y[b] >= 0 && y[b] < (int64_t)C;
-    if constexpr (MIX) valid = y[b] >= 0 && y[b] < (int64_t)C && y_b[b] >= 0 && y_b[b] < (int64_t)C;
-    if (valid) {
-      const int yy = (int)y[b];
+    const CeRow r = ce_row_of<WEIGHTED, MIX>(y, y_b, lam, denom, b, C);
+    if (r.counts) {
       int am;
-      if constexpr (MIX)
-        loss = ce_row<WEIGHTED, true>(logits + (long)b * C, yy, C, eps, w, denom, d_row, &am, (int)y_b[b], lam[0]);
-      else
-        loss = ce_row<WEIGHTED>(logits + (long)b * C, yy, C, eps, w, denom, d_row, &am);
-      ok = (am == yy);
+      loss = ce_row<WEIGHTED, MIX>(logits + (long)b * C, C, eps, w, r, d_row, &am);
+      ok = (am == r.yy);
     } else if (d_row) {
       for (int c = 0; c < C; ++c) d_row[c] = 0.f;
     }
@@ -245,7 +236,7 @@ __global__ __launch_bounds__(256) void class_weight_sum_kernel(const int64_t* __
   float s = 0.f;
   for (long i = threadIdx.x; i < n; i += 256) {
     const int64_t label = y[i];
-    if (label >= 0 && label < (int64_t)C) s += w[label];
+    if (ce_label_ok(label, C)) s += w[label];
   }
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -348,36 +339,40 @@ extern "C" int ss_dropout(const float* x, float* y, long n, float p, uint64_t se
   return ss_launch_status();
 }
 
+// the three CE entry points: what they all check, and the launch (which unpacks the loss: see ce_ls_kernel)
+static int ce_ls_launch(const float* logits, int B, int C, const CeLoss& ce, float* d_logits, float* loss_sum, int32_t* correct,
+                        ss_stream_t stream) {
+  SS_REQUIRE(logits && ce.y && B > 0 && C > 0, SS_ERR_ARG);
+  ce_dispatch(ce.cw, ce.y_b, [&](auto w, auto m) {
+    hipLaunchKernelGGL((ce_ls_kernel<decltype(w)::value, decltype(m)::value>), dim3(ceil_div(B, 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), logits, ce.y, B, C, ce.ls, ce.denom, ce.cw, ce.den, d_logits, loss_sum, correct,
+                       ce.y_b, ce.lam);
+  });
+  return ss_launch_status();
+}
+
 extern "C" int ss_ce_ls_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float label_smoothing,
                                 float denom, float* d_logits, float* loss_sum, int32_t* correct,
                                 ss_stream_t stream) {
-  SS_REQUIRE(logits && y && B > 0 && C > 0 && denom > 0.f, SS_ERR_ARG);
-  hipLaunchKernelGGL(ce_ls_kernel<false>, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, y,
-                     B, C, label_smoothing, denom, nullptr, nullptr, d_logits, loss_sum, correct, nullptr, nullptr);
-  return ss_launch_status();
+  SS_REQUIRE(denom > 0.f, SS_ERR_ARG);
+  return ce_ls_launch(logits, B, C, CeLoss{y, nullptr, nullptr, nullptr, nullptr, denom, label_smoothing}, d_logits, loss_sum,
+                      correct, stream);
 }
 
 extern "C" int ss_ce_ls_w_fwd_bwd(const float* logits, const int64_t* y, int B, int C, float label_smoothing,
                                   const float* w, const float* den, float* d_logits, float* loss_sum, int32_t* correct,
                                   ss_stream_t stream) {
-  SS_REQUIRE(logits && y && w && den && B > 0 && C > 0, SS_ERR_ARG);
-  hipLaunchKernelGGL(ce_ls_kernel<true>, dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits, y,
-                     B, C, label_smoothing, 1.0f, w, den, d_logits, loss_sum, correct, nullptr, nullptr);
-  return ss_launch_status();
+  SS_REQUIRE(w && den, SS_ERR_ARG);
+  return ce_ls_launch(logits, B, C, CeLoss{y, nullptr, nullptr, w, den, 1.0f, label_smoothing}, d_logits, loss_sum, correct,
+                      stream);
 }
 
 extern "C" int ss_ce_ls_mix_fwd_bwd(const float* logits, const int64_t* y, const int64_t* y_b, const float* lam, int B, int C,
                                     float label_smoothing, float denom, const float* w, const float* den, float* d_logits,
                                     float* loss_sum, int32_t* correct, ss_stream_t stream) {
-  SS_REQUIRE(logits && y && y_b && lam && B > 0 && C > 0, SS_ERR_ARG);
-  SS_REQUIRE((w == nullptr) == (den == nullptr) && (w || denom > 0.f), SS_ERR_ARG);
-  if (w)
-    hipLaunchKernelGGL((ce_ls_kernel<true, true>), dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
-                       y, B, C, label_smoothing, 1.0f, w, den, d_logits, loss_sum, correct, y_b, lam);
-  else
-    hipLaunchKernelGGL((ce_ls_kernel<false, true>), dim3(ceil_div(B, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
-                       y, B, C, label_smoothing, denom, nullptr, nullptr, d_logits, loss_sum, correct, y_b, lam);
-  return ss_launch_status();
+  SS_REQUIRE(y_b && lam && (w == nullptr) == (den == nullptr) && (w || denom > 0.f), SS_ERR_ARG);
+  return ce_ls_launch(logits, B, C, CeLoss{y, y_b, lam, w, den, w ? 1.0f : denom, label_smoothing}, d_logits, loss_sum, correct,
+                      stream);
 }
 
 extern "C" int ss_class_weight_sum(const int64_t* y, long n, const float* w, int C, float* out, ss_stream_t stream) {

@@ -37,38 +37,21 @@ __device__ __forceinline__ float block_sum(float v, float* red) {  // NWT waves;
 }
 
 struct TailFwdParams {
+  CeLoss ce;             // ce.y may be null: no loss.  (First: the kernel sits at its SGPR limit and where the loss lies among
+                         // the kernel arguments moves its scalar loads and spills; the timings of the layouts: DESIGN.md section 4.)
   const float* h;        // (B,T,D)
   const int* lengths;
   const float *w_score, *b_score, *gamma, *beta, *w1, *b1, *w4, *b4;
-  const int64_t* y;      // may be null: no loss
   int B, T, D, MID, C;
-  float eps, drop_p, ls, denom;
+  float eps, drop_p;
   uint64_t seed, offset;
   float *attn, *xhat, *rstd, *ln, *mid, *mid_d, *logits, *d_logits, *loss_sum;
   int* correct;
-  static constexpr bool weighted = false;
-  static constexpr bool mix = false;
 };
 
-// the class-weighted loss (ss_tail_fwd_w): class weights cw (C) and the normaliser on the device (*den) instead of `denom`
-struct TailFwdParamsW : TailFwdParams {
-  const float *cw, *den;
-  static constexpr bool weighted = true;
-};
-
-// the two-label loss of a mixup batch (ss_tail_fwd_mix), weighted (cw, den) or not (denom): second labels y_b and the factor *lam,
-// read from the device
-template <bool WEIGHTED>
-struct TailFwdParamsMix : TailFwdParamsW {
-  const int64_t* y_b;
-  const float* lam;
-  static constexpr bool weighted = WEIGHTED;
-  static constexpr bool mix = true;
-};
-
-// dynamic LDS: sc[T] | pooled[D] | lnv[D] | midv[MID] | lg[C]
-template <class Params>
-__global__ __launch_bounds__(TNT) void tail_fwd_kernel(Params p) {
+// dynamic LDS: sc[T] | pooled[D] | lnv[D] | midv[MID] | lg[C].  <WEIGHTED, MIX>: the loss of p.ce (ce_row.h), at compile time
+template <bool WEIGHTED, bool MIX>
+__global__ __launch_bounds__(TNT) void tail_fwd_kernel(TailFwdParams p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   __shared__ float red[2 * NWT];
   const int T = p.T, D = p.D, MID = p.MID, C = p.C;
@@ -230,33 +213,18 @@ __global__ __launch_bounds__(TNT) void tail_fwd_kernel(Params p) {
       p.logits[(long)b * C + c] = v;
     }
   }
-  if (!p.y) return;
+  if (!p.ce.y) return;
   __syncthreads();
-  // ---- CrossEntropyLoss(label_smoothing), mean over `denom` clips; d(loss)/d(logits): ce_row_wave (ce_row.h)
+  // ---- CrossEntropyLoss(label_smoothing), mean over the normaliser of p.ce; d(loss)/d(logits): ce_row_wave (ce_row.h)
   if (wv == 0) {
     float* d_row = p.d_logits + (long)b * C;
-    float denom = p.denom;
-    const float* cw = nullptr;
-    bool valid = true;
-    if constexpr (Params::weighted) {
-      denom = p.den[0];
-      cw = p.cw;
-      valid = p.y[b] >= 0 && p.y[b] < (int64_t)C;  // a label outside the classes is never an index here: the row adds nothing
-    }
-    int yb = 0;
-    float lam = 1.0f;
-    if constexpr (Params::mix) {  // either label outside the classes: the row adds nothing, weighted or not
-      valid = p.y[b] >= 0 && p.y[b] < (int64_t)C && p.y_b[b] >= 0 && p.y_b[b] < (int64_t)C;
-      yb = valid ? (int)p.y_b[b] : 0;
-      lam = p.lam[0];
-    }
-    if (valid) {
-      const int yy = (int)p.y[b];
+    const CeRow r = ce_row_of<WEIGHTED, MIX>(p.ce.y, p.ce.y_b, p.ce.lam, ce_denom<WEIGHTED>(p.ce), b, C);
+    if (r.counts) {
       int am;
-      const float loss = ce_row_wave<Params::weighted, Params::mix>(lg, yy, C, lane, p.ls, cw, denom, d_row, &am, yb, lam);
+      const float loss = ce_row_wave<WEIGHTED, MIX>(lg, C, lane, p.ce.ls, p.ce.cw, r, d_row, &am);
       if (lane == 0) {
-        if (p.loss_sum) atomicAdd(p.loss_sum, loss / denom);
-        if (p.correct && am == yy) atomicAdd(p.correct, 1);
+        if (p.loss_sum) atomicAdd(p.loss_sum, loss / r.denom);
+        if (p.correct && am == r.yy) atomicAdd(p.correct, 1);
       }
     } else {
       for (int c = lane; c < C; c += 64) d_row[c] = 0.f;
@@ -365,41 +333,28 @@ __global__ __launch_bounds__(TNT) void tail_bwd_kernel(TailBwdParams p) {
 
 }  // namespace
 
-// cw == NULL: the unweighted loss divided by `denom`; else the class-weighted one divided by *den.  y_b != NULL: the two-label
-// loss of a mixup batch (lam then too)
+// ce: the loss (ce_row.h); ce.y == NULL: none
 static int tail_fwd_launch(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
                            const float* gamma, const float* beta, const float* w1, const float* b1, const float* w4,
-                           const float* b4, const int64_t* y, int B, int T, int D, int MID, int C, float ln_eps,
-                           float drop_p, uint64_t seed, uint64_t offset, float label_smoothing, float denom,
-                           const float* cw, const float* den, float* attn, float* xhat, float* rstd, float* ln, float* mid,
-                           float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct,
-                           ss_stream_t stream, const int64_t* y_b = nullptr, const float* lam = nullptr) {
+                           const float* b4, const CeLoss& ce, int B, int T, int D, int MID, int C, float ln_eps, float drop_p,
+                           uint64_t seed, uint64_t offset, float* attn, float* xhat, float* rstd, float* ln, float* mid,
+                           float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream) {
   SS_REQUIRE(h && lengths && w_score && b_score && gamma && beta && w1 && b1 && w4 && b4 && logits, SS_ERR_ARG);
   SS_REQUIRE(B > 0 && T > 0 && D > 0 && MID > 0 && C > 0 && drop_p >= 0.f && drop_p < 1.f, SS_ERR_ARG);
-  SS_REQUIRE(!y || (d_logits && denom > 0.f), SS_ERR_ARG);
+  SS_REQUIRE(!ce.y || (d_logits && ce.denom > 0.f), SS_ERR_ARG);
   const size_t lds = (size_t)(T + 2 * D + MID + C) * sizeof(float);
   SS_REQUIRE(lds <= 60 * 1024, SS_ERR_UNSUPPORTED);
-  TailFwdParamsMix<true> p;
-  p.cw = cw; p.den = den; p.y_b = y_b; p.lam = lam;
+  TailFwdParams p;
   p.h = h; p.lengths = lengths; p.w_score = w_score; p.b_score = b_score; p.gamma = gamma; p.beta = beta;
-  p.w1 = w1; p.b1 = b1; p.w4 = w4; p.b4 = b4; p.y = y;
+  p.w1 = w1; p.b1 = b1; p.w4 = w4; p.b4 = b4; p.ce = ce;
   p.B = B; p.T = T; p.D = D; p.MID = MID; p.C = C;
-  p.eps = ln_eps; p.drop_p = drop_p; p.ls = label_smoothing; p.denom = denom; p.seed = seed; p.offset = offset;
+  p.eps = ln_eps; p.drop_p = drop_p; p.seed = seed; p.offset = offset;
   p.attn = attn; p.xhat = xhat; p.rstd = rstd; p.ln = ln; p.mid = mid; p.mid_d = mid_d; p.logits = logits;
   p.d_logits = d_logits; p.loss_sum = loss_sum; p.correct = correct;
-  if (y_b && cw) {
-    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParamsMix<true>>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream), p);
-  } else if (y_b) {
-    TailFwdParamsMix<false> q;
-    static_cast<TailFwdParamsW&>(q) = p;
-    q.y_b = y_b; q.lam = lam;
-    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParamsMix<false>>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream), q);
-  } else if (cw)
-    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParamsW>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream),
-                       static_cast<const TailFwdParamsW&>(p));
-  else
-    hipLaunchKernelGGL(tail_fwd_kernel<TailFwdParams>, dim3(B), dim3(TNT), lds, static_cast<hipStream_t>(stream),
-                       static_cast<const TailFwdParams&>(p));
+  ce_dispatch(ce.cw, ce.y_b, [&](auto w, auto m) {
+    hipLaunchKernelGGL((tail_fwd_kernel<decltype(w)::value, decltype(m)::value>), dim3(B), dim3(TNT), lds,
+                       static_cast<hipStream_t>(stream), p);
+  });
   return ss_launch_status();
 }
 
@@ -409,9 +364,9 @@ extern "C" int ss_tail_fwd(const float* h, const int32_t* lengths, const float* 
                            float drop_p, uint64_t seed, uint64_t offset, float label_smoothing, float denom,
                            float* attn, float* xhat, float* rstd, float* ln, float* mid, float* mid_d, float* logits,
                            float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream) {
-  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4, y, B, T, D, MID, C, ln_eps, drop_p, seed,
-                         offset, label_smoothing, denom, nullptr, nullptr, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits,
-                         loss_sum, correct, stream);
+  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4,
+                         CeLoss{y, nullptr, nullptr, nullptr, nullptr, denom, label_smoothing}, B, T, D, MID, C, ln_eps, drop_p,
+                         seed, offset, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits, loss_sum, correct, stream);
 }
 
 extern "C" int ss_tail_fwd_w(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
@@ -421,9 +376,9 @@ extern "C" int ss_tail_fwd_w(const float* h, const int32_t* lengths, const float
                              const float* den, float* attn, float* xhat, float* rstd, float* ln, float* mid, float* mid_d,
                              float* logits, float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream) {
   SS_REQUIRE(y && cw && den, SS_ERR_ARG);
-  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4, y, B, T, D, MID, C, ln_eps, drop_p, seed,
-                         offset, label_smoothing, 1.0f, cw, den, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits, loss_sum,
-                         correct, stream);
+  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4,
+                         CeLoss{y, nullptr, nullptr, cw, den, 1.0f, label_smoothing}, B, T, D, MID, C, ln_eps, drop_p, seed,
+                         offset, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits, loss_sum, correct, stream);
 }
 
 extern "C" int ss_tail_fwd_mix(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
@@ -434,9 +389,9 @@ extern "C" int ss_tail_fwd_mix(const float* h, const int32_t* lengths, const flo
                                float* mid, float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct,
                                ss_stream_t stream) {
   SS_REQUIRE(y && y_b && lam && (cw == nullptr) == (den == nullptr), SS_ERR_ARG);
-  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4, y, B, T, D, MID, C, ln_eps, drop_p, seed,
-                         offset, label_smoothing, cw ? 1.0f : denom, cw, den, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits,
-                         loss_sum, correct, stream, y_b, lam);
+  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4,
+                         CeLoss{y, y_b, lam, cw, den, cw ? 1.0f : denom, label_smoothing}, B, T, D, MID, C, ln_eps, drop_p, seed,
+                         offset, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits, loss_sum, correct, stream);
 }
 
 extern "C" int ss_tail_bwd(const float* h, const int32_t* lengths, const float* w_score, const float* gamma,

@@ -315,25 +315,44 @@ CNN_PARAMS = ("roi_cnn.net.0.weight", "roi_cnn.net.0.bias", "roi_cnn.net.3.weigh
               "roi_cnn.net.6.weight", "roi_cnn.net.6.bias", "roi_cnn.fc.weight", "roi_cnn.fc.bias")
 
 
-def tail_fwd(P, cfg: Config, ws, top, train, stash, seed, ce):
-    """AttnPool + head (+ loss) of both engines: one fused launch, a workgroup per clip; ``ce`` as ``forward`` takes it."""
+@dataclass(frozen=True)
+class Loss:
+    """The loss the fused tail evaluates next to the logits (``forward(ce=)``), as device tensors, which the object keeps alive.
+    ``y`` (B,) int64 labels; ``denom``: the mean's divisor (the global clip count); ``loss_sum`` (f32) and ``correct`` (int32): where
+    the launch adds this batch's loss and hit count.  ``cw`` (C,) f32 with ``den`` (1,) f32: the class-weighted loss divided by
+    ``den[0]`` (``denom`` is then unused).  ``y_b`` (B,) int64 with ``lam`` (1,) f32: the two-label loss of a mixup batch."""
+    y: torch.Tensor
+    label_smoothing: float
+    denom: float
+    loss_sum: torch.Tensor
+    correct: torch.Tensor
+    cw: Optional[torch.Tensor] = None
+    den: Optional[torch.Tensor] = None
+    y_b: Optional[torch.Tensor] = None
+    lam: Optional[torch.Tensor] = None
+
+    def tail_args(self):
+        """-> (the tail entry point of this loss, its label arguments, its normaliser arguments), in the order of
+        include/ss_hotpath.h (``ss_tail_fwd_mix`` takes ``cw`` and ``den`` NULL without weights)."""
+        if self.y_b is not None:
+            return ("ss_tail_fwd_mix", (self.y.data_ptr(), self.y_b.data_ptr(), self.lam.data_ptr()),
+                    (self.denom, L.ptr(self.cw), L.ptr(self.den)))
+        if self.cw is not None:
+            return "ss_tail_fwd_w", (self.y.data_ptr(),), (self.cw.data_ptr(), self.den.data_ptr())
+        return "ss_tail_fwd", (self.y.data_ptr(),), (self.denom,)
+
+
+def tail_fwd(P, cfg: Config, ws, top, train, stash, seed, ce: Optional[Loss]):
+    """AttnPool + head (+ loss) of both engines: one fused launch, a workgroup per clip; ``ce``: the ``Loss``, or None."""
     p_drop = cfg.head_dropout if train else 0.0
-    y_ptr, ls, denom, loss_ptr, correct_ptr, cw_ptr, den_ptr, yb_ptr, lam_ptr = (
-        (tuple(ce) + (None,) * 4)[:9] if ce is not None else (None, 0.0, 1.0, None, None, None, None, None, None))
-    # (class weights: the same launch with the weights and the device-side normaliser in place of the host denom; mixup: the
-    # two-label loss, which takes the partners' labels and the device-side factor and serves both normalisers)
-    if yb_ptr:
-        name, y_mix, ce_norm = "ss_tail_fwd_mix", (yb_ptr, lam_ptr), (denom, cw_ptr, den_ptr)
-    else:
-        name, y_mix, ce_norm = ("ss_tail_fwd_w", (), (cw_ptr, den_ptr)) if cw_ptr else ("ss_tail_fwd", (), (denom,))
+    name, labels, norm = ce.tail_args() if ce is not None else ("ss_tail_fwd", (None,), (1.0,))
+    ls, sums = (ce.label_smoothing, (ws.d_logits, ce.loss_sum, ce.correct)) if ce is not None else (0.0, (None,) * 3)
+    stashed = (ws.attn, ws.xhat, ws.rstd, ws.ln, ws.mid, ws.mid_drop) if stash else (None,) * 6
     L.call(name, top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
            P["pool.score.bias"].data_ptr(), P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(),
            P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(), P["head.4.weight"].data_ptr(),
-           P["head.4.bias"].data_ptr(), y_ptr, *y_mix, ws.B, ws.T, 2 * cfg.hidden, cfg.head_mid, cfg.num_classes, cfg.ln_eps, p_drop, seed,
-           7 << 40, ls, *ce_norm, ws.attn.data_ptr() if stash else None, ws.xhat.data_ptr() if stash else None,
-           ws.rstd.data_ptr() if stash else None, ws.ln.data_ptr() if stash else None,
-           ws.mid.data_ptr() if stash else None, ws.mid_drop.data_ptr() if stash else None, ws.logits.data_ptr(),
-           ws.d_logits.data_ptr() if ce is not None else None, loss_ptr, correct_ptr, L.stream())
+           P["head.4.bias"].data_ptr(), *labels, ws.B, ws.T, 2 * cfg.hidden, cfg.head_mid, cfg.num_classes, cfg.ln_eps, p_drop, seed,
+           7 << 40, ls, *norm, *map(L.ptr, stashed), ws.logits.data_ptr(), *map(L.ptr, sums), L.stream())
     return ws.logits
 
 
@@ -392,18 +411,17 @@ def join_side(ws, on: bool) -> None:
 
 
 def forward(P: Dict[str, torch.Tensor], cfg: Config, ws: Workspace, X: torch.Tensor, R: Optional[torch.Tensor], *,
-            train: bool, stash: bool = False, seed: int = 0, ce=None, x_in_place: bool = False, z_ready: bool = False) -> torch.Tensor:
+            train: bool, stash: bool = False, seed: int = 0, ce: Optional[Loss] = None, x_in_place: bool = False,
+            z_ready: bool = False) -> torch.Tensor:
     """Runs the forward kernels; returns ws.logits (B,C).  ``ws.lengths`` must already hold the int32 lengths.
     ``z_ready``: X (B,T,in_dim) already holds torch.cat((landmark features, ROI embeddings)) of train_model_official.py:297 -- the
     embeddings were made when the frames arrived (sliding-window serving) or once per run (a frozen ROI CNN:
     ``DeviceClipStore.embed``) -- and the ROI branch, the frame list and the CNN stash are skipped; the layer input is X itself.
     ``train`` / ``stash`` then need a workspace built with ``roi_hw=None`` (``backward(frozen_cnn=True)`` follows).
     ``train`` turns the two dropouts on (p from cfg); ``stash`` keeps what ``backward`` needs (needs a
-    Workspace built with train=True).  ``ce = (y_ptr, label_smoothing, denom, loss_ptr, correct_ptr)`` makes the
-    fused tail kernel also evaluate the loss and leave d(loss)/d(logits) in ``ws.d_logits``; two more entries,
-    ``(..., class_weights_ptr, den_ptr)``, make it the class-weighted loss divided by the device float ``*den_ptr``
-    (``ss_tail_fwd_w``; ``denom`` is then unused); two more again, ``(..., y_b_ptr, lam_ptr)`` -- the class-weight pair ``None, None``
-    without weights -- make it the two-label loss of a mixup batch (``ss_tail_fwd_mix``)."""
+    Workspace built with train=True).  ``ce`` (a ``Loss``) makes the fused tail kernel also evaluate that loss --
+    plain, class-weighted, or the two-label loss of a mixup batch -- add it and the hit count where the object says, and leave
+    d(loss)/d(logits) in ``ws.d_logits``."""
     if ws.bf16:
         from . import engine_bf16
 

@@ -133,6 +133,7 @@ def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = B
     loss_sum = torch.zeros(1, device=dev, dtype=torch.float32)   # sum of the per-clip losses (denom = 1)
     correct = torch.zeros(1, device=dev, dtype=torch.int32)
     every = torch.arange(len(store), dtype=torch.int32, device=store.device) if plan == "device" else None
+    cw_d = one = None
     if cw is not None:
         cw_d, one = torch.from_numpy(cw).to(dev), torch.ones(1, device=dev, dtype=torch.float32)
     for lo in range(0, len(store), batch_size):
@@ -144,12 +145,10 @@ def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = B
         logits = model(X, T, R if model.use_roi else None).contiguous()
         y = y.to(torch.int64).contiguous()
         # loss and hit count by the path's own cross-entropy kernel, predictions by its top-k kernel (no aten op)
-        if cw is None:
-            L.call("ss_ce_ls_fwd_bwd", logits.data_ptr(), y.data_ptr(), logits.shape[0], logits.shape[1], label_smoothing, 1.0,
-                   None, loss_sum.data_ptr(), correct.data_ptr(), L.stream())
-        else:  # (normaliser 1: the sum of the weighted per-clip losses)
-            L.call("ss_ce_ls_w_fwd_bwd", logits.data_ptr(), y.data_ptr(), logits.shape[0], logits.shape[1], label_smoothing,
-                   cw_d.data_ptr(), one.data_ptr(), None, loss_sum.data_ptr(), correct.data_ptr(), L.stream())
+        # (weighted: normaliser 1, the sum of the weighted per-clip losses)
+        name, norm = _weighted_entry(cw_d, ("ss_ce_ls_fwd_bwd", (1.0,)), ("ss_ce_ls_w_fwd_bwd", (L.ptr(cw_d), L.ptr(one))))
+        L.call(name, logits.data_ptr(), y.data_ptr(), logits.shape[0], logits.shape[1], label_smoothing, *norm, None,
+               loss_sum.data_ptr(), correct.data_ptr(), L.stream())
         _, top = softmax_topk(logits, 1)
         y_true += y.cpu().tolist()
         y_pred += top[:, 0].cpu().tolist()
@@ -160,6 +159,11 @@ def evaluate(model: BiGRUClassifier, store: DeviceClipStore, batch_size: int = B
         wsum = float(cw.astype(np.float64)[np.asarray(y_true, np.int64)].sum()) if y_true else 1.0
         return float(loss_sum) / wsum, int(correct) / n, y_true, y_pred
     return float(loss_sum) / n, int(correct) / n, y_true, y_pred
+
+
+def _weighted_entry(cw_d, plain, weighted):
+    """``plain`` or ``weighted``, each (entry point, the arguments in which the pair differs): the weighted one under class weights."""
+    return plain if cw_d is None else weighted
 
 
 def top_confusions_from_matrix(confusion, first_seen, id_to_label: Dict[int, str], k: int = 8) -> List[str]:
@@ -246,6 +250,7 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
     C, dev = model.cfg.num_classes, model.flat_params.device
     lo, hi = shard_range(len(store), rank, world_size)
     loss_sum = torch.zeros(1, device=dev, dtype=torch.float32)
+    cw_d = wsum = None
     if cw is not None:
         cw_d, wsum = torch.from_numpy(cw).to(dev), torch.zeros(1, device=dev, dtype=torch.float32)
     counts = torch.zeros(2, device=dev, dtype=torch.int32)  # [correct, bad-label flag]
@@ -264,14 +269,11 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
         else:
             X, T, R, y = store.batch(every[b0:b1], augment=False, rng="philox")
             logits = model(X, T, R if model.use_roi else None).contiguous()
-        if cw is None:
-            L.call("ss_eval_accum", logits.data_ptr(), y.data_ptr(), b1 - b0, C, label_smoothing, b0, loss_sum.data_ptr(),
-                   counts.data_ptr(), confusion.data_ptr(), first_seen.data_ptr(), y_true.data_ptr() + 4 * (b0 - lo),
-                   y_pred.data_ptr() + 4 * (b0 - lo), counts.data_ptr() + 4, L.stream())
-        else:
-            L.call("ss_eval_accum_w", logits.data_ptr(), y.data_ptr(), b1 - b0, C, label_smoothing, b0, cw_d.data_ptr(),
-                   loss_sum.data_ptr(), wsum.data_ptr(), counts.data_ptr(), confusion.data_ptr(), first_seen.data_ptr(),
-                   y_true.data_ptr() + 4 * (b0 - lo), y_pred.data_ptr() + 4 * (b0 - lo), counts.data_ptr() + 4, L.stream())
+        name, sums = _weighted_entry(cw_d, ("ss_eval_accum", (loss_sum.data_ptr(),)),
+                                     ("ss_eval_accum_w", (L.ptr(cw_d), loss_sum.data_ptr(), L.ptr(wsum))))
+        L.call(name, logits.data_ptr(), y.data_ptr(), b1 - b0, C, label_smoothing, b0, *sums, counts.data_ptr(), confusion.data_ptr(),
+               first_seen.data_ptr(), y_true.data_ptr() + 4 * (b0 - lo), y_pred.data_ptr() + 4 * (b0 - lo), counts.data_ptr() + 4,
+               L.stream())
     model.train(was_training)
     n_extra = 0 if extra_sums is None else extra_sums.numel()
     # [loss sum, correct, bad-label flag, n] + extra_sums (+ under class weights, last: the sum of w[label])

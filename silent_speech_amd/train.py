@@ -13,6 +13,7 @@ batch exactly as a single process would.  ``torch.distributed`` backend "nccl" i
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 from typing import Optional
 
 import numpy as np
@@ -147,8 +148,7 @@ class Trainer:
         self.cw = None if cw is None else torch.from_numpy(cw).to(dev)
         self.den = None if cw is None else torch.zeros(1, device=dev, dtype=torch.float32)
         self.freeze_cnn = bool(freeze_cnn)
-        self._ce_mix = ()  # step(mix=): the partners' labels and the factor, as engine.tail_fwd takes them
-        self._mix_keep = None  # (the two tensors behind those pointers, held until the next step)
+        self.loss = None  # the last step's engine.Loss, kept ONLY to keep its tensors alive until the next (built for empty shards too)
         # the optimiser's range of the flat bucket is [n_frozen, n): everything, or everything behind the ROI CNN
         self.n_frozen = model.cnn_param_range() if freeze_cnn else 0
         self.step_count = 0
@@ -203,11 +203,12 @@ class Trainer:
         ``mix`` = ``(y_b, lam)`` (a mixup batch: ``DeviceClipStore.mix[:2]``): the partners' labels (B,) int64 and the batch's factor
         (1,) f32, both on the device.  The loss is ``lam * CE(y) + (1 - lam) * CE(y_b)`` (``ss_tail_fwd_mix``), with class weights
         both terms over the one normaliser of ``y`` (``y_b`` is a permutation of it); ``correct`` counts ``argmax == y``.  Not with
-        ``micro_batches`` > 1 (``ValueError``)."""
+        ``micro_batches`` > 1 (``ValueError``).
+        All of it reaches the engine as ONE ``engine.Loss`` (``self.loss``: it keeps its tensors alive until the next step)."""
         model, cfg = self.model, self.model.cfg
         if self.freeze_cnn:
             raise RuntimeError("Trainer.step on a freeze_cnn trainer: it would train the ROI CNN (use step_embedded)")
-        self._ce_mix = self._check_mix(mix, X.shape[0], y)
+        y_b, lam = self._check_mix(mix, X.shape[0], y) or (None, None)
         if self._ema_swapped:
             raise RuntimeError("Trainer.step inside ema_weights(): the parameters are the averaged ones there")
         if model._bucket_version != self._bucket_version:
@@ -234,12 +235,12 @@ class Trainer:
             model.flat_grads.zero_()
             self.scal.zero_()
             self.correct.zero_()
-        self._weight_sum(B, y, y_global)
+        cw, den = self._weight_sum(B, y, y_global)
+        self.loss = loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den, y_b, lam)
         if B == 0:
             pass  # an empty shard: this rank's gradient is the zero bucket
         elif M == 1:
-            self._fwd_bwd(X, lengths, R, y, denom, train, seed=base_seed, slot=0, phase="both",
-                          prologue_done=fused_prologue)
+            self._fwd_bwd(X, lengths, R, loss, train, seed=base_seed, slot=0, phase="both", prologue_done=fused_prologue)
         else:
             n = B // M
             cur = torch.cuda.current_stream()
@@ -259,7 +260,8 @@ class Trainer:
                                 # chip-filling kernels of one slice run beside the 16-CU recurrence of the other
                                 prev = model._workspace(parts[m - 1][0], parts[m - 1][2], train=True, slot=m)
                                 self.streams[m].wait_event(prev.ev_cnn_fwd)
-                        self._fwd_bwd(Xm, Lm, Rm, ym, denom, train, seed=base_seed * M + m, slot=m + 1, phase=phase)
+                        self._fwd_bwd(Xm, Lm, Rm, dataclasses.replace(loss, y=ym), train, seed=base_seed * M + m, slot=m + 1,
+                                      phase=phase)
                         if phase == "bwd":
                             self.ev_done[m].record(self.streams[m])
             for ev in self.ev_done:
@@ -269,10 +271,9 @@ class Trainer:
         return self.scal[0], self.correct[0]
 
     def _check_mix(self, mix, B, y):
-        """``step(mix=)`` -> the two pointers ``engine.tail_fwd`` takes behind the class-weight pair (``()`` without mixup)."""
-        self._mix_keep = None
+        """``step(mix=)``, checked -> ``(y_b, lam)``, or None without mixup."""
         if mix is None:
-            return ()
+            return None
         if self.micro_batches > 1:
             raise ValueError("Trainer.step(mix=) does not combine with micro_batches > 1")
         y_b, lam = mix
@@ -283,12 +284,10 @@ class Trainer:
             raise ValueError("mix[1] must be a float32 device tensor of one element")
         if y.dtype != torch.int64:
             raise ValueError("Trainer.step(mix=) needs int64 labels")
-        self._mix_keep = (y_b, lam)
-        return (y_b.data_ptr(), lam.data_ptr())
+        return y_b, lam
 
     def _weight_sum(self, B, y, y_global):
-        """Class weights: the step's normaliser, sum of w[label] over the global batch, by one launch; sets ``self._ce_w``."""
-        ce_w = (None, None)
+        """Class weights: the step's normaliser, sum of w[label] over the global batch, by one launch -> ``(cw, den)`` or Nones."""
         if self.cw is not None and B > 0:
             yg = y if y_global is None else y_global
             if not yg.is_cuda or yg.dim() != 1 or yg.numel() == 0:
@@ -298,8 +297,8 @@ class Trainer:
             # (before the micro-batch streams fork: they wait for ev_start, recorded behind this launch)
             L.call("ss_class_weight_sum", yg.data_ptr(), yg.numel(), self.cw.data_ptr(), self.model.cfg.num_classes,
                    self.den.data_ptr(), L.stream())
-            ce_w = (self.cw.data_ptr(), self.den.data_ptr())
-        self._ce_w = ce_w
+            return self.cw, self.den
+        return None, None
 
     def _reduce_clip_adam(self):
         """Behind backward: the gradient all-reduce, the global norm, clip + Adam (+ the weight average), each on elements
@@ -361,14 +360,14 @@ class Trainer:
             model.flat_grads[lo:].zero_()
             self.scal.zero_()
             self.correct.zero_()
-        self._weight_sum(B, y, y_global)
+        cw, den = self._weight_sum(B, y, y_global)
+        self.loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den)
         if B > 0:
             ws = model._workspace_embedded(Z, train=True)
             P = model._param_dict()
             if not fused_prologue:
                 ws.lengths.copy_(lengths.to(torch.int32), non_blocking=True)
-            E.forward(P, cfg, ws, Z, None, train=train, stash=True, seed=seed, z_ready=True,
-                      ce=(y.data_ptr(), self.ls, denom, self.scal.data_ptr(), self.correct.data_ptr()) + self._ce_w)
+            E.forward(P, cfg, ws, Z, None, train=train, stash=True, seed=seed, z_ready=True, ce=self.loss)
             E.backward(P, self.G, cfg, ws, Z, None, ws.d_logits, train=train, seed=seed, frozen_cnn=True)
         self._reduce_clip_adam()
         return self.scal[0], self.correct[0]
@@ -438,16 +437,15 @@ class Trainer:
         self.betas, self.eps = (float(state["betas"][0]), float(state["betas"][1])), float(state["eps"])
         self.lr, self.max_norm = float(state["lr"]), float(state["max_norm"])
 
-    def _fwd_bwd(self, X, lengths, R, y, denom, train, seed, slot, phase, prologue_done=False):
-        """Forward + CE ("fwd"), backward ("bwd") or both of one micro-batch on the current stream."""
+    def _fwd_bwd(self, X, lengths, R, loss, train, seed, slot, phase, prologue_done=False):
+        """Forward + CE ("fwd"), backward ("bwd") or both of one micro-batch on the current stream; ``loss``: its ``engine.Loss``."""
         model, cfg = self.model, self.model.cfg
         ws = model._workspace(X, R, train=True, slot=slot)
         P = model._param_dict()
         if phase in ("fwd", "both"):
             if not prologue_done:
                 ws.lengths.copy_(lengths.to(torch.int32), non_blocking=True)
-            E.forward(P, cfg, ws, X, R, train=train, stash=True, seed=seed, x_in_place=prologue_done,
-                      ce=(y.data_ptr(), self.ls, denom, self.scal.data_ptr(), self.correct.data_ptr()) + self._ce_w + self._ce_mix)
+            E.forward(P, cfg, ws, X, R, train=train, stash=True, seed=seed, x_in_place=prologue_done, ce=loss)
         if phase in ("bwd", "both"):
             E.backward(P, self.G, cfg, ws, X, R, ws.d_logits, train=train, seed=seed)
 
