@@ -4,9 +4,10 @@ Checker: torch on the CPU with the operands rounded to bf16 exactly where the ke
 activations that enter an MFMA) and f32 accumulation -- what is left between kernel and checker is summation order, so the
 tolerances are f32-tight.  The distance of that bf16 arithmetic from the f32 oracle (oracle/model_ref.py) is measured
 separately at model level (tests/test_gpu_model_c5.py) against the tolerance DESIGN.md states."""
-import numpy as np
 import pytest
 import torch
+
+from cnn_bf16_ref import normalise_like_kernel  # (moved there unchanged: the float64 reference shares it)
 
 pytestmark = pytest.mark.gpu
 
@@ -477,27 +478,6 @@ def expand_ref(da, idx):
     for e in range(4):
         out[:, :, :, e >> 1, :, e & 1] = torch.where(idx == e, da, torch.zeros_like(da))
     return out.reshape(n, c, 2 * h, 2 * w)
-
-
-def normalise_like_kernel(R, standardize=True):
-    """The forward kernel's per-frame normalisation, operation by operation (exact integer sums, f64 mean / variance,
-    f32 table of the 256 grey levels, train_model_official.py:286-291): -> (xn f32 (N,96,96), mu (N,), sd (N,))."""
-    Rn = R.numpy().astype(np.int64)
-    N = Rn.shape[0]
-    xn = np.empty(Rn.shape, np.float32)
-    mus, sds = np.zeros(N, np.float32), np.ones(N, np.float32)
-    lev = np.arange(256, dtype=np.float32) / np.float32(255.0)
-    for n in range(N):
-        tab = lev
-        if standardize:
-            tsu, tsq, nn = float(Rn[n].sum()), float((Rn[n] ** 2).sum()), float(Rn[n].size)
-            mu = np.float32(np.float32(tsu / nn) / np.float32(255.0))
-            var = (tsq - tsu * tsu / nn) / (nn - 1.0)
-            sd = max(np.float32(np.sqrt(max(var, 0.0)) / 255.0), np.float32(1e-6))
-            tab = ((lev - mu) / sd).astype(np.float32)
-            mus[n], sds[n] = mu, sd
-        xn[n] = tab[Rn[n]]
-    return torch.from_numpy(xn), torch.from_numpy(mus), torch.from_numpy(sds)
 
 
 @pytest.fixture(params=[0, 7], ids=["grid=CUs", "grid=7"])
