@@ -7,6 +7,7 @@ separately at model level (tests/test_gpu_model_c5.py) against the tolerance DES
 import pytest
 import torch
 
+import gru_ref
 from cnn_bf16_ref import normalise_like_kernel  # (moved there unchanged: the float64 reference shares it)
 
 pytestmark = pytest.mark.gpu
@@ -203,24 +204,9 @@ def test_gemm_bf16_splitk_group(L, Bc, T, H, Kin):
 
 
 def _gru_emulated(gi, whh, bhh, lengths, T, H, reverse):
-    """One direction with the kernel's roundings: bf16 W_hh and bf16 previous state inside the matmul, f32 elsewhere."""
-    B = gi.shape[0]
-    h = gi.new_zeros(B, H)
-    outs = [None] * T
-    saves = [None] * T
-    wb = bf(whh)
-    for t in (range(T - 1, -1, -1) if reverse else range(T)):
-        valid = (lengths > t).float().unsqueeze(1)
-        gh = bf(h) @ wb.t()
-        r = torch.sigmoid(gi[:, t, :H] + gh[:, :H] + bhh[:H])
-        z = torch.sigmoid(gi[:, t, H:2 * H] + gh[:, H:2 * H] + bhh[H:2 * H])
-        hpre = gh[:, 2 * H:] + bhh[2 * H:]
-        n = torch.tanh(gi[:, t, 2 * H:] + r * hpre)
-        hn = (1 - z) * n + z * h
-        h = valid * hn  # the kernel's state past a clip's end is zero (nothing valid follows in either direction)
-        outs[t] = h
-        saves[t] = torch.stack([r, z, n, hpre], 1) * valid.unsqueeze(2)
-    return torch.stack(outs, 1), torch.stack(saves, 1)
+    """One direction with the kernel's roundings: bf16 W_hh and bf16 previous state inside the matmul, f32 elsewhere (the
+    bf16 mode of tests/gru_ref.py, moved there unchanged: the edge tests share it)."""
+    return gru_ref.direction(gi, whh, bhh, lengths, T, H, reverse, bf16=True)
 
 
 @pytest.mark.parametrize("persistent", [True, False])
