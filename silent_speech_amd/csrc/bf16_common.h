@@ -30,11 +30,16 @@ __device__ __forceinline__ s16x8 lds_frag(const bf16_t* p) { return *reinterpret
 // ds_read_b64_tr_b16 gathers a 4 (k) x 16 (x) block per 16-lane group and hands lane i column i.  Lane 4q + p of a group
 // supplies the address of block row q, columns 4p..4p+3 (8-byte aligned).  Two reads give the lane its 8 k values
 // k = 8 (l >> 4) + 0..7 for x = x0 + (l & 15).  ``base`` points at element (k0, x0) of the tile; EXEC must be all ones.
+// lds_frag_tr_at is the primitive for images with their own addressing: the lane's address in line 8 g + q and the byte
+// distance to line 8 g + 4 + q.
+__device__ __forceinline__ s16x8 lds_frag_tr_at(const void* lo_addr, int hi_bytes) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const char* a0 = static_cast<const char*>(lo_addr);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + hi_bytes));
+  return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
 __device__ __forceinline__ s16x8 lds_frag_tr(const bf16_t* base, int ld, int lane) {
   const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const bf16_t* a0 = base + (8 * g + q) * ld + 4 * p;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * ld));
-  return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return lds_frag_tr_at(base + (8 * g + q) * ld + 4 * p, 4 * ld * (int)sizeof(bf16_t));
 }

@@ -532,15 +532,6 @@ __device__ __forceinline__ void ring_k_loop(int nfull, int rem, Issue&& issue, S
   }
 }
 
-// Workgroup blockIdx.x of a grouped launch belongs to problem j: first[j] <= blockIdx.x < first[j + 1].
-__device__ __forceinline__ int group_index(const int* first, int n) {
-  int j = 0;
-#pragma unroll
-  for (int q = 1; q < GEMM_GROUP_MAX; ++q)
-    if (q < n && (int)blockIdx.x >= first[q]) j = q;
-  return j;
-}
-
 template <bool A_KC, bool B_KC>
 __device__ __forceinline__ void gemm_dma_body(GemmParams p, const TileId id, float* dlds /* the ring, at LDS address 0 */) {
   const int m0 = id.by * BM, n0 = id.bx * BN;
@@ -670,7 +661,7 @@ struct GemmGroup {
 template <bool A_KC, bool B_KC>
 __global__ __launch_bounds__(256, 3) void gemm_dma_group_kernel(GemmGroup gg) {
   extern __shared__ __attribute__((aligned(16))) float dlds[];
-  const int j = group_index(gg.first, gg.n);
+  const int j = group_index<GEMM_GROUP_MAX>(gg.first, gg.n, (int)blockIdx.x);
   const int local = blockIdx.x - gg.first[j], gx = gg.gx[j], gy = gg.gy[j];
   const int bx = local % gx, by = (local / gx) % gy, bz = local / (gx * gy);
   gemm_dma_body<A_KC, B_KC>(gg.p[j], TileId{bx, by, bz, gx, gy}, dlds);
@@ -723,7 +714,7 @@ __device__ __forceinline__ void splitk_reduce_body(const ReduceItem& r, int bloc
 }
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(ReduceItem r) { splitk_reduce_body(r, blockIdx.x); }
 __global__ __launch_bounds__(256) void splitk_reduce_group_kernel(ReduceGroup rg) {
-  const int j = group_index(rg.first, rg.n);
+  const int j = group_index<GEMM_GROUP_MAX>(rg.first, rg.n, (int)blockIdx.x);
   splitk_reduce_body(rg.it[j], blockIdx.x - rg.first[j]);
 }
 
@@ -811,7 +802,7 @@ struct WidePieces {
 // pipe.
 __global__ __launch_bounds__(WNT) void gemm_wide_group_kernel(WideGroup gg) {
   extern __shared__ __attribute__((aligned(16))) float dlds[];  // DSTAGES x (A image, B image), at LDS address 0
-  const int j = group_index(gg.first, gg.n);
+  const int j = group_index<GEMM_GROUP_MAX>(gg.first, gg.n, (int)blockIdx.x);
   const WideProblem& P = gg.p[j];
   const int local = blockIdx.x - gg.first[j];
   const int bx = local % P.gx, by = (local / P.gx) % P.gy, bz = local / (P.gx * P.gy);
@@ -875,7 +866,7 @@ __global__ __launch_bounds__(WNT) void gemm_wide_group_kernel(WideGroup gg) {
 
 // C[bi][row][col] += sum over the nz slices: one workgroup per (problem, batch entry, tile, accumulator quad)
 __global__ __launch_bounds__(WNT) void gemm_wide_reduce_kernel(WideGroup gg) {
-  const int j = group_index(gg.rfirst, gg.n);
+  const int j = group_index<GEMM_GROUP_MAX>(gg.rfirst, gg.n, (int)blockIdx.x);
   const WideProblem& P = gg.p[j];
   const int blk = blockIdx.x - gg.rfirst[j];
   slab_reduce<WT, WT, WNT, 48, 96>(P, reinterpret_cast<const f32x4*>(gg.ws + P.ws_off), blk % W_Q, blk / W_Q);
@@ -1225,21 +1216,8 @@ long splitk_slab_floats(int M, int N, int K, int splits, int batch) {
   return (long)batch * splitk_slices(K, splits, nullptr) * ceil_div(M, BM) * ceil_div(N, BN) * BM * BN;
 }
 
-bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 constexpr size_t dma_lds = (size_t)DSTAGES * D_STAGE * sizeof(float);
 constexpr size_t wide_lds = (size_t)DSTAGES * wide::W_STAGE * sizeof(float);
-
-// f(a, b) with the two layout flags as compile-time constants: launch(K<decltype(a)::value, decltype(b)::value>)
-template <class F>
-void by_layout(bool a_kcontig, bool b_kcontig, F&& f) {
-  using T = std::true_type;
-  using N = std::false_type;
-  if (a_kcontig && b_kcontig) f(T{}, T{});
-  else if (a_kcontig && !b_kcontig) f(T{}, N{});
-  else if (!a_kcontig && b_kcontig) f(N{}, T{});
-  else f(N{}, N{});
-}
 
 }  // namespace
 

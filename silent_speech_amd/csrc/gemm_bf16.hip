@@ -1,17 +1,32 @@
-// bf16-MFMA GEMM of the BASELINE config-5 GRU layers (H = 512): C[M,N] (+)= opA[M,K] * opB[K,N] (+ bias[N]).
+// bf16-MFMA GEMMs of the BASELINE config-5 GRU layers (H = 512): C[M,N] (+)= opA[M,K] * opB[K,N] (+ bias[N]).
 //
-// Same operand conventions as ss_gemm_f32_batched (include/ss_hotpath.h): f32 operands in HBM, either k-contiguous
-// ([row][k]) or k-major ([k][row]) with the storage-row remap that pairs dG[b][t] with h[b][t -+ 1].  The operands are
-// rounded to bf16 (nearest even) while they are staged into LDS and multiplied on v_mfma_f32_16x16x32_bf16 with f32
-// accumulation; C, the bias and every accumulation (split-K float atomics) stay f32.
+// Same operand conventions as ss_gemm_f32_batched (include/ss_hotpath.h): operands k-contiguous ([row][k]) or k-major ([k][row])
+// with the storage-row remap that pairs dG[b][t] with h[b][t -+ 1].  The multiplicands are bf16 on v_mfma_f32_16x16x32_bf16;
+// C, the bias and every accumulation stay f32.  The step's operands are bf16 already (flags bit 3): the recurrence kernels and
+// ss_cvt_bf16_rows leave bf16 copies of the layer inputs, the gate gradients and the weights.
 //
-// Operands may also be bf16 already (flags bit 3: the recurrence kernels and ss_cvt_bf16_rows leave bf16 copies of the layer
-// inputs, the gate gradients and the weights): 16-byte loads straight into LDS, 64-deep k tiles.
-// 128 x 128 x 32 tiles, 4 waves (2 x 2, 64 x 64 each = 16 accumulators), double-buffered LDS, one barrier per k tile,
-// global loads of tile t+1 issued before the MFMAs of tile t.  k-contiguous operands sit in LDS as [row][32 + 8] and
-// are read with ds_read_b128 (row stride 80 B = 20 banks: the 16 rows of a fragment cover all 64 banks); k-major
-// operands sit as [k][128 + 8] (written with 8-byte stores as they arrive) and are read with the transposing
-// ds_read_b64_tr_b16 -- no transpose pass, no strided global loads.
+// Three kernels:
+//   gemm_bf16_kernel<AKC, BKC, SRC16>  register-staged: 128 x 128 tiles, 4 waves of 64 x 64, two workgroups per CU, two LDS
+//       buffers, one barrier per k tile.  SRC16 = 1: bf16 operands, 64-deep k tiles, buffer loads with the range check as
+//       predicate; SRC16 = 0: f32 operands rounded to bf16 (nearest even) on their way into LDS, 32-deep k tiles.  LDS images
+//       (struct Tile): k-contiguous operands as [row][BK + 16] read with ds_read_b128, k-major operands as [k][128 + 24] read
+//       with the transposing ds_read_b64_tr_b16.  K slices add with float atomics.
+//   ring::gemm_bf16_ring_kernel<AKC, BKC>  bf16 operands, K a multiple of 64: 256 x 128 x 64 tiles, 8 waves of 64 x 64 in two
+//       staggered groups, one workgroup per CU, operands by LDS-DMA into a ring of three stages.  LDS images: unpadded
+//       [row][64 k] with 16-byte chunk c of row r at c ^ ((r >> 1) & 7), and [64 k][rows] with 32-byte segment s of line k at
+//       s ^ h(k); the swizzle is applied to the DMA's source addresses.  kcat > 1 multiplies that many operand pairs into one C.
+//   ring::gemm_bf16_ring_group_kernel (+ ring::gemm_bf16_ring_group_reduce_kernel)  up to 8 k-major problems in one launch
+//       on the ring kernel's main loop: one workgroup per output tile over all of K when the tiles fill half a chip to a
+//       chip, otherwise K dealt evenly over the CUs ("stream-K") into slabs that the reduce launch adds into C.
+//
+// Route rule of ss_gemm_bf16_batched (tests/gemm_bf16_ref.py restates it): bf16 operands (flags bit 3), K % 64 == 0 and
+// (M >= 128 or K concatenation, flags bit 4) -> ring kernel; everything else -> register-staged kernel, SRC16 by flags bit 3.
+// ss_gemm_bf16_splitk_group takes k-major bf16 problems with K % 64 == 0 only.
+//
+// What the config-5 step launches (engine_bf16.py): input projections ring<1,1>, layer 0 (K = 152) staged<1,1,1>; d layer_in
+// ring<1,0> with both directions K-concatenated (staged<1,0,1> with atomics where the ring does not take the shape); weight
+// gradients of all layers in one group launch when B is a multiple of 64 (216 tiles: one workgroup per tile, no reduce),
+// otherwise staged<0,0,1> with K slices.  How the kernels came to this form, with the measurements: docs/LAB_NOTES.md 8c-2, 12.
 #include <stdlib.h>
 
 #include "bf16_common.h"
@@ -32,8 +47,41 @@ struct GemmBfParams {
   long sa, sb, sc, sbias;
 };
 
+// `flags` of ss_gemm_bf16_batched (include/ss_hotpath.h numbers the bits; bit 1, the f32 GEMM's ReLU, is refused here)
+enum : int {
+  F_ACCUMULATE = 1,  // C += the product
+  F_ATOMIC = 4,      // ... with float atomics (K slices always do)
+  F_SRC16 = 8,       // A and B are bf16 in HBM
+  F_KCAT = 16,       // the `batch` (A, B) pairs are summed into ONE C (K concatenated)
+  // diagnostic, ring kernels only (tools/gemm_bf16_bench.py, test_ring_diagnostic_bits_give_the_same_bits):
+  F_DIAG_NO_DMA = 256,          // no refill of the ring past its first two tiles
+  F_DIAG_NO_MFMA = 512,         // no MFMAs
+  F_DIAG_LOCKSTEP = 1024,       // no stagger between the two wave groups
+  F_DIAG_AS_DISPATCHED = 2048,  // tiles in dispatch order, not contiguous per XCD
+  F_ACCEPTED = F_ACCUMULATE | F_ATOMIC | F_SRC16 | F_KCAT | F_DIAG_NO_DMA | F_DIAG_NO_MFMA | F_DIAG_LOCKSTEP | F_DIAG_AS_DISPATCHED
+};
+
 __device__ __forceinline__ long remap_row(int r, int group, int gstride, int off) {
   return (long)(r / group) * gstride + (r % group) + off;
+}
+
+// k tiles [kt0, kt1) of K slice `split` out of `splits` (whole k tiles; the last slices may be empty)
+struct KSlice { int kt0, kt1; };
+__device__ __forceinline__ KSlice k_slice(int nkt, int splits, int split) {
+  const int per = (nkt + splits - 1) / splits;
+  const int kt0 = split * per, kt1 = min(nkt, kt0 + per);
+  return KSlice{kt0, kt1};
+}
+
+// output tile t of a problem with gx x gy tiles per batch entry
+struct TileId { int bx, by, bi; };
+__device__ __forceinline__ TileId tile_of(int t, int gx, int gy) { return TileId{t % gx, (t / gx) % gy, t / (gx * gy)}; }
+
+__device__ __forceinline__ void clear_acc(f32x4 (&acc)[4][4]) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 // LDS images of one operand tile (128 rows x BK k): k-contiguous operands as [row][BK + 16] (conflict-free under the lane groups of
@@ -83,8 +131,7 @@ __device__ __forceinline__ void store_tile_f32(bf16_t* tile, int tid, const f32x
 // A chunk that starts inside the operand may run past its last row / k into the padding of the leading dimension (the caller
 // pads ld to a multiple of 8 with zeros: ss_cvt_bf16_rows), so only the chunk's first element is tested.
 // The storage-row remap (r / group) * gstride + r % group + off is an integer division per chunk: done ONCE, in front of the
-// k loop; a k-major operand then walks its rows tile by tile with an add and one conditional carry (the first version divided
-// per chunk and tile: 10 vector instructions per MFMA, the kernel was VALU-bound at 9 % MFMA occupancy).
+// k loop; a k-major operand then walks its rows tile by tile with an add and one conditional carry.
 // Loads are BUFFER loads with the range check doing the predication: a chunk outside the operand gets an offset beyond
 // num_records and comes back as zeros.  (Loads inside `if (in range)` branches made hipcc wait vmcnt(0) before the LDS stores --
 // it cannot count loads through divergent branches -- which also waited for the tiles just requested: no prefetch at all.)
@@ -180,21 +227,15 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBfParams p) {
   const int batch = blockIdx.z / p.splits, split = blockIdx.z % p.splits;
   float* C = p.C + batch * p.sc;
   const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  // K range of this split, in whole k tiles
-  const int nkt = (p.K + BK - 1) / BK;
-  const int per = (nkt + p.splits - 1) / p.splits;
-  const int kt0 = split * per, kt1 = min(nkt, kt0 + per);
+  const KSlice ks = k_slice((p.K + BK - 1) / BK, p.splits, split);
+  const int kt0 = ks.kt0, kt1 = ks.kt1;
   const int wm = (wv >> 1) * 64, wn = (wv & 1) * 64;
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc);
 
   // k tiles kt0 .. kt1-1.  Two register stages: the loads of tile t + 2 are issued before the MFMAs of tile t and written to LDS
-  // at the end of tile t + 1, so an operand has two tile times (and the other workgroup of the CU) to arrive -- with one stage a
-  // wave sat through a memory latency per tile (MFMA pipes 9 % busy).
+  // at the end of tile t + 1, so an operand has two tile times (and the other workgroup of the CU) to arrive.
   STAMP_ENTRY;
   STAMP_DECL;
   auto mainloop = [&](auto load_a, auto load_b, auto store_a, auto store_b, auto& va, auto& vb) {
@@ -215,13 +256,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBfParams p) {
         load_a((kt + 2) * BK, va[cur]);
         load_b((kt + 2) * BK, vb[cur]);
       }
-      // every fragment of the tile is requested before its first MFMA, behind a scheduling fence.  Stage timers of one workgroup
-      // alone on its CU (a d W_hh slice, 116 k tiles; finer stamps than the ones kept here): issuing the tile's 8 buffer loads and
-      // 32 transposing reads 980 cycles, the reads landing 260, the 32 MFMAs 760 (512 without the timers), the wait for the
-      // operands of the next tile + their LDS stores 970, the barrier 290 -- every phase waits for the one before it.  What the
-      // kernel needs next is the f32 GEMM's recipe (gemm.hip): operands by LDS-DMA into a ring three tiles deep, no staging
-      // registers, no LDS store instructions; the changes of round 3 (counted waits, scalar k advance, conflict-free strides)
-      // moved it from 250 to 400 - 500 TFLOP/s.
+      // every fragment of the tile is requested before its first MFMA, behind a scheduling fence (stage timers: LAB_NOTES 12)
       s16x8 fa[BK / 32][4], fb[BK / 32][4];
 #pragma unroll
       for (int k2 = 0; k2 < BK / 32; ++k2)
@@ -280,7 +315,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBfParams p) {
   }
 
   // epilogue: D row = 4 g + r, column = li
-  const bool accumulate = p.flags & 1, atomic = (p.flags & 4) || p.splits > 1;
+  const bool accumulate = p.flags & F_ACCUMULATE, atomic = (p.flags & F_ATOMIC) || p.splits > 1;
   const float* bias = p.bias ? p.bias + batch * p.sbias : nullptr;
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
@@ -304,20 +339,11 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmBfParams p) {
   STAMP_FLUSH();
 }
 
-// (A 256 x 256 x 64 tile with 8 waves of 128 x 64 -- half the operand bytes per FLOP -- was built and measured in round 3: the same
-// 400 - 470 TFLOP/s on the large shapes, half the rate on the small weight-gradient outputs.  The stage timers
-// (tools/gemm_bf16_stamp.py) put a k tile of this kernel at 3.7x its MFMA time inside the multiply phase itself: fragment reads and
-// MFMAs of a wave do not overlap as hipcc schedules them, and the padded [row][k] image is 2-way conflicted under the real lane
-// groups of ds_read_b128 (MI355X_MICROARCH.md, LDS table).  Next step: explicit read-ahead of the fragments and an XOR-swizzled
-// unpadded image; not a bigger tile.)
-
 
 // =====================================================================================================================
-// Ring kernel (round 3, second half): 256 x 128 x 64 tiles, 8 waves of 64 x 64, ONE workgroup per CU, bf16 operands in HBM.
+// Ring kernel: 256 x 128 x 64 tiles, 8 waves of 64 x 64, ONE workgroup per CU, bf16 operands in HBM.
 //
-// The kernel above is a register-staged pipeline: its stage timers put a k tile at ~3 000 cycles for 512 cycles of MFMA (issue
-// of the loads and reads, the reads landing, the MFMAs, the wait for the next operands + their LDS stores, the barrier: every
-// phase waits for the one before it).  This one is the f32 GEMM's recipe (gemm.hip::gemm_dma_body) on bf16 tiles:
+// The f32 GEMM's recipe (gemm.hip::gemm_dma_body) on bf16 tiles:
 //   * operands go HBM/L2 -> LDS by LDS-DMA (`buffer_load_dwordx4 ... lds`: no staging registers, no ds_write, the k advance in
 //     the instruction's SCALAR offset, rows / columns outside the operand get an offset beyond num_records and arrive as zeros);
 //   * a ring of three stages (3 x 48 KB): tile t + 2 is requested while tile t is multiplied, `s_waitcnt vmcnt(6)` (the six
@@ -370,7 +396,9 @@ struct Operand {
   __device__ __forceinline__ void init(const bf16_t* src, int ld_, int group_, int gstride_, int off_, int row0, int rows, int k0, int wv,
                                        int lane) {
     ld = ld_; group = group_; gstride = gstride_; off = off_;
-    const uintptr_t sa_ = reinterpret_cast<uintptr_t>(src);  // raw buffer: base, stride 0, num_records 2^31 - 1 bytes
+    // raw buffer: base, stride 0, num_records 2^31 - 1 bytes.  Hand-packed beside TileLoader16's builtin: the inline asm of
+    // buf_dma16 wants four SGPRs, and __amdgpu_buffer_rsrc_t is not trivially copyable (no __builtin_bit_cast to i32x4)
+    const uintptr_t sa_ = reinterpret_cast<uintptr_t>(src);
     rs = i32x4{(int)(unsigned)sa_, (int)((sa_ >> 32) & 0xffffu), 0x7FFFFFFF, 0x00020000};
     ident = KC || (group == 0x7FFFFFFF && off == 0);
     dm = RBK % group;
@@ -435,11 +463,7 @@ struct Frag {
   }
   __device__ __forceinline__ s16x8 read(const char* img, int t, int k2) const {
     if (KC) return *reinterpret_cast<const s16x8*>(img + o[k2] + 2048 * t);
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const char* a0 = img + o[t] + 32 * k2 * LINE;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)a0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0 + 4 * LINE));
-    return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return lds_frag_tr_at(img + o[t] + 32 * k2 * LINE, 4 * LINE);
   }
 };
 
@@ -448,10 +472,7 @@ struct Frag {
 //
 // Ping-pong: waves 0-3 (`early`) and 4-7 (`late`) -- one of each per SIMD -- run the SAME program one barrier apart.  A tile
 // is two phases with a barrier after each: [read tile t's fragments, request tile t + 2, wait for the own share of tile t + 1]
-// and [multiply tile t]; while one group multiplies, the other reads and requests.  (First version: all eight waves read,
-// requested and multiplied in lockstep -- the barrier starts them together -- and the three costs simply added up: 120 tiles
-// of a d W_ih slice 62 us with neither DMA nor MFMA, +25 us of DMA issue, +41 us of MFMA = 129 us.  In-process A/B of the
-// stagger, tools/gemm_bf16_bench.py diag: input projection 60 against 70 - 85 us, d layer_in 52 / 59, weight gradient 131 / 133.)
+// and [multiply tile t]; while one group multiplies, the other reads and requests (against lockstep: LAB_NOTES 12).
 // Hazards: tile t is read by the early group in phase A(t) and by the late group in phase B(t); tile t + 2 goes into the
 // stage of tile t - 1 (last read in phase B(t - 1)) and is requested in A(t) / B(t); a wave waits for its share of tile
 // t + 1 (requested a whole tile earlier) before the barrier that ends its read phase, i.e. before A(t + 1) starts.
@@ -472,13 +493,13 @@ __device__ __forceinline__ void ring_mainloop(const GemmBfParams& p, long ea, in
     db.issue(lds0 + (unsigned)(buf * STAGE_BYTES + A_BYTES), wv);
   };
   s16x8 fa[2][4], fb[2][4];
-  const bool late = wv >= 4 && !(p.flags & 1024);  // wave-uniform (1024: diagnostic, no stagger)
+  const bool late = wv >= 4 && !(p.flags & F_DIAG_LOCKSTEP);  // wave-uniform
   // the six DMA requests of a wave are spread between its fragment reads: a request holds the wave's issue for as long as the
   // CU's address path is busy with the other waves' requests (48 KB per tile at 64 B/clk), the reads issued before it land meanwhile
   auto load = [&](const char* st, int refill) {
     const char* As = st;
     const char* Bs = st + A_BYTES;
-    const bool dma = refill >= 0 && !(p.flags & 256);
+    const bool dma = refill >= 0 && !(p.flags & F_DIAG_NO_DMA);
     const unsigned ia = lds0 + (unsigned)(refill * STAGE_BYTES), ib = ia + A_BYTES;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -500,7 +521,7 @@ __device__ __forceinline__ void ring_mainloop(const GemmBfParams& p, long ea, in
     }
   };
   auto mult = [&]() {
-    if (p.flags & 512) {  // diagnostic: no MFMAs
+    if (p.flags & F_DIAG_NO_MFMA) {
 #pragma unroll
       for (int k2 = 0; k2 < 2; ++k2)
 #pragma unroll
@@ -563,7 +584,7 @@ __device__ __forceinline__ void ring_epilogue(const GemmBfParams& p, f32x4 (&acc
                                               bool add_bias, bool atomic, char* rlds) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, li = lane & 15;
   const int wm = (wv >> 1) * 64, wn = (wv & 1) * 64;
-  const bool accumulate = p.flags & 1;
+  const bool accumulate = p.flags & F_ACCUMULATE;
   if (!add_bias) bias = nullptr;
   if (!atomic && n0 + RBN <= p.N && (p.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0) {
     float* stage = reinterpret_cast<float*>(rlds);
@@ -614,19 +635,14 @@ template <int AKC, int BKC>
 __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(GemmBfParams p, int gx, int gy, int kcat) {
   extern __shared__ __attribute__((aligned(16))) char rlds[];
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)rlds;
-  const int wg = (p.flags & 2048) ? (int)blockIdx.x : xcd_contiguous_id();  // (2048: diagnostic, tiles as dispatched)
-  const int bx = wg % gx, by = (wg / gx) % gy, bz = wg / (gx * gy);
-  const int batch = bz / p.splits, split = bz % p.splits;
-  const int m0 = by * RBM, n0 = bx * RBN;
-  const int nkt = p.K / RBK;
-  const int per = (nkt + p.splits - 1) / p.splits;
-  const int kt0 = split * per, kt1 = min(nkt, kt0 + per), nk = max(0, kt1 - kt0);
+  const TileId t = tile_of((p.flags & F_DIAG_AS_DISPATCHED) ? (int)blockIdx.x : xcd_contiguous_id(), gx, gy);
+  const int batch = t.bi / p.splits, split = t.bi % p.splits;
+  const int m0 = t.by * RBM, n0 = t.bx * RBN;
+  const KSlice ks = k_slice(p.K / RBK, p.splits, split);
+  const int kt0 = ks.kt0, nk = max(0, ks.kt1 - kt0);
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc);
 
   // kcat > 1: that many (A, B) pairs, strides sa / sb apart, are multiplied into ONE C (d layer_in = dG_f W_f + dG_r W_r
   // without atomics or a cleared C); otherwise the pair of this batch entry
@@ -634,7 +650,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_kernel(GemmBfParams p, 
 
   // ---- epilogue
   ring_epilogue(p, acc, p.C + (kcat > 1 ? 0 : batch * p.sc), p.bias ? p.bias + batch * p.sbias : nullptr, m0, n0, split == 0,
-                (p.flags & 4) || p.splits > 1, rlds);
+                (p.flags & F_ATOMIC) || p.splits > 1, rlds);
 }
 
 template <int AKC, int BKC>
@@ -667,6 +683,16 @@ struct RingGroup {
   float* ws;
 };
 
+// Problem j of a group: its parameters, tiling and first unit / tile into locals of the given names.  A macro on purpose: as a
+// function returning a struct it sent the group kernel through 1 256 bytes of scratch, like a dynamically indexed kernel argument
+// would -- the problem's fields have to be selected one by one into plain locals.
+#define SS_SELECT_PROBLEM(gg, j, p, gx, gy, nkt, ub, tb)                                                      \
+  GemmBfParams p = gg.p[0];                                                                                   \
+  int gx = gg.gx[0], gy = gg.gy[0], nkt = gg.nkt[0], ub = gg.ubase[0], tb = gg.tbase[0];                      \
+  _Pragma("unroll") for (int q_ = 1; q_ < GROUP_MAX; ++q_) if (q_ == j) {                                     \
+    p = gg.p[q_]; gx = gg.gx[q_]; gy = gg.gy[q_]; nkt = gg.nkt[q_]; ub = gg.ubase[q_]; tb = gg.tbase[q_];     \
+  }
+
 __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_group_kernel(RingGroup gg) {
   extern __shared__ __attribute__((aligned(16))) char rlds[];
   const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)rlds;
@@ -676,21 +702,13 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_group_kernel(RingGroup 
     // Enough output tiles to fill the chip: workgroup w = tile w, whole K.  Neighbouring tiles (one XCD: xcd_contiguous_id) walk K
     // together and share their operand panels in that XCD's L2 -- the K ranges of the stream-K form below are staggered, every
     // workgroup then streams its own 3 MB from beyond L2 (845 MB per launch for 95 MB of operands: bound by exactly that).
-    int j = 0;
-#pragma unroll
-    for (int q = 1; q < GROUP_MAX; ++q)
-      if (q < gg.n && w >= gg.tbase[q]) j = q;
-    GemmBfParams p = gg.p[0];
-    int gx = gg.gx[0], gy = gg.gy[0], nkt = gg.nkt[0], tb = gg.tbase[0];
-#pragma unroll
-    for (int q = 1; q < GROUP_MAX; ++q)
-      if (q == j) { p = gg.p[q]; gx = gg.gx[q]; gy = gg.gy[q]; nkt = gg.nkt[q]; tb = gg.tbase[q]; }
-    const int tile = w - tb, bx = tile % gx, by = (tile / gx) % gy, bi = tile / (gx * gy);
+    const int j = group_index<GROUP_MAX>(gg.tbase, gg.n, w);
+    SS_SELECT_PROBLEM(gg, j, p, gx, gy, nkt, ub, tb);
+    (void)ub;
+    const TileId t = tile_of(w - tb, gx, gy);
+    const int bx = t.bx, by = t.by, bi = t.bi;
     f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    clear_acc(acc);
     ring_mainloop<0, 0>(p, bi, by * RBM, bx * RBN, 0, nkt, rlds, lds0, acc);
     ring_epilogue(p, acc, p.C + bi * p.sc, nullptr, by * RBM, bx * RBN, false, false, rlds);
     return;
@@ -698,24 +716,14 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_group_kernel(RingGroup 
   int u = w * gg.U;
   const int u1 = min(gg.ubase[gg.n], u + gg.U);
   while (u < u1) {  // wave-uniform
-    int j = 0;
-#pragma unroll
-    for (int q = 1; q < GROUP_MAX; ++q)
-      if (q < gg.n && u >= gg.ubase[q]) j = q;
-    // (a dynamically indexed kernel-argument struct would go through scratch: select the problem's fields one by one)
-    GemmBfParams p = gg.p[0];
-    int gx = gg.gx[0], gy = gg.gy[0], nkt = gg.nkt[0], ub = gg.ubase[0], tb = gg.tbase[0];
-#pragma unroll
-    for (int q = 1; q < GROUP_MAX; ++q)
-      if (q == j) { p = gg.p[q]; gx = gg.gx[q]; gy = gg.gy[q]; nkt = gg.nkt[q]; ub = gg.ubase[q]; tb = gg.tbase[q]; }
+    const int j = group_index<GROUP_MAX>(gg.ubase, gg.n, u);
+    SS_SELECT_PROBLEM(gg, j, p, gx, gy, nkt, ub, tb);
     const int local = u - ub, tile = local / nkt, kt0 = local - tile * nkt;
     const int nk = min(nkt - kt0, u1 - u);
-    const int bx = tile % gx, by = (tile / gx) % gy, bi = tile / (gx * gy);
+    const TileId t = tile_of(tile, gx, gy);
+    const int bx = t.bx, by = t.by, bi = t.bi;
     f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    clear_acc(acc);
     ring_mainloop<0, 0>(p, bi, by * RBM, bx * RBN, kt0, nk, rlds, lds0, acc);
     const int w_lo = (ub + tile * nkt) / gg.U;  // first workgroup with a unit of this tile
     f32x4* slab = reinterpret_cast<f32x4*>(gg.ws + ((long)(tb + tile) * gg.maxc + (w - w_lo)) * SLAB_FLOATS) + tid;
@@ -727,16 +735,16 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_ring_group_kernel(RingGroup 
   }
 }
 
+#undef SS_SELECT_PROBLEM
+
 // C[tile] += the tile's slabs.  One thread owns one accumulator quad (a, b, lane) of one output tile.
 __global__ __launch_bounds__(512) void gemm_bf16_ring_group_reduce_kernel(RingGroup gg) {
   const int q = blockIdx.x & 15, gt = blockIdx.x >> 4;
-  int j = 0;
-#pragma unroll
-  for (int k = 1; k < GROUP_MAX; ++k)
-    if (k < gg.n && gt >= gg.tbase[k]) j = k;
+  const int j = group_index<GROUP_MAX>(gg.tbase, gg.n, gt);
   const GemmBfParams& p = gg.p[j];
   const int tile = gt - gg.tbase[j], gx = gg.gx[j], gy = gg.gy[j], nkt = gg.nkt[j];
-  const int bx = tile % gx, by = (tile / gx) % gy, bi = tile / (gx * gy);
+  const TileId t = tile_of(tile, gx, gy);
+  const int bx = t.bx, by = t.by, bi = t.bi;
   const int ustart = gg.ubase[j] + tile * nkt;
   const int cnt = (ustart + nkt - 1) / gg.U - ustart / gg.U + 1;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, li = lane & 15;
@@ -765,13 +773,22 @@ int launch_one(const GemmBfParams& p, dim3 grid, hipStream_t s) {
   return ss_launch_status();
 }
 
-template <int SRC16>
-int launch_gemm_bf16(int a_kcontig, int b_kcontig, const GemmBfParams& p, dim3 grid, hipStream_t s) {
-  if (a_kcontig && b_kcontig) return launch_one<1, 1, SRC16>(p, grid, s);
-  if (a_kcontig) return launch_one<1, 0, SRC16>(p, grid, s);
-  if (b_kcontig) return launch_one<0, 1, SRC16>(p, grid, s);
-  return launch_one<0, 0, SRC16>(p, grid, s);
+// kernel parameters of one problem record; bias, flags and K slices as the entry point has them
+GemmBfParams bf_params(const ss_gemm_problem& q, const float* bias, long stride_bias, int flags, int splits) {
+  GemmBfParams p;
+  p.M = q.M; p.N = q.N; p.K = q.K;
+  p.A = q.A; p.lda = q.lda; p.a_group = q.a_group; p.a_gstride = q.a_gstride; p.a_off = q.a_off;
+  p.B = q.B; p.ldb = q.ldb; p.b_group = q.b_group; p.b_gstride = q.b_gstride; p.b_off = q.b_off;
+  p.C = q.C; p.ldc = q.ldc; p.bias = bias; p.flags = flags; p.splits = splits;
+  p.sa = q.stride_a; p.sb = q.stride_b; p.sc = q.stride_c; p.sbias = stride_bias;
+  return p;
 }
+
+// the checks both entry points answer with SS_ERR_ARG (leading dimensions and alignment get different codes: not here)
+bool operands_given(const ss_gemm_problem& q) {
+  return q.A && q.B && q.C && q.M > 0 && q.N > 0 && q.K > 0 && q.batch > 0 && q.a_group > 0 && q.b_group > 0;
+}
+bool extents_fit(const ss_gemm_problem& q) { return (q.a_kcontig ? q.K : q.M) <= q.lda && (q.b_kcontig ? q.K : q.N) <= q.ldb; }
 
 }  // namespace
 
@@ -785,16 +802,11 @@ static int ring_group_prepare(const ss_gemm_problem* pr, int n, float* ws, ring:
   int nkt_max = 1;
   for (int j = 0; j < n; ++j) {
     const ss_gemm_problem& q = pr[j];
-    SS_REQUIRE(q.A && q.B && q.C && q.M > 0 && q.N > 0 && q.K > 0 && q.batch > 0 && q.a_group > 0 && q.b_group > 0, SS_ERR_ARG);
+    SS_REQUIRE(operands_given(q), SS_ERR_ARG);
     SS_REQUIRE(!q.a_kcontig && !q.b_kcontig && q.K % ring::RBK == 0, SS_ERR_UNSUPPORTED);
-    SS_REQUIRE(q.lda % 8 == 0 && q.ldb % 8 == 0 && q.stride_a % 8 == 0 && q.stride_b % 8 == 0 && q.M <= q.lda && q.N <= q.ldb, SS_ERR_ARG);
-    SS_REQUIRE((reinterpret_cast<uintptr_t>(q.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(q.B) & 15) == 0 && q.ldc >= q.N, SS_ERR_ARG);
-    GemmBfParams& p = gg.p[j];
-    p.M = q.M; p.N = q.N; p.K = q.K;
-    p.A = q.A; p.lda = q.lda; p.a_group = q.a_group; p.a_gstride = q.a_gstride; p.a_off = q.a_off;
-    p.B = q.B; p.ldb = q.ldb; p.b_group = q.b_group; p.b_gstride = q.b_gstride; p.b_off = q.b_off;
-    p.C = q.C; p.ldc = q.ldc; p.bias = nullptr; p.flags = 8 | 1; p.splits = 1;
-    p.sa = q.stride_a; p.sb = q.stride_b; p.sc = q.stride_c; p.sbias = 0;
+    SS_REQUIRE(q.lda % 8 == 0 && q.ldb % 8 == 0 && q.stride_a % 8 == 0 && q.stride_b % 8 == 0 && extents_fit(q), SS_ERR_ARG);
+    SS_REQUIRE(al16(q.A) && al16(q.B) && q.ldc >= q.N, SS_ERR_ARG);
+    gg.p[j] = bf_params(q, nullptr, 0, F_SRC16 | F_ACCUMULATE, 1);
     gg.gx[j] = ceil_div(q.N, ring::RBN); gg.gy[j] = ceil_div(q.M, ring::RBM); gg.batch[j] = q.batch; gg.nkt[j] = q.K / ring::RBK;
     const int tiles = gg.gx[j] * gg.gy[j] * q.batch;
     gg.tbase[j + 1] = gg.tbase[j] + tiles;
@@ -823,7 +835,7 @@ extern "C" int ss_gemm_bf16_splitk_group_ws_floats(const ss_gemm_problem* proble
 }
 
 extern "C" int ss_gemm_bf16_splitk_group(const ss_gemm_problem* problems, int n, float* ws, long ws_floats, ss_stream_t stream) {
-  SS_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, SS_ERR_ARG);
+  SS_REQUIRE(ws && al16(ws), SS_ERR_ARG);
   ring::RingGroup gg;
   int wgs = 0;
   long floats = 0;
@@ -843,40 +855,37 @@ extern "C" int ss_gemm_bf16_batched(int a_kcontig, int b_kcontig, int M, int N, 
                                     int a_gstride, int a_off, const void* B, int ldb, int b_group, int b_gstride, int b_off,
                                     float* C, int ldc, const float* bias, int flags, int splits, int batch, long stride_a,
                                     long stride_b, long stride_c, long stride_bias, ss_stream_t stream) {
-  SS_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0 && batch > 0 && splits > 0, SS_ERR_ARG);
-  SS_REQUIRE(a_group > 0 && b_group > 0, SS_ERR_ARG);
-  // bit0 accumulate, bit2 atomics, bit3 operands are bf16 in HBM, bit4 the `batch` (A, B) pairs are summed into ONE C (K concatenated)
-  SS_REQUIRE(!(flags & ~(29 | 768 | 1024 | 2048)), SS_ERR_UNSUPPORTED);  // (256 / 512: diagnostic)
-  SS_REQUIRE(!(flags & 16) || ((flags & 8) && K % 64 == 0 && splits == 1 && !(flags & 4)), SS_ERR_UNSUPPORTED);
-  SS_REQUIRE(splits == 1 || (flags & 1), SS_ERR_ARG);            // K slices add into a C the caller initialised
-  SS_REQUIRE(!(flags & 4) || (flags & 1), SS_ERR_ARG);
-  const bool src16 = flags & 8;
+  const ss_gemm_problem q{a_kcontig, b_kcontig, M, N, K, static_cast<const float*>(A), lda, a_group, a_gstride, a_off,
+                          static_cast<const float*>(B), ldb, b_group, b_gstride, b_off, C, ldc, splits, batch, stride_a, stride_b, stride_c};
+  SS_REQUIRE(operands_given(q) && splits > 0, SS_ERR_ARG);
+  SS_REQUIRE(!(flags & ~F_ACCEPTED), SS_ERR_UNSUPPORTED);
+  SS_REQUIRE(!(flags & F_KCAT) || ((flags & F_SRC16) && K % 64 == 0 && splits == 1 && !(flags & F_ATOMIC)), SS_ERR_UNSUPPORTED);
+  SS_REQUIRE(splits == 1 || (flags & F_ACCUMULATE), SS_ERR_ARG);  // K slices add into a C the caller initialised
+  SS_REQUIRE(!(flags & F_ATOMIC) || (flags & F_ACCUMULATE), SS_ERR_ARG);
+  const bool src16 = flags & F_SRC16;
   // 16-byte loads along the contiguous dimension of either layout: 4 floats / 8 bf16 (bf16 operands: the leading dimension is
   // padded to it, the extent itself need not be)
-  const int q = src16 ? 8 : 4;
-  SS_REQUIRE(lda % q == 0 && ldb % q == 0 && stride_a % q == 0 && stride_b % q == 0, SS_ERR_UNSUPPORTED);
+  const int e = src16 ? 8 : 4;
+  SS_REQUIRE(lda % e == 0 && ldb % e == 0 && stride_a % e == 0 && stride_b % e == 0, SS_ERR_UNSUPPORTED);
   SS_REQUIRE(src16 || ((a_kcontig ? K : M) % 4 == 0 && (b_kcontig ? K : N) % 4 == 0), SS_ERR_UNSUPPORTED);
-  SS_REQUIRE(!src16 || ((a_kcontig ? K : M) <= lda && (b_kcontig ? K : N) <= ldb), SS_ERR_ARG);
+  SS_REQUIRE(!src16 || extents_fit(q), SS_ERR_ARG);
   // (bf16 operands are read through buffer descriptors: an operand of one batch entry must span less than 4 GB)
-  SS_REQUIRE((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0, SS_ERR_UNSUPPORTED);
-  GemmBfParams p;
-  p.M = M; p.N = N; p.K = K;
-  p.A = A; p.lda = lda; p.a_group = a_group; p.a_gstride = a_gstride; p.a_off = a_off;
-  p.B = B; p.ldb = ldb; p.b_group = b_group; p.b_gstride = b_gstride; p.b_off = b_off;
-  p.C = C; p.ldc = ldc; p.bias = bias; p.flags = flags;
+  SS_REQUIRE(al16(A) && al16(B), SS_ERR_UNSUPPORTED);
   const int bk = src16 ? 64 : 32;
   const int nkt = (K + bk - 1) / bk;
-  p.splits = splits < nkt ? splits : nkt;
-  p.sa = stride_a; p.sb = stride_b; p.sc = stride_c; p.sbias = stride_bias;
-  dim3 grid(ceil_div(N, BN), ceil_div(M, BM), batch * p.splits);
+  const GemmBfParams p = bf_params(q, bias, stride_bias, flags, splits < nkt ? splits : nkt);
   hipStream_t s = static_cast<hipStream_t>(stream);
+  int st = SS_ERR_LAUNCH;
   // bf16 operands, whole 64-deep k tiles, an output worth a 256 x 128 tile: the ring kernel
-  if (src16 && K % 64 == 0 && (M >= 128 || (flags & 16))) {
-    const int kcat = (flags & 16) ? batch : 1;
-    if (a_kcontig && b_kcontig) return ring::launch_ring<1, 1>(p, batch, kcat, s);
-    if (a_kcontig) return ring::launch_ring<1, 0>(p, batch, kcat, s);
-    if (b_kcontig) return ring::launch_ring<0, 1>(p, batch, kcat, s);
-    return ring::launch_ring<0, 0>(p, batch, kcat, s);
+  if (src16 && K % 64 == 0 && (M >= 128 || (flags & F_KCAT))) {
+    const int kcat = (flags & F_KCAT) ? batch : 1;
+    by_layout(a_kcontig, b_kcontig, [&](auto a, auto b) { st = ring::launch_ring<decltype(a)::value, decltype(b)::value>(p, batch, kcat, s); });
+    return st;
   }
-  return src16 ? launch_gemm_bf16<1>(a_kcontig, b_kcontig, p, grid, s) : launch_gemm_bf16<0>(a_kcontig, b_kcontig, p, grid, s);
+  const dim3 grid(ceil_div(N, BN), ceil_div(M, BM), batch * p.splits);
+  by_layout(a_kcontig, b_kcontig, [&](auto a, auto b) {
+    constexpr int AKC = decltype(a)::value, BKC = decltype(b)::value;
+    st = src16 ? launch_one<AKC, BKC, 1>(p, grid, s) : launch_one<AKC, BKC, 0>(p, grid, s);
+  });
+  return st;
 }

@@ -1,10 +1,14 @@
 // Host-side launch state, kept per device: the CU count, which kernels have had their dynamic-LDS limit raised, and the grid of a
-// persistent kernel.  Host only -- nothing here reaches device code.  One definition for the whole library: the functions are C++17
-// inline, so their local state is shared by every translation unit; hidden, so they add nothing to the exported C ABI.
+// persistent kernel; and the GEMM launchers' alignment test and layout dispatch.  Host only -- nothing here reaches device code.
+// One definition for the whole library: the functions are C++17 inline, so their local state is shared by every translation unit;
+// hidden, so they add nothing to the exported C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <stdint.h>
+
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/ss_hotpath.h"
 
@@ -64,6 +68,19 @@ inline int ss_cnn_max_wgs = 0;
 SS_HOST_INLINE int ss_persistent_grid(int items, int per_cu = 1) {
   const int cap = per_cu * (ss_cnn_max_wgs > 0 ? ss_cnn_max_wgs : ss_device_cus());
   return items < cap ? items : cap;
+}
+
+SS_HOST_INLINE bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// f(a, b) with the two layout flags of a GEMM as compile-time constants: launch(K<decltype(a)::value, decltype(b)::value>)
+template <class F>
+SS_HOST_INLINE void by_layout(bool a_kcontig, bool b_kcontig, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  if (a_kcontig && b_kcontig) f(T{}, T{});
+  else if (a_kcontig && !b_kcontig) f(T{}, N{});
+  else if (!a_kcontig && b_kcontig) f(N{}, T{});
+  else f(N{}, N{});
 }
 
 #undef SS_HOST_INLINE

@@ -144,6 +144,16 @@ __device__ __forceinline__ float relu_f(float x) { return x < 0.f ? 0.f : x; }
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// Item `key` (a workgroup, a tile, a work unit) of a grouped launch belongs to problem j: first[j] <= key < first[j + 1], j < n <= MAX.
+template <int MAX>
+__device__ __forceinline__ int group_index(const int* first, int n, int key) {
+  int j = 0;
+#pragma unroll
+  for (int q = 1; q < MAX; ++q)
+    if (q < n && key >= first[q]) j = q;
+  return j;
+}
+
 // Correctly rounded float32 square root (what np.sqrt / np.linalg.norm give on float32): the double root, rounded once more to
 // float32 -- exact, since 53 >= 2 * 24 + 2 bits.  HIP's __fsqrt_rn is the hardware's v_sqrt_f32, one ulp off on ~10 % of
 // arguments (found against the reference's own extract_83_and_openness outputs, tests/golden/serving.npz).
