@@ -1,7 +1,7 @@
 // Geometry shared by the bf16 ROI-CNN kernels of BASELINE config 5 (cnn_bf16.hip forward, cnn_bf16_bwd.hip backward):
 //   96x96 uint8 frame -> normalise -> conv 1->16 + ReLU + pool -> conv 16->32 + ReLU + pool -> conv 32->64 + ReLU + pool
 //   -> conv 64->96 + ReLU -> global average -> Linear(96 -> E)
-// i.e. TinyROICNN of /root/reference/train_model_official.py:209-229 with a fourth conv block and wider channels (the
+// i.e. TinyROICNN of the reference's train_model_official.py:209-229 with a fourth conv block and wider channels (the
 // reference does not define this model: SURVEY.md 8d row 5, "build-defined").
 //
 // One kernel per layer, one persistent workgroup per CU walking frames; a layer's whole input frame sits in LDS as a
@@ -74,7 +74,68 @@ struct Wmat {
   static constexpr int ELEMS = CN * LD, BYTES = ELEMS * 2;
 };
 
+__device__ __forceinline__ void zero_lds(void* base, int bytes, int tid) {
+  uint4* p = reinterpret_cast<uint4*>(base);
+  for (int q = tid; q < bytes / 16; q += NT) p[q] = uint4{0u, 0u, 0u, 0u};
+}
+
+// two ds_read_b64_tr_b16: the k-major operand fragment of a lane whose two pixels' 4-channel pieces sit at lo and hi
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+__device__ __forceinline__ s16x8 tr_pair(const bf16_t* lo, const bf16_t* hi) {
+  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo);
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)hi);
+  return s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+
+// bf16 weight matrix [COUT][kk = tap*CIN + ci] into LDS: the forward kernels' B operand
+template <int CIN, int COUT>
+__device__ __forceinline__ void stage_weights(const float* __restrict__ w, bf16_t* wl, int tid) {
+  using WM = Wmat<CIN, COUT>;
+  for (int q = tid; q < COUT * WM::KP; q += NT) {
+    const int co = q / WM::KP, kk = q % WM::KP, tap = kk / CIN, ci = kk % CIN;
+    wl[co * WM::LD + kk] = to_bf16(tap < 9 ? w[(co * CIN + ci) * 9 + tap] : 0.f);
+  }
+}
+// ---- the frame: 96 x 96 bytes -> exact integer statistics -> grey-level table -> haloed normalised bf16 image [98][RS0]
+// (the byte-by-byte decode through the table stays in the kernels: docs/LAB_NOTES.md 13).
+// No routine below holds a barrier: the kernels place their own between them.
 constexpr int RS0 = 104;  // row stride of the 98 x 98 haloed one-channel normalised image (elements)
+constexpr int FRAME_ELEMS = 98 * RS0, FRAME_BYTES = round_up(FRAME_ELEMS * 2, 16);
+
+// a frame's bytes, 16 per item: items tid and tid + NT of 576
+__device__ __forceinline__ void frame_px_load(const uint8_t* R, int n, int tid, uint4 (&px)[2]) {
+  const uint4* src = reinterpret_cast<const uint4*>(R + (long)n * HW0 * HW0);
+  px[0] = src[tid];
+  px[1] = (tid + NT < HW0 * HW0 / 16) ? src[tid + NT] : uint4{0u, 0u, 0u, 0u};
+}
+
+// The statistics are exact (train_model_official.py:286-290 of the reference): the waves' integer sums and sums of squares of the
+// bytes sit in s_red[NW][2]; thread 0 makes the mean and the unbiased std (units of 1/255, std >= 1e-6) into s_stat[2] and row n
+// of st (or null)
+__device__ __forceinline__ void frame_stats_block(const unsigned* s_red, int standardize, float* s_stat, float* st, int n, int tid) {
+  if (tid == 0) {
+    unsigned long long tsu = 0, tsq = 0;
+    for (int k = 0; k < NW; ++k) { tsu += s_red[2 * k]; tsq += s_red[2 * k + 1]; }
+    float mu = 0.f, sd = 1.f;
+    if (standardize) {
+      const double nn = (double)(HW0 * HW0);
+      mu = (float)((double)tsu / nn) / 255.0f;
+      const double var = ((double)tsq - (double)tsu * (double)tsu / nn) / (nn - 1.0);
+      sd = fmaxf((float)(sqrt(var > 0.0 ? var : 0.0) / 255.0), 1e-6f);
+    }
+    s_stat[0] = mu;
+    s_stat[1] = sd;
+    if (st) { st[2 * (long)n] = mu; st[2 * (long)n + 1] = sd; }
+  }
+}
+
+// s_xn[u] = the normalised value of byte u; stat = {mean, std} of the frame (read only when standardize is set)
+__device__ __forceinline__ void xn_table(float* s_xn, int standardize, const float* stat, int tid) {
+  if (tid < 256) {
+    const float rr = (float)tid / 255.0f;
+    s_xn[tid] = standardize ? (rr - stat[0]) / stat[1] : rr;
+  }
+}
 
 // The 12 constant B fragments of the conv1 patch GEMM (cnn_bf16.hip): output position q = (oy, ox) of a 4 x 8 patch reads patch
 // cell (oy + ky, ox + kx); lane (g = patch row, li = channel) holds the 8 cells of its row.
@@ -136,9 +197,10 @@ __device__ __forceinline__ void conv1_rows(const bf16_t* img, GETB getb, f32x4 b
 // The pool winners alone (conv1's weight gradient recomputes them from the frame): the [patch][channel] product of round 2 --
 // lane (g, li) holds channel li of the pooled pixels 3 (4g + r) + w -- kept for this use: measured, the transposed form with its
 // packed 4-byte stores made the fused conv2-dgrad / conv1-wgrad kernel slower (0.72 -> 0.77 ms).  bias = b1[li].
-template <class GETB>
+// VALS: the pooled values as well, va[((yp - ypb) * 48 + xp) * 16 + c] -- the unfused conv1 forward.
+template <bool VALS = false, class GETB>
 __device__ __forceinline__ void conv1_winners(const bf16_t* img, GETB getb, float bias, int yp0, int yp1, int ypb, uint8_t* ib, int wv,
-                                              int g, int li) {
+                                              int g, int li, bf16_t* va = nullptr) {
   for (int yp = yp0 + wv; yp < yp1; yp += NW) {
     const unsigned* ap = reinterpret_cast<const unsigned*>(img + (2 * yp + g) * RS0 + 6 * li);
     const s16x8 fa = __builtin_bit_cast(s16x8, uint4{ap[0], ap[1], ap[2], ap[3]});
@@ -155,8 +217,9 @@ __device__ __forceinline__ void conv1_winners(const bf16_t* img, GETB getb, floa
         if (acc[6 + 2 * w][r] > best) { best = acc[6 + 2 * w][r]; bi = 2; }
         if (acc[6 + 2 * w + 1][r] > best) { best = acc[6 + 2 * w + 1][r]; bi = 3; }
         const float v = fmaxf(best + bias, 0.f);
-        const int xp = 3 * (4 * g + r) + w;
-        ib[((yp - ypb) * 48 + xp) * C1 + li] = (uint8_t)(v > 0.f ? bi : IDX_DEAD);
+        const int o = ((yp - ypb) * 48 + 3 * (4 * g + r) + w) * C1 + li;
+        if (VALS) va[o] = to_bf16(v);
+        ib[o] = (uint8_t)(v > 0.f ? bi : IDX_DEAD);
       }
   }
 }
@@ -280,6 +343,25 @@ struct MaskLoad {
   }
 };
 
+// d feat[c] = sum_e dz[e] wfc[e][c] / (H*W): the gradient of Linear o global average, from the d z row in LDS
+template <int COUT>
+__device__ __forceinline__ void dfeat_from_dz(const float* s_dz, const float* wfc, int E, float inv_hw, float* s_dfeat, int tid) {
+  for (int c = tid; c < COUT; c += NT) {
+    float s = 0.f;
+    for (int e = 0; e < E; ++e) s += s_dz[e] * wfc[e * COUT + c];
+    s_dfeat[c] = s * inv_hw;
+  }
+}
+
+// ---- conv1's weight gradient on the pooled grid (cnn_bf16_bwd.hip: conv1_wgrad_kernel and the fused conv2_dgrad_w1_kernel)
+// one k step = 32 pooled pixels: the lane's two patch rows (v0, v1) against its two pixels (a0, a1) of the four slot-masked
+// gradient images, which lie slot_elems apart
+__device__ __forceinline__ void conv1_wgrad_kstep(const bf16_t* v0, const bf16_t* v1, const bf16_t* a0, const bf16_t* a1, int slot_elems,
+                                                  f32x4 (&acc)[4]) {
+  const s16x8 fb = tr_pair(v0, v1);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) acc[e] = mfma_bf16(tr_pair(a0 + e * slot_elems, a1 + e * slot_elems), fb, acc[e]);
+}
 // Launch of a persistent CNN kernel: min(N, wgs_per_cu x CUs) workgroups, each walking its share of the N frames.
 // wgs_per_cu: workgroups the LDS footprint lets a CU hold, so one workgroup's commit / barrier phases run under another's MFMAs
 // lds_bytes: a constant of the kernel instance (ss_dynamic_lds raises the limit at the first launch only)

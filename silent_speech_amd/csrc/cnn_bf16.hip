@@ -1,17 +1,19 @@
-// bf16 ROI-CNN forward of BASELINE config 5: geometry and data flow in cnn_bf16.h.
+// bf16 ROI-CNN forward of BASELINE config 5: geometry, data flow and the shared device routines in cnn_bf16.h.
+// Replaces the normalisation (train_model_official.py:286-291) and the CNN (:212-229) of the reference for the wider model.
 //
-//   ss_c5_conv1_fwd      uint8 frame -> exact integer statistics -> (u/255 - mu)/std table -> bf16 haloed image ->
-//                        conv 1->16 as a PATCH GEMM: K = 32 = a 4-row x 8-column input patch, M = the 16 patches of one
-//                        row pair (96 = 16 x 6 columns), one MFMA per output position of the patch (2 rows x 6 columns)
-//                        against a constant sparse weight fragment kept in registers -- 1 operand read per 12 MFMAs,
-//                        2x2 max-pool across the accumulators of a lane -> pooled map + argmax bytes
-//   ss_c5_conv_fwd       layers 2 and 3: implicit GEMM out of the haloed LDS image (cnn_bf16.h), bias + ReLU + 2x2
-//                        max-pool inside a lane (an M tile is 2 rows x 8 columns = 4 pool windows, the 4 rows a lane
-//                        holds of a 16x16 result are one window)
-//   ss_c5_conv_last_fwd  layer 4 (no pool): bias + ReLU + sign mask + global average + Linear(96 -> E), written
-//                        straight into the (B,T,x_dim+E) GRU input (the torch.cat of train_model_official.py:297)
-//
-// Replaces /root/reference/train_model_official.py:286-291 (normalise) and :212-229 (CNN) for the wider model.
+// Kernels and entry points.  [step] = launched by the training step of engine_bf16.py; the others are the older or alternative
+// forms that the tests keep alive.
+//   conv12_fwd_kernel        [step] ss_c5_conv12_fwd_i1; ss_c5_conv12_fwd (the same without conv1's winner bytes)
+//                            frame -> exact integer statistics -> grey-level table -> bf16 haloed image -> conv1 as a PATCH GEMM
+//                            (K = 32 = a 4-row x 8-column input patch, M = the 16 patches of a row pair, one MFMA per output position
+//                            against a constant sparse weight fragment in registers) + ReLU + pool -> [LDS] -> conv2 + ReLU + pool
+//   conv_fwd_kernel<.., false>  [step, layer 3] ss_c5_conv_fwd(2 | 3): implicit GEMM out of the haloed LDS image, bias + ReLU +
+//                            2x2 max-pool inside a lane (an M tile is 2 rows x 8 columns = 4 pool windows)
+//   conv_last_fwd_ws_kernel  [step] ss_c5_conv_last_fwd_feat: layer 4, weights stationary in registers; sign mask + global average
+//   conv1_fwd_kernel         ss_c5_conv1_fwd: conv1 alone, its pooled map and winner bytes to HBM
+//   conv_fwd_kernel<.., true>   ss_c5_conv_last_fwd: layer 4 with the weights in LDS, + Linear(96 -> E) written straight into the
+//                            (B,T,x_dim+E) GRU input (the torch.cat of train_model_official.py:297)
+// What the measurements behind these forms showed: docs/LAB_NOTES.md 8c and 13.
 #include <stdlib.h>
 
 #include "cnn_bf16.h"
@@ -20,11 +22,6 @@ namespace {
 using namespace c5;
 
 STAMP_TABLE(ss_debug_stamps_c5_fwd)
-
-__device__ __forceinline__ void zero_lds(void* base, int bytes, int tid) {
-  uint4* p = reinterpret_cast<uint4*>(base);
-  for (int q = tid; q < bytes / 16; q += NT) p[q] = uint4{0u, 0u, 0u, 0u};
-}
 
 // ------------------------------------------------------------------------------------------------ conv1
 struct Conv1Params {
@@ -36,46 +33,45 @@ struct Conv1Params {
   float* st;          // (N, 2): mean, std of the frame (backward reuses them) or null
 };
 
+// LDS of the frame front that conv1_fwd_kernel and conv12_fwd_kernel share, byte offsets
+struct FrameLds {
+  static constexpr int IMG = 0;                    // bf16 [98][RS0]
+  static constexpr int XN = FRAME_BYTES;           // f32 [256] grey-level table
+  static constexpr int RED = XN + 256 * 4;         // u32 [NW][2] the waves' integer sums (32 words)
+  static constexpr int STAT = RED + 32 * 4;        // f32 mean, std (32 words)
+  static constexpr int END = STAT + 32 * 4;
+};
+struct Conv1FwdLds : FrameLds {
+  static constexpr int HP = HW0 / 2;
+  static constexpr int A1 = END;                   // bf16 [48][48][16]
+  static constexpr int I1 = A1 + HP * HP * C1 * 2; // u8 [48][48][16]
+  static constexpr int BYTES = I1 + HP * HP * C1;
+};
+static_assert(Conv1FwdLds::BYTES == 132256, "conv1 forward LDS");
 
 __global__ __launch_bounds__(NT, 2) void conv1_fwd_kernel(Conv1Params p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int HP = HW0 / 2;
-  bf16_t* img = reinterpret_cast<bf16_t*>(smem);                         // [98][RS0]
-  constexpr int o_tab = round_up(98 * RS0 * 2, 16);
-  float* s_xn = reinterpret_cast<float*>(smem + o_tab);                  // [256]
-  float* s_misc = s_xn + 256;                                            // [64]
-  constexpr int o_a1 = o_tab + (256 + 64) * 4;
-  bf16_t* oa = reinterpret_cast<bf16_t*>(smem + o_a1);                   // [48][48][16]
-  uint8_t* oi = smem + o_a1 + HP * HP * C1 * 2;                          // [48][48][16]
-  unsigned* s_red = reinterpret_cast<unsigned*>(s_misc);                 // [NW][2]
-  float* s_stat = s_misc + 32;
+  using L = Conv1FwdLds;
+  constexpr int HP = L::HP;
+  bf16_t* img = reinterpret_cast<bf16_t*>(smem + L::IMG);
+  float* s_xn = reinterpret_cast<float*>(smem + L::XN);
+  unsigned* s_red = reinterpret_cast<unsigned*>(smem + L::RED);
+  float* s_stat = reinterpret_cast<float*>(smem + L::STAT);
+  bf16_t* oa = reinterpret_cast<bf16_t*>(smem + L::A1);
+  uint8_t* oi = smem + L::I1;
 
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, li = lane & 15;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform by construction: as an SGPR the tile / row arithmetic that hangs on it runs on the scalar unit
-  zero_lds(img, o_tab, tid);
-  // constant B fragments: output position q = (oy, ox) of a patch reads patch cell (oy + ky, ox + kx)
+  zero_lds(img, FRAME_BYTES, tid);
   s16x8 bq[12];
 #pragma unroll
-  for (int q = 0; q < 12; ++q) {
-    const int oy = q / 6, ox = q % 6;
-    s16x8 f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int ky = g - oy, kx = j - ox;
-      const float w = (ky >= 0 && ky <= 2 && kx >= 0 && kx <= 2) ? p.w1[li * 9 + ky * 3 + kx] : 0.f;
-      f[j] = (short)to_bf16(w);
-    }
-    bq[q] = f;
-  }
+  for (int q = 0; q < 12; ++q) bq[q] = conv1_bfrag(p.w1, q, g, li);
   const float bias = p.b1[li];
   __syncthreads();
 
   for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
-    // ---- frame bytes, exact statistics (train_model_official.py:286-290)
-    const uint4* src = reinterpret_cast<const uint4*>(p.R + (long)n * HW0 * HW0);
     uint4 px[2];
-    px[0] = src[tid];
-    px[1] = (tid + NT < HW0 * HW0 / 16) ? src[tid + NT] : uint4{0u, 0u, 0u, 0u};
+    frame_px_load(p.R, n, tid, px);
     unsigned su = 0, sq = 0;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -93,25 +89,9 @@ __global__ __launch_bounds__(NT, 2) void conv1_fwd_kernel(Conv1Params p) {
     sq = wave_sum_u32(sq);
     if (lane == 0) { s_red[2 * wv] = su; s_red[2 * wv + 1] = sq; }
     __syncthreads();
-    if (tid == 0) {
-      unsigned long long tsu = 0, tsq = 0;
-      for (int k = 0; k < NW; ++k) { tsu += s_red[2 * k]; tsq += s_red[2 * k + 1]; }
-      float mu = 0.f, sd = 1.f;
-      if (p.standardize) {
-        const double nn = (double)(HW0 * HW0);
-        mu = (float)((double)tsu / nn) / 255.0f;
-        const double var = ((double)tsq - (double)tsu * (double)tsu / nn) / (nn - 1.0);
-        sd = fmaxf((float)(sqrt(var > 0.0 ? var : 0.0) / 255.0), 1e-6f);
-      }
-      s_stat[0] = mu;
-      s_stat[1] = sd;
-      if (p.st) { p.st[2 * (long)n] = mu; p.st[2 * (long)n + 1] = sd; }
-    }
+    frame_stats_block(s_red, p.standardize, s_stat, p.st, n, tid);
     __syncthreads();
-    if (tid < 256) {
-      const float rr = (float)tid / 255.0f;
-      s_xn[tid] = p.standardize ? (rr - s_stat[0]) / s_stat[1] : rr;
-    }
+    xn_table(s_xn, p.standardize, s_stat, tid);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -128,28 +108,7 @@ __global__ __launch_bounds__(NT, 2) void conv1_fwd_kernel(Conv1Params p) {
     }
     __syncthreads();
     // ---- patch GEMM: row pair yp, patch i = li covers haloed rows 2yp..2yp+3, haloed columns 6i..6i+7
-    for (int yp = wv; yp < HP; yp += NW) {
-      const unsigned* ap = reinterpret_cast<const unsigned*>(img + (2 * yp + g) * RS0 + 6 * li);
-      const unsigned a0 = ap[0], a1v = ap[1], a2 = ap[2], a3 = ap[3];
-      const s16x8 fa = __builtin_bit_cast(s16x8, uint4{a0, a1v, a2, a3});
-      f32x4 acc[12];
-#pragma unroll
-      for (int q = 0; q < 12; ++q) acc[q] = mfma_bf16(fa, bq[q], f32x4{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int w = 0; w < 3; ++w) {
-          float best = acc[2 * w][r];
-          int bi = 0;
-          if (acc[2 * w + 1][r] > best) { best = acc[2 * w + 1][r]; bi = 1; }
-          if (acc[6 + 2 * w][r] > best) { best = acc[6 + 2 * w][r]; bi = 2; }
-          if (acc[6 + 2 * w + 1][r] > best) { best = acc[6 + 2 * w + 1][r]; bi = 3; }
-          const float v = fmaxf(best + bias, 0.f);
-          const int o = (yp * HP + 3 * (4 * g + r) + w) * C1 + li;
-          oa[o] = to_bf16(v);
-          oi[o] = (uint8_t)(v > 0.f ? bi : IDX_DEAD);
-        }
-    }
+    conv1_winners<true>(img, [&](int q) { return bq[q]; }, bias, 0, HP, 0, oi, wv, g, li, oa);
     __syncthreads();
     uint4* da = reinterpret_cast<uint4*>(p.a1 + (long)n * HP * HP * C1);
     for (int q = tid; q < HP * HP * C1 * 2 / 16; q += NT) da[q] = reinterpret_cast<const uint4*>(oa)[q];
@@ -159,7 +118,6 @@ __global__ __launch_bounds__(NT, 2) void conv1_fwd_kernel(Conv1Params p) {
   }
 }
 
-constexpr int CONV1_LDS = round_up(98 * RS0 * 2, 16) + (256 + 64) * 4 + 48 * 48 * C1 * 3;
 
 // ------------------------------------------------------------------------------------------------ layers 2..4
 struct ConvFwdParams {
@@ -177,26 +135,6 @@ struct ConvFwdParams {
   float* feat;        // (N, COUT) averaged features, or null
 };
 
-// bf16 weight matrix [COUT][kk = tap*CIN + ci] into LDS
-template <int CIN, int COUT>
-__device__ __forceinline__ void stage_weights(const float* __restrict__ w, bf16_t* wl, int tid) {
-  using WM = Wmat<CIN, COUT>;
-  for (int q = tid; q < COUT * WM::KP; q += NT) {
-    const int co = q / WM::KP, kk = q % WM::KP, tap = kk / CIN, ci = kk % CIN;
-    wl[co * WM::LD + kk] = to_bf16(tap < 9 ? w[(co * CIN + ci) * 9 + tap] : 0.f);
-  }
-}
-
-// un-haloed NHWC frame (HBM) -> haloed LDS image, 16-byte pieces
-template <class IM>
-__device__ __forceinline__ void load_image(const bf16_t* __restrict__ src, bf16_t* img, int tid) {
-  constexpr int CH = IM::C / 8;  // 16-byte pieces per pixel
-  for (int q = tid; q < IM::H * IM::W * CH; q += NT) {
-    const int pix = q / CH, c8 = q % CH;
-    *reinterpret_cast<uint4*>(img + IM::at(pix / IM::W, pix % IM::W) + 8 * c8) = reinterpret_cast<const uint4*>(src)[q];
-  }
-}
-
 // element offset of the A fragment of k step s relative to the lane's base (pixel (y-1, x-1), chunk folded into the base)
 template <class IM>
 __device__ __forceinline__ int koff(int s, int hi) {
@@ -210,20 +148,32 @@ __device__ __forceinline__ int koff(int s, int hi) {
   return (tap / 3) * IM::RS + (tap % 3) * IM::PS;
 }
 
+// LDS of conv_fwd_kernel, byte offsets
+template <int CIN, int COUT, int H, int W, bool LAST>
+struct ConvFwdLds {
+  static constexpr int HO = H / 2, WO = W / 2;
+  static constexpr int IMG = 0;                                                // Img<CIN, H, W>
+  static constexpr int WL = Img<CIN, H, W>::BYTES;                             // Wmat<CIN, COUT>
+  static constexpr int OUT = WL + round_up(Wmat<CIN, COUT>::BYTES, 16);        // pooled: bf16 [HO][WO][COUT]
+  static constexpr int IDX = OUT + (LAST ? 0 : HO * WO * COUT * 2);            // pooled: argmax; last: mask [H*W][COUT]
+  static constexpr int BIAS = round_up(OUT + (LAST ? H * W * COUT : HO * WO * COUT * 3), 16);  // f32 [COUT]
+  static constexpr int FEAT = BIAS + COUT * 4;                                 // f32 [COUT]
+  static constexpr int BYTES = FEAT + COUT * 4 + 16;                           // (16 bytes nobody uses: the launch size as it has always been)
+};
+
 template <int CIN, int COUT, int H, int W, bool LAST, int MT, int NTL>
 __global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(ConvFwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using IM = Img<CIN, H, W>;
   using WM = Wmat<CIN, COUT>;
+  using L = ConvFwdLds<CIN, COUT, H, W, LAST>;
   constexpr int HO = H / 2, WO = W / 2;
-  bf16_t* img = reinterpret_cast<bf16_t*>(smem);
-  bf16_t* wl = reinterpret_cast<bf16_t*>(smem + IM::BYTES);
-  constexpr int o_out = IM::BYTES + round_up(WM::BYTES, 16);
-  bf16_t* oa = reinterpret_cast<bf16_t*>(smem + o_out);                       // pooled: [HO][WO][COUT]
-  uint8_t* oi = smem + o_out + (LAST ? 0 : HO * WO * COUT * 2);               // pooled: argmax; last: mask [H*W][COUT]
-  constexpr int o_misc = o_out + (LAST ? H * W * COUT : HO * WO * COUT * 3);
-  float* s_bias = reinterpret_cast<float*>(smem + round_up(o_misc, 16));      // [COUT]
-  float* s_feat = s_bias + COUT;                                              // [COUT]
+  bf16_t* img = reinterpret_cast<bf16_t*>(smem + L::IMG);
+  bf16_t* wl = reinterpret_cast<bf16_t*>(smem + L::WL);
+  bf16_t* oa = reinterpret_cast<bf16_t*>(smem + L::OUT);
+  uint8_t* oi = smem + L::IDX;
+  float* s_bias = reinterpret_cast<float*>(smem + L::BIAS);
+  float* s_feat = reinterpret_cast<float*>(smem + L::FEAT);
 
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, li = lane & 15;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform by construction: as an SGPR the tile / row arithmetic that hangs on it runs on the scalar unit
@@ -547,12 +497,6 @@ __global__ __launch_bounds__(NT, 2) void conv_last_fwd_ws_kernel(ConvLastWsParam
   STAMP_FLUSH();
 }
 
-template <int CIN, int COUT, int H, int W, bool LAST>
-constexpr int conv_fwd_lds() {
-  return Img<CIN, H, W>::BYTES + round_up(Wmat<CIN, COUT>::BYTES, 16) +
-         round_up(LAST ? H * W * COUT : (H / 2) * (W / 2) * COUT * 3, 16) + 16 + 2 * COUT * 4;
-}
-
 // ------------------------------------------------------------------------------------------------ conv1 + conv2 fused
 // The pooled conv1 map (73.7 KB per frame as bf16, plus 36.9 KB of argmax bytes) is the largest tensor of the net and was 43 % of
 // the CNN's HBM traffic when every layer was its own kernel.  Here it is born in conv2's haloed LDS image and never leaves the
@@ -569,44 +513,44 @@ struct Conv12Params {
                       // which spent 9.9 k of its 55 k cycles per frame recomputing them from the frame (stage timers, round 3)
 };
 
+struct Conv12Lds : FrameLds {
+  using IM = Img<C1, 48, 48>;                                    // conv2's haloed input: the pooled conv1 map
+  using WM = Wmat<C1, C2>;
+  static constexpr int HO = 24, WO = 24, HH = 12;                // conv2's pooled output, rows per flush
+  static constexpr int A1 = END;                                 // IM
+  static constexpr int WL = A1 + IM::BYTES;                      // WM
+  static constexpr int OUT = WL + round_up(WM::BYTES, 16);       // bf16 [HH][WO][32]
+  static constexpr int IDX = OUT + HH * WO * C2 * 2;             // u8 [HH][WO][32]
+  static constexpr int BIAS = OUT + HH * WO * C2 * 3;            // f32 [32]
+  static constexpr int BYTES = BIAS + C2 * 4;
+};
+
 __global__ __launch_bounds__(NT, 2) void conv12_fwd_kernel(Conv12Params p) {
   STAMP_ENTRY;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  using IM = Img<C1, 48, 48>;
-  using WM = Wmat<C1, C2>;
-  constexpr int HO = 24, WO = 24, HH = 12;                     // conv2's pooled output, rows per flush
-  bf16_t* img = reinterpret_cast<bf16_t*>(smem);               // [98][RS0]
-  constexpr int o_tab = round_up(98 * RS0 * 2, 16);
-  float* s_xn = reinterpret_cast<float*>(smem + o_tab);        // [256]
-  float* s_misc = s_xn + 256;                                  // [64]
-  constexpr int o_a1 = o_tab + (256 + 64) * 4;
-  bf16_t* a1 = reinterpret_cast<bf16_t*>(smem + o_a1);         // Img<16,48,48>
-  bf16_t* wl = reinterpret_cast<bf16_t*>(smem + o_a1 + IM::BYTES);
-  constexpr int o_out = o_a1 + IM::BYTES + round_up(WM::BYTES, 16);
-  bf16_t* oa = reinterpret_cast<bf16_t*>(smem + o_out);        // [HH][WO][32]
-  uint8_t* oi = smem + o_out + HH * WO * C2 * 2;               // [HH][WO][32]
-  float* s_bias = reinterpret_cast<float*>(smem + o_out + HH * WO * C2 * 3);  // [32]
-  unsigned* s_red = reinterpret_cast<unsigned*>(s_misc);
-  float* s_stat = s_misc + 32;
+  using L = Conv12Lds;
+  using IM = L::IM;
+  using WM = L::WM;
+  constexpr int HO = L::HO, WO = L::WO, HH = L::HH;
+  bf16_t* img = reinterpret_cast<bf16_t*>(smem + L::IMG);
+  float* s_xn = reinterpret_cast<float*>(smem + L::XN);
+  unsigned* s_red = reinterpret_cast<unsigned*>(smem + L::RED);
+  float* s_stat = reinterpret_cast<float*>(smem + L::STAT);
+  bf16_t* a1 = reinterpret_cast<bf16_t*>(smem + L::A1);
+  bf16_t* wl = reinterpret_cast<bf16_t*>(smem + L::WL);
+  bf16_t* oa = reinterpret_cast<bf16_t*>(smem + L::OUT);
+  uint8_t* oi = smem + L::IDX;
+  float* s_bias = reinterpret_cast<float*>(smem + L::BIAS);
 
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, li = lane & 15;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform by construction: as an SGPR the tile / row arithmetic that hangs on it runs on the scalar unit
-  zero_lds(smem, o_tab, tid);
+  zero_lds(img, FRAME_BYTES, tid);
   zero_lds(a1, IM::BYTES, tid);
   stage_weights<C1, C2>(p.w2, wl, tid);
   if (tid < C2) s_bias[tid] = p.b2[tid];
   s16x8 bq[12];
 #pragma unroll
-  for (int q = 0; q < 12; ++q) {
-    const int oy = q / 6, ox = q % 6;
-    s16x8 f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int ky = g - oy, kx = j - ox;
-      f[j] = (short)to_bf16((ky >= 0 && ky <= 2 && kx >= 0 && kx <= 2) ? p.w1[li * 9 + ky * 3 + kx] : 0.f);
-    }
-    bq[q] = f;
-  }
+  for (int q = 0; q < 12; ++q) bq[q] = conv1_bfrag(p.w1, q, g, li);
   const f32x4 bias1 = *reinterpret_cast<const f32x4*>(p.b1 + 4 * g);  // channels 4g .. 4g+3 (conv1_rows)
   const int chunk = g & 1, hi = g >> 1;
   int lane_s[WM::KSTEPS];  // conv2: this lane's pixel of a 2 x 8 tile + its k chunk + the tap of k step s
@@ -615,12 +559,7 @@ __global__ __launch_bounds__(NT, 2) void conv12_fwd_kernel(Conv12Params p) {
     lane_s[s] = ((li >> 1) & 1) * IM::RS + (2 * (li >> 2) + (li & 1)) * IM::PS + 8 * chunk + (hi ? koff<IM>(s, 1) : koff<IM>(s, 0));
   const int lane_o = g * C2 + li;  // conv2's staged output: window g of a tile, channel li (+ 16 per n tile)
   uint4 px[2];
-  auto load_px = [&](int n) {
-    const uint4* src = reinterpret_cast<const uint4*>(p.R + (long)n * HW0 * HW0);
-    px[0] = src[tid];
-    px[1] = (tid + NT < HW0 * HW0 / 16) ? src[tid + NT] : uint4{0u, 0u, 0u, 0u};
-  };
-  if ((int)blockIdx.x < p.N) load_px(blockIdx.x);
+  if ((int)blockIdx.x < p.N) frame_px_load(p.R, blockIdx.x, tid, px);
   __syncthreads();
   STAMP_DECL;
 
@@ -636,7 +575,7 @@ __global__ __launch_bounds__(NT, 2) void conv12_fwd_kernel(Conv12Params p) {
   int n_pending = -1;
   for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
     STAMP(15);
-    // ---- statistics, table, bf16 image (as conv1_fwd_kernel)
+    // ---- statistics, table, bf16 image
     unsigned su = 0, sq = 0;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -658,25 +597,9 @@ __global__ __launch_bounds__(NT, 2) void conv12_fwd_kernel(Conv12Params p) {
       n_pending = -1;
     }
     __syncthreads();
-    if (tid == 0) {
-      unsigned long long tsu = 0, tsq = 0;
-      for (int k = 0; k < NW; ++k) { tsu += s_red[2 * k]; tsq += s_red[2 * k + 1]; }
-      float mu = 0.f, sd = 1.f;
-      if (p.standardize) {
-        const double nn = (double)(HW0 * HW0);
-        mu = (float)((double)tsu / nn) / 255.0f;
-        const double var = ((double)tsq - (double)tsu * (double)tsu / nn) / (nn - 1.0);
-        sd = fmaxf((float)(sqrt(var > 0.0 ? var : 0.0) / 255.0), 1e-6f);
-      }
-      s_stat[0] = mu;
-      s_stat[1] = sd;
-      if (p.st) { p.st[2 * (long)n] = mu; p.st[2 * (long)n + 1] = sd; }
-    }
+    frame_stats_block(s_red, p.standardize, s_stat, p.st, n, tid);
     __syncthreads();
-    if (tid < 256) {
-      const float rr = (float)tid / 255.0f;
-      s_xn[tid] = p.standardize ? (rr - s_stat[0]) / s_stat[1] : rr;
-    }
+    xn_table(s_xn, p.standardize, s_stat, tid);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -693,7 +616,7 @@ __global__ __launch_bounds__(NT, 2) void conv12_fwd_kernel(Conv12Params p) {
     }
     __syncthreads();
     STAMP(0);
-    if (n + (int)gridDim.x < p.N) load_px(n + gridDim.x);  // the next frame's bytes, under both convolutions
+    if (n + (int)gridDim.x < p.N) frame_px_load(p.R, n + gridDim.x, tid, px);  // the next frame's bytes, under both convolutions
     // ---- conv1 -> conv2's haloed input image
     if (p.i1)  // (wave-uniform; the winner bytes of a lane's four channels leave as one 4-byte global store)
       conv1_rows(img, [&](int q) { return bq[q]; }, bias1, 0, 48, 0, a1, IM::at(0, 0), IM::RS, IM::PS, p.i1 + (long)n * 48 * 48 * C1, wv, g, li);
@@ -764,9 +687,6 @@ __global__ __launch_bounds__(NT, 2) void conv12_fwd_kernel(Conv12Params p) {
   STAMP_FLUSH();
 }
 
-constexpr int CONV12_LDS = round_up(98 * RS0 * 2, 16) + (256 + 64) * 4 + Img<C1, 48, 48>::BYTES + round_up(Wmat<C1, C2>::BYTES, 16) +
-                           12 * 24 * C2 * 3 + C2 * 4;
-
 }  // namespace
 
 extern "C" int ss_c5_conv12_fwd_i1(const uint8_t* R, int N, int standardize, const float* w1, const float* b1, const float* w2,
@@ -774,7 +694,7 @@ extern "C" int ss_c5_conv12_fwd_i1(const uint8_t* R, int N, int standardize, con
   SS_REQUIRE(R && w1 && b1 && w2 && b2 && a2 && i2 && N > 0, SS_ERR_ARG);
   SS_REQUIRE((reinterpret_cast<uintptr_t>(i1) & 15) == 0, SS_ERR_ARG);
   Conv12Params p{R, N, standardize, w1, b1, w2, b2, a2, i2, st, i1};
-  return launch_persistent(conv12_fwd_kernel, p, CONV12_LDS, N, static_cast<hipStream_t>(stream));
+  return launch_persistent(conv12_fwd_kernel, p, Conv12Lds::BYTES, N, static_cast<hipStream_t>(stream));
 }
 extern "C" int ss_c5_conv12_fwd(const uint8_t* R, int N, int standardize, const float* w1, const float* b1, const float* w2,
                                 const float* b2, uint16_t* a2, uint8_t* i2, float* st, ss_stream_t stream) {
@@ -793,7 +713,7 @@ extern "C" int ss_c5_conv1_fwd(const uint8_t* R, int N, int standardize, const f
                                uint8_t* i1, float* st, ss_stream_t stream) {
   SS_REQUIRE(R && w1 && b1 && a1 && i1 && N > 0, SS_ERR_ARG);
   Conv1Params p{R, N, standardize, w1, b1, a1, i1, st};
-  return launch_persistent(conv1_fwd_kernel, p, CONV1_LDS, N, static_cast<hipStream_t>(stream));
+  return launch_persistent(conv1_fwd_kernel, p, Conv1FwdLds::BYTES, N, static_cast<hipStream_t>(stream));
 }
 
 // layer = 2: (N,48,48,16) -> (N,24,24,32);  layer = 3: (N,24,24,32) -> (N,12,12,64)
@@ -803,8 +723,8 @@ extern "C" int ss_c5_conv_fwd(int layer, const uint16_t* in, int N, const float*
   ConvFwdParams p{};
   p.in = in; p.N = N; p.w = w; p.b = b; p.out = out; p.idx = idx;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (layer == 2) return launch_persistent(conv_fwd_kernel<C1, C2, 48, 48, false, 3, 2>, p, conv_fwd_lds<C1, C2, 48, 48, false>(), N, s);
-  if (layer == 3) return launch_persistent(conv_fwd_kernel<C2, C3, 24, 24, false, 9, 2>, p, conv_fwd_lds<C2, C3, 24, 24, false>(), N, s);
+  if (layer == 2) return launch_persistent(conv_fwd_kernel<C1, C2, 48, 48, false, 3, 2>, p, ConvFwdLds<C1, C2, 48, 48, false>::BYTES, N, s);
+  if (layer == 3) return launch_persistent(conv_fwd_kernel<C2, C3, 24, 24, false, 9, 2>, p, ConvFwdLds<C2, C3, 24, 24, false>::BYTES, N, s);
   return SS_ERR_UNSUPPORTED;
 }
 
@@ -814,6 +734,6 @@ extern "C" int ss_c5_conv_last_fwd(const uint16_t* in, int N, const float* w, co
   SS_REQUIRE((mask == nullptr) == (feat == nullptr), SS_ERR_ARG);
   ConvFwdParams p{};
   p.in = in; p.N = N; p.w = w; p.b = b; p.wfc = wfc; p.bfc = bfc; p.E = E; p.z = z; p.ld_z = ld_z; p.mask = mask; p.feat = feat;
-  return launch_persistent(conv_fwd_kernel<C3, C4, 12, 12, true, 3, 3>, p, conv_fwd_lds<C3, C4, 12, 12, true>(), N,
+  return launch_persistent(conv_fwd_kernel<C3, C4, 12, 12, true, 3, 3>, p, ConvFwdLds<C3, C4, 12, 12, true>::BYTES, N,
                            static_cast<hipStream_t>(stream));
 }

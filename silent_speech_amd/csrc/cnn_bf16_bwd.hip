@@ -15,6 +15,23 @@
 // dy is rebuilt in LDS from the pooled-grid gradient + the argmax bytes (pooled layers) or from d feat + the sign mask
 // (last layer).  Large maps are processed in row bands so that dy (dense, bf16) fits beside the other operand.
 //   conv1 wgrad: 1 input channel -- a GEMM on the pooled grid against the 4 x 4 input patch under every pool window.
+//
+// Kernels and entry points.  [step] = launched by the training step of engine_bf16.py; the others are the older or alternative
+// forms that the tests keep alive.
+//   conv_wgrad_kernel<C3, C4, .., FCX>   [step] ss_c5_conv_last_wgrad_df (d feat ready-made, fc gradients elsewhere)
+//   conv_wgrad_kernel<C2, C3, ..>        [step] ss_c5_conv_wgrad(3), ss_c5_conv_wgrad_ws(3)
+//   conv_wgrad_kernel<C1, C2, .., RC>    [step] ss_c5_conv2_wgrad_rc, ss_c5_conv2_wgrad_rc_ws (input recomputed from the frame)
+//   wgrad_reduce_kernel                  [step] behind the _ws / _df forms: folds the workgroups' partial sums
+//   conv_dgrad_kernel<C2, C3, ..>        [step] ss_c5_conv_dgrad(3)
+//   conv_last_dgrad_ws_kernel            [step] ss_c5_conv_last_dgrad_df (weights stationary in registers)
+//   conv2_dgrad_w1_kernel                [step] ss_c5_conv2_dgrad_conv1_wgrad_i1; ss_c5_conv2_dgrad_conv1_wgrad (winners recomputed)
+//   conv_wgrad_kernel<C1, C2, ..>        ss_c5_conv_wgrad(2): layer 2 with its input read from HBM
+//   conv_wgrad_kernel<C3, C4, ..>        ss_c5_conv_last_wgrad: d feat and the fc gradients made per frame in the kernel
+//   conv_dgrad_kernel<C1, C2, ..>        ss_c5_conv_dgrad(2): d a1 to HBM
+//   conv_dgrad_kernel<C3, C4, .., LAST>  ss_c5_conv_last_dgrad: weights in LDS, d feat from d z per frame
+//   conv1_wgrad_kernel                   ss_c5_conv1_wgrad: reads d a1 from HBM
+// What the measurements behind these forms showed, and which shared routines the compiler did not take at which site:
+// docs/LAB_NOTES.md 8c and 13.
 #include <stdlib.h>
 
 #include "cnn_bf16.h"
@@ -23,18 +40,6 @@ namespace {
 using namespace c5;
 
 STAMP_TABLE(ss_debug_stamps_c5_bwd)
-
-__device__ __forceinline__ void zero_lds(void* base, int bytes, int tid) {
-  uint4* p = reinterpret_cast<uint4*>(base);
-  for (int q = tid; q < bytes / 16; q += NT) p[q] = uint4{0u, 0u, 0u, 0u};
-}
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-__device__ __forceinline__ s16x8 tr_pair(const bf16_t* lo, const bf16_t* hi) {
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo);
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)hi);
-  return s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 
 struct ConvBwdParams {
   int N;
@@ -60,84 +65,6 @@ struct ConvBwdParams {
   const float *w1, *b1;   // conv1
 };
 
-// dense dy rows [y0, y0 + rows) of a pooled layer into an LDS image whose local row 0 is y0 (rows outside the frame: zeros)
-//   dst(yl, x) = img + off0 + yl * RS + x * PS
-template <int COUT, int H, int W>
-__device__ __forceinline__ void expand_dy(const bf16_t* __restrict__ da, const uint8_t* __restrict__ idx, bf16_t* img, int off0, int RS,
-                                          int PS, int y0, int rows, int tid) {
-  constexpr int WO = W / 2, CH = COUT / 8;
-  for (int q = tid; q < rows * WO * CH; q += NT) {
-    const int c8 = q % CH, xp = (q / CH) % WO, yl = q / (CH * WO);
-    const int y = y0 + yl;
-    uint4 v0 = {0u, 0u, 0u, 0u}, v1 = v0;
-    if (y >= 0 && y < H) {
-      const long src = ((long)(y >> 1) * WO + xp) * COUT + 8 * c8;
-      const uint4 dv = *reinterpret_cast<const uint4*>(da + src);
-      const uint2 iv = *reinterpret_cast<const uint2*>(idx + src);
-      const unsigned d[4] = {dv.x, dv.y, dv.z, dv.w};
-      const unsigned e0 = (unsigned)(y & 1) * 2u;
-      unsigned o0[4], o1[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {  // channels 2k, 2k+1
-        const unsigned ib = (k < 2 ? iv.x : iv.y) >> (16 * (k & 1));
-        const unsigned ia = ib & 255u, ic = (ib >> 8) & 255u;
-        const unsigned lo = d[k] & 0xffffu, hi = d[k] & 0xffff0000u;
-        o0[k] = (ia == e0 ? lo : 0u) | (ic == e0 ? hi : 0u);
-        o1[k] = (ia == e0 + 1u ? lo : 0u) | (ic == e0 + 1u ? hi : 0u);
-      }
-      v0 = uint4{o0[0], o0[1], o0[2], o0[3]};
-      v1 = uint4{o1[0], o1[1], o1[2], o1[3]};
-    }
-    bf16_t* dst = img + off0 + yl * RS + (2 * xp) * PS + 8 * c8;
-    *reinterpret_cast<uint4*>(dst) = v0;
-    *reinterpret_cast<uint4*>(dst + PS) = v1;
-  }
-}
-
-// last layer: dy[P][co] = mask[P][co] ? dfeat[co] / (H*W) : 0, all pixels
-template <int COUT, int NPIX>
-__device__ __forceinline__ void expand_dy_last(const uint8_t* __restrict__ mask, const float* s_dfeat, bf16_t* img, int off0, int RS,
-                                               int PS, int W, int tid) {
-  constexpr int CH = COUT / 8;
-  for (int q = tid; q < NPIX * CH; q += NT) {
-    const int c8 = q % CH, P = q / CH;
-    const uint2 mv = *reinterpret_cast<const uint2*>(mask + (long)P * COUT + 8 * c8);
-    unsigned o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned mb = (k < 2 ? mv.x : mv.y) >> (16 * (k & 1));
-      const float a = (mb & 255u) ? s_dfeat[8 * c8 + 2 * k] : 0.f, b = ((mb >> 8) & 255u) ? s_dfeat[8 * c8 + 2 * k + 1] : 0.f;
-      o[k] = pack_bf16(a, b);
-    }
-    *reinterpret_cast<uint4*>(img + off0 + (P / W) * RS + (P % W) * PS + 8 * c8) = uint4{o[0], o[1], o[2], o[3]};
-  }
-}
-
-// rows [y0, y0 + rows) of an NHWC frame into a haloed LDS image whose local row -1 is y0 (frame rows outside [0,H): zeros)
-template <class IM, int HF>
-__device__ __forceinline__ void load_band(const bf16_t* __restrict__ src, bf16_t* img, int y0, int rows, int tid) {
-  constexpr int CH = IM::C / 8;
-  for (int q = tid; q < rows * IM::W * CH; q += NT) {
-    const int c8 = q % CH, x = (q / CH) % IM::W, yl = q / (CH * IM::W);
-    const int y = y0 + yl;
-    uint4 v = {0u, 0u, 0u, 0u};
-    if (y >= 0 && y < HF) v = *reinterpret_cast<const uint4*>(src + ((long)y * IM::W + x) * IM::C + 8 * c8);
-    *reinterpret_cast<uint4*>(img + IM::at(yl - 1, x) + 8 * c8) = v;
-  }
-}
-
-// d feat[co] = sum_e dz[e] wfc[e][co] / (H*W)  (gradient of Linear o global average)
-template <int COUT>
-__device__ __forceinline__ void last_dfeat(const ConvBwdParams& p, int n, float* s_dz, float* s_dfeat, float inv_hw, int tid) {
-  for (int e = tid; e < p.E; e += NT) s_dz[e] = p.dz[(long)n * p.ld_dz + e];
-  __syncthreads();
-  for (int c = tid; c < COUT; c += NT) {
-    float s = 0.f;
-    for (int e = 0; e < p.E; ++e) s += s_dz[e] * p.wfc[e * COUT + c];
-    s_dfeat[c] = s * inv_hw;
-  }
-}
-
 // ================================================================================================ wgrad
 // BH = rows of a band; WCO x WCI x WK = 8 waves: a wave owns COUT/16/WCO co tiles x CIN/16/WCI ci tiles (all 9 taps) and
 // every WK-th 32-pixel k step
@@ -148,50 +75,67 @@ __device__ __forceinline__ void last_dfeat(const ConvBwdParams& p, int n, float*
 // the per-frame "d z -> d feat (96 threads walking 64 rows of W_fc in global memory), fc gradients, dy image" stage at 19.9 k of
 // the kernel's 30.4 k cycles per frame: as three small GEMMs over all frames that work leaves the kernel (and its 12 registers
 // of fc partial sums leave an instantiation that sat at 256 registers and spilled).
+// LDS of conv_wgrad_kernel, byte offsets: the operand images of the walk, and the [co][ci][tap] f32 image the gradients leave
+// through afterwards, over the same bytes
+template <int CIN, int COUT, int W, int BH, bool RC = false>
+struct WgradLds {
+  using IA = Img<CIN, BH, W, true>;                             // haloed input band
+  static constexpr int PSD = COUT + TR_PAD, RSD = W * PSD;      // dense dy band, no halo
+  static constexpr int DY = 0, DY_BYTES = BH * RSD * 2;
+  static constexpr int A = DY + DY_BYTES;                       // IA
+  static constexpr int ZEROS = A + IA::BYTES, ZB = 256;         // a pixel's worth of zeros (COUT <= 96 channels + the lane's piece): what pixels past the band read
+  static_assert((COUT + TR_PAD) * 2 <= ZB, "zero pixel");
+  static constexpr int DZ = ZEROS + ZB;                         // f32 [64]
+  static constexpr int DFEAT = DZ + 64 * 4;                     // f32 [96]
+  static constexpr int FEAT = DFEAT + 96 * 4;                   // f32 [96]
+  // RC: normalised bf16 frame [98][RS0], grey-level table, the 12 conv1 B fragments as [q][lane][8]
+  static constexpr int RC_IMG = FEAT + 96 * 4;
+  static constexpr int RC_XN = RC_IMG + FRAME_BYTES;
+  static constexpr int RC_BQ = RC_XN + 256 * 4;
+  static constexpr int OPERANDS = RC ? RC_BQ + 12 * 64 * 16 : RC_IMG;
+  // the flush image holds COUT/HALVES output channels at a time so that the last layer's 221 KB of gradients fit
+  static constexpr int HALVES = (COUT * CIN * 9 * 4 > 120 * 1024) ? 2 : 1, CO_H = COUT / HALVES;
+  static constexpr int FLUSH = CO_H * CIN * 9 * 4;
+  static_assert(CO_H % 16 == 0 && FLUSH <= 150 * 1024, "gradient image");
+  static constexpr int BYTES = OPERANDS > FLUSH ? OPERANDS : FLUSH;
+};
+
 template <int CIN, int COUT, int H, int W, bool LAST, int BH, int WCO, int WCI, int WK, bool RC = false, int MINW = 2, bool FCX = false>
 __global__ __launch_bounds__(NT, MINW) void conv_wgrad_kernel(ConvBwdParams p) {
   static_assert(WCO * WCI * WK == NW && H % BH == 0, "wave split");
   static_assert(!RC || (CIN == C1 && H == 48 && W == 48 && !LAST), "recompute form: layer 2");
   STAMP_ENTRY;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  using IA = Img<CIN, BH, W, true>;
-  constexpr int PSD = COUT + TR_PAD, RSD = W * PSD;      // dense dy band, no halo
-  constexpr int DY_BYTES = BH * RSD * 2;
+  using L = WgradLds<CIN, COUT, W, BH, RC>;
+  using IA = typename L::IA;
+  constexpr int PSD = L::PSD, RSD = L::RSD;
   constexpr int NCO = COUT / 16 / WCO, NCI = CIN / 16 / WCI;
   constexpr int NPIX = BH * W, NCH = (NPIX + 31) / 32;
-  bf16_t* dyi = reinterpret_cast<bf16_t*>(smem);
-  bf16_t* ai = reinterpret_cast<bf16_t*>(smem + DY_BYTES);
-  constexpr int ZB = 256;  // a pixel's worth of zeros (COUT <= 96 channels + the lane's piece): what pixels past the band read
-  float* s_dz = reinterpret_cast<float*>(smem + DY_BYTES + IA::BYTES + ZB);  // [64]
-  float* s_dfeat = s_dz + 64;                                                // [COUT]
-  float* s_feat = s_dfeat + 96;                                              // [COUT]
-  // RC: normalised bf16 frame [98][RS0], grey-level table, the 12 conv1 B fragments as [q][lane][8]
-  constexpr int o_rc = DY_BYTES + IA::BYTES + ZB + (64 + 96 + 96) * 4;
-  bf16_t* ximg = reinterpret_cast<bf16_t*>(smem + o_rc);
-  float* s_xn = reinterpret_cast<float*>(smem + o_rc + round_up(98 * RS0 * 2, 16));
-  bf16_t* bqs = reinterpret_cast<bf16_t*>(s_xn + 256);
+  bf16_t* dyi = reinterpret_cast<bf16_t*>(smem + L::DY);
+  bf16_t* ai = reinterpret_cast<bf16_t*>(smem + L::A);
+  float* s_dz = reinterpret_cast<float*>(smem + L::DZ);
+  float* s_dfeat = reinterpret_cast<float*>(smem + L::DFEAT);
+  float* s_feat = reinterpret_cast<float*>(smem + L::FEAT);
+  bf16_t* ximg = reinterpret_cast<bf16_t*>(smem + L::RC_IMG);
+  float* s_xn = reinterpret_cast<float*>(smem + L::RC_XN);
+  bf16_t* bqs = reinterpret_cast<bf16_t*>(smem + L::RC_BQ);
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, li = lane & 15;
-  // (wv as an SGPR -- readfirstlane, as in the forward kernels -- was measured here: the last layer's weight gradient 0.32 -> 0.47 ms)
+  // do not make wv an SGPR (readfirstlane, as in the forward kernels): measured slower here (docs/LAB_NOTES.md 13); the other
+  // backward kernels of this file keep it in a VGPR for the same reason
   const int q4 = li >> 2, p4 = li & 3;
   const int wco = wv % WCO, wci = (wv / WCO) % WCI, wk = wv / (WCO * WCI);
   f32x4 bias1 = {0.f, 0.f, 0.f, 0.f};
   uint4 px[2];
-  auto load_px = [&](int n) {
-    const uint4* src = reinterpret_cast<const uint4*>(p.R + (long)n * HW0 * HW0);
-    px[0] = src[tid];
-    px[1] = (tid + NT < HW0 * HW0 / 16) ? src[tid + NT] : uint4{0u, 0u, 0u, 0u};
-  };
   if (RC) {
-    zero_lds(ximg, round_up(98 * RS0 * 2, 16), tid);
+    zero_lds(ximg, FRAME_BYTES, tid);
     if (wv == 0)
 #pragma unroll
       for (int q = 0; q < 12; ++q) *reinterpret_cast<s16x8*>(bqs + (q * 64 + lane) * 8) = conv1_bfrag(p.w1, q, g, li);
     bias1 = *reinterpret_cast<const f32x4*>(p.b1 + 4 * g);  // channels 4g .. 4g+3 (conv1_rows)
-    if ((int)blockIdx.x < p.N) load_px(blockIdx.x);
+    if ((int)blockIdx.x < p.N) frame_px_load(p.R, blockIdx.x, tid, px);
   }
-  static_assert((COUT + TR_PAD) * 2 <= ZB, "zero pixel");
-  zero_lds(smem, DY_BYTES + IA::BYTES + ZB, tid);
+  zero_lds(smem, L::DZ, tid);
 
   f32x4 acc[NCO][NCI][9];
   f32x4 accb[NCO];
@@ -221,10 +165,10 @@ __global__ __launch_bounds__(NT, MINW) void conv_wgrad_kernel(ConvBwdParams p) {
   constexpr int NCHW = (NCH + WK - 1) / WK;
   constexpr bool PRE = RC && NCHW <= 3;
   const bf16_t* lds_b = reinterpret_cast<const bf16_t*>(smem);
-  const bf16_t* zeros = reinterpret_cast<const bf16_t*>(smem + DY_BYTES + IA::BYTES);
+  const bf16_t* zeros = reinterpret_cast<const bf16_t*>(smem + L::ZEROS);
   int o_dy0[PRE ? NCHW : 1], o_dy1[PRE ? NCHW : 1], o_a0[PRE ? NCHW : 1], o_a1[PRE ? NCHW : 1];
   if constexpr (PRE) {
-    const int z_off = (DY_BYTES + IA::BYTES) / 2, a_off = DY_BYTES / 2;  // element offsets of `zeros` and `ai`
+    const int z_off = L::ZEROS / 2, a_off = L::A / 2;  // element offsets of `zeros` and `ai`
 #pragma unroll
     for (int k = 0; k < NCHW; ++k) {
       const int ch = wk + k * WK;
@@ -255,10 +199,7 @@ __global__ __launch_bounds__(NT, MINW) void conv_wgrad_kernel(ConvBwdParams p) {
   for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
     STAMP(15);
     if (RC) {  // the frame's normalised image (statistics from the forward pass), once per frame
-      if (tid < 256) {
-        const float rr = (float)tid / 255.0f;
-        s_xn[tid] = p.standardize ? (rr - p.st[2 * (long)n]) / p.st[2 * (long)n + 1] : rr;
-      }
+      xn_table(s_xn, p.standardize, p.st + 2 * (long)n, tid);
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
@@ -273,7 +214,7 @@ __global__ __launch_bounds__(NT, MINW) void conv_wgrad_kernel(ConvBwdParams p) {
             for (int b = 0; b < 4; ++b) dst[4 * e + b] = to_bf16(s_xn[(wds[e] >> (8 * b)) & 255u]);
         }
       }
-      if (n + (int)gridDim.x < p.N) load_px(n + gridDim.x);
+      if (n + (int)gridDim.x < p.N) frame_px_load(p.R, n + gridDim.x, tid, px);
       __syncthreads();
     }
     STAMP(0);
@@ -286,11 +227,7 @@ __global__ __launch_bounds__(NT, MINW) void conv_wgrad_kernel(ConvBwdParams p) {
         if (tid < p.E) s_dz[tid] = pm.dz;
         if (tid < COUT) s_feat[tid] = pm.ft;
         __syncthreads();
-        for (int c = tid; c < COUT; c += NT) {  // d feat[co] = sum_e dz[e] wfc[e][co] / (H*W)
-          float s = 0.f;
-          for (int e = 0; e < p.E; ++e) s += s_dz[e] * p.wfc[e * COUT + c];
-          s_dfeat[c] = s * (1.0f / (float)(H * W));
-        }
+        dfeat_from_dz<COUT>(s_dz, p.wfc, p.E, 1.0f / (float)(H * W), s_dfeat, tid);
 #pragma unroll
         for (int k = 0; k < FCN; ++k) {
           const int q = tid + k * NT;
@@ -374,11 +311,9 @@ __global__ __launch_bounds__(NT, MINW) void conv_wgrad_kernel(ConvBwdParams p) {
   // order: (i) the WK waves that share a tile set (K split) are summed there first -- 256 workgroups x 8 waves of float atomics
   // onto the 4.6 k addresses of a small layer serialise at the memory side; (ii) an accumulator register holds elements that lie
   // 36 bytes apart (ci) in 4 rows (co): as global atomics that is 64 scattered dwords per wave instruction, 17x below the rate of
-  // 256 contiguous bytes (MI355X_MICROARCH.md, global float atomics: 0.7 ms of the last layer's 1.0 ms).  The image holds
-  // COUT/HALVES output channels at a time so that the last layer's 221 KB of gradients fit.
+  // 256 contiguous bytes (MI355X_MICROARCH.md, global float atomics: 0.7 ms of the last layer's 1.0 ms).
   float* redw = reinterpret_cast<float*>(smem);  // the operand images are dead
-  constexpr int HALVES = (COUT * CIN * 9 * 4 > 120 * 1024) ? 2 : 1, CO_H = COUT / HALVES;
-  static_assert(CO_H % 16 == 0 && CO_H * CIN * 9 * 4 <= 150 * 1024, "gradient image");
+  constexpr int HALVES = L::HALVES, CO_H = L::CO_H;
 #pragma unroll
   for (int hf = 0; hf < HALVES; ++hf) {
     // The WK waves that share a tile set add their sums one after the other with plain read-modify-writes (an element has one owner
@@ -461,32 +396,35 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   *dst += s0;
 }
 
-template <int CIN, int COUT, int W, int BH, bool RC = false>
-constexpr int wgrad_lds() {
-  const int operands = BH * W * (COUT + TR_PAD) * 2 + Img<CIN, BH, W, true>::BYTES + 256 + (64 + 96 + 96) * 4 +
-                       (RC ? round_up(98 * RS0 * 2, 16) + 256 * 4 + 12 * 64 * 16 : 0);
-  const int halves = (COUT * CIN * 9 * 4 > 120 * 1024) ? 2 : 1;
-  const int flush = COUT / halves * CIN * 9 * 4;  // the [co][ci][tap] image the gradients leave through
-  return operands > flush ? operands : flush;
-}
-
 // ================================================================================================ dgrad
 // STAGE: the band's result goes through LDS and leaves in 16-byte pieces; without it (last layer: dy + 110 KB of weights
 // leave no room) every lane stores its 2-byte results itself -- 18 KB per frame, the smallest map of the net
+// LDS of conv_dgrad_kernel, byte offsets
+template <int CIN, int COUT, int W, int BH, bool STAGE>
+struct DgradLds {
+  using ID = Img<COUT, BH, W>;         // haloed dy band
+  using WM = Wmat<COUT, CIN>;          // [ci][tap' * COUT + co]
+  static constexpr int DY = 0;
+  static constexpr int WL = ID::BYTES;
+  static constexpr int OUT = WL + round_up(WM::BYTES, 16);          // STAGE: bf16 [BH*W][CIN]
+  static constexpr int DZ = OUT + (STAGE ? BH * W * CIN * 2 : 0);   // f32 [64]
+  static constexpr int DFEAT = DZ + 64 * 4;                         // f32 [96]
+  static constexpr int BYTES = DFEAT + 96 * 4;
+};
+
 template <int CIN, int COUT, int H, int W, bool LAST, int BH, int MT, bool STAGE>
 __global__ __launch_bounds__(NT, 2) void conv_dgrad_kernel(ConvBwdParams p) {
   static_assert(H % BH == 0 && (BH * W) % 16 == 0, "band split");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  using ID = Img<COUT, BH, W>;         // haloed dy band
-  using WM = Wmat<COUT, CIN>;          // [ci][tap' * COUT + co]
-  bf16_t* dyi = reinterpret_cast<bf16_t*>(smem);
-  bf16_t* wl = reinterpret_cast<bf16_t*>(smem + ID::BYTES);
-  constexpr int o_out = ID::BYTES + round_up(WM::BYTES, 16);
-  bf16_t* oa = reinterpret_cast<bf16_t*>(smem + o_out);                         // [BH*W][CIN]
-  float* s_dz = reinterpret_cast<float*>(smem + o_out + (STAGE ? BH * W * CIN * 2 : 0));  // [64]
-  float* s_dfeat = s_dz + 64;                                                   // [96]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, li = lane & 15;
-  // (wv as an SGPR -- readfirstlane, as in the forward kernels -- was measured here: the last layer's weight gradient 0.32 -> 0.47 ms)
+  using L = DgradLds<CIN, COUT, W, BH, STAGE>;
+  using ID = typename L::ID;
+  using WM = typename L::WM;
+  bf16_t* dyi = reinterpret_cast<bf16_t*>(smem + L::DY);
+  bf16_t* wl = reinterpret_cast<bf16_t*>(smem + L::WL);
+  bf16_t* oa = reinterpret_cast<bf16_t*>(smem + L::OUT);
+  float* s_dz = reinterpret_cast<float*>(smem + L::DZ);
+  float* s_dfeat = reinterpret_cast<float*>(smem + L::DFEAT);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, li = lane & 15;  // wv stays a VGPR (conv_wgrad_kernel)
 
   zero_lds(dyi, ID::BYTES, tid);
   for (int q = tid; q < CIN * WM::KP; q += NT) {
@@ -522,11 +460,7 @@ __global__ __launch_bounds__(NT, 2) void conv_dgrad_kernel(ConvBwdParams p) {
         } else {
           if (tid < p.E) s_dz[tid] = pm.dz;
           __syncthreads();
-          for (int c = tid; c < COUT; c += NT) {
-            float s = 0.f;
-            for (int e = 0; e < p.E; ++e) s += s_dz[e] * p.wfc[e * COUT + c];
-            s_dfeat[c] = s * (1.0f / (float)(H * W));
-          }
+          dfeat_from_dz<COUT>(s_dz, p.wfc, p.E, 1.0f / (float)(H * W), s_dfeat, tid);
         }
         __syncthreads();
         pm.commit(s_dfeat, dyi, ID::at(0, 0), ID::RS, ID::PS, W, tid);
@@ -704,11 +638,6 @@ __global__ __launch_bounds__(NT, 2) void conv_last_dgrad_ws_kernel(ConvLastDgrad
   }
 }
 
-template <int CIN, int COUT, int W, int BH, bool STAGE>
-constexpr int dgrad_lds() {
-  return Img<COUT, BH, W>::BYTES + round_up(Wmat<COUT, CIN>::BYTES, 16) + (STAGE ? BH * W * CIN * 2 : 0) + (64 + 96) * 4;
-}
-
 // ================================================================================================ conv1 wgrad
 struct Conv1BwdParams {
   const uint8_t* R;
@@ -732,25 +661,32 @@ struct Conv1BwdParams {
 // pixels, serves the odd ones.  288 MFMAs per frame instead of 83 k FMAs per lane-frame on the VALU (measured: 1.79 ms per
 // step for 4 % of the backward MACs).
 constexpr int C1_BR = 16;                       // pooled rows per band
-constexpr int C1_XS = 104;                      // row stride of the two haloed 98 x 98 images (elements)
-constexpr int C1_IMG = 98 * C1_XS;              // elements per image
+constexpr int C1_XS = RS0;                      // row stride of the two haloed 98 x 98 images (elements)
+constexpr int C1_IMG = FRAME_ELEMS;             // elements per image
 constexpr int C1_AE = C1_BR * 48 * C1;          // elements per masked image of a band
-constexpr int CONV1_WGRAD_LDS = 2 * C1_IMG * 2 + 4 * C1_AE * 2 + 256 * 4 + 16 * 16 * 4 + C1_BR * 48 * C1;
+struct Conv1WgradLds {                          // byte offsets
+  static constexpr int IMG_E = 0;                         // imgE[r][c] = xn haloed (r, c)
+  static constexpr int IMG_O = IMG_E + C1_IMG * 2;        // imgO[r][c] = xn haloed (r, c + 2)
+  static constexpr int AE = IMG_O + C1_IMG * 2;           // bf16 [4][C1_BR * 48][16]
+  static constexpr int XN = AE + 4 * C1_AE * 2;           // f32 [256]
+  static constexpr int RED = XN + 256 * 4;                // f32 [16 c][16]: 9 weights + 1 bias per channel
+  static constexpr int IBL = RED + 16 * 16 * 4;           // u8 [C1_BR][48][16] recomputed pool winners of the band
+  static constexpr int BYTES = IBL + C1_BR * 48 * C1;
+};
 
 __global__ __launch_bounds__(NT, 2) void conv1_wgrad_kernel(Conv1BwdParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int HP = HW0 / 2;
-  bf16_t* imgE = reinterpret_cast<bf16_t*>(smem);           // imgE[r][c] = xn haloed (r, c)
-  bf16_t* imgO = imgE + C1_IMG;                             // imgO[r][c] = xn haloed (r, c + 2)
-  bf16_t* ae = imgO + C1_IMG;                               // [4][C1_BR * 48][16]
-  float* s_xn = reinterpret_cast<float*>(ae + 4 * C1_AE);   // [256]
-  float* s_red = s_xn + 256;                                // [16 c][16]: 9 weights + 1 bias per channel
-  uint8_t* ibl = reinterpret_cast<uint8_t*>(s_red + 16 * 16);  // [C1_BR][48][16] recomputed pool winners of the band
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, li = lane & 15;
-  // (wv as an SGPR -- readfirstlane, as in the forward kernels -- was measured here: the last layer's weight gradient 0.32 -> 0.47 ms)
+  using L = Conv1WgradLds;
+  bf16_t* imgE = reinterpret_cast<bf16_t*>(smem + L::IMG_E);
+  bf16_t* imgO = reinterpret_cast<bf16_t*>(smem + L::IMG_O);
+  bf16_t* ae = reinterpret_cast<bf16_t*>(smem + L::AE);
+  float* s_xn = reinterpret_cast<float*>(smem + L::XN);
+  float* s_red = reinterpret_cast<float*>(smem + L::RED);
+  uint8_t* ibl = smem + L::IBL;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, li = lane & 15;  // wv stays a VGPR (conv_wgrad_kernel)
   const int q4 = li >> 2, p4 = li & 3;
   const bool rc = p.i1 == nullptr;
-  static_assert(C1_XS == RS0, "conv1_rows reads the image with row stride RS0");
   s16x8 bq[12];
   float bias1 = 0.f;
   if (rc) {
@@ -758,7 +694,7 @@ __global__ __launch_bounds__(NT, 2) void conv1_wgrad_kernel(Conv1BwdParams p) {
     for (int q = 0; q < 12; ++q) bq[q] = conv1_bfrag(p.w1, q, g, li);
     bias1 = p.b1[li];
   }
-  zero_lds(smem, 2 * C1_IMG * 2, tid);
+  zero_lds(smem, L::AE, tid);
   f32x4 acc[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -774,11 +710,6 @@ __global__ __launch_bounds__(NT, 2) void conv1_wgrad_kernel(Conv1BwdParams p) {
   constexpr int NB = C1_BR * HP * 2 / NT;  // staging items (8 channels of a pooled pixel) per thread and band
   static_assert(NB * NT == C1_BR * HP * 2, "band items");
   uint4 px[2];
-  auto load_px = [&](int n) {
-    const uint4* src = reinterpret_cast<const uint4*>(p.R + (long)n * HW0 * HW0);
-    px[0] = src[tid];
-    px[1] = (tid + NT < HW0 * HW0 / 16) ? src[tid + NT] : uint4{0u, 0u, 0u, 0u};
-  };
   uint4 dpre[NB];
   uint2 ipre[NB];
   auto issue_band = [&](int n, int r0) {
@@ -791,15 +722,12 @@ __global__ __launch_bounds__(NT, 2) void conv1_wgrad_kernel(Conv1BwdParams p) {
     }
   };
   if ((int)blockIdx.x < p.N) {
-    load_px(blockIdx.x);
+    frame_px_load(p.R, blockIdx.x, tid, px);
     issue_band(blockIdx.x, 0);
   }
 
   for (int n = blockIdx.x; n < p.N; n += gridDim.x) {
-    if (tid < 256) {
-      const float rr = (float)tid / 255.0f;
-      s_xn[tid] = p.standardize ? (rr - p.st[2 * (long)n]) / p.st[2 * (long)n + 1] : rr;
-    }
+    xn_table(s_xn, p.standardize, p.st + 2 * (long)n, tid);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -852,7 +780,7 @@ __global__ __launch_bounds__(NT, 2) void conv1_wgrad_kernel(Conv1BwdParams p) {
         const int nn = last_band ? n + (int)gridDim.x : n;
         if (nn < p.N) {
           issue_band(nn, last_band ? 0 : r0 + C1_BR);
-          if (last_band) load_px(nn);
+          if (last_band) frame_px_load(p.R, nn, tid, px);
         }
       }
       for (int ch = wv; ch < C1_BR * HP / 32; ch += NW) {
@@ -861,11 +789,7 @@ __global__ __launch_bounds__(NT, 2) void conv1_wgrad_kernel(Conv1BwdParams p) {
         // patch row vy = p4 of the window: haloed image row 2 yq + p4, haloed columns 2 xq .. 2 xq + 3
         const bf16_t* v0 = ((x0 & 1) ? imgO - 2 : imgE) + (2 * y0 + p4) * C1_XS + 2 * x0;
         const bf16_t* v1 = ((x1 & 1) ? imgO - 2 : imgE) + (2 * y1 + p4) * C1_XS + 2 * x1;
-        const s16x8 fb = tr_pair(v0, v1);
-        const bf16_t* a0 = ae + P0 * C1 + 4 * p4;
-        const bf16_t* a1 = ae + P1 * C1 + 4 * p4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = mfma_bf16(tr_pair(a0 + e * C1_AE, a1 + e * C1_AE), fb, acc[e]);
+        conv1_wgrad_kstep(v0, v1, ae + P0 * C1 + 4 * p4, ae + P1 * C1 + 4 * p4, C1_AE, acc);
       }
       __syncthreads();
     }
@@ -915,26 +839,33 @@ struct Conv2DgradW1Params {
 constexpr int F_BH = 8;                                             // rows of d a1 per band
 using F_ID = Img<C2, F_BH, 48>;                                     // haloed dy2 band
 using F_WM = Wmat<C2, C1>;                                          // [ci][tap' * 32 + co]
-constexpr int F_O_W = F_ID::BYTES;
-constexpr int F_O_IMG = F_O_W + round_up(F_WM::BYTES, 16);          // imgE, imgO
 constexpr int F_AE = F_BH * 48 * C1;                                // elements per slot-masked image of a band
-constexpr int F_O_AE = F_O_IMG + 2 * C1_IMG * 2;
-constexpr int F_O_XN = F_O_AE + 4 * F_AE * 2;                       // [256] f32, then s_red [256] f32, then ibl bytes
-constexpr int CONV2_DGRAD_W1_LDS = F_O_XN + 256 * 4 + 256 * 4 + F_BH * 48 * C1;
-static_assert(CONV2_DGRAD_W1_LDS <= 160 * 1024, "LDS");
+struct Conv2DgradW1Lds {                                            // byte offsets
+  static constexpr int DY = 0;                                      // F_ID
+  static constexpr int WL = DY + F_ID::BYTES;                       // F_WM
+  static constexpr int IMG_E = WL + round_up(F_WM::BYTES, 16);      // as conv1_wgrad_kernel's two images
+  static constexpr int IMG_O = IMG_E + C1_IMG * 2;
+  static constexpr int AE = IMG_O + C1_IMG * 2;                     // bf16 [4 slots][8 * 48 pooled pixels][16 channels]
+  static constexpr int XN = AE + 4 * F_AE * 2;                      // f32 [256]
+  static constexpr int RED = XN + 256 * 4;                          // f32 [16 c][16]
+  static constexpr int IBL = RED + 256 * 4;                         // u8 [8][48][16] pool winners of the band
+  static constexpr int BYTES = IBL + F_BH * 48 * C1;
+};
+static_assert(Conv2DgradW1Lds::BYTES <= 160 * 1024, "LDS");
 
 __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Params p) {
   STAMP_ENTRY;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int HP = 48, H = 48, W = 48;
-  bf16_t* dyi = reinterpret_cast<bf16_t*>(smem);
-  bf16_t* wl = reinterpret_cast<bf16_t*>(smem + F_O_W);
-  bf16_t* imgE = reinterpret_cast<bf16_t*>(smem + F_O_IMG);
-  bf16_t* imgO = imgE + C1_IMG;
-  bf16_t* ae = reinterpret_cast<bf16_t*>(smem + F_O_AE);             // [4 slots][8 * 48 pooled pixels][16 channels]
-  float* s_xn = reinterpret_cast<float*>(smem + F_O_XN);
-  float* s_red = s_xn + 256;
-  uint8_t* ibl = reinterpret_cast<uint8_t*>(s_red + 256);            // [8][48][16] recomputed pool winners of the band
+  using L = Conv2DgradW1Lds;
+  bf16_t* dyi = reinterpret_cast<bf16_t*>(smem + L::DY);
+  bf16_t* wl = reinterpret_cast<bf16_t*>(smem + L::WL);
+  bf16_t* imgE = reinterpret_cast<bf16_t*>(smem + L::IMG_E);
+  bf16_t* imgO = reinterpret_cast<bf16_t*>(smem + L::IMG_O);
+  bf16_t* ae = reinterpret_cast<bf16_t*>(smem + L::AE);
+  float* s_xn = reinterpret_cast<float*>(smem + L::XN);
+  float* s_red = reinterpret_cast<float*>(smem + L::RED);
+  uint8_t* ibl = smem + L::IBL;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4, li = lane & 15;
   const int q4 = li >> 2, p4 = li & 3;
 
@@ -943,7 +874,7 @@ __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Param
   for (int q = 0; q < 12; ++q) bq[q] = conv1_bfrag(p.w1, q, g, li);
   const float bias_li = p.b1[li];
   zero_lds(dyi, F_ID::BYTES, tid);
-  zero_lds(imgE, 2 * C1_IMG * 2, tid);
+  zero_lds(imgE, L::AE - L::IMG_E, tid);
   for (int q = tid; q < C1 * F_WM::KP; q += NT) {  // flipped, transposed conv2 weights (conv_dgrad_kernel)
     const int ci = q / F_WM::KP, kk = q % F_WM::KP, tap = kk / C2, co = kk % C2;
     wl[ci * F_WM::LD + kk] = to_bf16(tap < 9 ? p.w2[((long)co * C1 + ci) * 9 + (8 - tap)] : 0.f);
@@ -954,11 +885,6 @@ __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Param
   f32x4 gb = {0.f, 0.f, 0.f, 0.f};  // bias gradient of channels 4g .. 4g+3 (the lane's four rows of the transposed product)
 
   uint4 px[2];
-  auto load_px = [&](int n) {
-    const uint4* src = reinterpret_cast<const uint4*>(p.R + (long)n * HW0 * HW0);
-    px[0] = src[tid];
-    px[1] = (tid + NT < HW0 * HW0 / 16) ? src[tid + NT] : uint4{0u, 0u, 0u, 0u};
-  };
   ExpandLoad<C2, H, W, F_BH + 2> pe;
   // the band's pool winners (8 rows x 48 pixels x 16 channels = 384 x 16 bytes) ride with the band's other loads when the forward
   // pass left them in HBM
@@ -968,7 +894,7 @@ __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Param
     if (p.i1 && tid < F_BH * 48) iw = reinterpret_cast<const uint4*>(p.i1 + ((long)n * HP + y0) * HP * C1)[tid];
   };
   if ((int)blockIdx.x < p.N) {
-    load_px(blockIdx.x);
+    frame_px_load(p.R, blockIdx.x, tid, px);
     issue(blockIdx.x, 0);
   }
   __syncthreads();
@@ -993,10 +919,7 @@ __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Param
     // ---- the frame's normalised image, twice (conv1_wgrad_kernel).  The last band's MFMAs of the previous frame still read the
     // images: a barrier in front (the frame loop has two barriers per band and none behind the last one)
     __syncthreads();
-    if (tid < 256) {
-      const float rr = (float)tid / 255.0f;
-      s_xn[tid] = p.standardize ? (rr - p.st[2 * (long)n]) / p.st[2 * (long)n + 1] : rr;
-    }
+    xn_table(s_xn, p.standardize, p.st + 2 * (long)n, tid);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -1039,7 +962,7 @@ __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Param
         const int nn = last_band ? n + (int)gridDim.x : n;
         if (nn < p.N) {
           issue(nn, last_band ? 0 : y0 + F_BH);
-          if (last_band) load_px(nn);
+          if (last_band) frame_px_load(p.R, nn, tid, px);
         }
       }
       // ---- d a1 rows y0 .. y0+7, one unit of 3 m tiles per wave, as a TRANSPOSED product (weights = A operand): the lane ends up
@@ -1086,16 +1009,12 @@ __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Param
       STAMP(3);
       __syncthreads();
       STAMP(5);
-      // ---- conv1's weight gradient over the band: 12 k steps of 32 pooled pixels (conv1_wgrad_kernel's routine)
+      // ---- conv1's weight gradient over the band: 12 k steps of 32 pooled pixels (conv1_wgrad_kstep, as conv1_wgrad_kernel)
 #pragma unroll
       for (int k = 0; k < F_NCH; ++k) {
         if (wv + k * NW >= F_BH * HP / 32) break;  // wave-uniform
         const int boff = 2 * y0 * C1_XS;           // the band's rows of the frame images
-        const s16x8 fb = tr_pair(imgE + o_v0[k] + boff, imgE + o_v1[k] + boff);
-        const bf16_t* a0 = ae + o_ae0[k];
-        const bf16_t* a1 = a0 + 4 * C1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc1[e] = mfma_bf16(tr_pair(a0 + e * F_AE, a1 + e * F_AE), fb, acc1[e]);
+        conv1_wgrad_kstep(imgE + o_v0[k] + boff, imgE + o_v1[k] + boff, ae + o_ae0[k], ae + o_ae0[k] + 4 * C1, F_AE, acc1);
       }
       STAMP(8);
       // no barrier here: the next band's commit / winners rewrite the dy band and ibl, which this band read before its second
@@ -1103,7 +1022,7 @@ __global__ __launch_bounds__(NT, 2) void conv2_dgrad_w1_kernel(Conv2DgradW1Param
     }
   }
   STAMP_FLUSH();
-  // ---- fold the slots into the 3 x 3 taps, the waves through LDS, one atomic per element (conv1_wgrad_kernel)
+  // ---- fold the slots into the 3 x 3 taps, the waves through LDS, one atomic per element (as conv1_wgrad_kernel)
   __syncthreads();
   for (int q = tid; q < 16 * 16; q += NT) s_red[q] = 0.f;
   __syncthreads();
@@ -1150,9 +1069,9 @@ extern "C" int ss_c5_conv_wgrad_ws(int layer, const uint16_t* a_in, const uint16
   p.N = N; p.a_in = a_in; p.da_out = da_out; p.idx = idx; p.g_w = g_w; p.g_b = g_b;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (layer == 2)
-    return launch_wgrad(conv_wgrad_kernel<C1, C2, 48, 48, false, 16, 1, 1, 8>, p, wgrad_lds<C1, C2, 48, 16>(), N, C2 * C1 * 9, part, part_floats, s);
+    return launch_wgrad(conv_wgrad_kernel<C1, C2, 48, 48, false, 16, 1, 1, 8>, p, WgradLds<C1, C2, 48, 16>::BYTES, N, C2 * C1 * 9, part, part_floats, s);
   if (layer == 3)
-    return launch_wgrad(conv_wgrad_kernel<C2, C3, 24, 24, false, 24, 2, 2, 2>, p, wgrad_lds<C2, C3, 24, 24>(), N, C3 * C2 * 9, part, part_floats, s);
+    return launch_wgrad(conv_wgrad_kernel<C2, C3, 24, 24, false, 24, 2, 2, 2>, p, WgradLds<C2, C3, 24, 24>::BYTES, N, C3 * C2 * 9, part, part_floats, s);
   return SS_ERR_UNSUPPORTED;
 }
 extern "C" int ss_c5_conv_wgrad(int layer, const uint16_t* a_in, const uint16_t* da_out, const uint8_t* idx, int N, float* g_w,
@@ -1168,7 +1087,7 @@ extern "C" int ss_c5_conv2_wgrad_rc_ws(const uint8_t* R, const float* st, int st
   SS_REQUIRE((reinterpret_cast<uintptr_t>(part) & 15) == 0 && (reinterpret_cast<uintptr_t>(g_w) & 15) == 0, SS_ERR_ARG);
   ConvBwdParams p{};
   p.N = N; p.da_out = da_out; p.idx = idx; p.g_w = g_w; p.g_b = g_b; p.R = R; p.st = st; p.standardize = standardize; p.w1 = w1; p.b1 = b1;
-  return launch_wgrad(conv_wgrad_kernel<C1, C2, 48, 48, false, 16, 1, 1, 8, true>, p, wgrad_lds<C1, C2, 48, 16, true>(), N, C2 * C1 * 9,
+  return launch_wgrad(conv_wgrad_kernel<C1, C2, 48, 48, false, 16, 1, 1, 8, true>, p, WgradLds<C1, C2, 48, 16, true>::BYTES, N, C2 * C1 * 9,
                       part, part_floats, static_cast<hipStream_t>(stream));
 }
 extern "C" int ss_c5_conv2_wgrad_rc(const uint8_t* R, const float* st, int standardize, const float* w1, const float* b1,
@@ -1185,7 +1104,7 @@ extern "C" int ss_c5_conv2_dgrad_conv1_wgrad_i1(const uint16_t* da2, const uint8
   SS_REQUIRE(da2 && i2 && w2 && R && st && w1 && b1 && g_w1 && g_b1 && N > 0, SS_ERR_ARG);
   SS_REQUIRE((reinterpret_cast<uintptr_t>(i1) & 15) == 0, SS_ERR_ARG);
   Conv2DgradW1Params p{N, da2, i2, w2, R, st, standardize, w1, b1, da1, g_w1, g_b1, i1};
-  return launch_persistent(conv2_dgrad_w1_kernel, p, CONV2_DGRAD_W1_LDS, N, static_cast<hipStream_t>(stream));
+  return launch_persistent(conv2_dgrad_w1_kernel, p, Conv2DgradW1Lds::BYTES, N, static_cast<hipStream_t>(stream));
 }
 extern "C" int ss_c5_conv2_dgrad_conv1_wgrad(const uint16_t* da2, const uint8_t* i2, int N, const float* w2, const uint8_t* R,
                                              const float* st, int standardize, const float* w1, const float* b1, uint16_t* da1,
@@ -1199,8 +1118,8 @@ extern "C" int ss_c5_conv_dgrad(int layer, const uint16_t* da_out, const uint8_t
   ConvBwdParams p{};
   p.N = N; p.da_out = da_out; p.idx = idx; p.w = w; p.da_in = da_in;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (layer == 2) return launch_persistent(conv_dgrad_kernel<C1, C2, 48, 48, false, 8, 3, true>, p, dgrad_lds<C1, C2, 48, 8, true>(), N, s, 2);
-  if (layer == 3) return launch_persistent(conv_dgrad_kernel<C2, C3, 24, 24, false, 4, 2, true>, p, dgrad_lds<C2, C3, 24, 4, true>(), N, s, 2);
+  if (layer == 2) return launch_persistent(conv_dgrad_kernel<C1, C2, 48, 48, false, 8, 3, true>, p, DgradLds<C1, C2, 48, 8, true>::BYTES, N, s, 2);
+  if (layer == 3) return launch_persistent(conv_dgrad_kernel<C2, C3, 24, 24, false, 4, 2, true>, p, DgradLds<C2, C3, 24, 4, true>::BYTES, N, s, 2);
   return SS_ERR_UNSUPPORTED;
 }
 
@@ -1213,7 +1132,7 @@ extern "C" int ss_c5_conv_last_wgrad(const uint16_t* a_in, const float* dz, int 
   ConvBwdParams p{};
   p.N = N; p.a_in = a_in; p.dz = dz; p.ld_dz = ld_dz; p.E = E; p.wfc = wfc; p.mask = mask; p.feat = feat;
   p.g_w = g_w; p.g_b = g_b; p.g_wfc = g_wfc; p.g_bfc = g_bfc;
-  return launch_persistent(conv_wgrad_kernel<C3, C4, 12, 12, true, 12, 2, 4, 1>, p, wgrad_lds<C3, C4, 12, 12>(), N,
+  return launch_persistent(conv_wgrad_kernel<C3, C4, 12, 12, true, 12, 2, 4, 1>, p, WgradLds<C3, C4, 12, 12>::BYTES, N,
                            static_cast<hipStream_t>(stream));
 }
 
@@ -1225,7 +1144,7 @@ extern "C" int ss_c5_conv_last_wgrad_df(const uint16_t* a_in, const float* dfeat
   SS_REQUIRE((reinterpret_cast<uintptr_t>(part) & 15) == 0 && (reinterpret_cast<uintptr_t>(g_w) & 15) == 0, SS_ERR_ARG);
   ConvBwdParams p{};
   p.N = N; p.a_in = a_in; p.dfeat = dfeat; p.mask = mask; p.g_w = g_w; p.g_b = g_b;
-  return launch_wgrad(conv_wgrad_kernel<C3, C4, 12, 12, true, 12, 2, 4, 1, false, 2, true>, p, wgrad_lds<C3, C4, 12, 12>(), N,
+  return launch_wgrad(conv_wgrad_kernel<C3, C4, 12, 12, true, 12, 2, 4, 1, false, 2, true>, p, WgradLds<C3, C4, 12, 12>::BYTES, N,
                       C4 * C3 * 9, part, part_floats, static_cast<hipStream_t>(stream));
 }
 extern "C" int ss_c5_conv_last_dgrad_df(const float* dfeat, const uint8_t* mask, int N, const float* w, uint16_t* da_in,
@@ -1241,7 +1160,7 @@ extern "C" int ss_c5_conv_last_dgrad(const float* dz, int ld_dz, int E, const fl
   SS_REQUIRE(E > 0 && E <= 64 && ld_dz >= E, SS_ERR_UNSUPPORTED);
   ConvBwdParams p{};
   p.N = N; p.dz = dz; p.ld_dz = ld_dz; p.E = E; p.wfc = wfc; p.mask = mask; p.w = w; p.da_in = da_in;
-  return launch_persistent(conv_dgrad_kernel<C3, C4, 12, 12, true, 12, 3, false>, p, dgrad_lds<C3, C4, 12, 12, false>(), N,
+  return launch_persistent(conv_dgrad_kernel<C3, C4, 12, 12, true, 12, 3, false>, p, DgradLds<C3, C4, 12, 12, false>::BYTES, N,
                            static_cast<hipStream_t>(stream));
 }
 
@@ -1250,5 +1169,5 @@ extern "C" int ss_c5_conv1_wgrad(const uint8_t* R, int N, int standardize, const
   SS_REQUIRE(R && st && da1 && g_w1 && g_b1 && N > 0, SS_ERR_ARG);
   SS_REQUIRE(i1 || (w1 && b1), SS_ERR_ARG);  // stored pool winners, or the conv1 parameters to recompute them
   Conv1BwdParams p{R, N, standardize, st, da1, i1, w1, b1, g_w1, g_b1};
-  return launch_persistent(conv1_wgrad_kernel, p, CONV1_WGRAD_LDS, N, static_cast<hipStream_t>(stream));
+  return launch_persistent(conv1_wgrad_kernel, p, Conv1WgradLds::BYTES, N, static_cast<hipStream_t>(stream));
 }
