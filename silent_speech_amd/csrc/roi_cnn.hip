@@ -1,8 +1,19 @@
-// ROI normalise + TinyROICNN forward, fused: one persistent 512-thread workgroup per CU walks
+// ROI normalise + TinyROICNN forward, fused: two persistent 256-thread workgroups per CU walk
 // frames; a frame's uint8 pixels are read once from HBM and every activation stays in LDS.
 //
-// Replaces /root/reference/train_model_official.py:286-291 (normalise) and :212-229 (CNN); with
-// standardize = 0 the live variant /root/reference/live_infer_official.py:126-127.
+// Replaces the reference's train_model_official.py:286-291 (normalise) and :212-229 (CNN); with
+// standardize = 0 the live variant live_infer_official.py:126-127.
+//
+// Kernel:         roi_cnn_fwd_kernel<Geom<H, W>>, one instantiation per shape of SS_CNN_SHAPES (64 x 64, 48 x 96, 32 x 32);
+//                 the frame list (p.frames) and the stash (p.st_*) are run-time switches of the one kernel.
+// Entry points:   ss_roi_cnn_fwd_frames   everything: optional stash, optional frame list.  The f32 training step launches
+//                                         this one (engine.py, timing tag "ss_roi_cnn_fwd_stash"), with or without a list
+//                 ss_roi_cnn_fwd_stash    = _frames without a list
+//                 ss_roi_cnn_fwd          = _stash without a stash (inference)
+//                 ss_roi_cnn_stash_size   the six per-frame stash sizes of a shape
+//                 ss_roi_cnn_set_max_workgroups   grid cap of both ROI-CNN kernels (tests)
+// Shared with the backward: roi_cnn_geom.h (geometry, weight sizes, dispatch, device routines).  Measurements and the variants
+// that were tried and rejected: docs/LAB_NOTES.md sections 8 - 8c and 14.
 //
 //   stage 0  u8 frame -> exact integer sum / sum of squares -> mean, unbiased std (clamp 1e-6)
 //            -> xn = (u/255 - mu) / std  into a zero-haloed LDS image
@@ -32,14 +43,8 @@ extern "C" int ss_roi_cnn_set_max_workgroups(int n) {
 
 namespace {
 
-// (Round 3: 384 threads = two 6-wave workgroups per CU, a third wave per SIMD to fill the issue slots two leave empty -- MFMA
-// busy is 0.58 with each wave in MFMAs 29 % of its time.  168 registers per wave do not hold the 93 weight fragments plus a
-// stage's working set: 33 spilled, 719 us per launch against 459.  LDS (66 KB per frame image) rules out a third workgroup.
-// Also measured: the NEXT frame's pixel sums taken behind conv3, its mean / std by one thread of wave 1 beside the feature sums
-// and its grey-level table beside the fc -- three barriers and the serial f64 section out of a frame's front: 458.8 / 461.8 us
-// against 459.0 / 458.6.  And: conv2 / conv3 with two register sets of A values, the next nine k steps' ds_reads issued under the
-// current nine's MFMAs and the next unit's first nine under this unit's last (counted lgkmcnt waits in the ISA): 457.9 / 459.8
-// against 459.0 / 458.8.  A workgroup's own latency chain is not what bounds the CU's rate.)
+// A wave needs its 256 registers for the 93 weight fragments plus a stage's working set, and the LDS image rules out a third
+// workgroup: more waves per SIMD were tried and spilled (LAB_NOTES section 14, "384 threads").
 constexpr int NT = 256;  // threads per workgroup; TWO workgroups per CU (LDS image <= 80 KB): while one is in an epilogue, a
                          // barrier or the statistics, the other's MFMAs keep the matrix pipes busy
 constexpr int NWV = NT / 64;
@@ -62,10 +67,7 @@ struct CnnFwdParams {
   const int* frames;  // null, or [0] = how many frames to walk, [1 ...] their numbers (ss_roi_active_frames): padded frames are skipped
 };
 
-// MEASURED AND NOT USED (round 4, A/B on one box, tools/cnn_ab.py, 64 x 64: 437.7 us per launch against 427.3; 48 x 96: 535.1 /
-// 538.5): conv1 with the 2 x 2 max-pool inside ONE lane (M tile = four windows x four positions, K = 5 x 3 -> 16, a frame row
-// stride == 8 (mod 32)): its 128 extra MFMAs per frame cost what the 17 instructions saved per pooled output gain -- the same null
-// result as round 1's lane-local pool, now with the cheap epilogue.
+// (conv1 with the 2 x 2 max-pool inside one lane was measured twice and is no faster: LAB_NOTES section 14)
 
 // Diagnostic (-DSS_FWD_STOP=k, tools/fwd_stage_pmc.py): a frame ends behind stage k, so that the difference between two builds'
 // hardware counters is one stage's share (LDS bank conflicts per stage: rocprofv3 has no per-stage view of a persistent kernel).
@@ -88,8 +90,22 @@ struct FwdLds {
   static constexpr int o_m3 = o_a1;                      // bytes [P][32] conv3 sign mask, staged for the stash over the
                                                          // pooled-1 map (dead once conv2 is through)
   static_assert(8 * G::P <= 8 * G::P1, "mask staging fits the pooled-1 planes");
-  static constexpr int o_misc = o_a1 + 8 * G::P1 + 256;  // the 256 floats in front hold the grey-level table
-  static constexpr int total = o_misc + 512;
+  static constexpr int o_xn = o_a1 + 8 * G::P1;  // [256] normalised value of every uint8 level (own 256-float block)
+  static constexpr int o_misc = o_xn + 256, MISC_N = 512;
+  struct Misc {  // float offsets of the small per-frame values
+    static constexpr int b1 = o_misc;             // [8]
+    static constexpr int b2 = o_misc + 16;        // [16]
+    static constexpr int b3 = o_misc + 32;        // [24] (+8 pad)
+    static constexpr int feat = o_misc + 64;      // [24]
+    static constexpr int stat = o_misc + 96;      // mu, std
+    static constexpr int red = o_misc + 104;      // unsigned [NWV][2]
+    static constexpr int fp = o_misc + 128;       // [NWV][32] per-wave partial channel sums
+    static constexpr int cp = fp + NWV * 32;      // [NWV][32] per-wave counts of positive outputs
+    static_assert(b1 + 8 <= b2 && b2 + 16 <= b3 && b3 + 24 <= feat && feat + 24 <= stat && stat + 2 <= red && red + 2 * NWV <= fp &&
+                      cp + NWV * 32 <= o_misc + MISC_N, "misc slots overlap");
+  };
+  static constexpr int total = o_misc + MISC_N;
+  static_assert(total >= W2_N + W3_N, "weight staging area");
 };
 
 template <class G>
@@ -106,16 +122,16 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
   uint8_t* i1s = reinterpret_cast<uint8_t*>(lds + LL::o_i1);
   uint8_t* i2s = reinterpret_cast<uint8_t*>(lds + LL::o_i2);
   uint8_t* m3s = reinterpret_cast<uint8_t*>(lds + LL::o_m3);
-  float* misc = lds + LL::o_misc;
-  float* s_b1 = misc;                       // [8]
-  float* s_b2 = misc + 16;                  // [16]
-  float* s_b3 = misc + 32;                  // [24] (+8 pad)
-  float* s_feat = misc + 64;                // [24]
-  float* s_stat = misc + 96;                // mu, std
-  unsigned* s_red = reinterpret_cast<unsigned*>(misc + 104);  // [NWV][2]
-  float* s_fp = misc + 128;                 // [NWV][32] per-wave partial channel sums
-  float* s_cp = misc + 128 + NWV * 32;      // [NWV][32] per-wave counts of positive outputs
-  float* s_xn = misc - 256;                 // [256] normalised value of every uint8 level (own 256-float block)
+  using MS = typename LL::Misc;
+  float* s_b1 = lds + MS::b1;
+  float* s_b2 = lds + MS::b2;
+  float* s_b3 = lds + MS::b3;
+  float* s_feat = lds + MS::feat;
+  float* s_stat = lds + MS::stat;
+  unsigned* s_red = reinterpret_cast<unsigned*>(lds + MS::red);
+  float* s_fp = lds + MS::fp;
+  float* s_cp = lds + MS::cp;
+  float* s_xn = lds + LL::o_xn;
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int i = lane & 15, g = lane >> 4;
@@ -124,19 +140,18 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
   // ---- one-time: load weights into MFMA B fragments, zero LDS (halos).  W2 and W3 go through LDS (coalesced 16-byte loads, then
   // 90 ds_read_b32 per lane): read straight from global memory the 90 strided 4-byte loads per lane were most of the 30 k cycles
   // a workgroup spent in front of its frame loop (14 us of a 470 us launch, stage timers)
-  static_assert(LL::total >= 1152 + 3456, "weight staging area");
   if (((reinterpret_cast<uintptr_t>(p.w2) | reinterpret_cast<uintptr_t>(p.w3)) & 15) == 0) {  // (views of a flat bucket need not be)
     const f32x4* g2 = reinterpret_cast<const f32x4*>(p.w2);
     const f32x4* g3 = reinterpret_cast<const f32x4*>(p.w3);
-    for (int q = tid; q < 1152 / 4; q += NT) reinterpret_cast<f32x4*>(lds)[q] = g2[q];
-    for (int q = tid; q < 3456 / 4; q += NT) reinterpret_cast<f32x4*>(lds + 1152)[q] = g3[q];
+    for (int q = tid; q < W2_N / 4; q += NT) reinterpret_cast<f32x4*>(lds)[q] = g2[q];
+    for (int q = tid; q < W3_N / 4; q += NT) reinterpret_cast<f32x4*>(lds + W2_N)[q] = g3[q];
   } else {
-    for (int q = tid; q < 1152; q += NT) lds[q] = p.w2[q];
-    for (int q = tid; q < 3456; q += NT) lds[1152 + q] = p.w3[q];
+    for (int q = tid; q < W2_N; q += NT) lds[q] = p.w2[q];
+    for (int q = tid; q < W3_N; q += NT) lds[W2_N + q] = p.w3[q];
   }
-  __syncthreads();
+  __syncthreads();  // the staged weights are complete
   const float* w2s = lds;
-  const float* w3s = lds + 1152;
+  const float* w3s = lds + W2_N;
   // conv1: k = 4kk+g -> (ry = k/3, kx = k%3) over the 4x3 input window of output rows y, y+1;
   // column i = (c = i&7, s = i>>3): W1[c][ky = ry - s][kx], zero outside the 3x3 kernel
   float bw1[3];
@@ -149,7 +164,7 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
   }
   float bw2[18];  // conv2: k-step kk -> tap = kk/2, c = 4*(kk%2)+g ; n = i
 #pragma unroll
-  for (int kk = 0; kk < 18; ++kk) bw2[kk] = w2s[i * 72 + (4 * (kk & 1) + g) * 9 + (kk >> 1)];
+  for (int kk = 0; kk < 18; ++kk) bw2[kk] = w2s[i * W2_ROW + (4 * (kk & 1) + g) * 9 + (kk >> 1)];
   // conv3: 24 output channels on 16-wide tiles.  Channels 0..15 fill one tile (k-step kk: tap = kk/4, c = 4*(kk%4)+g; n = i).
   // Channels 16..23 would waste half of a second one (round 3: 25 % of conv3's MFMAs multiplied zero columns), so they share a
   // tile between the pixel rows y and y+1 -- column i = (channel 16 + (i&7), row y + (i>>3)) -- over the 4 x 3 window both rows
@@ -159,12 +174,12 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
 #pragma unroll
   for (int kk = 0; kk < 36; ++kk) {
     const int c = 4 * (kk & 3) + g, tap = kk >> 2;
-    bw3a[kk] = w3s[i * 144 + c * 9 + tap];
+    bw3a[kk] = w3s[i * W3_ROW + c * 9 + tap];
   }
 #pragma unroll
   for (int kk = 0; kk < 48; ++kk) {  // kk = (ry * 3 + kx) * 4 + cg
     const int c = 4 * (kk & 3) + g, ry = (kk >> 2) / 3, kx = (kk >> 2) % 3, ky = ry - (i >> 3);
-    bw3b[kk] = (ky >= 0 && ky <= 2) ? w3s[(16 + (i & 7)) * 144 + c * 9 + ky * 3 + kx] : 0.f;
+    bw3b[kk] = (ky >= 0 && ky <= 2) ? w3s[(16 + (i & 7)) * W3_ROW + c * 9 + ky * 3 + kx] : 0.f;
   }
   __syncthreads();
   for (int q = tid; q < LL::total; q += NT) lds[q] = 0.f;
@@ -183,16 +198,13 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
     }
   };
   // the frames this launch walks: all N, or the listed ones (rows of a clip's padding never reach the packed recurrence)
-  const int n_walk = p.frames ? min(p.frames[0], p.N) : p.N;
-  auto frame_at = [&](int it) { return p.frames ? (int)min((unsigned)p.frames[1 + it], (unsigned)(p.N - 1)) : it; };
+  const int n_walk = p.frames ? listed_count(p.frames, p.N) : p.N;
+  auto frame_at = [&](int it) { return p.frames ? listed_frame(p.frames, p.N, it) : it; };
   // frame numbers are read two frames ahead (a scalar load that misses would otherwise be waited for inside a stage)
   int n = (int)blockIdx.x < n_walk ? frame_at(blockIdx.x) : -1;
   int n_next = (int)(blockIdx.x + gridDim.x) < n_walk ? frame_at(blockIdx.x + gridDim.x) : -1, n_after = -1;
   if (n >= 0) load_frame(n);
-  // (Round 3 experiment: the second workgroup of every CU started 16 k / 32 k / 49 k cycles late, so that its vector-heavy stages
-  // -- statistics, conv1 -- would meet the first one's MFMA-heavy ones -- conv2, conv3 -- instead of its own kind: 471.8 / 469.7 /
-  // 473.2 us per launch against 462.6, i.e. the sleep itself and nothing else.  The two workgroups of a CU do not get in each
-  // other's way whatever their phase: each is bound by its own chain of reads, MFMAs and barriers, not by a shared pipe.)
+  // (the two workgroups of a CU need no phase shift against each other: the late-start experiment, LAB_NOTES section 14)
   STAMP_DECL;
 
   for (int it = blockIdx.x; it < n_walk; it += gridDim.x, n = n_next, n_next = n_after) {
@@ -243,8 +255,8 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
       }
     }
     __syncthreads();
-    if (tid < 256) s_xn[tid] = p.standardize ? (level_f - s_stat[0]) / s_stat[1] : level_f;  // one IEEE divide per grey level
-    __syncthreads();
+    if (tid < 256) s_xn[tid] = xn_of_level(level_f, p.standardize, s_stat);
+    __syncthreads();  // the table is complete
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
       const int q = tid + k * NT;
@@ -334,10 +346,7 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
           const unsigned long long r1c = (oc & S) | (rc & ~S), r0c = (rc & S) | (oc & ~S);
           const unsigned long long b0 = (t1 & r1c) | (~t1 & r0c);
           const float best = fmaxf(fmaxf(own, recv), 0.f);
-          int hi, bi;
-          unsigned long long carry_out;
-          asm("v_cndmask_b32_e64 %0, 0, 2, %1" : "=v"(hi) : "s"(t1));
-          asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(bi), "=s"(carry_out) : "v"(hi), "s"(b0));
+          const int bi = pool_index_byte(t1, b0);
           aw[8 * q] = best;
           iw[8 * q] = (uint8_t)bi;
         }
@@ -390,7 +399,7 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
       // The CU's other workgroup is usually in a different stage: while this wave streams MFMAs its issue slots must not
       // go to the partner's vector instructions (each holds the SIMD's issue port for 4+ cycles and the in-order wave
       // then misses its MFMA slot).  Raised priority through the MFMA-dense stages, the default for epilogue-heavy conv1,
-      // the statistics and the copies: 472 -> 462 us per launch, the largest single gain of the round for two lines.
+      // the statistics and the copies (472 -> 462 us per launch).
       __builtin_amdgcn_s_setprio(2);
       for (int u = wv; u < units; u += NWV) {
         const int yp = u / XT, xt = u % XT;
@@ -427,10 +436,7 @@ __global__ __launch_bounds__(NT, 2) void roi_cnn_fwd_kernel(CnnFwdParams p) {
           const unsigned long long t1 = __ballot(m1 > m0);  // strictly: ties go to the first in row-major order
           const unsigned long long b0 = (t1 & c1) | (~t1 & c0);
           const float best = fmaxf(fmaxf(m0, m1), 0.f);
-          int hi, bi;
-          unsigned long long carry_out;
-          asm("v_cndmask_b32_e64 %0, 0, 2, %1" : "=v"(hi) : "s"(t1));
-          asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(bi), "=s"(carry_out) : "v"(hi), "s"(b0));
+          const int bi = pool_index_byte(t1, b0);
           aw[e] = best;
           iw[16 * e] = (uint8_t)bi;
         }
@@ -561,22 +567,14 @@ extern "C" int ss_roi_cnn_fwd_frames(const uint8_t* R, int N, int H, int W, int 
   const bool any = st_a1 || st_i1 || st_a2 || st_i2 || st_m3 || st_feat;
   const bool all = st_a1 && st_i1 && st_a2 && st_i2 && st_m3 && st_feat;
   SS_REQUIRE(!any || (all && stash_sizes), SS_ERR_ARG);
-  CnnFwdParams p;
-  p.R = R; p.N = N; p.standardize = standardize;
-  p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.w3 = w3; p.b3 = b3; p.wfc = wfc; p.bfc = bfc;
-  p.E = E; p.out = out; p.ld_out = ld_out;
-  p.st_a1 = st_a1; p.st_i1 = st_i1; p.st_a2 = st_a2; p.st_i2 = st_i2; p.st_m3 = st_m3; p.st_feat = st_feat;
-  p.frames = frames;
+  const CnnFwdParams p{R,   N,      standardize, w1,    b1,    w2,    b2,    w3,    b3,      wfc,   bfc,
+                       E,   out,    ld_out,      st_a1, st_i1, st_a2, st_i2, st_m3, st_feat, frames};
   hipStream_t s = static_cast<hipStream_t>(stream);
-#define SS_DISPATCH(HH, WW)                                                                                      \
-  if (H == HH && W == WW) {                                                                                     \
-    using G_ = Geom<HH, WW>;                                                                                    \
-    SS_REQUIRE(!all || stash_sizes_match<G_>(stash_sizes), SS_ERR_ARG);                                         \
-    return launch_fwd<G_>(p, s);                                                                                \
-  }
-  SS_CNN_SHAPES(SS_DISPATCH)
-#undef SS_DISPATCH
-  return SS_ERR_UNSUPPORTED;
+  return for_geom(H, W, [&](auto geom) -> int {
+    using G = decltype(geom);
+    SS_REQUIRE(!all || stash_sizes_match<G>(stash_sizes), SS_ERR_ARG);
+    return launch_fwd<G>(p, s);
+  });
 }
 
 extern "C" int ss_roi_cnn_fwd_stash(const uint8_t* R, int N, int H, int W, int standardize, const float* w1,
@@ -591,14 +589,10 @@ extern "C" int ss_roi_cnn_fwd_stash(const uint8_t* R, int N, int H, int W, int s
 
 extern "C" int ss_roi_cnn_stash_size(int H, int W, int* sizes) {
   SS_REQUIRE(sizes, SS_ERR_ARG);
-#define SS_DISPATCH(HH, WW)               \
-  if (H == HH && W == WW) {               \
-    stash_sizes_of<Geom<HH, WW>>(sizes);  \
-    return SS_OK;                         \
-  }
-  SS_CNN_SHAPES(SS_DISPATCH)
-#undef SS_DISPATCH
-  return SS_ERR_UNSUPPORTED;
+  return for_geom(H, W, [&](auto geom) -> int {
+    stash_sizes_of<decltype(geom)>(sizes);
+    return SS_OK;
+  });
 }
 
 extern "C" int ss_roi_cnn_fwd(const uint8_t* R, int N, int H, int W, int standardize, const float* w1,

@@ -1,6 +1,14 @@
 // Backward of the fused ROI normalise + TinyROICNN block w.r.t. its eight parameter tensors
-// (the uint8 image has no gradient).  Autograd counterpart of
-// /root/reference/train_model_official.py:212-229 as driven by loss.backward() (:437).
+// (the uint8 image has no gradient).  Autograd counterpart of the reference's
+// train_model_official.py:212-229 as driven by loss.backward() (:437).
+//
+// Kernels:        roi_cnn_bwd_kernel<Geom<H, W>, LISTED>: the three shapes of SS_CNN_SHAPES (64 x 64, 48 x 96, 32 x 32) x
+//                 LISTED = false (walks frames 0 .. N-1) | true (walks the numbers in p.frames): six instantiations.
+// Entry points:   ss_roi_cnn_bwd_frames   picks LISTED by whether a frame list is passed.  The f32 training step launches this
+//                                         one (engine.py, timing tag "ss_roi_cnn_bwd"), with a list when the batch has padding
+//                 ss_roi_cnn_bwd          = _frames without a list
+// Shared with the forward: roi_cnn_geom.h (geometry, weight sizes, dispatch, device routines).  Measurements and the variants
+// that were tried and rejected: docs/LAB_NOTES.md sections 8b, 8c and 14.
 //
 // One persistent 512-thread workgroup per CU walks frames.  Per frame it reads the forward's stash
 // (pooled maps a1, a2, pool argmaxes, conv3 sign mask, averaged features: 67 KB for 64x64) plus the
@@ -21,7 +29,8 @@
 // Weight-gradient partial sums stay in registers for the whole frame walk (K = pixels split over the
 // 8 waves) and are reduced through LDS, then one float atomic per element per workgroup, at the end.
 //
-// Frame schedule (a frame starts at S1; seven workgroup barriers):
+// Frame schedule (a frame starts at S1; six workgroup barriers per frame: behind S1, D, behind T, behind S3, behind S4, E.
+// The front of the next frame runs per wave inside S5 and holds none):
 //   [E] pixels / pool-2 argmaxes out of staging | S1 (+ the pooled-1 map's DMA, + the NEXT frame's d_out row) | barrier |
 //   S2 | [D] phase switch T: the dy2 scatter (two barriers) | S3 (+ per wave, without a barrier, the two waves of a SIMD
 //   at different passes: the normalised frame, the pool-1 argmax bytes, dy2's zero columns, d feat of the next frame) |
@@ -50,8 +59,7 @@ struct BwdLds {
   // dy3 is pixel-major, pixel stride DS floats.  S2 reads the 16 pixels of a row tile with one ds_read_b128 (channels 4g .. 4g+3)
   // and one ds_read_b64 (channels 16+2g, 17+2g) per lane.  The hardware serves a b128 read in groups of 16 lanes that are pixels
   // 0-3 and 12-15 at chunk g with pixels 4-11 at chunk g + 1 (MI355X_MICROARCH.md, LDS table): conflict-free iff DS/4 == 2 (mod 4),
-  // i.e. 24 floats, no padding (round 2 had reasoned with 16 consecutive lanes and padded to 28: 2-way on the b128 reads,
-  // conflict-free on the b64 ones; A/B on one box: 716.6 -> 715.0 us per launch -- S2 is not LDS-bound any more either way)
+  // i.e. 24 floats, no padding (a pad to 28 is 2-way on the b128 reads: LAB_NOTES section 14)
   static constexpr int DS = 24;
   static constexpr int o_da2m = o_dy3h + DS * G::P2;
   static constexpr int o_i2b = o_da2m + 16 * G::P;
@@ -72,22 +80,44 @@ struct BwdLds {
   static constexpr int end2 = (o_i1b + 2 * I1SB + 3) & ~3;
   // W3 (13.8 KB) stays resident behind the phase area when the CU's 160 KB allow it; otherwise it lives in the
   // phase-1 part and is re-staged from L2 every frame
-  static constexpr int fixed = 192 * 16 + 512;             // w2t + misc
-  static constexpr bool W3_RESIDENT = ((end1a > end2 ? end1a : end2) + 3456 + fixed) * 4 <= 160 * 1024;
-  static constexpr int end1 = W3_RESIDENT ? end1a : end1a + 3456;
+  static constexpr int MISC_N = 512;
+  static constexpr int fixed = W2T_N + MISC_N;              // w2t + misc
+  static constexpr bool W3_RESIDENT = ((end1a > end2 ? end1a : end2) + W3_N + fixed) * 4 <= 160 * 1024;
+  static constexpr int end1 = W3_RESIDENT ? end1a : end1a + W3_N;
   static_assert(o_i1b >= end1, "the pool-1 argmax image is filled while phase 1 is live");
   static constexpr int ph_end = end1 > end2 ? end1 : end2;
   static constexpr int o_w3s = W3_RESIDENT ? ph_end : end1a;
-  static constexpr int o_w2t = W3_RESIDENT ? ph_end + 3456 : ph_end;
-  static constexpr int o_misc = o_w2t + 192 * 16;
+  static constexpr int o_w2t = W3_RESIDENT ? ph_end + W3_N : ph_end;
+  static constexpr int o_misc = o_w2t + W2T_N;
+  struct Misc {  // float offsets of the small per-frame values; misc_dma fills dout, feat, cnt and stat one frame ahead
+    static constexpr int dout = o_misc;         // [64]  the frame's d_out row (slots beyond E stay zero)
+    static constexpr int feat = o_misc + 64;    // [32]  averaged conv3 features
+    static constexpr int dfeat = o_misc + 96;   // [32]  d feat[c] / P
+    static constexpr int stat = o_misc + 128;   // mu, sd of this frame (prefetched: dead after the grey-level table is built)
+    static constexpr int gb3 = o_misc + 160;    // [32]  d b3, accumulated over the frame walk
+    static constexpr int xn = o_misc + 192;     // [256] normalised value of every uint8 level for this frame
+    static constexpr int cnt = o_misc + 448;    // [24]  positive conv3 outputs per channel of this frame (from the forward's stash)
+    static_assert(dout + 64 <= feat && feat + 32 <= dfeat && dfeat + 32 <= stat && stat + 2 <= gb3 && gb3 + 32 <= xn &&
+                      xn + 256 <= cnt && cnt + 24 <= o_misc + MISC_N, "misc slots overlap");
+  };
   // staging of the NEXT frame's uint8 pixels and pool-2 argmaxes (they are consumed at the top of that frame, after the
   // dy3 image -- where the mask bytes are staged -- has been filled): the part of the da2m planes that the normalised
   // frame does not cover is free while S5 runs; shapes where that is too small get an area of their own
   static constexpr int stg2_need = G::HW / 4 + 4 * G::P;
   static constexpr bool STG2_IN_DA2M = o_xh - o_da2m >= stg2_need;
-  static constexpr int o_stg2 = STG2_IN_DA2M ? o_da2m : o_misc + 512;
-  static constexpr int total = o_misc + 512 + (STG2_IN_DA2M ? 0 : stg2_need);
+  static constexpr int o_stg2 = STG2_IN_DA2M ? o_da2m : o_misc + MISC_N;
+  static constexpr int total = o_misc + MISC_N + (STG2_IN_DA2M ? 0 : stg2_need);
   static_assert(total * 4 <= 160 * 1024, "LDS image exceeds a CU");
+  // The flush overlays a1h and the phase area, both dead by then (Misc::gb3 is untouched).  d W3 and d W2 go through one
+  // region per wave (wave w at w * wave_stride) where eight regions fit in front of the misc block, else through one image
+  // that the waves add into; the small gradients follow the last region.
+  static constexpr int RW = W3_N + W2_N;
+  static constexpr bool REGIONS = 8 * RW + W1_N + 8 + 16 + 64 * 24 <= o_misc;
+  struct Flush {
+    static constexpr int w3 = 0, w2 = W3_N, wave_stride = REGIONS ? RW : 0;     // [W3_N] [W2_N]
+    static constexpr int w1 = REGIONS ? 8 * RW : RW, b1 = w1 + W1_N, b2 = b1 + 8, fc = b2 + 16;  // [W1_N] [8] [16] [E * 24]
+    static_assert(fc % 4 == 0, "cleared in 16-byte pieces");
+  };
 };
 
 struct CnnBwdParams {
@@ -159,16 +189,16 @@ __device__ __forceinline__ void s1_rows(const float* dy3h, const float* a2h, int
 
 // LISTED: the frames are p.frames[1 ...] (a clip's padding frames have d feat == 0 and add nothing: they are not walked);
 // otherwise frame `it` is frame number `it`.  Two kernels because the indirection is not free in THIS one: with five more scalar
-// values alive through a frame (list pointer, count, three frame numbers) it spills 48 instead of 38 scalar registers and a launch
-// over all frames took 692 instead of 682 us, 924 instead of 917 at 48 x 96 (A/B on one box, gpurun_out/r4_fr_ab2.log; both walks
-// inlined into one kernel behind a branch on the count were worse: 689 and 949, r4_fr_ab3.log).  The host picks (engine.py).
+// values alive through a frame (list pointer, count, three frame numbers) it spills more scalar registers (46 instead of 37 at
+// 64 x 64, 55 instead of 52 at 48 x 96) and a launch over all frames is about 1 % slower; both walks in one kernel behind a
+// branch were worse still (figures: LAB_NOTES section 14).  The host picks (launch_bwd).
 template <class G, bool LISTED>
 __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
   STAMP_ENTRY;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using LL = BwdLds<G>;
-  const int n_walk = LISTED ? min(p.frames[0], p.N) : p.N;
-  auto frame_at = [&](int it) { return LISTED ? (int)min((unsigned)p.frames[1 + it], (unsigned)(p.N - 1)) : it; };
+  const int n_walk = LISTED ? listed_count(p.frames, p.N) : p.N;
+  auto frame_at = [&](int it) { return LISTED ? listed_frame(p.frames, p.N, it) : it; };
   if (LISTED && (int)blockIdx.x >= n_walk) return;  // (the grid is sized for N: a workgroup without frames has nothing to add)
   constexpr int P = G::P, HW2 = G::HW2, HW = G::HW, H = G::H, XS = LL::XSB;
   constexpr int W = G::W, W2 = G::W2, W4 = G::W4, H2 = G::H2, S1 = G::S1, S2 = G::S2, P1 = G::P1, P2 = G::P2, W2H = LL::W2H;
@@ -189,14 +219,14 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
   float* dy2 = lds + LL::o_ph;
   float* xh = lds + LL::o_xh;
   float* w2t = lds + LL::o_w2t;
-  float* misc = lds + LL::o_misc;
-  float* s_dout = misc;          // [64]
-  float* s_feat = misc + 64;     // [32]
-  float* s_dfeat = misc + 96;    // [32]  d feat[c] / P
-  float* s_stat = misc + 128;    // mu, sd of this frame (prefetched: dead after the grey-level table is built)
-  float* s_gb3 = misc + 160;     // [32]  accumulated over the frame walk
-  float* s_cnt = misc + 448;     // [24] positive conv3 outputs per channel of this frame (from the forward's stash)
-  float* s_xn = misc + 192;      // [256] normalised value of every uint8 level for this frame
+  using MS = typename LL::Misc;
+  float* s_dout = lds + MS::dout;
+  float* s_feat = lds + MS::feat;
+  float* s_dfeat = lds + MS::dfeat;
+  float* s_stat = lds + MS::stat;
+  float* s_gb3 = lds + MS::gb3;
+  float* s_cnt = lds + MS::cnt;
+  float* s_xn = lds + MS::xn;
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int wvu = __builtin_amdgcn_readfirstlane(wv);
@@ -207,58 +237,59 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
   __syncthreads();
   // S2's B operand, one ds_read_b128 + one ds_read_b64 per tap: the 24 output channels n of conv3 are the K index
   // (slot (e, g) of the first four k-steps carries n = 4g + e, of the last two n = 16 + 2g + e), column = input channel c:
-  //   [0, 2304)    ((tap*4 + g)*16 + c)*4 + e  = W3[4g+e][c][tap]
-  //   [2304, 3456) ((tap*4 + g)*16 + c)*2 + e  = W3[16+2g+e][c][tap]
+  //   [0, W3_LO)     ((tap*4 + g)*16 + c)*4 + e  = W3[4g+e][c][tap]
+  //   [W3_LO, W3_N)  ((tap*4 + g)*16 + c)*2 + e  = W3[16+2g+e][c][tap]
+  // (the decode stands in both stagings: shared, it moved the per-frame one at 48 x 96, LAB_NOTES section 14)
   auto stage_w3 = [&]() {
-    for (int q = tid; q < 3456; q += NT) {
+    for (int q = tid; q < W3_N; q += NT) {
       int nn, c, tap;
-      if (q < 2304) {
+      if (q < W3_LO) {
         const int e = q & 3, r = q >> 2;
         c = r & 15;
         nn = 4 * ((r >> 4) & 3) + e;
         tap = r >> 6;
       } else {
-        const int q2 = q - 2304, e = q2 & 1, r = q2 >> 1;
+        const int q2 = q - W3_LO, e = q2 & 1, r = q2 >> 1;
         c = r & 15;
         nn = 16 + 2 * ((r >> 4) & 3) + e;
         tap = r >> 6;
       }
-      w3s[q] = p.w3[nn * 144 + c * 9 + tap];
+      w3s[q] = p.w3[nn * W3_ROW + c * 9 + tap];
     }
   };
   if (LL::W3_RESIDENT) stage_w3();
   // Shapes whose LDS image has no room to keep W3 (48 x 96: the slot lies under phase 2's normalised frame) re-stage it every
-  // frame.  Round 3 did that with plain loads at the frame top -- seven dependent 4-byte L2 gathers per thread with every wave
-  // waiting: 3.6 k of the frame's 78.8 k cycles (profiles/round3_f_stamp_64x64_vs_48x96.txt).  Now the same gather goes by
+  // frame.  Plain loads at the frame top -- seven dependent 4-byte L2 gathers per thread with every wave waiting -- cost 3.6 k
+  // of the frame's 78.8 k cycles (profiles/round3_f_stamp_64x64_vs_48x96.txt), so the gather goes by
   // LDS-DMA with per-lane source addresses (global_load_lds_dword: lane l's word lands at base + 4 l, i.e. w3s[64 piece + l]),
   // issued at the frame top and landing under S1, which does not read W3; the wait sits in front of the barrier that ends S1.
   auto stage_w3_dma = [&]() {
-    static_assert(3456 % 64 == 0, "whole wave pieces");
-    for (int piece = wvu; piece < 3456 / 64; piece += NWV) {
+    static_assert(W3_N % 64 == 0, "whole wave pieces");
+    for (int piece = wvu; piece < W3_N / 64; piece += NWV) {
       const int q = piece * 64 + lane;
       int nn, c, tap;
-      if (q < 2304) {
+      if (q < W3_LO) {
         const int e = q & 3, r = q >> 2;
         c = r & 15;
         nn = 4 * ((r >> 4) & 3) + e;
         tap = r >> 6;
       } else {
-        const int q2 = q - 2304, e = q2 & 1, r = q2 >> 1;
+        const int q2 = q - W3_LO, e = q2 & 1, r = q2 >> 1;
         c = r & 15;
         nn = 16 + 2 * ((r >> 4) & 3) + e;
         tap = r >> 6;
       }
-      ss_dma4(p.w3 + nn * 144 + c * 9 + tap, (unsigned)((LL::o_w3s + piece * 64) * 4));
+      ss_dma4(p.w3 + nn * W3_ROW + c * 9 + tap, (unsigned)((LL::o_w3s + piece * 64) * 4));
     }
   };
   // S4's B operand: k = (t*3+kx)*16 + n, column j = (c, s): W2[n][c][ky = s+2-t][kx], zero outside the 3x3 window.
   // Stored [tap tk][g][column j][e] with n = 4g + e: lane (j, g) takes its four k-steps of a tap in ONE ds_read_b128
   // (MFMA slot (e, g) carries n = 4g + e for both operands).
-  for (int q = tid; q < 192 * 16; q += NT) {
+  for (int q = tid; q < W2T_N; q += NT) {
     const int e = q & 3, j = (q >> 2) & 15, gg = (q >> 6) & 3, tk = q >> 8;
     const int n = 4 * gg + e, t = tk / 3, kx = tk % 3, c = j & 7, s = j >> 3;
     const int ky = s + 2 - t;
-    w2t[q] = (ky >= 0 && ky <= 2) ? p.w2[n * 72 + c * 9 + ky * 3 + kx] : 0.f;
+    w2t[q] = (ky >= 0 && ky <= 2) ? p.w2[n * W2_ROW + c * 9 + ky * 3 + kx] : 0.f;
   }
 
   // persistent per-thread accumulators
@@ -279,7 +310,7 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
   for (int nt = 0; nt < 5; ++nt) {
     const int idx = 16 * nt + i;
     const int tap = idx >> 3, c = idx & 7;
-    boff[nt] = (idx < 72) ? c * P1 + (tap / 3) * S1 + (tap % 3) : 0;
+    boff[nt] = (idx < W2_ROW) ? c * P1 + (tap / 3) * S1 + (tap % 3) : 0;
   }
 
   __syncthreads();
@@ -289,86 +320,73 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
   // pooled-2 map straight into its place (phase 1's a2h lies under the dense dy2 image, dead by then), the conv3 sign mask
   // into the (equally dead) dy3 planes, the uint8 frame / pool-2 argmaxes into the second staging area, the d_out row and
   // the averaged features into their misc slots.  The front of the next frame -- d feat, the dy3 image, the grey-level
-  // table: barriers and LDS round trips with no MFMA beside them -- then runs INSIDE the last quarter of S5 (top1 / top2
+  // table: barriers and LDS round trips with no MFMA beside them -- then runs INSIDE S5 (front_own
   // below): a frame starts at S1.  No registers are involved, so
   // nothing the compiler does with its own loads can wait on these (a register prefetch cost 2.8 us of serialised HBM
   // round trips per frame: spilled pointers and split destination registers each forced an s_waitcnt vmcnt(0)).
-  constexpr int STG_M3 = LL::o_dy3h, STG_PX = LL::o_stg2, STG_I2 = STG_PX + HW / 4;   // float offsets
+  constexpr int STG_PX = LL::o_stg2, STG_I2 = STG_PX + HW / 4;   // float offsets
   static_assert(8 * P <= DS * P2 && HW % 16 == 0 && P % 16 == 0, "staging");
   uint2 px[NCH];
   // fc weight column of this thread's channel (c = tid / 16; e = tid % 16 + 16 k): d feat needs nothing staged per frame
   float wq[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) wq[k] = (tid < 24 * 16 && (tid & 15) + 16 * k < E) ? p.wfc[((tid & 15) + 16 * k) * 24 + (tid >> 4)] : 0.f;
-  // FAST (one 16-byte mask item per thread, whole rows of the pooled-2 grid per wave -- the 64x64 frames of BASELINE.json):
-  // the front of the next frame needs no workgroup barrier.  Every wave fetches the 1 KB of mask bytes of ITS pixels into
+  // The front of the next frame needs no workgroup barrier.  Every wave fetches the 1 KB of mask bytes of ITS pixels into
   // the dy3 cells of those same pixels, reads them back after its own s_waitcnt and fills its rows; d feat is made two stages
   // earlier, inside S3 (its inputs are requested in S1).  The two waves of a SIMD then run their fronts at DIFFERENT passes of S5, one
   // wave's vector / LDS work under the other's MFMAs (tools/microbench/mfma_valu: a wave's v_fma stream does not slow the
   // partner's MFMAs at all); with barriers in it the front costs its full length wherever it is put.
-  // Round 4: any shape whose waves own whole rows of the pooled-2 grid -- wave w rows [w H4 / NWV, (w + 1) H4 / NWV), one or
+  // It holds for any shape whose waves own whole rows of the pooled-2 grid -- wave w rows [w H4 / NWV, (w + 1) H4 / NWV), one or
   // two mask items per lane (48 x 96: 12 rows over 8 waves, 48 or 96 items per wave) -- as long as a wave's mask bytes (32 per
-  // pixel) fit into the cells of its first row (96 bytes per pixel): up to three rows per wave.  The 48 x 96 frames of the
-  // reference ran the generic form (two workgroup barriers inside S5, the front at full length: S5 15.2 k cycles against 8.1 k).
+  // pixel) fit into the cells of its first row (96 bytes per pixel): up to three rows per wave.  Every built shape is one; the
+  // form for other shapes (two workgroup barriers inside S5, the front at full length: at 48 x 96 an S5 of 15.2 k cycles against
+  // 8.1 k) was never instantiated and is gone (LAB_NOTES section 14).
   constexpr int H4 = G::H4;
   constexpr int RPW_MAX = (H4 + NWV - 1) / NWV;          // rows a wave owns at most
   constexpr int NM3F = (RPW_MAX * 2 * W4 + 63) / 64;      // mask items per lane at most
-  constexpr bool FAST = H4 >= NWV && RPW_MAX <= 3 && 2 * W4 <= 64;
+  static_assert(H4 >= NWV && RPW_MAX <= 3 && 2 * W4 <= 64, "a wave owns whole rows of the pooled-2 grid, at most three");
   const int own_r0 = (wvu * H4) / NWV, own_r1 = ((wvu + 1) * H4) / NWV;  // this wave's rows of the pooled-2 grid
   const int own_items = (own_r1 - own_r0) * 2 * W4;
   auto m3_own_dst = [&]() {  // float offset of this wave's first interior pixel in the dy3 image
     return LL::o_dy3h + ((own_r0 + 1) * S2 + 1) * DS;
   };
-  static_assert(!FAST || RPW_MAX * 2 * W4 * 16 <= W4 * DS * 4, "a wave's mask piece stays inside its first row");
+  static_assert(RPW_MAX * 2 * W4 * 16 <= W4 * DS * 4, "a wave's mask piece stays inside its first row");
   auto misc_dma = [&](int nf) {  // d_out row, averaged features, counts, mean / std: one wave, four tiny DMAs
     if (wvu == NWV - 1) {
-      if (lane < E) ss_dma4(p.d_out + (long)nf * p.ld_dout + lane, (unsigned)((LL::o_misc) * 4));
-      if (lane < 24) ss_dma4(p.st_feat + (long)nf * ST_FEAT + lane, (unsigned)((LL::o_misc + 64) * 4));
-      if (lane < 24) ss_dma4(p.st_feat + (long)nf * ST_FEAT + 24 + lane, (unsigned)((LL::o_misc + 448) * 4));
-      if (lane < 2) ss_dma4(p.st_feat + (long)nf * ST_FEAT + 48 + lane, (unsigned)((LL::o_misc + 128) * 4));  // mean, std
+      if (lane < E) ss_dma4(p.d_out + (long)nf * p.ld_dout + lane, (unsigned)(MS::dout * 4));
+      if (lane < 24) ss_dma4(p.st_feat + (long)nf * ST_FEAT + lane, (unsigned)(MS::feat * 4));
+      if (lane < 24) ss_dma4(p.st_feat + (long)nf * ST_FEAT + 24 + lane, (unsigned)(MS::cnt * 4));
+      if (lane < 2) ss_dma4(p.st_feat + (long)nf * ST_FEAT + 48 + lane, (unsigned)(MS::stat * 4));  // mean, std
     }
   };
   // (a 1 KB DMA instruction occupies the CU's vector-memory path for ~30 cycles; 39 of them back to back at a barrier
   // stalled every wave for 1.2 k cycles per frame, under MFMAs they are free)
   auto prefetch_frame = [&](int nf) {
-    constexpr int A2_PIECES = (16 * P2 * 4 + 1023) / 1024, PX_PIECES = (HW + 1023) / 1024,
-                  M3_PIECES = FAST ? 0 : (32 * P + 1023) / 1024, I2_PIECES = (16 * P + 1023) / 1024;
+    constexpr int A2_PIECES = (16 * P2 * 4 + 1023) / 1024, PX_PIECES = (HW + 1023) / 1024, I2_PIECES = (16 * P + 1023) / 1024;
     const char* a2src = reinterpret_cast<const char*>(p.st_a2 + (long)nf * 16 * P2);
     const char* pxsrc = reinterpret_cast<const char*>(p.R + (long)nf * HW);
     const char* m3src = reinterpret_cast<const char*>(p.st_m3 + (long)nf * 32 * P);
     const char* i2src = reinterpret_cast<const char*>(p.st_i2 + (long)nf * 16 * P);
-    if (FAST) {  // this wave's mask bytes into the cells of its own first row (front_own reads them back)
+    // this wave's mask bytes into the cells of its own first row (front_own reads them back)
 #pragma unroll
-      for (int k = 0; k < NM3F; ++k)
-        if (lane + 64 * k < own_items)
-          ss_dma16(m3src + (2 * own_r0 * W4 + 64 * k + lane) * 16, (unsigned)(m3_own_dst() * 4 + k * 1024));
-    }
-    for (int piece = wvu; piece < A2_PIECES + PX_PIECES + M3_PIECES + I2_PIECES; piece += NWV) {
+    for (int k = 0; k < NM3F; ++k)
+      if (lane + 64 * k < own_items)
+        ss_dma16(m3src + (2 * own_r0 * W4 + 64 * k + lane) * 16, (unsigned)(m3_own_dst() * 4 + k * 1024));
+    for (int piece = wvu; piece < A2_PIECES + PX_PIECES + I2_PIECES; piece += NWV) {
       int q = piece;
       if (q < A2_PIECES) {
-        const int off = q * 1024 + lane * 16;
-        if (off < 16 * P2 * 4) ss_dma16(a2src + off, (unsigned)(LL::o_ph * 4 + q * 1024));
+        dma_pieces(a2src, 16 * P2 * 4, LL::o_ph, q, lane);
         continue;
       }
       q -= A2_PIECES;
       if (q < PX_PIECES) {
-        const int off = q * 1024 + lane * 16;
-        if (off < HW) ss_dma16(pxsrc + off, (unsigned)(STG_PX * 4 + q * 1024));
+        dma_pieces(pxsrc, HW, STG_PX, q, lane);
         continue;
       }
       q -= PX_PIECES;
-      if (q < M3_PIECES) {
-        const int off = q * 1024 + lane * 16;
-        if (off < 32 * P) ss_dma16(m3src + off, (unsigned)(STG_M3 * 4 + q * 1024));
-        continue;
-      }
-      q -= M3_PIECES;
-      const int off = q * 1024 + lane * 16;
-      if (off < 16 * P) ss_dma16(i2src + off, (unsigned)(STG_I2 * 4 + q * 1024));
+      dma_pieces(i2src, 16 * P, STG_I2, q, lane);
     }
-    if (!FAST) misc_dma(nf);
   };
-  constexpr int NM3 = (2 * P + NT - 1) / NT;  // 16-byte mask items (pixel, channel half) per thread
   // ---- the pieces of a frame's front
   auto front_dfeat = [&]() {  // needs the d_out row and the averaged features (landed and published)
     if (tid < 24 * 16) {  // d feat[c] = sum_e d_out[e] * Wfc[e][c]: 16 lanes per channel (one DPP row), then a shuffle tree
@@ -390,8 +408,7 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
   };
   auto front_table = [&]() {
     if (tid < 256) {  // the forward's xn = (u/255 - mu)/sd, once per grey level instead of once per pixel
-      const float rr = (float)tid / 255.0f;
-      s_xn[tid] = p.standardize ? (rr - s_stat[0]) / s_stat[1] : rr;
+      s_xn[tid] = xn_of_level((float)tid / 255.0f, p.standardize, s_stat);
     }
   };
   // dy3 = mask3 * dfeat / P, pixel-major [haloed pixel][24 channels]: an item is 16 mask bytes = 16 channels of one
@@ -411,39 +428,10 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
       }
     }
   };
-  auto front_fill = [&](const uint4 (&m3w)[NM3]) {
-#pragma unroll
-    for (int k = 0; k < NM3; ++k)
-      if (tid + k * NT < 2 * P) fill_item(tid + k * NT, m3w[k]);
-  };
   auto front_gb3 = [&]() {
     if (tid < 24) s_gb3[tid] += s_dfeat[tid] * s_cnt[tid];  // d b3 = d feat x (number of positive conv3 outputs)
   };
-  // generic path, top1: after the barrier behind which every wave's DMA pieces have landed.  Mask bytes into registers
-  // (the dy3 image is about to be written over their staging area), d feat, the grey-level table.
-  auto top1 = [&](uint4 (&m3w)[NM3]) {
-#pragma unroll
-    for (int k = 0; k < NM3; ++k)
-      m3w[k] = (tid + k * NT < 2 * P) ? reinterpret_cast<const uint4*>(lds + STG_M3)[tid + k * NT] : uint4{0, 0, 0, 0};
-    front_dfeat();
-    front_table();
-  };
-  // generic path, top2: after the barrier behind which every mask byte is in a register and d feat is published: the halo
-  // pixels of the dy3 image back to zero (the planes held the staged mask), every interior pixel written
-  auto top2 = [&](const uint4 (&m3w)[NM3]) {
-    for (int q = tid; q < (2 * S2 + 2 * G::H4) * 6; q += NT) {
-      const int hp = q / 6, part = q - 6 * hp;
-      int pixh;
-      if (hp < S2) pixh = hp;                                           // top row
-      else if (hp < 2 * S2) pixh = (G::H4 + 1) * S2 + (hp - S2);        // bottom row
-      else if (hp < 2 * S2 + G::H4) pixh = (hp - 2 * S2 + 1) * S2;      // left column
-      else pixh = (hp - 2 * S2 - G::H4 + 1) * S2 + W4 + 1;              // right column
-      reinterpret_cast<f32x4*>(dy3h + pixh * DS)[part] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    front_fill(m3w);
-    front_gb3();
-  };
-  // FAST path: one wave's share of the front, no barrier.  Its own DMA pieces have landed (s_waitcnt), its mask bytes come
+  // One wave's share of the front, no barrier.  Its own DMA pieces have landed (s_waitcnt), its mask bytes come
   // back out of the cells of its own pixels, which it then fills; it zeroes the halo cells of its own rows (waves 0 and
   // NWV - 1 the top / bottom row as well); d feat was published a stage ago
   auto front_own = [&]() {
@@ -480,19 +468,12 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
   };
   if (LISTED || (int)blockIdx.x < p.N) {  // the first frame's inputs and front, outside the pipeline
     prefetch_frame(n);
-    if (FAST) misc_dma(n);
+    misc_dma(n);
     ss_dma_wait();
-    __syncthreads();
-    if (FAST) {
-      front_dfeat();
-      __syncthreads();
-      front_own();
-    } else {
-      uint4 m3w[NM3];
-      top1(m3w);
-      __syncthreads();
-      top2(m3w);
-    }
+    __syncthreads();  // every wave's pieces have landed
+    front_dfeat();
+    __syncthreads();  // d feat is published
+    front_own();
     __syncthreads();
   }
 
@@ -503,7 +484,7 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
     }
     STAMP(15);
     // ---------------- frame top: d feat, the dy3 image and the grey-level table of this frame were made during S5 of the
-    // previous one (top1 / top2); what is left are two copies out of the second staging area, needed at the phase switch
+    // previous one (front_own); what is left are two copies out of the second staging area, needed at the phase switch
 #pragma unroll
     for (int k = 0; k < NCH; ++k)
       if ((tid + k * NT) * 8 < HW) px[k] = reinterpret_cast<const uint2*>(lds + STG_PX)[tid + k * NT];
@@ -515,20 +496,15 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
     // the pooled-1 map arrives by LDS-DMA (1 KB per wave instruction) under S1 / S2, one share per row iteration; it is
     // waited for before S3.  a1h held da1 of the previous frame, dead since barrier E
     auto a1_dma = [&](int part, int nparts) {
-      // FAST: the next frame's d_out row / features / statistics are requested here (d feat is made inside S3)
-      if (FAST && part == 0 && has_next()) misc_dma(next_frame());
+      // the next frame's d_out row / features / statistics are requested here (d feat is made inside S3)
+      if (part == 0 && has_next()) misc_dma(next_frame());
       constexpr int BYTES = 8 * P1 * 4, A1_PIECES = (BYTES + 1023) / 1024;
       constexpr int I1_BYTES = 8 * I1S, I1_PIECES = I1_BY_DMA ? (I1_BYTES + 1023) / 1024 : 0;  // the pool-1 argmax image rides along
       const char* src = reinterpret_cast<const char*>(p.st_a1 + (long)n * 8 * P1);
       const char* isrc = reinterpret_cast<const char*>(p.st_i1 + (long)n * 8 * I1S);
       for (int piece = wvu + NWV * part; piece < A1_PIECES + I1_PIECES; piece += NWV * nparts) {
-        if (piece < A1_PIECES) {
-          const int off = piece * 1024 + lane * 16;
-          if (off < BYTES) ss_dma16(src + off, (unsigned)(LL::o_a1h * 4 + piece * 1024));
-        } else {
-          const int off = (piece - A1_PIECES) * 1024 + lane * 16;
-          if (off < I1_BYTES) ss_dma16(isrc + off, (unsigned)(LL::o_i1b * 4 + (piece - A1_PIECES) * 1024));
-        }
+        if (piece < A1_PIECES) dma_pieces(src, BYTES, LL::o_a1h, piece, lane);
+        else dma_pieces(isrc, I1_BYTES, LL::o_i1b, piece - A1_PIECES, lane);
       }
     };
     if (s1_half == 0) s1_rows<G, 0>(dy3h, a2h, s1_kg, i, g, acc3, a1_dma);
@@ -549,9 +525,8 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
       if (!I1_BY_DMA && (tid + k * NT) * 16 < 8 * I1S)
         ix1[k] = reinterpret_cast<const uint4*>(p.st_i1 + (long)n * 8 * I1S)[tid + k * NT];
     // ---------------- S2: da2 (masked by a2 > 0), kept in registers ; db2.  ONE pass per wave over all its pixel tiles (tile
-    // w, w + NWV, w + 2 NWV: two at 64 x 64, two or three at 48 x 96), which share the W3 reads.  (Round 3 ran 48 x 96's 18 tiles
-    // as a pass of sixteen and a second pass of two: a second set of B reads, a second epilogue and two register sets of results
-    // held through the phase switch -- S2 13.0 k cycles for an MFMA floor of 8.6 k.)
+    // w, w + NWV, w + 2 NWV: two at 64 x 64, two or three at 48 x 96), which share the W3 reads (a second pass for the two odd
+    // tiles of 48 x 96 means a second set of B reads and a second epilogue: LAB_NOTES section 14).
     constexpr int S2_TILES = P / 16;
     constexpr int S2_MAXT = (S2_TILES + NWV - 1) / NWV;  // tiles of a wave at most
     constexpr int S2_FULL = S2_TILES % NWV;              // waves [0, S2_FULL) hold S2_MAXT tiles, the others one fewer (0: all S2_MAXT)
@@ -561,7 +536,7 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
     {
       auto s2_pass = [&](auto nt_c) {
         constexpr int NTW = decltype(nt_c)::value;  // tiles of this wave
-        int w3off = (LL::o_w3s + (g * 16 + i) * 4) * 4, w3off8 = (LL::o_w3s + 2304 + (g * 16 + i) * 2) * 4;
+        int w3off = (LL::o_w3s + (g * 16 + i) * 4) * 4, w3off8 = (LL::o_w3s + W3_LO + (g * 16 + i) * 2) * 4;
         asm volatile("" : "+v"(w3off), "+v"(w3off8));  // W3 may lie beyond the 64 KB reach of a ds_read immediate (see S5)
         const float* bt16 = reinterpret_cast<const float*>(reinterpret_cast<const char*>(lds) + w3off);
         const float* bt8 = reinterpret_cast<const float*>(reinterpret_cast<const char*>(lds) + w3off8);
@@ -628,7 +603,7 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
       if (S2_FULL == 0 || wvu < S2_FULL) s2_pass(std::integral_constant<int, S2_MAXT>{});
       else if constexpr (S2_MAXT > 1) s2_pass(std::integral_constant<int, (S2_MAXT > 1 ? S2_MAXT - 1 : 1)>{});
     }
-    if (FAST && wvu == NWV - 1) ss_dma_wait();  // the next frame's d_out row has landed: published by barrier D
+    if (wvu == NWV - 1) ss_dma_wait();  // the next frame's d_out row has landed: published by barrier D
     __syncthreads();  // D: dy3h / a2h / w3 / the pool-2 argmaxes are dead
     STAMP(4);
 
@@ -665,7 +640,7 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
 
     // The normalised frame (interior by table lookup, halo cells zeroed: the area held phase-1 data) and the pool-1 argmax
     // bytes are needed by S5 only; the frame is made by every thread from its OWN registers (px) and the grey-level table (the
-    // argmax bytes arrive by DMA since round 4):
+    // argmax bytes arrive by DMA or through registers, I1_BY_DMA):
     // like the next frame's front they run per wave, without a barrier, inside S3 -- the two waves of a SIMD at
     // different passes, one wave's table lookups and LDS stores under its partner's MFMAs (they were 2.4 k cycles of
     // the phase switch, with every wave storing and nobody multiplying).  The zero columns of dy2 and the next frame's
@@ -704,9 +679,9 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
         const int y = q >> 3, side = (q >> 2) & 1, part = q & 3;
         reinterpret_cast<f32x4*>(dy2)[(y * W2H + (side ? W2 + 1 : 0)) * 4 + part] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
-      // FAST: d feat of the NEXT frame (its d_out row landed before barrier D; s_dfeat of THIS frame was last read in S5 of
+      // d feat of the NEXT frame (its d_out row landed before barrier D; s_dfeat of THIS frame was last read in S5 of
       // the previous one, the new value is read in S5 of this one, two barriers on)
-      if (FAST && has_next()) front_dfeat();
+      if (has_next()) front_dfeat();
     };
     // ---------------- S3: dW2.  A wave owns whole rows of the pooled-1 grid: one A base and five B bases per wave,
     // everything else is an immediate offset (VALU work between MFMAs is not hidden by them).  The two waves of a SIMD
@@ -859,8 +834,8 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
       const float* xp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(lds) + xoff);
       constexpr int KP = 4;                  // k-steps per pass: 3 KP LDS reads, 2 KP selects, 2 KP MFMAs
       constexpr int PPR = W2 / 4 / KP, NP = rows * PPR;
-      constexpr int FRONT = NP - (NP + 3) / 4;  // pass after which the next frame's front runs (the DMA has ~3/4 of S5 to land)
-      constexpr int FRONT_A = NP / 2;           // FAST: waves 0 .. NWV/2 - 1 run theirs here
+      constexpr int FRONT = NP - (NP + 3) / 4;  // pass after which waves NWV/2 .. NWV-1 run the next frame's front (the DMA has ~3/4 of S5 to land)
+      constexpr int FRONT_A = NP / 2;           // waves 0 .. NWV/2 - 1 run theirs here
       const bool more = has_next();
       // fully unrolled, the next pass's reads issued before this pass's selects and MFMAs (see S3)
       float d[2][KP], xv[2][KP];
@@ -896,17 +871,9 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
           }
         }
         SS_SCHED_FENCE();
-        if (FAST) {  // the two waves of a SIMD (w, w + NWV / 2) take different passes
-          if (ps == FRONT_A - 1 && more && wvu < NWV / 2) front_own();
-          if (ps == FRONT - 1 && more && wvu >= NWV / 2) front_own();
-        } else if (ps == FRONT - 1 && more) {  // (wave-uniform; the reads of pass FRONT are already in flight)
-          ss_dma_wait();
-          __syncthreads();  // F1: every wave's pieces of the next frame have landed
-          uint4 m3w[NM3];
-          top1(m3w);
-          __syncthreads();  // F2: mask bytes are in registers, d feat is published
-          top2(m3w);
-        }
+        // the two waves of a SIMD (w, w + NWV / 2) take different passes (wave-uniform; the next pass's reads are in flight)
+        if (ps == FRONT_A - 1 && more && wvu < NWV / 2) front_own();
+        if (ps == FRONT - 1 && more && wvu >= NWV / 2) front_own();
       }
     }
     __syncthreads();  // E
@@ -914,30 +881,25 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
   }
 
   // ---------------- flush: reduce the per-wave partials through LDS, then one atomic per element
-  float* r_w3 = lds;            // [3456]
-  float* r_w2 = r_w3 + 3456;    // [1152]
-  float* r_w1 = r_w2 + 1152;    // [72]
-  float* r_b1 = r_w1 + 72;      // [8]
-  float* r_b2 = r_b1 + 8;       // [16]
-  float* r_fc = r_b2 + 16;      // [E*24]
-  const int rtot = 3456 + 1152 + 72 + 8 + 16 + E * 24;
-  // (r_* overlay a1h and the phase area, both dead; s_gb3 in misc is untouched)
+  using FL = typename LL::Flush;
+  constexpr int RW = LL::RW;
+  constexpr bool REGIONS = LL::REGIONS;
+  float* r_w3 = lds + FL::w3;
+  float* r_w2 = lds + FL::w2;
+  float* r_w1 = lds + FL::w1;
+  float* r_b1 = lds + FL::b1;
+  float* r_b2 = lds + FL::b2;
+  float* r_fc = lds + FL::fc;
   // d W3 and d W2 -- 48 of a lane's 56 partial sums -- go through one LDS REGION PER WAVE with plain stores and are summed over the
   // eight regions by the threads that then issue the global atomics.  The first version added all partials into one image with LDS
   // float atomics: ds_add_f32 retires well under one lane-operation per clock (measured on the config-5 weight gradients: 110 k of
   // them in 178 k cycles), 25 k of them here.  Shapes whose LDS image is too small for eight regions keep the atomics.
-  constexpr int RW = 3456 + 1152;
-  constexpr bool REGIONS = 8 * RW + 96 + 64 * 24 <= LL::o_misc;
-  float* r_w3w = REGIONS ? lds + wvu * RW : r_w3;  // this wave's region (d W3, then d W2)
-  float* r_w2w = r_w3w + 3456;
+  float* r_w3w = r_w3 + wvu * FL::wave_stride;  // this wave's region (d W3, then d W2)
+  float* r_w2w = r_w2 + wvu * FL::wave_stride;
   if (REGIONS) {
-    r_w1 = lds + 8 * RW;
-    r_b1 = r_w1 + 72;
-    r_b2 = r_b1 + 8;
-    r_fc = r_b2 + 16;
-    for (int q = tid; q < (8 * RW + 96) / 4; q += NT) reinterpret_cast<f32x4*>(lds)[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = tid; q < FL::fc / 4; q += NT) reinterpret_cast<f32x4*>(lds)[q] = f32x4{0.f, 0.f, 0.f, 0.f};
   } else {
-    for (int q = tid; q < rtot; q += NT) lds[q] = 0.f;
+    for (int q = tid; q < FL::fc + E * 24; q += NT) lds[q] = 0.f;
   }
   __syncthreads();
 #pragma unroll
@@ -951,19 +913,19 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
       else if (t % 3 == 1) { nn = row < 8 ? 16 + row : row - 8; tap = row < 8 ? t0 : t0 + 1; }
       else { nn = 8 + row; tap = t0 + 1; }
       if (nn < 24) {
-        if (REGIONS) r_w3w[nn * 144 + i * 9 + tap] = acc3[t][r];  // (a wave holds every element at most once)
-        else atomicAdd(&r_w3[nn * 144 + i * 9 + tap], acc3[t][r]);
+        if (REGIONS) r_w3w[nn * W3_ROW + i * 9 + tap] = acc3[t][r];  // (a wave holds every element at most once)
+        else atomicAdd(&r_w3[nn * W3_ROW + i * 9 + tap], acc3[t][r]);
       }
     }
 #pragma unroll
   for (int nt = 0; nt < 5; ++nt) {
     const int idx = 16 * nt + i;
-    if (idx < 72) {
+    if (idx < W2_ROW) {
       const int tap = idx >> 3, c = idx & 7;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        if (REGIONS) r_w2w[(4 * g + r) * 72 + c * 9 + tap] = acc2[nt][r];
-        else atomicAdd(&r_w2[(4 * g + r) * 72 + c * 9 + tap], acc2[nt][r]);
+        if (REGIONS) r_w2w[(4 * g + r) * W2_ROW + c * 9 + tap] = acc2[nt][r];
+        else atomicAdd(&r_w2[(4 * g + r) * W2_ROW + c * 9 + tap], acc2[nt][r]);
       }
     }
   }
@@ -1002,13 +964,13 @@ __global__ __launch_bounds__(NT) void roi_cnn_bwd_kernel(CnnBwdParams p) {
 #pragma unroll
       for (int w = 0; w < 8; ++w) s8[w] = lds[w * RW + q];
       const float sum = ((s8[0] + s8[1]) + (s8[2] + s8[3])) + ((s8[4] + s8[5]) + (s8[6] + s8[7]));
-      atomicAdd(q < 3456 ? &p.g_w3[q] : &p.g_w2[q - 3456], sum);
+      atomicAdd(q < W3_N ? &p.g_w3[q] : &p.g_w2[q - W3_N], sum);
     }
   } else {
-    for (int q = tid; q < 3456; q += NT) atomicAdd(&p.g_w3[q], r_w3[q]);
-    for (int q = tid; q < 1152; q += NT) atomicAdd(&p.g_w2[q], r_w2[q]);
+    for (int q = tid; q < W3_N; q += NT) atomicAdd(&p.g_w3[q], r_w3[q]);
+    for (int q = tid; q < W2_N; q += NT) atomicAdd(&p.g_w2[q], r_w2[q]);
   }
-  if (tid < 72) atomicAdd(&p.g_w1[tid], r_w1[tid]);
+  if (tid < W1_N) atomicAdd(&p.g_w1[tid], r_w1[tid]);
   if (tid < 8) atomicAdd(&p.g_b1[tid], r_b1[tid]);
   if (tid < 16) atomicAdd(&p.g_b2[tid], r_b2[tid]);
   if (tid < 24) atomicAdd(&p.g_b3[tid], s_gb3[tid]);
@@ -1044,23 +1006,15 @@ extern "C" int ss_roi_cnn_bwd_frames(const uint8_t* R, int N, int H, int W, int 
   SS_REQUIRE(g_w1 && g_b1 && g_w2 && g_b2 && g_w3 && g_b3 && g_wfc && g_bfc, SS_ERR_ARG);
   SS_REQUIRE(N > 0 && E > 0 && ld_dout >= E, SS_ERR_ARG);
   SS_REQUIRE(E <= 64, SS_ERR_UNSUPPORTED);
-  CnnBwdParams p;
-  p.R = R; p.N = N; p.standardize = standardize; p.w2 = w2; p.w3 = w3; p.wfc = wfc; p.E = E;
-  p.st_a1 = st_a1; p.st_i1 = st_i1; p.st_a2 = st_a2; p.st_i2 = st_i2; p.st_m3 = st_m3; p.st_feat = st_feat;
-  p.d_out = d_out; p.ld_dout = ld_dout;
-  p.g_w1 = g_w1; p.g_b1 = g_b1; p.g_w2 = g_w2; p.g_b2 = g_b2; p.g_w3 = g_w3; p.g_b3 = g_b3; p.g_wfc = g_wfc; p.g_bfc = g_bfc;
-  p.frames = frames;
+  const CnnBwdParams p{R,     N,     standardize, w2,      w3,    wfc,     E,    st_a1, st_i1, st_a2, st_i2, st_m3,
+                       st_feat, d_out, ld_dout,   g_w1,    g_b1,  g_w2,    g_b2, g_w3,  g_b3,  g_wfc, g_bfc, frames};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // the stash must have been laid out by a forward kernel compiled against the same Geom as this file
-#define SS_DISPATCH(HH, WW)                                                                             \
-  if (H == HH && W == WW) {                                                                            \
-    using G_ = Geom<HH, WW>;                                                                           \
-    SS_REQUIRE(stash_sizes_match<G_>(stash_sizes), SS_ERR_ARG);                                        \
-    return launch_bwd<G_>(p, s);                                                                       \
-  }
-  SS_CNN_SHAPES(SS_DISPATCH)
-#undef SS_DISPATCH
-  return SS_ERR_UNSUPPORTED;
+  return for_geom(H, W, [&](auto geom) -> int {
+    using G = decltype(geom);
+    // the stash must have been laid out by a forward kernel compiled against the same Geom as this file
+    SS_REQUIRE(stash_sizes_match<G>(stash_sizes), SS_ERR_ARG);
+    return launch_bwd<G>(p, s);
+  });
 }
 
 extern "C" int ss_roi_cnn_bwd(const uint8_t* R, int N, int H, int W, int standardize, const float* w1,

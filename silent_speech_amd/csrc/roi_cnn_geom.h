@@ -1,10 +1,26 @@
-// Compile-time LDS geometry shared by the ROI-CNN forward and backward kernels.  The kernels are instantiated per
+// What the f32 ROI-CNN forward (roi_cnn.hip) and backward (roi_cnn_bwd.hip) share: the compile-time LDS geometry, the weight
+// sizes, the geometry dispatch, and one copy of each device routine both kernels use.  The kernels are instantiated per
 // frame size so every plane / row stride is an immediate in the ds_read/ds_write offsets and every pixel -> (y, x)
 // split is a multiply-shift; SS_CNN_SHAPES lists the sizes built (the reference ships 48x96, BASELINE.json's
-// synthetic configs use 64x64).
+// synthetic configs use 64x64).  No routine here holds a barrier or a wait: those stay
+// in the kernels, next to the comment that says what they protect.  What the compiler made of each routine, and the
+// ones it refused, are in docs/LAB_NOTES.md section 14.
 #pragma once
+#include "ss_common.h"
+
+// X(H, W) for every instantiated frame size
+#define SS_CNN_SHAPES(X) X(64, 64) X(48, 96) X(32, 32)
 
 namespace {
+
+// element counts of the weight tensors and of the operand images made from them
+constexpr int W1_N = 8 * 9;         // conv1 [8][1][3][3]
+constexpr int W2_ROW = 8 * 9;       // conv2, one output channel: [8][3][3]
+constexpr int W2_N = 16 * W2_ROW;   // conv2 [16][8][3][3]
+constexpr int W3_ROW = 16 * 9;      // conv3, one output channel: [16][3][3]
+constexpr int W3_N = 24 * W3_ROW;   // conv3 [24][16][3][3]
+constexpr int W3_LO = 16 * W3_ROW;  // its output channels 0..15: the ds_read_b128 part of the backward's W3 operand image
+constexpr int W2T_N = 192 * 16;     // the backward's S4 operand image of W2: K = 4 rows x 3 columns x 16 channels, 16 columns
 
 constexpr int plane_stride(int n) {  // smallest >= n that is == 18 (mod 32): conflict-free MFMA operand reads
   return n + (18 - n % 32 + 32) % 32;  // both when lanes walk pixels (stride 1) and when they walk planes
@@ -45,7 +61,45 @@ inline bool stash_sizes_match(const int* s) {
   return true;
 }
 
-}  // namespace
+// ---- device routines both kernels use
 
-// X(H, W) for every instantiated frame size
-#define SS_CNN_SHAPES(X) X(64, 64) X(48, 96) X(32, 32)
+// Grey-level table entry: the normalised value of the uint8 level whose fl(level / 255) is level_f (one IEEE divide per
+// grey level and frame instead of one per pixel); stat = {mean, std}
+__device__ __forceinline__ float xn_of_level(float level_f, int standardize, const float* stat) {
+  return standardize ? (level_f - stat[0]) / stat[1] : level_f;
+}
+
+// Walk of a frame list (ss_roi_active_frames): frames[0] = how many frames to walk, frames[1 ...] their numbers, both
+// clamped to the N frames the buffers hold.  Whether there is a list is the kernel's business.
+__device__ __forceinline__ int listed_count(const int* frames, int N) { return min(frames[0], N); }
+__device__ __forceinline__ int listed_frame(const int* frames, int N, int it) {
+  return (int)min((unsigned)frames[1 + it], (unsigned)(N - 1));
+}
+
+// Pool argmax byte 2 * (row bit) + (column bit) of every lane from the two lane masks: two vector instructions
+__device__ __forceinline__ int pool_index_byte(unsigned long long t1, unsigned long long b0) {
+  int hi, bi;
+  unsigned long long carry_out;
+  asm("v_cndmask_b32_e64 %0, 0, 2, %1" : "=v"(hi) : "s"(t1));
+  asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(bi), "=s"(carry_out) : "v"(hi), "s"(b0));
+  return bi;
+}
+
+// 1 KB piece `piece` of a linear copy of `bytes` bytes from src to LDS float offset lds_float_off: one wave instruction,
+// 16 bytes per lane, lanes past the end idle.  The issuing wave waits (ss_dma_wait) before the barrier that publishes it.
+__device__ __forceinline__ void dma_pieces(const char* src, int bytes, int lds_float_off, int piece, int lane) {
+  const int off = piece * 1024 + lane * 16;
+  if (off < bytes) ss_dma16(src + off, (unsigned)(lds_float_off * 4 + piece * 1024));
+}
+
+// f(Geom<H, W>{}) for the built shape (H, W); every entry point that takes a frame size goes through here
+template <class F>
+inline int for_geom(int H, int W, F&& f) {
+#define SS_GEOM_CASE(HH, WW) \
+  if (H == HH && W == WW) return f(Geom<HH, WW>{});
+  SS_CNN_SHAPES(SS_GEOM_CASE)
+#undef SS_GEOM_CASE
+  return SS_ERR_UNSUPPORTED;
+}
+
+}  // namespace

@@ -4,6 +4,9 @@ SS_HOTPATH_LIB (default: the in-tree build).  Run it once per variant inside ONE
 per cent between boxes, not between processes on one box.
 
     SS_HOTPATH_LIB=silent_speech_amd/libA.so python tools/cnn_ab.py && SS_HOTPATH_LIB=.../libB.so python tools/cnn_ab.py
+
+AB_RAGGED=1 draws the clip lengths below T, so that the engine lists the active frames: both launches then walk the list and
+the backward is the LISTED kernel.  The engine times them under the same two tags; the line says which walk was measured.
 """
 import os
 import sys
@@ -27,7 +30,11 @@ def main():
     X = torch.randn(B, T, 84, device=dev)
     hh, ww = (int(v) for v in os.environ.get("AB_ROI", "64,64").split(","))  # 64,64 (BASELINE.json) | 48,96 (the reference's ROI) | 32,32
     R = torch.randint(0, 256, (B, T, hh, ww), device=dev, dtype=torch.uint8)
-    lengths = torch.full((B,), T, device=dev)
+    ragged = os.environ.get("AB_RAGGED", "0") == "1"
+    if ragged:
+        lengths = torch.randint(T // 2, T, (B,), device=dev)
+    else:
+        lengths = torch.full((B,), T, device=dev)
     y = torch.randint(0, 5, (B,), device=dev)
     for _ in range(5):
         tr.step(X, lengths, R, y)
@@ -42,7 +49,8 @@ def main():
     for k in ("ss_roi_cnn_fwd_stash", "ss_roi_cnn_bwd"):
         ts = sorted(a.elapsed_time(b) for a, b in prof[k])
         out.append(f"{k} median {ts[len(ts) // 2] * 1e3:.1f} us  min {ts[0] * 1e3:.1f}")
-    print(os.path.basename(os.environ.get("SS_HOTPATH_LIB", "libss_hotpath.so")), " | ".join(out), flush=True)
+    walk = "listed frames" if ragged else "all frames"
+    print(os.path.basename(os.environ.get("SS_HOTPATH_LIB", "libss_hotpath.so")), f"{hh}x{ww} {walk}", " | ".join(out), flush=True)
 
 
 if __name__ == "__main__":
