@@ -761,6 +761,28 @@ int ss_adam_clip(float* p, const float* g, float* m, float* v, long n, const flo
 int ss_adam_clip_ema(float* p, const float* g, float* m, float* v, float* ema, long n, const float* sumsq, float grad_scale,
                      float max_norm, float lr, float beta1, float beta2, float eps, int step, float ema_decay, ss_stream_t stream);
 
+/* Grouped AdamW: ss_adam_clip / ss_adam_clip_ema (ema != NULL) with torch's decoupled weight decay and a learning-rate scale per
+ * parameter group, in the same single pass over the flat bucket.  The bucket is cut into n_seg <= 64 segments, segment s covering
+ * elements [seg_end[s-1], seg_end[s]) with seg_end[-1] = 0: strictly increasing, every end but the last a multiple of 4, the last
+ * equal to n.  seg_group[s] in [0, n_groups) names the segment's group, n_groups <= 8.  Per element of group G:
+ *     lr_G        = float(double(lr) * double(group_lr_scale[G]))
+ *     step_size_G = float(double(lr_G) / (1 - beta1^step))              (as ss_adam_clip takes it from lr)
+ *     decay_G     = float(1 - double(lr_G) * double(group_weight_decay[G]))
+ *     p1 = p * decay_G, rounded to f32 on its own (torch's in-place mul_; the decay is no part of the gradient)
+ *     m, v, p  <-  the update of ss_adam_clip on (p1, g, m, v) with step_size_G; ema as ss_adam_clip_ema's
+ * The clip coefficient is ss_adam_clip's, from the one sumsq word over the whole range.  So one segment of a group {scale 1,
+ * decay 0} writes the bits of ss_adam_clip (ss_adam_clip_ema), and with all decays 0 every segment gets the bits of an
+ * ss_adam_clip launch on its sub-range with lr = lr_G and the same sumsq word.  A scale of 0 leaves p at p1; m and v still move.
+ * seg_end, seg_group, group_lr_scale and group_weight_decay are HOST arrays -- the first arguments of this interface that are:
+ * they are read during the call and reach the kernel by value; nothing is allocated, copied to the device or kept, and the caller
+ * may free or change them as soon as the call returns.  Every other pointer is device memory.
+ * p, g, m, v, ema 16-byte aligned; ema must not overlap p and then 0 <= ema_decay < 1 (ema == NULL: ema_decay is ignored); scales
+ * and decays finite and >= 0; step >= 1.  SS_ERR_ARG otherwise, before any launch: nothing is written. */
+int ss_adamw_clip_groups(float* p, const float* g, float* m, float* v, float* ema, long n, const float* sumsq, float grad_scale,
+                         float max_norm, float lr, float beta1, float beta2, float eps, int step, float ema_decay,
+                         const long* seg_end, const int* seg_group, int n_seg, const float* group_lr_scale,
+                         const float* group_weight_decay, int n_groups, ss_stream_t stream);
+
 /* exchanges the contents of two f32 buffers of n elements in place (the weights and their average, Trainer.ema_weights).
  * Both 16-byte aligned; ranges that overlap are SS_ERR_ARG. */
 int ss_swap_f32(float* a, float* b, long n, ss_stream_t stream);

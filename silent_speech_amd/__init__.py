@@ -13,9 +13,9 @@ from .engine import Config
 from .features import crop_boxes, crop_rois, extract_features
 from .infer import GraphedInference
 from .serving import ClipGateServer, LiveFrontEnd, StreamServer, mouth_openness
-from .model import AttnPool, BiGRUClassifier, TinyROICNN
-from .train import Trainer, allreduce_flat_grads, shard_range
+from .model import AttnPool, BiGRUClassifier, ParamGroup, TinyROICNN, no_decay
+from .train import LrSchedule, PlateauSchedule, Trainer, allreduce_flat_grads, shard_range
 
 __all__ = ["AugmentPolicy", "Config", "BiGRUClassifier", "TinyROICNN", "AttnPool", "Trainer", "allreduce_flat_grads", "shard_range",
            "extract_features", "crop_boxes", "GraphedInference", "load_classifier", "save_checkpoint", "topk_from_logits", "features",
-           "data", "checkpoint"]
+           "data", "checkpoint", "ParamGroup", "no_decay", "LrSchedule", "PlateauSchedule"]

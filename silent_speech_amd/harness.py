@@ -23,9 +23,11 @@ from __future__ import annotations
 
 import collections
 import contextlib
+import copy
 import dataclasses
 import glob
 import hashlib
+import math
 import os
 import random
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
@@ -36,8 +38,8 @@ import torch
 from .checkpoint import (TRAIN_STATE_FORMAT, fingerprint_difference, load_train_state, save_checkpoint,
                          save_train_state)
 from .device_data import MASK_FIELDS, MIXUP_FIELDS, AugmentPolicy, DeviceClipStore
-from .model import BiGRUClassifier
-from .train import Trainer, check_class_weights, shard_range
+from .model import BiGRUClassifier, ParamGroup
+from .train import LrSchedule, PlateauSchedule, Trainer, check_class_weights, shard_range
 
 VAL_FRAC, SEED, PATIENCE, EPOCHS, BATCH_SIZE = 0.15, 42, 12, 80, 16
 I32_MAX = 2 ** 31 - 1  # "no clip yet" in a first_seen matrix
@@ -295,14 +297,26 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
 
 
 def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_roi, n_train, n_val, class_weights,
-                    augment_policy, ema_decay, init_from=None, freeze_cnn=False) -> dict:
+                    augment_policy, ema_decay, init_from=None, freeze_cnn=False, weight_decay=0.0, param_groups=None,
+                    lr_schedule=None, lr_plateau=None) -> dict:
     """What a resumable ``fit`` run depends on, as plain values (``checkpoint.FINGERPRINT_FIELDS``): a train-state file is
     resumed only by a call whose fingerprint equals the saved one.  ``epochs`` and ``patience`` are not part of it: a run may be
     resumed to train longer.  ``init_from`` (the sha256 of the checkpoint file the run started from, a hex string) and
     ``freeze_cnn`` are entries only when they are set: the fingerprint of a run without them is what it always was.  The same holds
     for the policy's mask fields (``AugmentPolicy.mask_fields``): each is an entry only where it differs from its default; and for
-    its two mixup fields (``AugmentPolicy.mixup_fields``), which are entries only when mixup is on."""
+    its two mixup fields (``AugmentPolicy.mixup_fields``), which are entries only when mixup is on; and for ``weight_decay`` (when
+    not 0), ``param_groups`` (the groups as written: patterns, scale, decay), ``lr_schedule`` (as written: a ``total_steps`` that
+    ``fit`` fills in from ``epochs`` stays None, since ``epochs`` is no part of the fingerprint) and ``lr_plateau`` (its settings; its
+    state travels in the train-state file)"""
     extra = {}
+    if float(weight_decay) != 0.0:
+        extra["weight_decay"] = float(weight_decay)
+    if param_groups is not None:
+        extra["param_groups"] = [dict(match=list(g.match), lr_scale=g.lr_scale, weight_decay=g.weight_decay) for g in param_groups]
+    if lr_schedule is not None:
+        extra["lr_schedule"] = lr_schedule.plain()
+    if lr_plateau is not None:
+        extra["lr_plateau"] = lr_plateau.plain()
     if init_from is not None:
         extra["init_from"] = str(init_from)
     if freeze_cnn:
@@ -345,7 +359,7 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
         log=print, plan: str = "host", rank: int = 0, world_size: int = 1, process_group=None,
         history: Optional[list] = None, class_weights=None, augment_policy=None, ema_decay: Optional[float] = None,
         state_path: Optional[str] = None, resume: bool = False, init_from: Optional[str] = None,
-        freeze_cnn: bool = False) -> float:
+        freeze_cnn: bool = False, weight_decay: float = 0.0, param_groups=None, lr_schedule=None, lr_plateau=None) -> float:
     """The reference's ``main()``: scan, split, train with class-balanced sampling and on-device augmentation, evaluate
     every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement.
 
@@ -412,7 +426,28 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     an ``augment_policy`` is refused (it acts on pixels).
 
     ``state_path``: the fingerprint holds ``init_from`` (the file's sha256) and ``freeze_cnn`` only when they are set, so the
-    files of runs without them are unchanged."""
+    files of runs without them are unchanged.
+
+    ``weight_decay``, ``param_groups`` (``ParamGroup``, ``no_decay()``): AdamW with per-group learning-rate scales and decays
+    (``Trainer``): inactive/train_model_1130pm.py:191 trains with ``AdamW(weight_decay=1e-3)``.  ``lr_schedule`` (``LrSchedule``): a
+    warm-up and a linear or cosine decay by the step count; a ``total_steps=None`` becomes ``epochs`` x the batches of an epoch.
+    ``lr_plateau`` (``PlateauSchedule``; ``fit`` works on a copy that starts fresh): stepped once per epoch behind the validation,
+    on its accuracy (mode "max", as inactive/train_reduced.py:199,242 steps ``ReduceLROnPlateau``) or its loss (mode "min"); the
+    scale it arrives at multiplies the learning rate of the following epochs.  Data parallel, every rank holds the same reduced
+    metrics and takes the same decision; rank 0 logs a reduction.  The learning rate of a step is ``lr * plateau scale *
+    lr_schedule(step count)``.  With a schedule or a plateau the ``history`` dicts gain ``lr``, the rate of the epoch's last step.
+    ``state_path``: the train-state file carries the plateau's state (best, bad count, scale) and the fingerprint these four
+    settings, each only when it is set: files and fingerprints of runs without them are unchanged."""
+    if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
+        raise TypeError("lr_schedule must be an LrSchedule")
+    if lr_plateau is not None and not isinstance(lr_plateau, PlateauSchedule):
+        raise TypeError("lr_plateau must be a PlateauSchedule")
+    if not (math.isfinite(float(weight_decay)) and float(weight_decay) >= 0.0):
+        raise ValueError(f"weight_decay must be finite and >= 0, not {weight_decay!r}")
+    if param_groups is not None:
+        param_groups = tuple(param_groups)
+        if not all(isinstance(g, ParamGroup) for g in param_groups):
+            raise TypeError("param_groups must be ParamGroup objects")
     if plan not in ("host", "device"):
         raise ValueError(f"plan must be 'host' or 'device', not {plan!r}")
     if freeze_cnn:  # (before anything touches a device or the clips)
@@ -468,7 +503,9 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     if state_path is not None:
         fingerprint = run_fingerprint(seed, batch_size, world_size, max_t, lr, info["uniq"], info["x_dim"], use_roi,
                                       len(train_files), len(val_files), class_weights, augment_policy, ema_decay,
-                                      init_from=None if init_from is None else file_sha256(init_from), freeze_cnn=freeze_cnn)
+                                      init_from=None if init_from is None else file_sha256(init_from), freeze_cnn=freeze_cnn,
+                                      weight_decay=weight_decay, param_groups=param_groups, lr_schedule=lr_schedule,
+                                      lr_plateau=lr_plateau)
         if resume and os.path.exists(state_path):
             saved = load_train_state(state_path)
             field = fingerprint_difference(saved["fingerprint"], fingerprint)
@@ -498,9 +535,15 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
         import torch.distributed as dist
 
         dist.broadcast(model.flat_params, src=dist.get_global_rank(process_group, 0), group=process_group)
+    if lr_schedule is not None and lr_schedule.decay != "none" and lr_schedule.total_steps is None:
+        lr_schedule = dataclasses.replace(lr_schedule, total_steps=epochs * -(-len(train_files) // batch_size))
+    plateau = None
+    if lr_plateau is not None:  # (a copy that starts fresh: the caller's object may have served another run)
+        plateau = copy.copy(lr_plateau)
+        plateau.reset()
     trainer = Trainer(model, lr=lr, world_size=world_size, process_group=process_group,
                       always_allreduce=process_group is not None, class_weights=class_weights, ema_decay=ema_decay,
-                      freeze_cnn=freeze_cnn)
+                      freeze_cnn=freeze_cnn, weight_decay=weight_decay, param_groups=param_groups, lr_schedule=lr_schedule)
     trainer.rank = rank
     # validation and the checkpoint see the averaged weights when there are any (two swap launches around each)
     averaged = trainer.ema_weights if ema_decay is not None else contextlib.nullcontext
@@ -511,6 +554,9 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
         model.load_state_dict(saved["model"])
         trainer.load_state_dict(saved["trainer"])
         best, bad, first_epoch = float(saved["best"]), int(saved["bad"]), int(saved["epoch"]) + 1
+        if plateau is not None:
+            plateau.load_state_dict(saved["plateau"])
+            trainer.lr_scale = plateau.scale
         log(f"Resuming from {state_path} at epoch {first_epoch} (best val acc {best:.3f})")
     if freeze_cnn:  # (behind the load, the broadcast and a resume: the CNN is final now, and the same on every rank)
         train_store.embed(model)
@@ -564,9 +610,14 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
             confs = top_confusions(y_true, y_pred, info["id_to_label"], k=6)
         n = max(1, len(order))
         if history is not None:
-            history.append(dict(epoch=ep, train_loss=float(tr_loss) / n, train_acc=int(tr_ok) / n, val_loss=va_loss, val_acc=va_acc))
+            history.append(dict(epoch=ep, train_loss=float(tr_loss) / n, train_acc=int(tr_ok) / n, val_loss=va_loss, val_acc=va_acc,
+                                **({} if lr_schedule is None and plateau is None else {"lr": trainer.current_lr()})))
         log(f"ep {ep:02d} | train loss {float(tr_loss) / n:.4f} acc {int(tr_ok) / n:.3f} | val loss {va_loss:.4f} acc {va_acc:.3f}"
             + ((" | top confusions: " + ", ".join(confs)) if confs else ""))
+        if plateau is not None:  # (every rank holds the same reduced metrics: the same decision everywhere)
+            if plateau.step(va_acc if plateau.mode == "max" else va_loss):
+                log(f"  lr plateau: scale {trainer.lr_scale:g} -> {plateau.scale:g}")
+            trainer.lr_scale = plateau.scale
         stop = False
         if va_acc > best:
             best, bad = va_acc, 0
@@ -579,7 +630,8 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
             stop = bad >= patience
         if state_path is not None and rank == 0:
             save_train_state(state_path, dict(format=TRAIN_STATE_FORMAT, model=model.state_dict(), trainer=trainer.state_dict(),
-                                              epoch=ep, best=float(best), bad=int(bad), stopped=bool(stop), fingerprint=fingerprint))
+                                              epoch=ep, best=float(best), bad=int(bad), stopped=bool(stop), fingerprint=fingerprint,
+                                              **({} if plateau is None else {"plateau": plateau.state_dict()})))
         if stop:
             log(f"Early stopping. Best val acc: {best:.3f}")
             break

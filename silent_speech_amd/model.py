@@ -12,13 +12,60 @@ contiguous bucket.
 """
 from __future__ import annotations
 
+import dataclasses
 import math
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence, Union
 
 import torch
 import torch.nn as nn
 
 from . import engine as E
+
+
+@dataclasses.dataclass(frozen=True)
+class ParamGroup:
+    """A parameter group of ``Trainer(param_groups=)``: the parameters whose ``named_parameters()`` name starts with ``match`` (a
+    prefix such as ``"roi_cnn."``, ``"gru."``, ``"head.0."``, or a sequence of them; a pattern with a leading ``*`` is matched
+    against the END of the name instead: ``"*bias"``) train with ``lr * lr_scale`` and with ``weight_decay`` (None: the
+    trainer's).  A parameter belongs to the first group of the list that matches it, and to the default group -- scale 1, the
+    trainer's decay -- when none does."""
+    match: Union[str, Sequence[str]]
+    lr_scale: float = 1.0
+    weight_decay: Optional[float] = None
+
+    def __post_init__(self):
+        pats = (self.match,) if isinstance(self.match, str) else tuple(self.match)
+        if not pats or not all(isinstance(p, str) and p not in ("", "*") for p in pats):
+            raise ValueError(f"ParamGroup.match must be a non-empty name prefix (or '*' + suffix) or a sequence of them, not {self.match!r}")
+        object.__setattr__(self, "match", pats)
+        for field in ("lr_scale", "weight_decay"):
+            x = getattr(self, field)
+            if x is None and field == "weight_decay":
+                continue
+            if not (math.isfinite(float(x)) and float(x) >= 0.0):
+                raise ValueError(f"ParamGroup.{field} must be finite and >= 0, not {x!r}")
+            object.__setattr__(self, field, float(x))
+
+    @staticmethod
+    def pattern_matches(pattern: str, name: str) -> bool:
+        return name.endswith(pattern[1:]) if pattern.startswith("*") else name.startswith(pattern)
+
+    def matches(self, name: str) -> bool:
+        return any(self.pattern_matches(p, name) for p in self.match)
+
+
+def no_decay(names=("bias", "head.0.")) -> ParamGroup:
+    """The standard group that is exempt from weight decay: the biases and the LayerNorm (``head.0.``), at the trainer's learning
+    rate.  A name that ends in ``.`` is a prefix; any other is the word a parameter's own name begins with: ``"bias"`` stands for
+    ``"*bias"`` (``roi_cnn.net.0.bias``, ``head.1.bias``, ...) and for ``"gru.bias_"``, since ``nn.GRU``'s names carry the layer
+    and the direction behind the word (``gru.bias_ih_l0_reverse``).  Put it behind groups it should not take parameters from."""
+    pats = []
+    for n in names:
+        pats += [n] if n.endswith(".") else ["*" + n, "gru." + n + "_"]
+    return ParamGroup(tuple(pats), lr_scale=1.0, weight_decay=0.0)
+
+
+MAX_SEGMENTS, MAX_GROUPS = 64, 8  # ss_adamw_clip_groups (include/ss_hotpath.h)
 
 
 def _uniform_(t: torch.Tensor, bound: float) -> torch.Tensor:
@@ -191,6 +238,46 @@ class BiGRUClassifier(nn.Module):
         n_cnn = lay[len(cnn)][1] if len(cnn) < len(lay) else total
         assert n_cnn % 4 == 0
         return n_cnn
+
+    def param_segments(self, groups: Sequence[ParamGroup] = (), lo: int = 0):
+        """The segment table of ``ss_adamw_clip_groups`` for elements ``[lo, n)`` of the flat bucket (``lo``: 0 or
+        ``cnn_param_range()``) -> ``(ends, ids, members)``: segment ``s`` covers ``[ends[s-1], ends[s])`` relative to ``lo``
+        (``ends[-1] = 0``) and belongs to group ``ids[s]``: the index of the first of ``groups`` that matches, or ``len(groups)``,
+        the default group; ``members[g]`` lists the names of group ``g``.  A tensor's segment ends where the next tensor starts, so
+        the alignment gap behind a tensor stays with it (those elements are zero and have zero gradients: every group leaves them
+        zero), every end is a multiple of 4 and the last is ``n - lo``; adjacent tensors of one group share a segment.
+        ``ValueError`` beyond ``MAX_GROUPS`` groups (the default one included) or ``MAX_SEGMENTS`` segments, and when ``lo`` > 0
+        and a prefix of a group matches parameters of the frozen range only.  Host code."""
+        groups = tuple(groups)
+        if not all(isinstance(g, ParamGroup) for g in groups):
+            raise TypeError("param_groups must be ParamGroup objects")
+        if len(groups) + 1 > MAX_GROUPS:
+            raise ValueError(f"{len(groups)} parameter groups and the default one: at most {MAX_GROUPS} groups fit one launch")
+        lay, total = self._layout()
+        if lo:
+            frozen = [name for name, off, *_ in lay if off < lo]
+            live = [name for name, off, *_ in lay if off >= lo]
+            for g in groups:
+                for pat in g.match:
+                    hit = lambda names: any(ParamGroup.pattern_matches(pat, n) for n in names)  # noqa: E731
+                    if not pat.startswith("*") and hit(frozen) and not hit(live):
+                        raise ValueError(f"ParamGroup({pat!r}) names parameters of the frozen ROI CNN only: with freeze_cnn they "
+                                         "are not trained")
+        ends, ids, members = [], [], [[] for _ in range(len(groups) + 1)]
+        for k, (name, off, n, shape) in enumerate(lay):
+            if off < lo:
+                continue
+            gi = next((i for i, g in enumerate(groups) if g.matches(name)), len(groups))
+            members[gi].append(name)
+            end = (lay[k + 1][1] if k + 1 < len(lay) else total) - lo
+            if ids and ids[-1] == gi:
+                ends[-1] = end
+            else:
+                ends.append(end)
+                ids.append(gi)
+        if len(ends) > MAX_SEGMENTS:
+            raise ValueError(f"these groups cut the bucket into {len(ends)} segments: at most {MAX_SEGMENTS} fit one launch")
+        return ends, ids, members
 
     def _views_of(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         return {name: flat[off:off + n].view(shape) for name, off, n, shape in self._layout()[0]}

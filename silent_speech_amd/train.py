@@ -13,7 +13,9 @@ batch exactly as a single process would.  ``torch.distributed`` backend "nccl" i
 from __future__ import annotations
 
 import contextlib
+import ctypes as C
 import dataclasses
+import math
 from typing import Optional
 
 import numpy as np
@@ -69,6 +71,135 @@ def ema_decay_at(decay: float, t: int, warmup: bool = True) -> float:
     return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
 
 
+@dataclasses.dataclass(frozen=True)
+class LrSchedule:
+    """A learning-rate factor that is a pure function of ``Trainer.step_count`` (the number of the step being taken, 1 for the
+    first), evaluated in float64 -- nothing to save, so a resumed run continues it exactly:
+
+        step <= warmup_steps                 step / warmup_steps                 (linear warm-up; its last step runs at 1)
+        decay "none"                         1
+        warmup_steps < step < total_steps    t = (step - warmup_steps) / (total_steps - warmup_steps)
+            "linear"                         1 - (1 - final_frac) * t
+            "cosine"                         final_frac + (1 - final_frac) * (1 + cos(pi * t)) / 2
+        step >= total_steps                  final_frac                          (held there)
+
+    ``total_steps=None`` with a decay is filled by ``harness.fit`` (epochs x batches per epoch); evaluating such a schedule
+    without it is a ``ValueError``."""
+    warmup_steps: int = 0
+    decay: str = "none"
+    total_steps: Optional[int] = None
+    final_frac: float = 0.0
+
+    def __post_init__(self):
+        if self.decay not in ("none", "linear", "cosine"):
+            raise ValueError(f"LrSchedule.decay must be 'none', 'linear' or 'cosine', not {self.decay!r}")
+        if int(self.warmup_steps) != self.warmup_steps or self.warmup_steps < 0:
+            raise ValueError(f"LrSchedule.warmup_steps must be an integer >= 0, not {self.warmup_steps!r}")
+        if self.total_steps is not None and (int(self.total_steps) != self.total_steps or self.total_steps <= self.warmup_steps):
+            raise ValueError(f"LrSchedule.total_steps must be an integer > warmup_steps, not {self.total_steps!r}")
+        if not 0.0 <= float(self.final_frac) <= 1.0:  # (a NaN fails both)
+            raise ValueError(f"LrSchedule.final_frac must lie in [0, 1], not {self.final_frac!r}")
+
+    def __call__(self, step: int) -> float:
+        step, w = max(int(step), 1), int(self.warmup_steps)
+        if step <= w:  # (w > 0: a step count is at least 1)
+            return max(step, 0) / float(w)
+        if self.decay == "none":
+            return 1.0
+        if self.total_steps is None:
+            raise ValueError("LrSchedule: a decay needs total_steps (harness.fit fills it in)")
+        f = float(self.final_frac)
+        if step >= self.total_steps:
+            return f
+        t = (step - w) / float(int(self.total_steps) - w)
+        return 1.0 - (1.0 - f) * t if self.decay == "linear" else f + (1.0 - f) * 0.5 * (1.0 + math.cos(math.pi * t))
+
+    def plain(self) -> dict:
+        return dict(warmup_steps=int(self.warmup_steps), decay=self.decay,
+                    total_steps=None if self.total_steps is None else int(self.total_steps), final_frac=float(self.final_frac))
+
+
+class PlateauSchedule:
+    """torch's ``ReduceLROnPlateau`` (relative threshold, cooldown 0) as a scale on the learning rate; the defaults are
+    inactive/train_reduced.py:199's (``mode='max', factor=0.5, patience=10``) and torch's (``threshold=1e-4``).  ``step(metric)``
+    once per epoch: a metric that beats the best one by more than the threshold -- ``> best * (1 + threshold)`` for "max",
+    ``< best * (1 - threshold)`` for "min" -- becomes the best and clears the count of bad epochs; any other adds one to it, and
+    when the count exceeds ``patience`` the scale becomes ``max(scale * factor, min_scale)`` and the count starts again.  (torch
+    also ignores reductions of the lr by less than ``eps=1e-8``; a scale has no such floor but ``min_scale``.)  -> True when the
+    scale moved.  The state -- ``best``, ``bad``, ``scale`` -- is three numbers (``state_dict`` / ``load_state_dict``)."""
+
+    def __init__(self, mode: str = "max", factor: float = 0.5, patience: int = 10, threshold: float = 1e-4, min_scale: float = 0.0):
+        if mode not in ("max", "min"):
+            raise ValueError(f"PlateauSchedule.mode must be 'max' or 'min', not {mode!r}")
+        if not 0.0 < float(factor) < 1.0:
+            raise ValueError(f"PlateauSchedule.factor must lie in (0, 1), not {factor!r}")
+        if int(patience) != patience or patience < 0:
+            raise ValueError(f"PlateauSchedule.patience must be an integer >= 0, not {patience!r}")
+        if not (float(threshold) >= 0.0 and 0.0 <= float(min_scale) <= 1.0):
+            raise ValueError("PlateauSchedule: threshold must be >= 0 and min_scale lie in [0, 1]")
+        self.mode, self.factor, self.patience = mode, float(factor), int(patience)
+        self.threshold, self.min_scale = float(threshold), float(min_scale)
+        self.reset()
+
+    def reset(self) -> None:
+        self.best = -math.inf if self.mode == "max" else math.inf
+        self.bad, self.scale = 0, 1.0
+
+    def step(self, metric: float) -> bool:
+        metric = float(metric)
+        better = metric > self.best * (1.0 + self.threshold) if self.mode == "max" else metric < self.best * (1.0 - self.threshold)
+        if better:
+            self.best, self.bad = metric, 0
+        else:
+            self.bad += 1
+        if self.bad > self.patience:
+            self.bad = 0
+            new = max(self.scale * self.factor, self.min_scale)
+            moved, self.scale = new != self.scale, new
+            return moved
+        return False
+
+    def plain(self) -> dict:
+        return dict(mode=self.mode, factor=self.factor, patience=self.patience, threshold=self.threshold, min_scale=self.min_scale)
+
+    def state_dict(self) -> dict:
+        return dict(best=float(self.best), bad=int(self.bad), scale=float(self.scale))
+
+    def load_state_dict(self, state: dict) -> None:
+        self.best, self.bad, self.scale = float(state["best"]), int(state["bad"]), float(state["scale"])
+
+
+class SegmentTable:
+    """The host arrays of one ``ss_adamw_clip_groups`` launch, built once per ``Trainer``: the segments of
+    ``model.param_segments(param_groups, lo)`` and one (lr scale, weight decay) pair per group, the default group last (scale 1,
+    the trainer's decay; a group's ``weight_decay=None`` inherits it).  The library reads them during the call and hands them to
+    the kernel by value: nothing here lives on the device.  ``plain()`` is the table as lists, for ``state_dict``."""
+
+    def __init__(self, model: BiGRUClassifier, param_groups, weight_decay: float, lo: int = 0):
+        groups = tuple(param_groups or ())
+        ends, ids, members = model.param_segments(groups, lo)
+        self.n = model._layout()[1] - lo
+        assert ends[-1] == self.n and all(e % 4 == 0 for e in ends)
+        self.match = [list(g.match) for g in groups] + [[]]
+        self.lr_scale = [g.lr_scale for g in groups] + [1.0]
+        self.weight_decay = [float(weight_decay) if g.weight_decay is None else g.weight_decay for g in groups] + [float(weight_decay)]
+        self.seg_end, self.seg_group, self.members = list(ends), list(ids), members
+        self._end = (C.c_long * len(ends))(*ends)
+        self._group = (C.c_int * len(ids))(*ids)
+        self._scale = (C.c_float * len(self.lr_scale))(*self.lr_scale)
+        self._decay = (C.c_float * len(self.weight_decay))(*self.weight_decay)
+
+    @property
+    def args(self):
+        """(seg_end, seg_group, n_seg, group_lr_scale, group_weight_decay, n_groups) as the entry point takes them."""
+        return (C.addressof(self._end), C.addressof(self._group), len(self.seg_end), C.addressof(self._scale),
+                C.addressof(self._decay), len(self.lr_scale))
+
+    def plain(self) -> dict:
+        return dict(seg_end=[int(e) for e in self.seg_end], seg_group=[int(g) for g in self.seg_group], match=self.match,
+                    lr_scale=[float(np.float32(x)) for x in self.lr_scale], weight_decay=[float(np.float32(x)) for x in self.weight_decay])
+
+
 class Trainer:
     """``micro_batches`` > 1 splits this rank's clips into that many equal slices which travel through forward and
     backward on their own HIP streams.  The GRU recurrence is latency-bound and occupies only one CU per
@@ -106,7 +237,18 @@ class Trainer:
     ``requires_grad=False``, and ``grad_norm()`` reports that norm.  ``step`` on such a trainer raises, and so does
     ``step_embedded`` on any other: mixing the two would silently skip or apply CNN updates.  ``micro_batches`` > 1 is a
     ``ValueError``.  Class weights, the weight average, ``state_dict`` / ``load_state_dict`` and empty shards work as in ``step``.
-    Without ``freeze_cnn`` a step issues exactly the launches it always has."""
+    Without ``freeze_cnn`` a step issues exactly the launches it always has.
+
+    ``weight_decay`` / ``param_groups`` (``model.ParamGroup``, ``model.no_decay()``): torch's decoupled AdamW with a learning-rate
+    scale and a decay per parameter group -- a lower rate on the CNN, decay on the matrices but not on the biases or the LayerNorm.
+    The one ``ss_adam_clip`` / ``ss_adam_clip_ema`` launch of a step becomes one ``ss_adamw_clip_groups`` launch on the same
+    range with the ``SegmentTable`` of the groups (host arrays, built once); nothing else in the step changes, the clip still is
+    one global norm, and with ``freeze_cnn`` the table covers ``[n_cnn, n)``.  With ``weight_decay == 0`` and no groups a step
+    issues exactly the launches it always has.
+
+    ``lr_schedule`` (``LrSchedule``) and ``lr_scale`` (an attribute: the plateau scale ``harness.fit(lr_plateau=)`` sets, 1
+    otherwise): the learning rate of a step is ``lr * lr_scale * lr_schedule(step_count)`` in float64 (``current_lr()``); it is a
+    per-launch scalar of either entry point, so a schedule alone changes no launch."""
 
     # CUs left to the other micro-batch's recurrence while a persistent ROI-CNN kernel runs (2 directions x 8 slices)
     CNN_RESERVED_CUS = 32
@@ -114,7 +256,17 @@ class Trainer:
     def __init__(self, model: BiGRUClassifier, lr: float = 3e-4, max_norm: float = 1.0,
                  label_smoothing: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  process_group=None, dropout: bool = True, micro_batches: int = 1, always_allreduce: bool = False,
-                 class_weights=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, freeze_cnn: bool = False):
+                 class_weights=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, freeze_cnn: bool = False,
+                 weight_decay: float = 0.0, param_groups=None, lr_schedule: Optional[LrSchedule] = None):
+        weight_decay = float(weight_decay)
+        if not (math.isfinite(weight_decay) and weight_decay >= 0.0):
+            raise ValueError(f"weight_decay must be finite and >= 0, not {weight_decay!r}")
+        if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
+            raise TypeError("lr_schedule must be an LrSchedule")
+        # (host code: the ValueErrors of the groups come before anything touches a device)
+        table = None
+        if weight_decay != 0.0 or param_groups is not None:
+            table = SegmentTable(model, param_groups, weight_decay, model.cnn_param_range() if freeze_cnn and model.cfg.use_roi else 0)
         if freeze_cnn:
             if not model.cfg.use_roi or model.cfg.precision != "f32":
                 raise RuntimeError("freeze_cnn needs an f32 use_roi model (the bf16 engine has no frozen-CNN path)")
@@ -148,6 +300,7 @@ class Trainer:
         self.cw = None if cw is None else torch.from_numpy(cw).to(dev)
         self.den = None if cw is None else torch.zeros(1, device=dev, dtype=torch.float32)
         self.freeze_cnn = bool(freeze_cnn)
+        self.weight_decay, self.table, self.lr_schedule, self.lr_scale = weight_decay, table, lr_schedule, 1.0
         self.loss = None  # the last step's engine.Loss, kept ONLY to keep its tensors alive until the next (built for empty shards too)
         # the optimiser's range of the flat bucket is [n_frozen, n): everything, or everything behind the ROI CNN
         self.n_frozen = model.cnn_param_range() if freeze_cnn else 0
@@ -316,15 +469,28 @@ class Trainer:
         n_el, at = model.flat_grads.numel() - lo, 4 * lo
         L.call("ss_sumsq_f32", model.flat_grads.data_ptr() + at, n_el, self.scal.data_ptr() + 4, s)
         # d_logits already carries 1/(B*world), so the summed bucket IS the global-mean gradient
-        if self.ema is None:
+        lr = self.lr if self.lr_schedule is None and self.lr_scale == 1.0 else self.current_lr()
+        if self.table is not None:  # AdamW with parameter groups: the same pass, one launch in place of either one below
+            assert self.table.n == n_el
+            L.call("ss_adamw_clip_groups", model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at,
+                   self.m.data_ptr() + at, self.v.data_ptr() + at, None if self.ema is None else self.ema.data_ptr() + at, n_el,
+                   self.scal.data_ptr() + 4, 1.0, self.max_norm, lr, self.betas[0], self.betas[1], self.eps, self.step_count,
+                   0.0 if self.ema is None else ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup), *self.table.args, s)
+        elif self.ema is None:
             L.call("ss_adam_clip", model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at, self.m.data_ptr() + at,
-                   self.v.data_ptr() + at, n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr, self.betas[0],
+                   self.v.data_ptr() + at, n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, lr, self.betas[0],
                    self.betas[1], self.eps, self.step_count, s)
         else:  # the same update of p, m, v, and the weight average in the same pass over the bucket
             L.call("ss_adam_clip_ema", model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at, self.m.data_ptr() + at,
-                   self.v.data_ptr() + at, self.ema.data_ptr() + at, n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, self.lr,
+                   self.v.data_ptr() + at, self.ema.data_ptr() + at, n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, lr,
                    self.betas[0], self.betas[1], self.eps, self.step_count,
                    ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup), s)
+
+    def current_lr(self, step: Optional[int] = None) -> float:
+        """The learning rate of step ``step`` (default: the last one taken, ``step_count``): ``lr * lr_scale *
+        lr_schedule(step)`` in float64; the launches take it as float32."""
+        sched = 1.0 if self.lr_schedule is None else self.lr_schedule(self.step_count if step is None else step)
+        return float(self.lr) * float(self.lr_scale) * sched
 
     def step_embedded(self, Z: torch.Tensor, lengths: torch.Tensor, y: torch.Tensor, global_batch: Optional[int] = None,
                       y_global: Optional[torch.Tensor] = None, mix=None):
@@ -404,15 +570,20 @@ class Trainer:
         step uses.  Plain tensors, numbers and lists: ``torch.save`` writes it and ``torch.load(weights_only=True)`` reads it."""
         if self._ema_swapped:
             raise RuntimeError("Trainer.state_dict inside ema_weights(): the weights and their average are exchanged there")
+        extra = {"freeze_cnn": True} if self.freeze_cnn else {}
+        if self.table is not None or self.lr_schedule is not None or self.lr_scale != 1.0:  # (keys of trainers that use them only)
+            extra.update(weight_decay=float(self.weight_decay), param_groups=None if self.table is None else self.table.plain(),
+                         lr_schedule=None if self.lr_schedule is None else self.lr_schedule.plain(), lr_scale=float(self.lr_scale))
         return dict(m=self.m.detach().clone(), v=self.v.detach().clone(), ema=None if self.ema is None else self.ema.detach().clone(),
                     step_count=int(self.step_count), ema_decay=self.ema_decay, ema_warmup=bool(self.ema_warmup),
                     betas=[float(b) for b in self.betas], eps=float(self.eps), lr=float(self.lr), max_norm=float(self.max_norm),
-                    numel=int(self.model.flat_params.numel()), **({"freeze_cnn": True} if self.freeze_cnn else {}))
+                    numel=int(self.model.flat_params.numel()), **extra)
 
     def load_state_dict(self, state: dict) -> None:
         """Take over a ``state_dict()``: the tensors are copied into this trainer's device buffers (nothing is re-allocated), the
         step count and the hyperparameters are set.  ``ValueError`` when the bucket has another element count, when one side
-        keeps a weight average and the other does not, or when one side freezes the ROI CNN and the other does not."""
+        keeps a weight average and the other does not, when one side freezes the ROI CNN and the other does not, or when the
+        segment tables (groups, scales, decays) differ."""
         if self._ema_swapped:
             raise RuntimeError("Trainer.load_state_dict inside ema_weights()")
         if self.model._bucket_version != self._bucket_version:
@@ -423,6 +594,10 @@ class Trainer:
         if bool(state.get("freeze_cnn", False)) != self.freeze_cnn:
             raise ValueError("the saved trainer state and this Trainer disagree about freeze_cnn: "
                              f"saved {bool(state.get('freeze_cnn', False))!r}, this one {self.freeze_cnn!r}")
+        saved_table, table = state.get("param_groups"), None if self.table is None else self.table.plain()
+        if saved_table != table:
+            raise ValueError("the saved trainer state and this Trainer disagree about weight_decay / param_groups: "
+                             f"saved table {saved_table!r}, this one {table!r}")
         if (state["ema"] is None) != (self.ema is None):
             raise ValueError("the saved trainer state and this Trainer disagree about ema_decay: "
                              f"saved {state['ema_decay']!r}, this one {self.ema_decay!r}")
@@ -436,6 +611,7 @@ class Trainer:
         self.step_count = int(state["step_count"])
         self.betas, self.eps = (float(state["betas"][0]), float(state["betas"][1])), float(state["eps"])
         self.lr, self.max_norm = float(state["lr"]), float(state["max_norm"])
+        self.lr_scale = float(state.get("lr_scale", 1.0))  # (the schedule is this trainer's own: a pure function of the step count)
 
     def _fwd_bwd(self, X, lengths, R, loss, train, seed, slot, phase, prologue_done=False):
         """Forward + CE ("fwd"), backward ("bwd") or both of one micro-batch on the current stream; ``loss``: its ``engine.Loss``."""
