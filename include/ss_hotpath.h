@@ -679,6 +679,25 @@ int ss_tail_fwd_mix(const float* h, const int32_t* lengths, const float* w_score
                     uint64_t seed, uint64_t offset, float label_smoothing, float denom, const float* cw, const float* den,
                     float* attn, float* xhat, float* rstd, float* ln, float* mid, float* mid_d, float* logits, float* d_logits,
                     float* loss_sum, int32_t* correct, ss_stream_t stream);
+/* Any of the three losses above blended with a teacher's soft targets (knowledge distillation): t_logits (B, ld_t) f32 teacher
+ * logits (rows ld_t >= C apart; they must be finite: the caller vouches for it), kd_alpha in [0, 1], kd_tau > 0 and finite.
+ * y_b / lam and cw / den are each both given or both NULL, as under ss_tail_fwd_mix.  Per row, with q = softmax(z / tau) of the
+ * row's own logits z and pt = softmax(t / tau):
+ *   l           = (1 - alpha) * hard / hard_norm        + alpha * tau^2 * sum_c pt_c (log pt_c - log q_c) / denom,
+ *   d_logits[c] = (1 - alpha) * hard_grad_c / hard_norm + alpha * tau * (q_c - pt_c) / denom,
+ * `hard` the loss the other arguments describe over its own normaliser (denom, or *den with weights).  The soft term is not
+ * class-weighted and is ALWAYS divided by `denom` (the global clip count: kl_div's "batchmean"), so `denom` > 0 is required
+ * with weights too.  The label rule is that of the hard loss; a row that does not count adds nothing, soft term included;
+ * correct counts argmax == y.  kd_alpha == 0: the bits of ss_tail_fwd / _w / _mix, d_logits and loss alike.  t_logits equal to
+ * the row's own logits: the soft term and its gradient are exactly 0.  The logits and stashes are those of ss_tail_fwd.
+ * ss_tail_bwd serves this one too. */
+int ss_tail_fwd_kd(const float* h, const int32_t* lengths, const float* w_score, const float* b_score, const float* gamma,
+                   const float* beta, const float* w1, const float* b1, const float* w4, const float* b4, const int64_t* y,
+                   const int64_t* y_b, const float* lam, int B, int T, int D, int MID, int C, float ln_eps, float drop_p,
+                   uint64_t seed, uint64_t offset, float label_smoothing, float denom, const float* cw, const float* den,
+                   float* attn, float* xhat, float* rstd, float* ln, float* mid, float* mid_d, float* logits, float* d_logits,
+                   float* loss_sum, int32_t* correct, const float* t_logits, int ld_t, float kd_alpha, float kd_tau,
+                   ss_stream_t stream);
 /* Backward of the tail from d_logits (B,C) down to d_h (B,T,D) (written) and d_mid (B,MID) (written: the input of the
  * first Linear's weight-gradient GEMM); g_gamma, g_beta (D), g_wscore (D), g_bscore (1) are accumulated -- unless
  * col_part (B,3,D) is given: then every clip STORES its terms of g_gamma | g_beta | g_wscore there and the caller adds the
@@ -712,6 +731,12 @@ int ss_ce_ls_w_fwd_bwd(const float* logits, const int64_t* y, int B, int C, floa
 int ss_ce_ls_mix_fwd_bwd(const float* logits, const int64_t* y, const int64_t* y_b, const float* lam, int B, int C,
                          float label_smoothing, float denom, const float* w, const float* den, float* d_logits, float* loss_sum,
                          int32_t* correct, ss_stream_t stream);
+/* The stand-alone form of ss_tail_fwd_kd's loss on given logits (B, C): y_b / lam and w / den each both given or both NULL;
+ * t_logits (B, ld_t), kd_alpha, kd_tau and the always-required `denom` as there.  d_logits, loss_sum and correct may each be
+ * NULL.  kd_alpha == 0: the bits of ss_ce_ls_fwd_bwd / _w_ / _mix_. */
+int ss_ce_ls_kd_fwd_bwd(const float* logits, const int64_t* y, const int64_t* y_b, const float* lam, int B, int C,
+                        float label_smoothing, float denom, const float* w, const float* den, float* d_logits, float* loss_sum,
+                        int32_t* correct, const float* t_logits, int ld_t, float kd_alpha, float kd_tau, ss_stream_t stream);
 /* out[0] = sum of w[y_i] over the n int64 labels y (device), written (not accumulated).  One workgroup, a fixed reduction
  * order: the result is a pure function of (the labels in order, w), so ranks that hold the same labels get the same bits.
  * A label outside [0, C) adds nothing. */

@@ -113,6 +113,7 @@ SIGNATURES = {
     "ss_tail_fwd": [_vp] * 11 + [_i] * 5 + [_f, _f, _u64, _u64, _f, _f] + [_vp] * 10 + [_vp],
     "ss_tail_fwd_w": [_vp] * 11 + [_i] * 5 + [_f, _f, _u64, _u64, _f, _vp, _vp] + [_vp] * 10 + [_vp],
     "ss_tail_fwd_mix": [_vp] * 13 + [_i] * 5 + [_f, _f, _u64, _u64, _f, _f, _vp, _vp] + [_vp] * 10 + [_vp],
+    "ss_tail_fwd_kd": [_vp] * 13 + [_i] * 5 + [_f, _f, _u64, _u64, _f, _f, _vp, _vp] + [_vp] * 10 + [_vp, _i, _f, _f] + [_vp],
     "ss_tail_bwd": [_vp] * 11 + [_i] * 5 + [_f, _u64, _u64] + [_vp] * 7 + [_vp],
     "ss_layernorm_fwd": [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp],
     "ss_layernorm_bwd": [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
@@ -121,6 +122,7 @@ SIGNATURES = {
     "ss_eval_accum": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ss_ce_ls_w_fwd_bwd": [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "ss_ce_ls_mix_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ss_ce_ls_kd_fwd_bwd": [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp],
     "ss_class_weight_sum": [_vp, _l, _vp, _i, _vp, _vp],
     "ss_eval_accum_w": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ss_softmax_topk": [_vp, _i, _i, _i, _vp, _vp, _vp],

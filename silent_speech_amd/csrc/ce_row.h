@@ -20,10 +20,25 @@
 // (unweighted: A = 1 for both labels, so A_mix = 1 and is not blended).  MIX = false is every operation the row has always had, in
 // its order; MIX = true with lam == 1 gives those bits again (1 * x + 0 * z is x, fused or not, for finite z).
 //
+// KD = true adds a teacher's soft targets (ss_ce_ls_kd_fwd_bwd, ss_tail_fwd_kd): teacher logits t, temperature tau > 0, weight
+// alpha in [0, 1]; q = softmax(z / tau), pt = softmax(t / tau), lq and lpt their logs,
+//   loss      = (1 - alpha) * hard / hard_norm        + alpha * tau^2 * KL(pt || q) / denom,   KL = sum_c pt_c * (lpt_c - lq_c)
+//   d logit_c = (1 - alpha) * hard_grad_c / hard_norm + alpha * tau * (q_c - pt_c) / denom.
+// `hard` is everything above (smoothing, weights, both labels) over its own normaliser (denom, or *den with weights); the soft
+// term is never class-weighted and always over CeKd::denom, the global clip count (kl_div's "batchmean" under data parallelism),
+// so a weighted launch carries that count as well.  The KL is taken from the two LOG-softmaxes, never from the log of a
+// probability: a pt_c that underflows to 0 adds 0 * finite = 0.  Both softmaxes go through ONE pair of helpers (ce_lsm_tau /
+// ce_lsm_tau_wave and ce_lp_tau), called once for z and once for t, so t == z gives equal bits, q - pt = 0 and KL = 0 exactly.
+// The row has no label in the soft term, so it composes with WEIGHTED and MIX; the label rule is unchanged and a row that does
+// not count gets nothing, soft term included.  The teacher logits must be finite: the caller vouches for it, as the plain path
+// does for its labels.  KD = false is every operation the row has always had, in its order (kd is not read); KD = true with
+// alpha == 0 gives those bits again, gradient row and loss alike: each output is (1 - alpha) * x + alpha * k with x the old
+// value, and 1 * x + 0 * k is x, fused or not, for finite k (ce_kd_blend).
+//
 // Two forms, because the callers spread a row differently: ce_row (one thread walks the row) and ce_row_wave (the 64 lanes of a
 // wave share it, classes lane, lane + 64, ...).  They differ in the order of their C-term sums, as the kernels always have.
 //
-// A launch's loss is one CeLoss, what it means for row b one CeRow (ce_row_of); ce_dispatch picks <WEIGHTED, MIX> on the host.
+// A launch's loss is one CeLoss, what it means for row b one CeRow (ce_row_of); ce_dispatch picks <WEIGHTED, MIX, KD> on the host.
 #pragma once
 #include <type_traits>
 
@@ -34,6 +49,15 @@
 struct CeLoss { const int64_t *y, *y_b; const float *lam, *cw, *den; float denom, ls; };
 // Row b of a CeLoss: does it count, its labels as indices, the mixing factor and the normaliser.
 struct CeRow { bool counts; int yy, yb; float lam, denom; };
+
+// The soft targets of a launch (KD): t (B, ld_t) teacher logits, the blend alpha, the temperature tau and the soft term's
+// normaliser, the global clip count.  Apart from CeLoss, so that a kernel can take it where its other instantiations never look.
+struct CeKd { const float* t; int ld_t; float alpha, tau, denom; };
+
+// Host: what both _kd entry points require of their soft targets (NaN fails every comparison)
+static inline bool ce_kd_ok(const float* t, int ld_t, int C, float alpha, float tau, float denom) {
+  return t && ld_t >= C && alpha >= 0.f && alpha <= 1.f && tau > 0.f && tau <= 3.4e38f && denom > 0.f;
+}
 
 __device__ __forceinline__ bool ce_label_ok(int64_t label, int C) { return label >= 0 && label < (int64_t)C; }
 
@@ -78,11 +102,49 @@ __device__ __forceinline__ float ce_a(float wl, float sw, float eps, int C) {
   else return 1.0f;
 }
 
+// ---- softmax at temperature (KD): the ONE code path of both the student's and the teacher's row.
+// ce_lsm_tau[_wave] -> the row's maximum *m_out and log(sum_c exp((x_c - m) / tau)); ce_lp_tau: log softmax(x / tau)_c from them.
+__device__ __forceinline__ float ce_lsm_tau(const float* __restrict__ x, int C, float tau, float* m_out) {
+  float m = x[0];
+  for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+  float se = 0.f;
+  for (int c = 0; c < C; ++c) se += expf((x[c] - m) / tau);
+  *m_out = m;
+  return logf(se);
+}
+__device__ __forceinline__ float ce_lsm_tau_wave(const float* x, int C, int lane, float tau, float* m_out) {
+  float m = -3.4e38f;
+  for (int c = lane; c < C; c += 64) m = fmaxf(m, x[c]);
+  m = wave_max(m);
+  float se = 0.f;
+  for (int c = lane; c < C; c += 64) se += expf((x[c] - m) / tau);
+  *m_out = m;
+  return logf(wave_sum(se));
+}
+__device__ __forceinline__ float ce_lp_tau(float x, float m, float tau, float ls) { return (x - m) / tau - ls; }
+// class c of the soft term: its KL summand is added to *kl, its gradient tau * (q_c - pt_c) / denom returned
+__device__ __forceinline__ float ce_kd_class(float z, float mz, float lsz, float t, float mt, float lst, const CeKd& kd, float* kl) {
+  const float lq = ce_lp_tau(z, mz, kd.tau, lsz), lpt = ce_lp_tau(t, mt, kd.tau, lst);
+  const float q = expf(lq), pt = expf(lpt);
+  *kl += pt * (lpt - lq);
+  return kd.tau * (q - pt) / kd.denom;
+}
+// (1 - alpha) * hard + alpha * soft: with alpha == 0 the bits of `hard` (header)
+__device__ __forceinline__ float ce_kd_blend(float hard, float soft, float alpha) { return (1.0f - alpha) * hard + alpha * soft; }
+// what a row adds to the launch's loss sum: loss / its normaliser, under KD blended with the soft term tau^2 * KL / kd.denom
+template <bool KD>
+__device__ __forceinline__ float ce_row_loss(float loss, float denom, float kl, const CeKd& kd) {
+  if constexpr (KD) return ce_kd_blend(loss / denom, kd.tau * kd.tau * kl / kd.denom, kd.alpha);
+  else return loss / denom;
+}
+
 // One thread per row.  lr = the row's C logits, r = ce_row_of a row that counts (without MIX r.yb and r.lam are not read).
 // d_row (may be NULL): the gradient row / r.denom; *am_out: the lowest index among equal maxima (torch.argmax).  Returns the loss, undivided.
-template <bool WEIGHTED, bool MIX = false>
+// KD: tr = the row's teacher logits; d_row gets the blended gradient and *kl_out the row's KL (ce_row_loss blends the loss).
+template <bool WEIGHTED, bool MIX = false, bool KD = false>
 __device__ __forceinline__ float ce_row(const float* __restrict__ lr, int C, float eps, const float* __restrict__ w,
-                                        const CeRow& r, float* __restrict__ d_row, int* am_out) {
+                                        const CeRow& r, float* __restrict__ d_row, int* am_out, const CeKd& kd = CeKd{},
+                                        const float* __restrict__ tr = nullptr, float* kl_out = nullptr) {
   const int yy = r.yy, yb = r.yb;
   const float lam = r.lam, oml = 1.0f - r.lam;  // (MIX only)
   float m = lr[0];
@@ -105,6 +167,11 @@ __device__ __forceinline__ float ce_row(const float* __restrict__ lr, int C, flo
   if constexpr (WEIGHTED && MIX) wyb = w[yb];
   float loss = ce_label_loss<WEIGHTED>(lse, lr[yy], wy, slp, eps, C);
   if constexpr (MIX) loss = lam * loss + oml * ce_label_loss<WEIGHTED>(lse, lr[yb], wyb, slp, eps, C);
+  float mz = 0.f, lsz = 0.f, mt = 0.f, lst = 0.f, kl = 0.f;  // (KD only)
+  if constexpr (KD) {
+    lsz = ce_lsm_tau(lr, C, kd.tau, &mz);
+    lst = ce_lsm_tau(tr, C, kd.tau, &mt);
+  }
   if (d_row) {
     float a = ce_a<WEIGHTED>(wy, sw, eps, C);
     if constexpr (WEIGHTED && MIX) a = lam * a + oml * ce_a<WEIGHTED>(wyb, sw, eps, C);
@@ -112,18 +179,24 @@ __device__ __forceinline__ float ce_row(const float* __restrict__ lr, int C, flo
       const float pr = expf(lr[c] - lse);
       float tgt = ce_tgt<WEIGHTED>(c, yy, wy, w, eps, C);
       if constexpr (MIX) tgt = lam * tgt + oml * ce_tgt<WEIGHTED>(c, yb, wyb, w, eps, C);
-      d_row[c] = (pr * a - tgt) / r.denom;
+      if constexpr (KD) d_row[c] = ce_kd_blend((pr * a - tgt) / r.denom, ce_kd_class(lr[c], mz, lsz, tr[c], mt, lst, kd, &kl), kd.alpha);
+      else d_row[c] = (pr * a - tgt) / r.denom;
     }
+  } else if constexpr (KD) {
+    for (int c = 0; c < C; ++c) ce_kd_class(lr[c], mz, lsz, tr[c], mt, lst, kd, &kl);
   }
+  if constexpr (KD) *kl_out = kl;
   *am_out = am;
   return loss;
 }
 
 // One wave per row; every lane of the wave calls it.  lg = the row's C logits (LDS or global), lane = 0..63, r as in ce_row.
 // d_row (not NULL) gets the gradient row / r.denom.  Returns the row's loss, not divided, and the arg-max in *am_out (every lane).
-template <bool WEIGHTED, bool MIX = false>
+// KD: tr = the row's teacher logits; d_row gets the blended gradient and *kl_out (every lane) the row's KL.
+template <bool WEIGHTED, bool MIX = false, bool KD = false>
 __device__ __forceinline__ float ce_row_wave(const float* lg, int C, int lane, float eps, const float* __restrict__ w,
-                                             const CeRow& r, float* __restrict__ d_row, int* am_out) {
+                                             const CeRow& r, float* __restrict__ d_row, int* am_out, const CeKd& kd = CeKd{},
+                                             const float* __restrict__ tr = nullptr, float* kl_out = nullptr) {
   const int yy = r.yy, yb = r.yb;
   const float lam = r.lam, oml = 1.0f - r.lam;  // (MIX only)
   float mx = -3.4e38f;
@@ -156,24 +229,36 @@ __device__ __forceinline__ float ce_row_wave(const float* lg, int C, int lane, f
   }
   float a = ce_a<WEIGHTED>(wy, sw, eps, C);
   if constexpr (WEIGHTED && MIX) a = lam * a + oml * ce_a<WEIGHTED>(wyb, sw, eps, C);
+  float mz = 0.f, lsz = 0.f, mt = 0.f, lst = 0.f, kl = 0.f;  // (KD only)
+  if constexpr (KD) {
+    lsz = ce_lsm_tau_wave(lg, C, lane, kd.tau, &mz);
+    lst = ce_lsm_tau_wave(tr, C, lane, kd.tau, &mt);
+  }
   for (int c = lane; c < C; c += 64) {
     const float pr = expf(lg[c] - lse);
     float tgt = ce_tgt<WEIGHTED>(c, yy, wy, w, eps, C);
     if constexpr (MIX) tgt = lam * tgt + oml * ce_tgt<WEIGHTED>(c, yb, wyb, w, eps, C);
-    d_row[c] = (pr * a - tgt) / r.denom;
+    if constexpr (KD) d_row[c] = ce_kd_blend((pr * a - tgt) / r.denom, ce_kd_class(lg[c], mz, lsz, tr[c], mt, lst, kd, &kl), kd.alpha);
+    else d_row[c] = (pr * a - tgt) / r.denom;
   }
+  if constexpr (KD) *kl_out = wave_sum(kl);
   float loss = ce_label_loss<WEIGHTED>(lse, lg[yy], wy, sl, eps, C);
   if constexpr (MIX) loss = lam * loss + oml * ce_label_loss<WEIGHTED>(lse, lg[yb], wyb, sl, eps, C);
   *am_out = am;
   return loss;
 }
 
-// Host: f(std::bool_constant<WEIGHTED>, std::bool_constant<MIX>) for a loss with class weights (cw != NULL) and / or second
-// labels (y_b != NULL): the one if-ladder over the instantiations of the three kernels.
+// Host: f(std::bool_constant<WEIGHTED>, std::bool_constant<MIX>, std::bool_constant<KD>) for a loss with class weights
+// (cw != NULL), second labels (y_b != NULL) and / or teacher logits (t != NULL): the one if-ladder over the instantiations of
+// tail_fwd_kernel and ce_ls_kernel.  (Evaluation is the hard loss: eval.hip has no soft targets.)
 template <class F>
-static inline void ce_dispatch(const void* cw, const void* y_b, F&& f) {
-  if (cw && y_b) f(std::true_type{}, std::true_type{});
-  else if (y_b) f(std::false_type{}, std::true_type{});
-  else if (cw) f(std::true_type{}, std::false_type{});
-  else f(std::false_type{}, std::false_type{});
+static inline void ce_dispatch(const void* cw, const void* y_b, const void* t, F&& f) {
+  auto kd = [&](auto w, auto m) {
+    if (t) f(w, m, std::true_type{});
+    else f(w, m, std::false_type{});
+  };
+  if (cw && y_b) kd(std::true_type{}, std::true_type{});
+  else if (y_b) kd(std::false_type{}, std::true_type{});
+  else if (cw) kd(std::true_type{}, std::false_type{});
+  else kd(std::false_type{}, std::false_type{});
 }

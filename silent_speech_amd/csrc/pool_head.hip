@@ -201,28 +201,32 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ 
 // one thread per clip (C is a handful of words); the row arithmetic is ce_row, the label rule ce_row_of (both ce_row.h).  The
 // launch's CeLoss arrives field by field: only a `const T* __restrict__` kernel ARGUMENT has its uniform reads (w[c] in the class
 // loops, lam[0]) done by scalar loads; as struct members they were vector loads and cost 1 to 3 VGPRs.
-template <bool WEIGHTED, bool MIX>
+// The soft targets (KD: t, ld_t, kd_alpha, kd_tau) trail the list, where the instantiations without KD never look; their
+// normaliser is the argument `denom`, which a weighted launch with KD therefore carries too.
+template <bool WEIGHTED, bool MIX, bool KD>
 __global__ __launch_bounds__(256) void ce_ls_kernel(const float* __restrict__ logits, const int64_t* __restrict__ y, int B,
                                                     int C, float eps, float denom, const float* __restrict__ w,
                                                     const float* __restrict__ den, float* __restrict__ d_logits,
                                                     float* __restrict__ loss_sum, int* __restrict__ correct,
-                                                    const int64_t* __restrict__ y_b, const float* __restrict__ lam) {
+                                                    const int64_t* __restrict__ y_b, const float* __restrict__ lam,
+                                                    const float* __restrict__ t, int ld_t, float kd_alpha, float kd_tau) {
   const int b = blockIdx.x * 256 + threadIdx.x;
+  const CeKd kd = {t, ld_t, kd_alpha, kd_tau, denom};  // (KD only)
   if constexpr (WEIGHTED) denom = den[0];
-  float loss = 0.f;
+  float loss = 0.f, kl = 0.f;
   int ok = 0;
   if (b < B) {
     float* d_row = d_logits ? d_logits + (long)b * C : nullptr;
     const CeRow r = ce_row_of<WEIGHTED, MIX>(y, y_b, lam, denom, b, C);
     if (r.counts) {
       int am;
-      loss = ce_row<WEIGHTED, MIX>(logits + (long)b * C, C, eps, w, r, d_row, &am);
+      loss = ce_row<WEIGHTED, MIX, KD>(logits + (long)b * C, C, eps, w, r, d_row, &am, kd, KD ? t + (long)b * ld_t : nullptr, &kl);
       ok = (am == r.yy);
     } else if (d_row) {
       for (int c = 0; c < C; ++c) d_row[c] = 0.f;
     }
   }
-  loss = wave_sum(loss / denom);
+  loss = wave_sum(ce_row_loss<KD>(loss, denom, kl, kd));
   if ((threadIdx.x & 63) == 0 && loss_sum) atomicAdd(loss_sum, loss);
   if (correct && ok) atomicAdd(correct, 1);
 }
@@ -341,12 +345,12 @@ extern "C" int ss_dropout(const float* x, float* y, long n, float p, uint64_t se
 
 // the three CE entry points: what they all check, and the launch (which unpacks the loss: see ce_ls_kernel)
 static int ce_ls_launch(const float* logits, int B, int C, const CeLoss& ce, float* d_logits, float* loss_sum, int32_t* correct,
-                        ss_stream_t stream) {
+                        ss_stream_t stream, const CeKd& kd = CeKd{}) {
   SS_REQUIRE(logits && ce.y && B > 0 && C > 0, SS_ERR_ARG);
-  ce_dispatch(ce.cw, ce.y_b, [&](auto w, auto m) {
-    hipLaunchKernelGGL((ce_ls_kernel<decltype(w)::value, decltype(m)::value>), dim3(ceil_div(B, 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), logits, ce.y, B, C, ce.ls, ce.denom, ce.cw, ce.den, d_logits, loss_sum, correct,
-                       ce.y_b, ce.lam);
+  ce_dispatch(ce.cw, ce.y_b, kd.t, [&](auto w, auto m, auto k) {
+    hipLaunchKernelGGL((ce_ls_kernel<decltype(w)::value, decltype(m)::value, decltype(k)::value>), dim3(ceil_div(B, 256)),
+                       dim3(256), 0, static_cast<hipStream_t>(stream), logits, ce.y, B, C, ce.ls, ce.denom, ce.cw, ce.den, d_logits,
+                       loss_sum, correct, ce.y_b, ce.lam, kd.t, kd.ld_t, kd.alpha, kd.tau);
   });
   return ss_launch_status();
 }
@@ -373,6 +377,16 @@ extern "C" int ss_ce_ls_mix_fwd_bwd(const float* logits, const int64_t* y, const
   SS_REQUIRE(y_b && lam && (w == nullptr) == (den == nullptr) && (w || denom > 0.f), SS_ERR_ARG);
   return ce_ls_launch(logits, B, C, CeLoss{y, y_b, lam, w, den, w ? 1.0f : denom, label_smoothing}, d_logits, loss_sum, correct,
                       stream);
+}
+
+extern "C" int ss_ce_ls_kd_fwd_bwd(const float* logits, const int64_t* y, const int64_t* y_b, const float* lam, int B, int C,
+                                   float label_smoothing, float denom, const float* w, const float* den, float* d_logits,
+                                   float* loss_sum, int32_t* correct, const float* t_logits, int ld_t, float kd_alpha,
+                                   float kd_tau, ss_stream_t stream) {
+  SS_REQUIRE((y_b == nullptr) == (lam == nullptr) && (w == nullptr) == (den == nullptr), SS_ERR_ARG);
+  SS_REQUIRE(ce_kd_ok(t_logits, ld_t, C, kd_alpha, kd_tau, denom), SS_ERR_ARG);
+  return ce_ls_launch(logits, B, C, CeLoss{y, y_b, lam, w, den, denom, label_smoothing}, d_logits, loss_sum, correct, stream,
+                      CeKd{t_logits, ld_t, kd_alpha, kd_tau, denom});
 }
 
 extern "C" int ss_class_weight_sum(const int64_t* y, long n, const float* w, int C, float* out, ss_stream_t stream) {

@@ -49,9 +49,11 @@ struct TailFwdParams {
   int* correct;
 };
 
-// dynamic LDS: sc[T] | pooled[D] | lnv[D] | midv[MID] | lg[C].  <WEIGHTED, MIX>: the loss of p.ce (ce_row.h), at compile time
-template <bool WEIGHTED, bool MIX>
-__global__ __launch_bounds__(TNT) void tail_fwd_kernel(TailFwdParams p) {
+// dynamic LDS: sc[T] | pooled[D] | lnv[D] | midv[MID] | lg[C].  <WEIGHTED, MIX, KD>: the loss of p.ce (ce_row.h), at compile time.
+// kd (the soft targets, read under KD only) is a kernel argument of its own BEHIND p: the instantiations without KD never load
+// it, and every field of p stays at the offset it has always had (the register figures: DESIGN.md section 4).
+template <bool WEIGHTED, bool MIX, bool KD>
+__global__ __launch_bounds__(TNT) void tail_fwd_kernel(TailFwdParams p, CeKd kd) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   __shared__ float red[2 * NWT];
   const int T = p.T, D = p.D, MID = p.MID, C = p.C;
@@ -221,9 +223,11 @@ __global__ __launch_bounds__(TNT) void tail_fwd_kernel(TailFwdParams p) {
     const CeRow r = ce_row_of<WEIGHTED, MIX>(p.ce.y, p.ce.y_b, p.ce.lam, ce_denom<WEIGHTED>(p.ce), b, C);
     if (r.counts) {
       int am;
-      const float loss = ce_row_wave<WEIGHTED, MIX>(lg, C, lane, p.ce.ls, p.ce.cw, r, d_row, &am);
+      float kl = 0.f;
+      const float loss = ce_row_wave<WEIGHTED, MIX, KD>(lg, C, lane, p.ce.ls, p.ce.cw, r, d_row, &am, kd,
+                                                            KD ? kd.t + (long)b * kd.ld_t : nullptr, &kl);
       if (lane == 0) {
-        if (p.loss_sum) atomicAdd(p.loss_sum, loss / r.denom);
+        if (p.loss_sum) atomicAdd(p.loss_sum, ce_row_loss<KD>(loss, r.denom, kl, kd));
         if (p.correct && am == r.yy) atomicAdd(p.correct, 1);
       }
     } else {
@@ -333,12 +337,13 @@ __global__ __launch_bounds__(TNT) void tail_bwd_kernel(TailBwdParams p) {
 
 }  // namespace
 
-// ce: the loss (ce_row.h); ce.y == NULL: none
+// ce: the loss (ce_row.h); ce.y == NULL: none.  kd: its soft targets; kd.t == NULL: none
 static int tail_fwd_launch(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
                            const float* gamma, const float* beta, const float* w1, const float* b1, const float* w4,
                            const float* b4, const CeLoss& ce, int B, int T, int D, int MID, int C, float ln_eps, float drop_p,
                            uint64_t seed, uint64_t offset, float* attn, float* xhat, float* rstd, float* ln, float* mid,
-                           float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream) {
+                           float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct, ss_stream_t stream,
+                           const CeKd& kd = CeKd{}) {
   SS_REQUIRE(h && lengths && w_score && b_score && gamma && beta && w1 && b1 && w4 && b4 && logits, SS_ERR_ARG);
   SS_REQUIRE(B > 0 && T > 0 && D > 0 && MID > 0 && C > 0 && drop_p >= 0.f && drop_p < 1.f, SS_ERR_ARG);
   SS_REQUIRE(!ce.y || (d_logits && ce.denom > 0.f), SS_ERR_ARG);
@@ -351,9 +356,9 @@ static int tail_fwd_launch(const float* h, const int32_t* lengths, const float* 
   p.eps = ln_eps; p.drop_p = drop_p; p.seed = seed; p.offset = offset;
   p.attn = attn; p.xhat = xhat; p.rstd = rstd; p.ln = ln; p.mid = mid; p.mid_d = mid_d; p.logits = logits;
   p.d_logits = d_logits; p.loss_sum = loss_sum; p.correct = correct;
-  ce_dispatch(ce.cw, ce.y_b, [&](auto w, auto m) {
-    hipLaunchKernelGGL((tail_fwd_kernel<decltype(w)::value, decltype(m)::value>), dim3(B), dim3(TNT), lds,
-                       static_cast<hipStream_t>(stream), p);
+  ce_dispatch(ce.cw, ce.y_b, kd.t, [&](auto w, auto m, auto k) {
+    hipLaunchKernelGGL((tail_fwd_kernel<decltype(w)::value, decltype(m)::value, decltype(k)::value>), dim3(B), dim3(TNT), lds,
+                       static_cast<hipStream_t>(stream), p, kd);
   });
   return ss_launch_status();
 }
@@ -392,6 +397,22 @@ extern "C" int ss_tail_fwd_mix(const float* h, const int32_t* lengths, const flo
   return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4,
                          CeLoss{y, y_b, lam, cw, den, cw ? 1.0f : denom, label_smoothing}, B, T, D, MID, C, ln_eps, drop_p, seed,
                          offset, attn, xhat, rstd, ln, mid, mid_d, logits, d_logits, loss_sum, correct, stream);
+}
+
+extern "C" int ss_tail_fwd_kd(const float* h, const int32_t* lengths, const float* w_score, const float* b_score,
+                              const float* gamma, const float* beta, const float* w1, const float* b1, const float* w4,
+                              const float* b4, const int64_t* y, const int64_t* y_b, const float* lam, int B, int T, int D,
+                              int MID, int C, float ln_eps, float drop_p, uint64_t seed, uint64_t offset, float label_smoothing,
+                              float denom, const float* cw, const float* den, float* attn, float* xhat, float* rstd, float* ln,
+                              float* mid, float* mid_d, float* logits, float* d_logits, float* loss_sum, int32_t* correct,
+                              const float* t_logits, int ld_t, float kd_alpha, float kd_tau, ss_stream_t stream) {
+  SS_REQUIRE(y && (y_b == nullptr) == (lam == nullptr) && (cw == nullptr) == (den == nullptr), SS_ERR_ARG);
+  SS_REQUIRE(ce_kd_ok(t_logits, ld_t, C, kd_alpha, kd_tau, denom), SS_ERR_ARG);
+  // (the hard term's `denom` is not read under weights, where *den divides; the soft term's always is)
+  return tail_fwd_launch(h, lengths, w_score, b_score, gamma, beta, w1, b1, w4, b4,
+                         CeLoss{y, y_b, lam, cw, den, denom, label_smoothing}, B, T, D, MID, C, ln_eps, drop_p, seed, offset, attn,
+                         xhat, rstd, ln, mid, mid_d, logits, d_logits, loss_sum, correct, stream,
+                         CeKd{t_logits, ld_t, kd_alpha, kd_tau, denom});
 }
 
 extern "C" int ss_tail_bwd(const float* h, const int32_t* lengths, const float* w_score, const float* gamma,

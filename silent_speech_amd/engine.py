@@ -320,7 +320,10 @@ class Loss:
     """The loss the fused tail evaluates next to the logits (``forward(ce=)``), as device tensors, which the object keeps alive.
     ``y`` (B,) int64 labels; ``denom``: the mean's divisor (the global clip count); ``loss_sum`` (f32) and ``correct`` (int32): where
     the launch adds this batch's loss and hit count.  ``cw`` (C,) f32 with ``den`` (1,) f32: the class-weighted loss divided by
-    ``den[0]`` (``denom`` is then unused).  ``y_b`` (B,) int64 with ``lam`` (1,) f32: the two-label loss of a mixup batch."""
+    ``den[0]`` (``denom`` is then unused).  ``y_b`` (B,) int64 with ``lam`` (1,) f32: the two-label loss of a mixup batch.
+    ``t_logits`` (B, C) f32 contiguous with ``kd_alpha`` and ``kd_tau`` (all three or none): a teacher's soft targets,
+    ``(1 - kd_alpha) * that loss + kd_alpha * kd_tau^2 * KL(softmax(t / tau) || softmax(z / tau)) / denom`` (``ss_tail_fwd_kd``;
+    the soft term is always divided by ``denom``, with class weights too)."""
     y: torch.Tensor
     label_smoothing: float
     denom: float
@@ -330,10 +333,20 @@ class Loss:
     den: Optional[torch.Tensor] = None
     y_b: Optional[torch.Tensor] = None
     lam: Optional[torch.Tensor] = None
+    t_logits: Optional[torch.Tensor] = None
+    kd_alpha: Optional[float] = None
+    kd_tau: Optional[float] = None
 
     def tail_args(self):
-        """-> (the tail entry point of this loss, its label arguments, its normaliser arguments), in the order of
-        include/ss_hotpath.h (``ss_tail_fwd_mix`` takes ``cw`` and ``den`` NULL without weights)."""
+        """-> (the tail entry point of this loss, its label arguments, its normaliser arguments, its soft-target arguments), in
+        the order of include/ss_hotpath.h (``ss_tail_fwd_mix`` and ``ss_tail_fwd_kd`` take NULL for what the loss has not)."""
+        if self.t_logits is not None:
+            return ("ss_tail_fwd_kd", (self.y.data_ptr(), L.ptr(self.y_b), L.ptr(self.lam)),
+                    (self.denom, L.ptr(self.cw), L.ptr(self.den)),
+                    (self.t_logits.data_ptr(), self.t_logits.shape[1], self.kd_alpha, self.kd_tau))
+        return (*self._hard_args(), ())
+
+    def _hard_args(self):
         if self.y_b is not None:
             return ("ss_tail_fwd_mix", (self.y.data_ptr(), self.y_b.data_ptr(), self.lam.data_ptr()),
                     (self.denom, L.ptr(self.cw), L.ptr(self.den)))
@@ -345,14 +358,14 @@ class Loss:
 def tail_fwd(P, cfg: Config, ws, top, train, stash, seed, ce: Optional[Loss]):
     """AttnPool + head (+ loss) of both engines: one fused launch, a workgroup per clip; ``ce``: the ``Loss``, or None."""
     p_drop = cfg.head_dropout if train else 0.0
-    name, labels, norm = ce.tail_args() if ce is not None else ("ss_tail_fwd", (None,), (1.0,))
+    name, labels, norm, soft = ce.tail_args() if ce is not None else ("ss_tail_fwd", (None,), (1.0,), ())
     ls, sums = (ce.label_smoothing, (ws.d_logits, ce.loss_sum, ce.correct)) if ce is not None else (0.0, (None,) * 3)
     stashed = (ws.attn, ws.xhat, ws.rstd, ws.ln, ws.mid, ws.mid_drop) if stash else (None,) * 6
     L.call(name, top.data_ptr(), ws.lengths.data_ptr(), P["pool.score.weight"].data_ptr(),
            P["pool.score.bias"].data_ptr(), P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(),
            P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(), P["head.4.weight"].data_ptr(),
            P["head.4.bias"].data_ptr(), *labels, ws.B, ws.T, 2 * cfg.hidden, cfg.head_mid, cfg.num_classes, cfg.ln_eps, p_drop, seed,
-           7 << 40, ls, *norm, *map(L.ptr, stashed), ws.logits.data_ptr(), *map(L.ptr, sums), L.stream())
+           7 << 40, ls, *norm, *map(L.ptr, stashed), ws.logits.data_ptr(), *map(L.ptr, sums), *soft, L.stream())
     return ws.logits
 
 

@@ -35,11 +35,11 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .checkpoint import (TRAIN_STATE_FORMAT, fingerprint_difference, load_train_state, save_checkpoint,
+from .checkpoint import (TRAIN_STATE_FORMAT, fingerprint_difference, load_classifier, load_train_state, save_checkpoint,
                          save_train_state)
 from .device_data import MASK_FIELDS, MIXUP_FIELDS, AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier, ParamGroup
-from .train import LrSchedule, PlateauSchedule, Trainer, check_class_weights, shard_range
+from .train import LrSchedule, PlateauSchedule, Trainer, check_class_weights, check_distill, shard_range
 
 VAL_FRAC, SEED, PATIENCE, EPOCHS, BATCH_SIZE = 0.15, 42, 12, 80, 16
 I32_MAX = 2 ** 31 - 1  # "no clip yet" in a first_seen matrix
@@ -298,7 +298,7 @@ def evaluate_device(model: BiGRUClassifier, store: DeviceClipStore, batch_size: 
 
 def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_roi, n_train, n_val, class_weights,
                     augment_policy, ema_decay, init_from=None, freeze_cnn=False, weight_decay=0.0, param_groups=None,
-                    lr_schedule=None, lr_plateau=None) -> dict:
+                    lr_schedule=None, lr_plateau=None, distill_from=None, distill_alpha=0.5, distill_temperature=2.0) -> dict:
     """What a resumable ``fit`` run depends on, as plain values (``checkpoint.FINGERPRINT_FIELDS``): a train-state file is
     resumed only by a call whose fingerprint equals the saved one.  ``epochs`` and ``patience`` are not part of it: a run may be
     resumed to train longer.  ``init_from`` (the sha256 of the checkpoint file the run started from, a hex string) and
@@ -307,7 +307,9 @@ def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_
     its two mixup fields (``AugmentPolicy.mixup_fields``), which are entries only when mixup is on; and for ``weight_decay`` (when
     not 0), ``param_groups`` (the groups as written: patterns, scale, decay), ``lr_schedule`` (as written: a ``total_steps`` that
     ``fit`` fills in from ``epochs`` stays None, since ``epochs`` is no part of the fingerprint) and ``lr_plateau`` (its settings; its
-    state travels in the train-state file)"""
+    state travels in the train-state file); and for ``distill_from`` (the sha256 of the teacher's checkpoint file, or ``"module"``
+    for a teacher handed over as a module), ``distill_alpha`` and ``distill_temperature``, all three entries only when
+    ``distill_from`` is set."""
     extra = {}
     if float(weight_decay) != 0.0:
         extra["weight_decay"] = float(weight_decay)
@@ -321,6 +323,9 @@ def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_
         extra["init_from"] = str(init_from)
     if freeze_cnn:
         extra["freeze_cnn"] = True
+    if distill_from is not None:
+        extra.update(distill_from=str(distill_from), distill_alpha=float(distill_alpha),
+                     distill_temperature=float(distill_temperature))
     return dict(seed=int(seed), batch_size=int(batch_size), world_size=int(world_size), max_t=int(max_t), lr=float(lr),
                 labels=[str(lab) for lab in labels], x_dim=int(x_dim), use_roi=bool(use_roi), n_train=int(n_train),
                 n_val=int(n_val), class_weights=None if class_weights is None else [float(w) for w in class_weights],
@@ -354,12 +359,28 @@ def load_init_checkpoint(path: str, x_dim: int, use_roi: bool, roi_emb: int, hid
     return ckpt
 
 
+def check_teacher(x_dim: int, use_roi: bool, num_classes: int, labels, clip_x_dim: int, run_use_roi: bool, clip_labels) -> None:
+    """A distillation teacher against the run: ``ValueError`` naming ``x_dim``, ``use_roi`` or the labels -- a checkpoint teacher's
+    list must be the clips', in content and order; a module teacher has none (``labels=None``) and its ``num_classes`` must be
+    their count.  Host code."""
+    if int(x_dim) != int(clip_x_dim):
+        raise ValueError(f"distill_from: the teacher's x_dim is {int(x_dim)}, the clips' is {int(clip_x_dim)}")
+    if bool(use_roi) != bool(run_use_roi):
+        raise ValueError(f"distill_from: the teacher's use_roi is {bool(use_roi)}, the run's is {bool(run_use_roi)}")
+    if labels is not None and list(labels) != list(clip_labels):
+        raise ValueError(f"distill_from: the teacher's labels {list(labels)!r} differ from the clips' labels {list(clip_labels)!r} "
+                         "(content and order must match)")
+    if int(num_classes) != len(clip_labels):
+        raise ValueError(f"distill_from: the teacher's num_classes is {int(num_classes)}, the clips have {len(clip_labels)} labels")
+
+
 def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BATCH_SIZE, patience: int = PATIENCE,
         max_t: int = 90, lr: float = 3e-4, seed: int = SEED, use_roi_if_present: bool = True, device="cuda",
         log=print, plan: str = "host", rank: int = 0, world_size: int = 1, process_group=None,
         history: Optional[list] = None, class_weights=None, augment_policy=None, ema_decay: Optional[float] = None,
         state_path: Optional[str] = None, resume: bool = False, init_from: Optional[str] = None,
-        freeze_cnn: bool = False, weight_decay: float = 0.0, param_groups=None, lr_schedule=None, lr_plateau=None) -> float:
+        freeze_cnn: bool = False, weight_decay: float = 0.0, param_groups=None, lr_schedule=None, lr_plateau=None,
+        distill_from=None, distill_alpha: float = 0.5, distill_temperature: float = 2.0) -> float:
     """The reference's ``main()``: scan, split, train with class-balanced sampling and on-device augmentation, evaluate
     every epoch, keep the best checkpoint (reference schema), stop after ``patience`` epochs without improvement.
 
@@ -437,7 +458,27 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     metrics and takes the same decision; rank 0 logs a reduction.  The learning rate of a step is ``lr * plateau scale *
     lr_schedule(step count)``.  With a schedule or a plateau the ``history`` dicts gain ``lr``, the rate of the epoch's last step.
     ``state_path``: the train-state file carries the plateau's state (best, bad count, scale) and the fingerprint these four
-    settings, each only when it is set: files and fingerprints of runs without them are unchanged."""
+    settings, each only when it is set: files and fingerprints of runs without them are unchanged.
+
+    ``distill_from`` (knowledge distillation; needs ``plan="device"``; the reference has no teacher): a checkpoint path, read by
+    ``load_classifier``, or a ``BiGRUClassifier`` already on the device -- any width, depth or precision, which is how a large
+    bf16 model teaches the shipped one.  The teacher is put in ``eval()`` and is never trained, saved or averaged.  Every
+    training step runs ``teacher(X, T, R)`` under ``no_grad`` on the batch the student sees (augmented and mixed included) and
+    hands its logits to ``Trainer.step(teacher_logits=)`` with ``distill_alpha`` and ``distill_temperature`` (``Trainer``):
+    enqueue-only, nothing is read back.  Its ``x_dim`` and ``use_roi`` must be the run's and a checkpoint teacher's label list the
+    clips', in content and order (``ValueError`` naming the field).  Not with ``freeze_cnn`` (embedded batches hold no pixels for
+    the teacher).  Data parallel, every rank holds the teacher and runs it on its own shard: no collective is added.  Validation,
+    the checkpoint, the weight average, the schedules and the logged train accuracy are as without; the logged train loss is the
+    blended one.  ``state_path``: the fingerprint holds ``distill_from`` (the file's sha256, or ``"module"``), ``distill_alpha`` and
+    ``distill_temperature`` only when ``distill_from`` is set; a resumed run must be given the same teacher."""
+    if distill_from is not None:  # (host code, before anything touches a device or the clips)
+        distill_alpha, distill_temperature = check_distill(distill_alpha, distill_temperature)
+        if not isinstance(distill_from, (str, os.PathLike, BiGRUClassifier)):
+            raise TypeError("distill_from must be a checkpoint path or a BiGRUClassifier")
+        if plan != "device":
+            raise ValueError("distill_from needs plan='device': the teacher's forward joins the enqueue-only epoch")
+        if freeze_cnn:
+            raise ValueError("distill_from does not combine with freeze_cnn: embedded batches hold no pixels for the teacher")
     if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
         raise TypeError("lr_schedule must be an LrSchedule")
     if lr_plateau is not None and not isinstance(lr_plateau, PlateauSchedule):
@@ -499,13 +540,25 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     init_ckpt = None
     if init_from is not None:  # (host code: the mismatches raise before anything is uploaded)
         init_ckpt = load_init_checkpoint(init_from, info["x_dim"], use_roi, 32, 192)
+    teacher_ckpt = None
+    if distill_from is not None:  # (host code again: the mismatches raise before anything is uploaded)
+        if isinstance(distill_from, BiGRUClassifier):
+            cfg_t = distill_from.cfg
+            check_teacher(cfg_t.x_dim, cfg_t.use_roi, cfg_t.num_classes, None, info["x_dim"], use_roi, info["uniq"])
+        else:
+            teacher_ckpt = torch.load(distill_from, map_location="cpu", weights_only=False)
+            check_teacher(teacher_ckpt["x_dim"], teacher_ckpt.get("use_roi", False), len(teacher_ckpt["labels"]),
+                          teacher_ckpt["labels"], info["x_dim"], use_roi, info["uniq"])
     saved, fingerprint = None, None
     if state_path is not None:
         fingerprint = run_fingerprint(seed, batch_size, world_size, max_t, lr, info["uniq"], info["x_dim"], use_roi,
                                       len(train_files), len(val_files), class_weights, augment_policy, ema_decay,
                                       init_from=None if init_from is None else file_sha256(init_from), freeze_cnn=freeze_cnn,
                                       weight_decay=weight_decay, param_groups=param_groups, lr_schedule=lr_schedule,
-                                      lr_plateau=lr_plateau)
+                                      lr_plateau=lr_plateau,
+                                      distill_from=None if distill_from is None else
+                                      ("module" if teacher_ckpt is None else file_sha256(distill_from)),
+                                      distill_alpha=distill_alpha, distill_temperature=distill_temperature)
         if resume and os.path.exists(state_path):
             saved = load_train_state(state_path)
             field = fingerprint_difference(saved["fingerprint"], fingerprint)
@@ -543,8 +596,15 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
         plateau.reset()
     trainer = Trainer(model, lr=lr, world_size=world_size, process_group=process_group,
                       always_allreduce=process_group is not None, class_weights=class_weights, ema_decay=ema_decay,
-                      freeze_cnn=freeze_cnn, weight_decay=weight_decay, param_groups=param_groups, lr_schedule=lr_schedule)
+                      freeze_cnn=freeze_cnn, weight_decay=weight_decay, param_groups=param_groups, lr_schedule=lr_schedule,
+                      **({} if distill_from is None else dict(distill_alpha=distill_alpha, distill_temperature=distill_temperature)))
     trainer.rank = rank
+    teacher = None
+    if distill_from is not None:
+        teacher = distill_from if teacher_ckpt is None else load_classifier(distill_from, device=device)[0]
+        if teacher.flat_params is None or not teacher.flat_params.is_cuda:
+            raise ValueError("distill_from: a module teacher must already be on the device")
+        teacher.eval()
     # validation and the checkpoint see the averaged weights when there are any (two swap launches around each)
     averaged = trainer.ema_weights if ema_decay is not None else contextlib.nullcontext
     roi_hw = train_store.roi_hw or (48, 96)
@@ -587,7 +647,12 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                     loss, correct = trainer.step_embedded(X, T, y, global_batch=global_batch, y_global=y_glob)
                 else:
                     mix = train_store.mix[:2] if mixup and hi > lo else None
-                    loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch, y_global=y_glob, mix=mix)
+                    t_logits = None
+                    if teacher is not None and hi > lo:  # (the batch the student sees; enqueue-only: T is on the device)
+                        with torch.no_grad():
+                            t_logits = teacher(X, T, R if use_roi else None)
+                    loss, correct = trainer.step(X, T, R if use_roi else None, y, global_batch=global_batch, y_global=y_glob, mix=mix,
+                                                 teacher_logits=t_logits)
                 tr_loss += loss * global_batch
                 tr_ok += correct
             with averaged():

@@ -63,6 +63,20 @@ def check_class_weights(class_weights, num_classes: int) -> np.ndarray:
     return np.ascontiguousarray(w)
 
 
+def check_distill(alpha, temperature):
+    """The blend and the temperature of a distillation loss as floats.  ``ValueError`` unless 0 <= alpha <= 1 and temperature is
+    finite and > 0, both as the float32 the kernels take.  Host code: nothing here touches a device."""
+    try:
+        a, t = float(np.float32(alpha)), float(np.float32(temperature))
+    except (TypeError, ValueError):
+        raise ValueError(f"distill_alpha and distill_temperature must be numbers, not {alpha!r} and {temperature!r}") from None
+    if not 0.0 <= a <= 1.0:
+        raise ValueError(f"distill_alpha must lie in [0, 1], not {alpha!r}")
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"distill_temperature must be finite and > 0, not {temperature!r}")
+    return float(alpha), float(temperature)
+
+
 def ema_decay_at(decay: float, t: int, warmup: bool = True) -> float:
     """The decay of the weight average at step ``t`` (``Trainer.step_count`` of the step being taken: 1 for the first), in
     double: ``min(decay, (1 + t) / (10 + t))`` -- the early steps, whose average would otherwise be dominated by the initial
@@ -248,7 +262,17 @@ class Trainer:
 
     ``lr_schedule`` (``LrSchedule``) and ``lr_scale`` (an attribute: the plateau scale ``harness.fit(lr_plateau=)`` sets, 1
     otherwise): the learning rate of a step is ``lr * lr_scale * lr_schedule(step_count)`` in float64 (``current_lr()``); it is a
-    per-launch scalar of either entry point, so a schedule alone changes no launch."""
+    per-launch scalar of either entry point, so a schedule alone changes no launch.
+
+    ``step(teacher_logits=)`` / ``step_embedded(teacher_logits=)`` (knowledge distillation): a (B, C) float32 contiguous device
+    tensor of a teacher's logits on this batch.  The loss becomes ``(1 - distill_alpha) * hard + distill_alpha *
+    distill_temperature^2 * KL(softmax(t / tau) || softmax(z / tau)) / global_batch``, ``hard`` being the loss of the step
+    without a teacher (smoothing, class weights, ``mix=``) over its own normaliser; the fused tail evaluates it in the launch it
+    always was (``ss_tail_fwd_kd`` in place of ``ss_tail_fwd`` / ``_w`` / ``_mix``), so nothing else in the step changes.
+    ``distill_alpha`` (0.5) and ``distill_temperature`` (2.0) are checked on the host (``ValueError``) and used only when
+    teacher logits are given.  The teacher logits must be finite; with ``mix=`` the teacher is expected to have seen the blended
+    batch.  Not with ``micro_batches`` > 1 (``ValueError``).  Without ``teacher_logits`` a step issues exactly the launches it
+    always has."""
 
     # CUs left to the other micro-batch's recurrence while a persistent ROI-CNN kernel runs (2 directions x 8 slices)
     CNN_RESERVED_CUS = 32
@@ -257,7 +281,9 @@ class Trainer:
                  label_smoothing: float = 0.05, betas=(0.9, 0.999), eps: float = 1e-8, world_size: int = 1,
                  process_group=None, dropout: bool = True, micro_batches: int = 1, always_allreduce: bool = False,
                  class_weights=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, freeze_cnn: bool = False,
-                 weight_decay: float = 0.0, param_groups=None, lr_schedule: Optional[LrSchedule] = None):
+                 weight_decay: float = 0.0, param_groups=None, lr_schedule: Optional[LrSchedule] = None,
+                 distill_alpha: float = 0.5, distill_temperature: float = 2.0):
+        self.distill_alpha, self.distill_temperature = check_distill(distill_alpha, distill_temperature)  # (host code)
         weight_decay = float(weight_decay)
         if not (math.isfinite(weight_decay) and weight_decay >= 0.0):
             raise ValueError(f"weight_decay must be finite and >= 0, not {weight_decay!r}")
@@ -340,7 +366,7 @@ class Trainer:
         self._bucket_version = model._bucket_version
 
     def step(self, X: torch.Tensor, lengths: torch.Tensor, R: Optional[torch.Tensor], y: torch.Tensor,
-             global_batch: Optional[int] = None, y_global: Optional[torch.Tensor] = None, mix=None):
+             global_batch: Optional[int] = None, y_global: Optional[torch.Tensor] = None, mix=None, teacher_logits=None):
         """One optimiser step on this rank's shard.  Returns (loss, correct) device tensors:
         loss = this shard's contribution to the global mean loss (sum over ranks = global loss).
         ``global_batch`` = clips of ALL ranks in this step; needed only when the shards are unequal (``shard_range``
@@ -357,11 +383,13 @@ class Trainer:
         (1,) f32, both on the device.  The loss is ``lam * CE(y) + (1 - lam) * CE(y_b)`` (``ss_tail_fwd_mix``), with class weights
         both terms over the one normaliser of ``y`` (``y_b`` is a permutation of it); ``correct`` counts ``argmax == y``.  Not with
         ``micro_batches`` > 1 (``ValueError``).
+        ``teacher_logits`` (B, C) f32 contiguous on the device: the distillation loss of the class docstring.
         All of it reaches the engine as ONE ``engine.Loss`` (``self.loss``: it keeps its tensors alive until the next step)."""
         model, cfg = self.model, self.model.cfg
         if self.freeze_cnn:
             raise RuntimeError("Trainer.step on a freeze_cnn trainer: it would train the ROI CNN (use step_embedded)")
         y_b, lam = self._check_mix(mix, X.shape[0], y) or (None, None)
+        soft = self._check_teacher(teacher_logits, X.shape[0])
         if self._ema_swapped:
             raise RuntimeError("Trainer.step inside ema_weights(): the parameters are the averaged ones there")
         if model._bucket_version != self._bucket_version:
@@ -389,7 +417,7 @@ class Trainer:
             self.scal.zero_()
             self.correct.zero_()
         cw, den = self._weight_sum(B, y, y_global)
-        self.loss = loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den, y_b, lam)
+        self.loss = loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den, y_b, lam, *soft)
         if B == 0:
             pass  # an empty shard: this rank's gradient is the zero bucket
         elif M == 1:
@@ -438,6 +466,18 @@ class Trainer:
         if y.dtype != torch.int64:
             raise ValueError("Trainer.step(mix=) needs int64 labels")
         return y_b, lam
+
+    def _check_teacher(self, teacher_logits, B):
+        """``step(teacher_logits=)``, checked -> ``(t_logits, kd_alpha, kd_tau)`` for ``engine.Loss``, or ``()`` without a teacher."""
+        if teacher_logits is None:
+            return ()
+        if self.micro_batches > 1:
+            raise ValueError("teacher_logits does not combine with micro_batches > 1")
+        t, C = teacher_logits, self.model.cfg.num_classes
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                and t.shape == (B, C)):
+            raise ValueError(f"teacher_logits must be a contiguous float32 device tensor of shape ({B}, {C})")
+        return t, self.distill_alpha, self.distill_temperature
 
     def _weight_sum(self, B, y, y_global):
         """Class weights: the step's normaliser, sum of w[label] over the global batch, by one launch -> ``(cw, den)`` or Nones."""
@@ -493,16 +533,17 @@ class Trainer:
         return float(self.lr) * float(self.lr_scale) * sched
 
     def step_embedded(self, Z: torch.Tensor, lengths: torch.Tensor, y: torch.Tensor, global_batch: Optional[int] = None,
-                      y_global: Optional[torch.Tensor] = None, mix=None):
+                      y_global: Optional[torch.Tensor] = None, mix=None, teacher_logits=None):
         """``step`` of a ``freeze_cnn`` trainer: ``Z`` (B, T, x_dim + roi_emb) f32 on the device already holds
         torch.cat((features, ROI embeddings)) (``store.batch(embedded=True)``).  Same returns, ``global_batch``, ``y_global`` and
-        empty-shard rule as ``step``; the dropout seeds are the same function of the step count, so with embeddings of the
+        empty-shard rule and ``teacher_logits`` as ``step``; the dropout seeds are the same function of the step count, so with embeddings of the
         current CNN it is the step ``step`` takes, minus everything that belongs to the CNN (class docstring)."""
         model, cfg = self.model, self.model.cfg
         if mix is not None:
             raise ValueError("Trainer.step_embedded(mix=): mixup of embedded batches is not built")
         if not self.freeze_cnn:
             raise RuntimeError("Trainer.step_embedded needs Trainer(freeze_cnn=True): this trainer updates the ROI CNN")
+        soft = self._check_teacher(teacher_logits, Z.shape[0])
         if self._ema_swapped:
             raise RuntimeError("Trainer.step_embedded inside ema_weights(): the parameters are the averaged ones there")
         if Z.dim() != 3 or Z.shape[2] != cfg.in_dim or not Z.is_cuda or Z.dtype != torch.float32:
@@ -527,7 +568,7 @@ class Trainer:
             self.scal.zero_()
             self.correct.zero_()
         cw, den = self._weight_sum(B, y, y_global)
-        self.loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den)
+        self.loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den, None, None, *soft)
         if B > 0:
             ws = model._workspace_embedded(Z, train=True)
             P = model._param_dict()
