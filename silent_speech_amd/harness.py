@@ -27,7 +27,6 @@ import copy
 import dataclasses
 import glob
 import hashlib
-import math
 import os
 import random
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
@@ -39,7 +38,8 @@ from .checkpoint import (TRAIN_STATE_FORMAT, fingerprint_difference, load_classi
                          save_train_state)
 from .device_data import MASK_FIELDS, MIXUP_FIELDS, AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier, ParamGroup
-from .train import LrSchedule, PlateauSchedule, Trainer, check_class_weights, check_distill, shard_range
+from .train import (PlateauSchedule, Trainer, check_class_weights, check_distill, check_lr_schedule, check_weight_decay,
+                    shard_range)
 
 VAL_FRAC, SEED, PATIENCE, EPOCHS, BATCH_SIZE = 0.15, 42, 12, 80, 16
 I32_MAX = 2 ** 31 - 1  # "no clip yet" in a first_seen matrix
@@ -374,6 +374,13 @@ def check_teacher(x_dim: int, use_roi: bool, num_classes: int, labels, clip_x_di
         raise ValueError(f"distill_from: the teacher's num_classes is {int(num_classes)}, the clips have {len(clip_labels)} labels")
 
 
+def _barrier(process_group) -> None:
+    if process_group is not None:
+        import torch.distributed as dist
+
+        dist.barrier(group=process_group)
+
+
 def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BATCH_SIZE, patience: int = PATIENCE,
         max_t: int = 90, lr: float = 3e-4, seed: int = SEED, use_roi_if_present: bool = True, device="cuda",
         log=print, plan: str = "host", rank: int = 0, world_size: int = 1, process_group=None,
@@ -479,12 +486,10 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
             raise ValueError("distill_from needs plan='device': the teacher's forward joins the enqueue-only epoch")
         if freeze_cnn:
             raise ValueError("distill_from does not combine with freeze_cnn: embedded batches hold no pixels for the teacher")
-    if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
-        raise TypeError("lr_schedule must be an LrSchedule")
+    check_lr_schedule(lr_schedule)
     if lr_plateau is not None and not isinstance(lr_plateau, PlateauSchedule):
         raise TypeError("lr_plateau must be a PlateauSchedule")
-    if not (math.isfinite(float(weight_decay)) and float(weight_decay) >= 0.0):
-        raise ValueError(f"weight_decay must be finite and >= 0, not {weight_decay!r}")
+    check_weight_decay(weight_decay)
     if param_groups is not None:
         param_groups = tuple(param_groups)
         if not all(isinstance(g, ParamGroup) for g in param_groups):
@@ -540,15 +545,14 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     init_ckpt = None
     if init_from is not None:  # (host code: the mismatches raise before anything is uploaded)
         init_ckpt = load_init_checkpoint(init_from, info["x_dim"], use_roi, 32, 192)
-    teacher_ckpt = None
-    if distill_from is not None:  # (host code again: the mismatches raise before anything is uploaded)
-        if isinstance(distill_from, BiGRUClassifier):
-            cfg_t = distill_from.cfg
-            check_teacher(cfg_t.x_dim, cfg_t.use_roi, cfg_t.num_classes, None, info["x_dim"], use_roi, info["uniq"])
-        else:
-            teacher_ckpt = torch.load(distill_from, map_location="cpu", weights_only=False)
-            check_teacher(teacher_ckpt["x_dim"], teacher_ckpt.get("use_roi", False), len(teacher_ckpt["labels"]),
-                          teacher_ckpt["labels"], info["x_dim"], use_roi, info["uniq"])
+    module_teacher = isinstance(distill_from, BiGRUClassifier)
+    if module_teacher:  # (host code again: the mismatches raise before anything is uploaded)
+        cfg_t = distill_from.cfg
+        check_teacher(cfg_t.x_dim, cfg_t.use_roi, cfg_t.num_classes, None, info["x_dim"], use_roi, info["uniq"])
+    elif distill_from is not None:
+        teacher_ckpt = torch.load(distill_from, map_location="cpu", weights_only=False)
+        check_teacher(teacher_ckpt["x_dim"], teacher_ckpt.get("use_roi", False), len(teacher_ckpt["labels"]),
+                      teacher_ckpt["labels"], info["x_dim"], use_roi, info["uniq"])
     saved, fingerprint = None, None
     if state_path is not None:
         fingerprint = run_fingerprint(seed, batch_size, world_size, max_t, lr, info["uniq"], info["x_dim"], use_roi,
@@ -557,7 +561,7 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                                       weight_decay=weight_decay, param_groups=param_groups, lr_schedule=lr_schedule,
                                       lr_plateau=lr_plateau,
                                       distill_from=None if distill_from is None else
-                                      ("module" if teacher_ckpt is None else file_sha256(distill_from)),
+                                      ("module" if module_teacher else file_sha256(distill_from)),
                                       distill_alpha=distill_alpha, distill_temperature=distill_temperature)
         if resume and os.path.exists(state_path):
             saved = load_train_state(state_path)
@@ -567,10 +571,7 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                                  f"this call {fingerprint.get(field)!r})")
             if saved["stopped"] or saved["epoch"] >= epochs:  # nothing left to train: no store, no model
                 log(f"Nothing to resume: {state_path} ends at epoch {saved['epoch']}. Best val acc: {saved['best']:.3f}")
-                if process_group is not None:
-                    import torch.distributed as dist
-
-                    dist.barrier(group=process_group)
+                _barrier(process_group)
                 return float(saved["best"])
     train_store = DeviceClipStore(train_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
     val_store = DeviceClipStore(val_files, info["label_to_id"], max_t=max_t, use_roi=use_roi, device=device)
@@ -601,7 +602,7 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     trainer.rank = rank
     teacher = None
     if distill_from is not None:
-        teacher = distill_from if teacher_ckpt is None else load_classifier(distill_from, device=device)[0]
+        teacher = distill_from if module_teacher else load_classifier(distill_from, device=device)[0]
         if teacher.flat_params is None or not teacher.flat_params.is_cuda:
             raise ValueError("distill_from: a module teacher must already be on the device")
         teacher.eval()
@@ -700,8 +701,5 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
         if stop:
             log(f"Early stopping. Best val acc: {best:.3f}")
             break
-    if process_group is not None:
-        import torch.distributed as dist
-
-        dist.barrier(group=process_group)
+    _barrier(process_group)
     return best

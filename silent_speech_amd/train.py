@@ -77,6 +77,18 @@ def check_distill(alpha, temperature):
     return float(alpha), float(temperature)
 
 
+def check_weight_decay(weight_decay) -> None:
+    """``ValueError`` unless ``weight_decay`` is finite and >= 0.  Host code, for ``Trainer`` and ``harness.fit`` alike."""
+    if not (math.isfinite(float(weight_decay)) and float(weight_decay) >= 0.0):
+        raise ValueError(f"weight_decay must be finite and >= 0, not {weight_decay!r}")
+
+
+def check_lr_schedule(lr_schedule) -> None:
+    """``TypeError`` unless ``lr_schedule`` is None or an ``LrSchedule``.  Host code, for ``Trainer`` and ``harness.fit`` alike."""
+    if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
+        raise TypeError("lr_schedule must be an LrSchedule")
+
+
 def ema_decay_at(decay: float, t: int, warmup: bool = True) -> float:
     """The decay of the weight average at step ``t`` (``Trainer.step_count`` of the step being taken: 1 for the first), in
     double: ``min(decay, (1 + t) / (10 + t))`` -- the early steps, whose average would otherwise be dominated by the initial
@@ -285,10 +297,8 @@ class Trainer:
                  distill_alpha: float = 0.5, distill_temperature: float = 2.0):
         self.distill_alpha, self.distill_temperature = check_distill(distill_alpha, distill_temperature)  # (host code)
         weight_decay = float(weight_decay)
-        if not (math.isfinite(weight_decay) and weight_decay >= 0.0):
-            raise ValueError(f"weight_decay must be finite and >= 0, not {weight_decay!r}")
-        if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
-            raise TypeError("lr_schedule must be an LrSchedule")
+        check_weight_decay(weight_decay)
+        check_lr_schedule(lr_schedule)
         # (host code: the ValueErrors of the groups come before anything touches a device)
         table = None
         if weight_decay != 0.0 or param_groups is not None:
@@ -385,71 +395,94 @@ class Trainer:
         ``micro_batches`` > 1 (``ValueError``).
         ``teacher_logits`` (B, C) f32 contiguous on the device: the distillation loss of the class docstring.
         All of it reaches the engine as ONE ``engine.Loss`` (``self.loss``: it keeps its tensors alive until the next step)."""
-        model, cfg = self.model, self.model.cfg
         if self.freeze_cnn:
             raise RuntimeError("Trainer.step on a freeze_cnn trainer: it would train the ROI CNN (use step_embedded)")
-        y_b, lam = self._check_mix(mix, X.shape[0], y) or (None, None)
-        soft = self._check_teacher(teacher_logits, X.shape[0])
+        B = X.shape[0]
+        y_b, lam = self._check_mix(mix, B, y) or (None, None)
+        soft = self._check_teacher(teacher_logits, B)
+        return self._step("step", B, lengths, y, global_batch, y_global, (y_b, lam, *soft), self._slices(B) == 1 and X.is_contiguous(),
+                          self._prologue_args, self._fan_out, X, R)
+
+    def _slices(self, B):
+        """The micro-batches a batch of ``B`` clips travels in: ``micro_batches`` equal slices of at least 16 clips, or 1."""
+        M = self.micro_batches
+        return M if (M > 1 and B % M == 0 and B // M >= 16) else 1
+
+    def _step(self, name, B, lengths, y, global_batch, y_global, labels_soft, may_fuse, prologue_args, fwd_bwd, *batch, prepare=None):
+        """What ``step`` and ``step_embedded`` (``name``) share, behind their own refusals; nothing has been launched yet.
+        ``labels_soft``: ``(y_b, lam)`` + ``_check_teacher``'s tuple, the tail of ``engine.Loss``.  ``batch``: the caller's input
+        tensors; ``prepare(*batch)`` -> ``batch``, if given, is the caller's last refusal, which belongs behind the one of
+        ``ema_weights()``.  The fused prologue (zero_grad, the scalars, the int32 lengths and, in ``step``, the landmark half of the
+        GRU input: one launch instead of six) runs when the caller allows it (``may_fuse``) and the lengths are what it reads;
+        ``prologue_args(*batch)`` are its arguments behind the lengths.  ``fwd_bwd(loss, train, seed, fused, lengths, *batch)`` is
+        the caller's forward and backward."""
+        model = self.model
         if self._ema_swapped:
-            raise RuntimeError("Trainer.step inside ema_weights(): the parameters are the averaged ones there")
+            raise RuntimeError(f"Trainer.{name} inside ema_weights(): the parameters are the averaged ones there")
+        if prepare is not None:
+            batch = prepare(*batch)
         if model._bucket_version != self._bucket_version:
             self._bind_bucket()
-        B = X.shape[0]
         self.step_count += 1
         train = self.dropout and model.training
         # CE is divided by the GLOBAL clip count, so the summed bucket is the global-mean gradient
         denom = float(global_batch if global_batch is not None else B * self.world)
         # dropout streams must differ between ranks (clip b of every rank would otherwise draw the same Philox masks)
-        base_seed = self.step_count * self.world + self.rank
-        M = self.micro_batches if (self.micro_batches > 1 and B % self.micro_batches == 0 and B // self.micro_batches >= 16) else 1
-        fused_prologue = (B > 0 and M == 1 and lengths.dtype == torch.int64 and lengths.is_cuda and lengths.is_contiguous()
-                          and X.is_contiguous())
-        if fused_prologue:
-            # zero_grad, the scalars, the int32 lengths and the landmark half of the GRU input: one launch instead of six
-            ws = model._workspace(X, R, train=True, slot=0)
-            T = X.shape[1]
-            L.call("ss_train_prologue", model.flat_grads.data_ptr(), model.flat_grads.numel(), self.scal.data_ptr(), 2,
-                   self.correct.data_ptr(), lengths.data_ptr(), ws.lengths.data_ptr(), B,
-                   X.data_ptr() if cfg.use_roi else None, cfg.x_dim, L.ptr(ws.Z), cfg.in_dim, B * T, cfg.x_dim,
-                   L.ptr(ws.frames), cfg.roi_emb if cfg.use_roi else 0, L.stream())
+        seed = self.step_count * self.world + self.rank
+        lo, grads = self.n_frozen, model.flat_grads  # (the trainable range [n_frozen, n): all of the bucket unless the CNN is frozen)
+        fused = may_fuse and B > 0 and lengths.dtype == torch.int64 and lengths.is_cuda and lengths.is_contiguous()
+        if fused:
+            L.call("ss_train_prologue", grads.data_ptr() + 4 * lo, grads.numel() - lo, self.scal.data_ptr(), 2,
+                   self.correct.data_ptr(), lengths.data_ptr(), *prologue_args(*batch), L.stream())
         else:
-            model.flat_grads.zero_()
+            (grads[lo:] if lo else grads).zero_()
             self.scal.zero_()
             self.correct.zero_()
         cw, den = self._weight_sum(B, y, y_global)
-        self.loss = loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den, y_b, lam, *soft)
-        if B == 0:
-            pass  # an empty shard: this rank's gradient is the zero bucket
-        elif M == 1:
-            self._fwd_bwd(X, lengths, R, loss, train, seed=base_seed, slot=0, phase="both", prologue_done=fused_prologue)
-        else:
-            n = B // M
-            cur = torch.cuda.current_stream()
-            self.ev_start.record(cur)
-            L.call("ss_roi_cnn_set_max_workgroups", torch.cuda.get_device_properties(X.device).multi_processor_count - self.CNN_RESERVED_CUS)
-            parts = [(X[m * n:(m + 1) * n], lengths[m * n:(m + 1) * n], None if R is None else R[m * n:(m + 1) * n],
-                      y[m * n:(m + 1) * n]) for m in range(M)]
-            # issue order fwd(0), fwd(1), ..., bwd(0), bwd(1), ...: the host never runs far ahead on one stream
-            for phase in ("fwd", "bwd"):
-                for m, (Xm, Lm, Rm, ym) in enumerate(parts):
-                    with torch.cuda.stream(self.streams[m]):
-                        if phase == "fwd":
-                            self.streams[m].wait_event(self.ev_start)
-                            model._workspace(Xm, Rm, train=True, slot=m + 1).stagger = True  # the next slice waits for its CNN
-                            if m > 0 and cfg.use_roi:
-                                # stagger: slice m starts its ROI-CNN when slice m-1 has left it for the recurrence, so the
-                                # chip-filling kernels of one slice run beside the 16-CU recurrence of the other
-                                prev = model._workspace(parts[m - 1][0], parts[m - 1][2], train=True, slot=m)
-                                self.streams[m].wait_event(prev.ev_cnn_fwd)
-                        self._fwd_bwd(Xm, Lm, Rm, dataclasses.replace(loss, y=ym), train, seed=base_seed * M + m, slot=m + 1,
-                                      phase=phase)
-                        if phase == "bwd":
-                            self.ev_done[m].record(self.streams[m])
-            for ev in self.ev_done:
-                cur.wait_event(ev)
-            L.call("ss_roi_cnn_set_max_workgroups", 0)
+        self.loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den, *labels_soft)
+        if B > 0:  # (an empty shard: this rank's gradient is the zero bucket)
+            fwd_bwd(self.loss, train, seed, fused, lengths, *batch)
         self._reduce_clip_adam()
         return self.scal[0], self.correct[0]
+
+    def _prologue_args(self, X, R):
+        """``ss_train_prologue``'s arguments behind the lengths, for ``step``: the workspace's lengths, and the rows to place."""
+        cfg, (B, T) = self.model.cfg, X.shape[:2]
+        ws = self.model._workspace(X, R, train=True, slot=0)
+        return (ws.lengths.data_ptr(), B, X.data_ptr() if cfg.use_roi else None, cfg.x_dim, L.ptr(ws.Z), cfg.in_dim, B * T, cfg.x_dim,
+                L.ptr(ws.frames), cfg.roi_emb if cfg.use_roi else 0)
+
+    def _fan_out(self, loss, train, base_seed, fused, lengths, X, R):
+        """Forward and backward of ``step``: in one piece, or as ``_slices`` micro-batches on their own streams."""
+        M = self._slices(X.shape[0])
+        if M == 1:
+            return self._fwd_bwd(X, lengths, R, loss, train, seed=base_seed, slot=0, phase="both", prologue_done=fused)
+        model, cfg, y = self.model, self.model.cfg, loss.y
+        n = X.shape[0] // M
+        cur = torch.cuda.current_stream()
+        self.ev_start.record(cur)
+        L.call("ss_roi_cnn_set_max_workgroups", torch.cuda.get_device_properties(X.device).multi_processor_count - self.CNN_RESERVED_CUS)
+        parts = [(X[m * n:(m + 1) * n], lengths[m * n:(m + 1) * n], None if R is None else R[m * n:(m + 1) * n],
+                  y[m * n:(m + 1) * n]) for m in range(M)]
+        # issue order fwd(0), fwd(1), ..., bwd(0), bwd(1), ...: the host never runs far ahead on one stream
+        for phase in ("fwd", "bwd"):
+            for m, (Xm, Lm, Rm, ym) in enumerate(parts):
+                with torch.cuda.stream(self.streams[m]):
+                    if phase == "fwd":
+                        self.streams[m].wait_event(self.ev_start)
+                        model._workspace(Xm, Rm, train=True, slot=m + 1).stagger = True  # the next slice waits for its CNN
+                        if m > 0 and cfg.use_roi:
+                            # stagger: slice m starts its ROI-CNN when slice m-1 has left it for the recurrence, so the
+                            # chip-filling kernels of one slice run beside the 16-CU recurrence of the other
+                            prev = model._workspace(parts[m - 1][0], parts[m - 1][2], train=True, slot=m)
+                            self.streams[m].wait_event(prev.ev_cnn_fwd)
+                    self._fwd_bwd(Xm, Lm, Rm, dataclasses.replace(loss, y=ym), train, seed=base_seed * M + m, slot=m + 1,
+                                  phase=phase)
+                    if phase == "bwd":
+                        self.ev_done[m].record(self.streams[m])
+        for ev in self.ev_done:
+            cur.wait_event(ev)
+        L.call("ss_roi_cnn_set_max_workgroups", 0)
 
     def _check_mix(self, mix, B, y):
         """``step(mix=)``, checked -> ``(y_b, lam)``, or None without mixup."""
@@ -507,24 +540,20 @@ class Trainer:
                 e1.record()
                 self.allreduce_events.append((e0, e1))
         n_el, at = model.flat_grads.numel() - lo, 4 * lo
-        L.call("ss_sumsq_f32", model.flat_grads.data_ptr() + at, n_el, self.scal.data_ptr() + 4, s)
+        sumsq = self.scal.data_ptr() + 4
+        L.call("ss_sumsq_f32", model.flat_grads.data_ptr() + at, n_el, sumsq, s)
         # d_logits already carries 1/(B*world), so the summed bucket IS the global-mean gradient
         lr = self.lr if self.lr_schedule is None and self.lr_scale == 1.0 else self.current_lr()
-        if self.table is not None:  # AdamW with parameter groups: the same pass, one launch in place of either one below
-            assert self.table.n == n_el
-            L.call("ss_adamw_clip_groups", model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at,
-                   self.m.data_ptr() + at, self.v.data_ptr() + at, None if self.ema is None else self.ema.data_ptr() + at, n_el,
-                   self.scal.data_ptr() + 4, 1.0, self.max_norm, lr, self.betas[0], self.betas[1], self.eps, self.step_count,
-                   0.0 if self.ema is None else ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup), *self.table.args, s)
-        elif self.ema is None:
-            L.call("ss_adam_clip", model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at, self.m.data_ptr() + at,
-                   self.v.data_ptr() + at, n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, lr, self.betas[0],
-                   self.betas[1], self.eps, self.step_count, s)
-        else:  # the same update of p, m, v, and the weight average in the same pass over the bucket
-            L.call("ss_adam_clip_ema", model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at, self.m.data_ptr() + at,
-                   self.v.data_ptr() + at, self.ema.data_ptr() + at, n_el, self.scal.data_ptr() + 4, 1.0, self.max_norm, lr,
-                   self.betas[0], self.betas[1], self.eps, self.step_count,
-                   ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup), s)
+        grouped, averaged = self.table is not None, self.ema is not None
+        assert not grouped or self.table.n == n_el
+        # one pass over the range: Adam; Adam and the weight average; or AdamW with parameter groups, average or not
+        entry = "ss_adamw_clip_groups" if grouped else "ss_adam_clip_ema" if averaged else "ss_adam_clip"
+        ranges = [t.data_ptr() + at for t in (model.flat_params, model.flat_grads, self.m, self.v)]
+        scalars = (n_el, sumsq, 1.0, self.max_norm, lr, self.betas[0], self.betas[1], self.eps, self.step_count)
+        if grouped or averaged:  # these two take the average's range and the step's decay as well: NULL and 0 without an average
+            ranges.append(self.ema.data_ptr() + at if averaged else None)
+            scalars += (ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup) if averaged else 0.0,)
+        L.call(entry, *ranges, *scalars, *(self.table.args if grouped else ()), s)
 
     def current_lr(self, step: Optional[int] = None) -> float:
         """The learning rate of step ``step`` (default: the last one taken, ``step_count``): ``lr * lr_scale *
@@ -538,46 +567,36 @@ class Trainer:
         torch.cat((features, ROI embeddings)) (``store.batch(embedded=True)``).  Same returns, ``global_batch``, ``y_global`` and
         empty-shard rule and ``teacher_logits`` as ``step``; the dropout seeds are the same function of the step count, so with embeddings of the
         current CNN it is the step ``step`` takes, minus everything that belongs to the CNN (class docstring)."""
-        model, cfg = self.model, self.model.cfg
         if mix is not None:
             raise ValueError("Trainer.step_embedded(mix=): mixup of embedded batches is not built")
         if not self.freeze_cnn:
             raise RuntimeError("Trainer.step_embedded needs Trainer(freeze_cnn=True): this trainer updates the ROI CNN")
         soft = self._check_teacher(teacher_logits, Z.shape[0])
-        if self._ema_swapped:
-            raise RuntimeError("Trainer.step_embedded inside ema_weights(): the parameters are the averaged ones there")
+        return self._step("step_embedded", Z.shape[0], lengths, y, global_batch, y_global, (None, None, *soft), True,
+                          self._prologue_args_embedded, self._fwd_bwd_embedded, Z, prepare=self._checked_Z)
+
+    def _checked_Z(self, Z):
+        """``step_embedded``'s ``Z``, tested and contiguous, as the batch of ``_step``."""
+        cfg = self.model.cfg
         if Z.dim() != 3 or Z.shape[2] != cfg.in_dim or not Z.is_cuda or Z.dtype != torch.float32:
             raise RuntimeError(f"Z must be f32 (B,T,{cfg.in_dim}) on the HIP device")
-        if model._bucket_version != self._bucket_version:
-            self._bind_bucket()
-        Z = Z.contiguous()
-        B, T = Z.shape[:2]
-        self.step_count += 1
-        train = self.dropout and model.training
-        denom = float(global_batch if global_batch is not None else B * self.world)
-        seed = self.step_count * self.world + self.rank
-        lo, n = self.n_frozen, model.flat_grads.numel()
-        fused_prologue = B > 0 and lengths.dtype == torch.int64 and lengths.is_cuda and lengths.is_contiguous()
-        if fused_prologue:  # the prologue of a landmark-only step: nothing to place, no frame list -- on the trainable range
-            ws = model._workspace_embedded(Z, train=True)
-            L.call("ss_train_prologue", model.flat_grads.data_ptr() + 4 * lo, n - lo, self.scal.data_ptr(), 2,
-                   self.correct.data_ptr(), lengths.data_ptr(), ws.lengths.data_ptr(), B, None, cfg.x_dim, None, cfg.in_dim,
-                   B * T, cfg.x_dim, None, 0, L.stream())
-        else:
-            model.flat_grads[lo:].zero_()
-            self.scal.zero_()
-            self.correct.zero_()
-        cw, den = self._weight_sum(B, y, y_global)
-        self.loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den, None, None, *soft)
-        if B > 0:
-            ws = model._workspace_embedded(Z, train=True)
-            P = model._param_dict()
-            if not fused_prologue:
-                ws.lengths.copy_(lengths.to(torch.int32), non_blocking=True)
-            E.forward(P, cfg, ws, Z, None, train=train, stash=True, seed=seed, z_ready=True, ce=self.loss)
-            E.backward(P, self.G, cfg, ws, Z, None, ws.d_logits, train=train, seed=seed, frozen_cnn=True)
-        self._reduce_clip_adam()
-        return self.scal[0], self.correct[0]
+        return (Z.contiguous(),)
+
+    def _prologue_args_embedded(self, Z):
+        """``ss_train_prologue``'s arguments behind the lengths for a landmark-only step: nothing to place, no frame list."""
+        cfg, (B, T) = self.model.cfg, Z.shape[:2]
+        return (self.model._workspace_embedded(Z, train=True).lengths.data_ptr(), B, None, cfg.x_dim, None, cfg.in_dim, B * T, cfg.x_dim,
+                None, 0)
+
+    def _fwd_bwd_embedded(self, loss, train, seed, fused, lengths, Z):
+        """Forward and backward of ``step_embedded``: the ``z_ready`` forward and a backward that stops at the GRU input."""
+        model, cfg = self.model, self.model.cfg
+        ws = model._workspace_embedded(Z, train=True)
+        P = model._param_dict()
+        if not fused:
+            ws.lengths.copy_(lengths.to(torch.int32), non_blocking=True)
+        E.forward(P, cfg, ws, Z, None, train=train, stash=True, seed=seed, z_ready=True, ce=loss)
+        E.backward(P, self.G, cfg, ws, Z, None, ws.d_logits, train=train, seed=seed, frozen_cnn=True)
 
     def _swap_ema(self):
         if self.model._bucket_version != self._bucket_version:
