@@ -19,8 +19,9 @@ import flat_ref as FR
 import launch_trace as LT
 import optim_ref as OR
 import weights as W
+from gpu_support import L, WORDS, ss, write_clips  # noqa: F401
 from oracle import model_ref as MR
-from test_gpu_ema_resume import ADAM, B_, FIT, LOSS_BOUND, ROI, T_, bits, write_clips
+from test_gpu_ema_resume import ADAM, B_, FIT, LOSS_BOUND, ROI, T_, bits
 
 pytestmark = pytest.mark.gpu
 
@@ -28,23 +29,6 @@ GUARD = 8  # words of NaN patterns in front of and behind every buffer (32 bytes
 LR = ADAM[2]
 SWEEP = 2048 * 256 * 4  # elements one sweep of the capped grid covers
 NS = [1, 3, 4, 5, 1027, SWEEP - 1, SWEEP, SWEEP + 7]
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
-
-
-@pytest.fixture(scope="module")
-def L(ss):
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernel
@@ -447,7 +431,7 @@ def test_fit_lr_follows_the_schedules_and_a_resumed_run_reproduces_it(ss, tmp_pa
     from silent_speech_amd import harness as Hn
 
     d = tmp_path
-    clips = write_clips(str(d / "clips_npz"))
+    clips = write_clips(str(d / "clips_npz"), WORDS)
     quiet = lambda *a, **k: None  # noqa: E731
     kw = dict(FIT, epochs=4, patience=9, weight_decay=WD, param_groups=[ss.no_decay()], log=quiet)
     total = ss.LrSchedule(warmup_steps=4, decay="cosine", final_frac=0.1, total_steps=12)

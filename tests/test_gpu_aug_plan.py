@@ -10,6 +10,7 @@ import torch
 
 import aug_plan_ref as A
 import batch_plan_ref as P
+from gpu_support import L, bits, sync  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -27,26 +28,8 @@ POLICIES = {
 }
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
-
-
-def sync():
-    torch.cuda.synchronize()
-
-
 def i32(v):
     return torch.tensor(np.asarray(v), dtype=torch.int32, device="cuda")
-
-
-def bits(a):
-    return np.asarray(a, np.float32).view(np.uint32)
 
 
 class Clips:

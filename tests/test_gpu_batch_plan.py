@@ -11,25 +11,12 @@ import pytest
 import torch
 
 import batch_plan_ref as P
+from gpu_support import L, sync  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SEED = 0x1234567890ABCDEF
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
-
-
-def sync():
-    torch.cuda.synchronize()
 
 
 def i32(v):

@@ -9,18 +9,9 @@ import torch
 
 import gru_ref
 from cnn_bf16_ref import normalise_like_kernel  # (moved there unchanged: the float64 reference shares it)
+from gpu_support import L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 def bf(x):

@@ -13,38 +13,11 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import weights as W  # noqa: E402
+from gpu_support import L, WORDS, cuda, make_weights, ss, tail_call, write_clips  # noqa: E402, F401
 
 U = 2.0 ** -24
 I32_MAX = 2 ** 31 - 1
 LOSS_BOUND = 10 * 9.781275e-08  # the run-to-run atomic noise tests/test_gpu_data_parallel.py allows on a loss
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
-
-
-def cuda(t):
-    return t.contiguous().cuda()
-
-
-def make_weights(g, C):
-    w = torch.rand(C, generator=g) * 2.8 + 0.2
-    return (w / w.mean()).float()
 
 
 def make_rows(g, B, C):
@@ -168,21 +141,6 @@ def test_unit_weights_give_the_bits_of_the_unweighted_kernel(L, B, C, eps):
         assert loss_w.cpu().numpy().tobytes() == loss_u.cpu().numpy().tobytes(), (float(loss_w), float(loss_u))
     else:
         assert abs(float(loss_w) - float(loss_u)) <= (B - 1) * U * abs(float(loss_u))
-
-
-def tail_call(L, name, P, h_d, len_d, y_d, dims, eps, norm):
-    B, T, D, MID, C = dims
-    f = lambda *s: torch.empty(*s, device="cuda")  # noqa: E731
-    out = dict(attn=f(B, T), xhat=f(B, D), rstd=f(B), ln=f(B, D), mid=f(B, MID), mid_d=f(B, MID), logits=f(B, C),
-               d_logits=torch.full((B, C), 3.0, device="cuda"), loss=torch.zeros(1, device="cuda"),
-               correct=torch.zeros(1, device="cuda", dtype=torch.int32))
-    L.call(name, h_d.data_ptr(), len_d.data_ptr(), P["pool.score.weight"].data_ptr(), P["pool.score.bias"].data_ptr(),
-           P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(), P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(),
-           P["head.4.weight"].data_ptr(), P["head.4.bias"].data_ptr(), y_d.data_ptr(), B, T, D, MID, C, 1e-5, 0.0, 0, 0, eps, *norm,
-           *(out[k].data_ptr() for k in ("attn", "xhat", "rstd", "ln", "mid", "mid_d", "logits", "d_logits", "loss", "correct")),
-           L.stream())
-    torch.cuda.synchronize()
-    return out
 
 
 def tail_inputs(B, T, C, Hd, lengths):
@@ -451,7 +409,6 @@ def test_shards_add_up(ss, one_process):
 
 
 # --------------------------------------------------------------------------------------------- 7. / 8. evaluation and fit
-WORDS = ["aura", "no", "yes"]
 COUNTS = (8, 5, 2)
 EVAL_W = (0.5, 1.0, 1.9)
 
@@ -459,20 +416,7 @@ EVAL_W = (0.5, 1.0, 1.9)
 @pytest.fixture(scope="module")
 def clip_dir(tmp_path_factory):
     """3 words x (8, 5, 2) clips, built the way test_harness_fit_evaluate_checkpoint builds its directory."""
-    from silent_speech_amd import data as Dm
-
-    rng = np.random.default_rng(0)
-    d = tmp_path_factory.mktemp("cw") / "clips_npz"
-    d.mkdir()
-    labels = sum(([c] * n for c, n in enumerate(COUNTS)), [])
-    rng.shuffle(labels)
-    for k, c in enumerate(labels):
-        T = int(rng.integers(14, 22))
-        X = (0.05 * rng.normal(size=(T, 20))).astype(np.float32)
-        X[:, c * 4:c * 4 + 4] += 0.5
-        roi = rng.integers(0, 256, (T, 32, 32), dtype=np.uint8)
-        Dm.save_clip(str(d / f"{k:03d}.npz"), X, np.arange(T), WORDS[c], "me", np.arange(4), roi)
-    return str(d)
+    return write_clips(str(tmp_path_factory.mktemp("cw") / "clips_npz"), WORDS, counts=COUNTS)
 
 
 def test_evaluate_under_class_weights(ss, clip_dir):

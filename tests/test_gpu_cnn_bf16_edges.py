@@ -27,6 +27,7 @@ import pytest
 import torch
 
 import cnn_bf16_ref as CR
+from gpu_support import L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -38,16 +39,6 @@ X_OFF, LD_Z = 84, 152            # the embedding columns inside a wider row
 FRONT, BACK = 64, 1024           # sentinel elements in front of / behind every output buffer
 SENT = {torch.float32: 12345.0, torch.int16: 0x7fc0, torch.uint8: 0xA5}
 SS_ERR_ARG, SS_ERR_UNSUPPORTED = -1, -3
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 @pytest.fixture(params=GRIDS, ids=GRID_IDS)

@@ -10,10 +10,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import WORDS, ss, write_clips  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORDS = ["aura", "no", "yes"]
 FIT = dict(epochs=3, batch_size=16, patience=3, max_t=24, lr=3e-3, plan="device")
 # Bound on the per-epoch losses of the one-rank RCCL run against the single-process run: measured, not chosen.  Two
 # single-process ``fit(plan="device")`` runs of this configuration (fresh processes, MI355X, the commit before this feature)
@@ -24,33 +25,8 @@ LOSS_BOUND = 10 * SPREAD
 
 
 @pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
-
-
-def write_clips(clip_dir, n=45, D=20, roi=(32, 32)):
-    """The synthetic directory of test_harness_fit_evaluate_checkpoint: three separable 'words' (a constant offset per class in a
-    few features), ragged lengths."""
-    from silent_speech_amd import data as Dm
-
-    rng = np.random.default_rng(0)
-    os.makedirs(clip_dir)
-    for k in range(n):
-        T = int(rng.integers(14, 22))
-        X = (0.05 * rng.normal(size=(T, D))).astype(np.float32)
-        X[:, (k % 3) * 4:(k % 3) * 4 + 4] += 0.5
-        r = rng.integers(0, 256, (T,) + roi, dtype=np.uint8) if roi else None
-        Dm.save_clip(os.path.join(clip_dir, f"{k:03d}.npz"), X, np.arange(T), WORDS[k % 3], "me", np.arange(4), r)
-    return clip_dir
-
-
-@pytest.fixture(scope="module")
 def clip_dir(tmp_path_factory):
-    return write_clips(str(tmp_path_factory.mktemp("dp") / "clips_npz"))
+    return write_clips(str(tmp_path_factory.mktemp("dp") / "clips_npz"), WORDS)
 
 
 @pytest.fixture(scope="module")
@@ -125,7 +101,7 @@ def test_rank_shards_rebuild_the_single_process_batch(ss, whole_store, tmp_path,
     if shape == "roi_d20":
         _, store = whole_store
     else:
-        info = Hn.scan_clips(write_clips(str(tmp_path / "plain"), D=5, roi=None))
+        info = Hn.scan_clips(write_clips(str(tmp_path / "plain"), WORDS, D=5, roi=None))
         store = ss.DeviceClipStore(info["files"], info["label_to_id"], max_t=7)
     seed, base, batch = 5, 45, 16  # (the second epoch of a run: draws 45 ...)
     order = store.sample_epoch(seed=seed, first=base)

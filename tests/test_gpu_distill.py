@@ -3,7 +3,6 @@ tests/distill_ref.py within its derived float32 bound, its bit-exact identities 
 that agrees adds nothing), the refusals, ``Trainer.step(teacher_logits=)`` against the CPU oracle under autograd, the launch list of
 such a step, and ``fit(distill_from=)`` with a resumed run.  Figures are printed before they are compared."""
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -15,6 +14,7 @@ pytestmark = pytest.mark.gpu
 import distill_ref as D  # noqa: E402
 import launch_trace as LT  # noqa: E402
 import weights as W  # noqa: E402
+from gpu_support import L, STASH, WORDS, cuda, make_weights, ss, tail_call, write_clips  # noqa: E402, F401
 from oracle import model_ref as MR  # noqa: E402
 from oracle import model_ref_bf16 as MB  # noqa: E402
 
@@ -22,34 +22,6 @@ U = 2.0 ** -24
 SS_ERR_ARG = -1
 EPS = float(np.float32(0.05))  # the smoothing as the kernels see it
 LOSS_BOUND = 10 * 9.781275e-08  # tests/test_gpu_ema_resume.py: a resumed epoch against the uninterrupted one
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
-
-
-def cuda(t):
-    return t.contiguous().cuda()
-
-
-def make_weights(g, C):
-    w = torch.rand(C, generator=g) * 2.8 + 0.2
-    return (w / w.mean()).float()
 
 
 # ------------------------------------------------------------------------------------------------ 1. the row kernel
@@ -196,26 +168,6 @@ def test_kd_row_identities(L, B, C):
 
 
 # ------------------------------------------------------------------------------------------------ 3. the fused tail
-STASH = ("attn", "xhat", "rstd", "ln", "mid", "mid_d")
-
-
-def tail_call(L, name, P, h_d, len_d, y_d, dims, eps, norm, mix=(), soft=(), status=False, fill=3.0):
-    B, T, Dm, MID, C = dims
-    f = lambda *s: torch.full(s, fill, device="cuda")  # noqa: E731
-    out = dict(attn=f(B, T), xhat=f(B, Dm), rstd=f(B), ln=f(B, Dm), mid=f(B, MID), mid_d=f(B, MID), logits=f(B, C),
-               d_logits=f(B, C), loss=torch.zeros(1, device="cuda"), correct=torch.zeros(1, device="cuda", dtype=torch.int32))
-    args = (h_d.data_ptr(), len_d.data_ptr(), P["pool.score.weight"].data_ptr(), P["pool.score.bias"].data_ptr(),
-            P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(), P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(),
-            P["head.4.weight"].data_ptr(), P["head.4.bias"].data_ptr(), y_d.data_ptr(), *mix, B, T, Dm, MID, C, 1e-5, 0.0, 0, 0, eps,
-            *norm, *(out[k].data_ptr() for k in STASH + ("logits", "d_logits", "loss", "correct")), *soft, L.stream())
-    if status:
-        out["status"] = getattr(L.load(), name)(*args)
-    else:
-        L.call(name, *args)
-    torch.cuda.synchronize()
-    return out
-
-
 @pytest.mark.parametrize("C", [2, 10, 64, 65, 100, 129])
 def test_kd_tail(L, C):
     """ss_tail_fwd_kd at the shape of test_mix_tail: logits and stashes are ss_tail_fwd's bits; d_logits and loss against
@@ -453,23 +405,7 @@ def test_a_step_with_a_teacher_replaces_one_launch(ss, monkeypatch, name):
 
 
 # ------------------------------------------------------------------------------------------------ 7. fit
-WORDS = ["aura", "no", "yes"]
 FIT = dict(batch_size=16, patience=5, max_t=24, lr=3e-3, plan="device", log=lambda *a: None)
-
-
-def write_clips(clip_dir, words, n=45, Dx=20, roi=(32, 32)):
-    """The synthetic directory of tests/test_gpu_ema_resume.py, by the same recipe."""
-    from silent_speech_amd import data as Dm
-
-    rng = np.random.default_rng(0)
-    os.makedirs(clip_dir)
-    for k in range(n):
-        T = int(rng.integers(14, 22))
-        X = (0.05 * rng.normal(size=(T, Dx))).astype(np.float32)
-        X[:, (k % 3) * 4:(k % 3) * 4 + 4] += 0.5
-        Dm.save_clip(os.path.join(clip_dir, f"{k:03d}.npz"), X, np.arange(T), words[k % 3], "me", np.arange(4),
-                     rng.integers(0, 256, (T,) + roi, dtype=np.uint8))
-    return clip_dir
 
 
 @pytest.fixture(scope="module")

@@ -15,6 +15,7 @@ import torch
 import flat_ref as FR
 import optim_ref as OR
 import weights as W
+from gpu_support import L, WORDS, ss, write_clips  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -27,25 +28,7 @@ NS_LARGE = [2097151, 2097152, 2097157, 4194311]
 NS_FLOAT64 = (2097157, 4194311)
 DECAYS = [0.0, 0.1, 0.999]
 ADAM = (1.0, 1.0, 3e-4, 0.9, 0.999, 1e-8)  # grad_scale, max_norm, lr, beta1, beta2, eps
-WORDS = ["aura", "no", "yes"]
 FIT = dict(epochs=3, batch_size=16, patience=3, max_t=24, lr=3e-3, plan="device")
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
-
-
-@pytest.fixture(scope="module")
-def L(ss):
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 def bits(t):
@@ -348,25 +331,9 @@ def test_trainer_state_round_trip(ss):
 
 
 # -------------------------------------------------------------------------------------------------------------------- fit
-def write_clips(clip_dir, n=45, D=20, roi=(32, 32)):
-    """The synthetic directory of tests/test_gpu_data_parallel.py, by the same recipe: three separable 'words' (a constant offset
-    per class in a few features), ragged lengths."""
-    from silent_speech_amd import data as Dm
-
-    rng = np.random.default_rng(0)
-    os.makedirs(clip_dir)
-    for k in range(n):
-        T = int(rng.integers(14, 22))
-        X = (0.05 * rng.normal(size=(T, D))).astype(np.float32)
-        X[:, (k % 3) * 4:(k % 3) * 4 + 4] += 0.5
-        r = rng.integers(0, 256, (T,) + roi, dtype=np.uint8) if roi else None
-        Dm.save_clip(os.path.join(clip_dir, f"{k:03d}.npz"), X, np.arange(T), WORDS[k % 3], "me", np.arange(4), r)
-    return clip_dir
-
-
 @pytest.fixture(scope="module")
 def clip_dir(tmp_path_factory):
-    return write_clips(str(tmp_path_factory.mktemp("resume") / "clips_npz"))
+    return write_clips(str(tmp_path_factory.mktemp("resume") / "clips_npz"), WORDS)
 
 
 @pytest.fixture(scope="module")

@@ -7,19 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import L  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 I32_MAX = 2 ** 31 - 1
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 def make_rows(rng, B, C):

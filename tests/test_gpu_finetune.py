@@ -10,14 +10,13 @@ uninterrupted runs).
 
 Run on the MI355X box with ``python -m pytest tests -m gpu``.
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import launch_trace as LT
 import weights as W
+from gpu_support import L, ss, write_clips  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,23 +27,6 @@ LOSS_BOUND = 10 * 9.781275e-08  # tests/test_gpu_ema_resume.py
 # one frame; the rest ordinary
 CLIPS = [(20, 20), (13, 13), (14, 14), (10, 7), (9, None), (5, None), (1, 1), (16, 16), (8, 8), (11, 11)]
 SENTINEL = -12345.0
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
-
-
-@pytest.fixture(scope="module")
-def L(ss):
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 def write_store_clips(tmp):
@@ -346,17 +328,8 @@ def test_stale_embeddings_are_reported(ss, files):
 
 # ---------------------------------------------------------------------------------------------------------------- fit
 def write_words(clip_dir, words, n, D=XD, seed=0):
-    from silent_speech_amd import data as Dm
-
-    rng = np.random.default_rng(seed)
-    os.makedirs(clip_dir)
-    for k in range(n):
-        T = int(rng.integers(9, 15))
-        X = (0.05 * rng.normal(size=(T, D))).astype(np.float32)
-        X[:, (k % len(words)) * 4:(k % len(words)) * 4 + 4] += 0.5
-        r = rng.integers(0, 256, (T,) + HW, dtype=np.uint8)
-        Dm.save_clip(os.path.join(clip_dir, f"{k:03d}.npz"), X, np.arange(T), words[k % len(words)], "me", np.arange(4), r)
-    return clip_dir
+    """The shared recipe at 9 to 14 frames a clip."""
+    return write_clips(clip_dir, words, n, D=D, roi=HW, frames=(9, 15), seed=seed)
 
 
 FIT = dict(batch_size=16, patience=5, max_t=MAX_T, lr=3e-3, plan="device", log=lambda *a, **k: None)

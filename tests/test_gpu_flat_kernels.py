@@ -14,26 +14,10 @@ import torch
 
 import flat_ref as FR
 import optim_ref as OR
+from gpu_support import L  # noqa: F401
 from test_gpu_ema_resume import ADAM, GUARD, NS, bits, guarded, optimiser_inputs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
-
-
-@pytest.fixture(scope="module")
-def L(ss):
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 def guard_fill(values, seed, dtype=torch.float32):

@@ -28,6 +28,7 @@ import gemm_bf16_ref as BR
 import gemm_ref as GR
 from gemm_bf16_ref import ceil8
 from gemm_ref import IDENT, INT_MAX, Call, ceil_div
+from gpu_support import L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -36,16 +37,6 @@ SENT = -77.0
 NAN = float("nan")
 LAYOUTS = [(1, 1), (1, 0), (0, 1), (0, 0)]
 SS_ERR_ARG, SS_ERR_UNSUPPORTED = -1, -3
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 @pytest.fixture(scope="module")

@@ -22,6 +22,7 @@ import torch
 
 import gemm_ref as GR
 from gemm_ref import IDENT, INT_MAX, Call, ceil_div
+from gpu_support import L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -29,16 +30,6 @@ GUARD_ROWS = 8
 SENT = -77.0
 NAN = float("nan")
 LAYOUTS = [(1, 1), (1, 0), (0, 1), (0, 0)]
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 @pytest.fixture(scope="module")

@@ -30,6 +30,7 @@ import pytest
 import torch
 
 import gru_ref as GR
+from gpu_support import L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -41,16 +42,6 @@ BAND_WS = 0x5A
 CAP_CUS = 160                     # any non-zero CU cap keeps the recurrences on six parts
 F32_TOL = dict(out=2e-5, save=2e-5, dg=(3e-5, 1e-4), gb=(2e-4, 1e-4))   # test_gru_fwd_bwd's bounds (atol, rtol)
 BF16_TOL = dict(out=2e-3, save=5e-3, dgi=2e-2, dw=3e-2)                 # test_gru_bf16_fwd_bwd's bounds
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 @pytest.fixture

@@ -12,20 +12,11 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+from gpu_support import L  # noqa: E402, F401
 from oracle import features_ref as FR  # noqa: E402
 from oracle import model_ref as MR  # noqa: E402
 
 INT_MAX = 2**31 - 1
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 _KEEP = []

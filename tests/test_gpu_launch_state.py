@@ -18,19 +18,11 @@ import sys
 import pytest
 import torch
 
+from gpu_support import L  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 def run_child(mode, tmp_path):

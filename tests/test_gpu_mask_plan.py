@@ -15,6 +15,7 @@ import torch
 import aug_plan_ref as A
 import batch_plan_ref as P
 import mask_plan_ref as M
+from gpu_support import L, bits, sync  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -40,26 +41,8 @@ def full_masks(D, hw):
     return dict(time_mask_prob=1.0, time_mask_max=100, feat_mask_prob=1.0, feat_mask_max=D + 5, cutout_prob=1.0, cutout_max=(hw[1], hw[0]))
 
 
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
-
-
-def sync():
-    torch.cuda.synchronize()
-
-
 def i32(v):
     return torch.tensor(np.asarray(v), dtype=torch.int32, device="cuda")
-
-
-def bits(a):
-    return np.asarray(a, np.float32).view(np.uint32)
 
 
 class Clips:

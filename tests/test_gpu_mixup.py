@@ -11,34 +11,12 @@ pytestmark = pytest.mark.gpu
 
 import mixup_ref as M  # noqa: E402
 import weights as W  # noqa: E402
+from gpu_support import L, WORDS, cuda, make_weights, ss, tail_call, write_clips  # noqa: E402, F401
 from oracle import model_ref as MR  # noqa: E402
 from oracle import model_ref_bf16 as MB  # noqa: E402
 
 U = 2.0 ** -24
 SS_ERR_ARG = -1
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
-
-
-def cuda(t):
-    return t.contiguous().cuda()
 
 
 @pytest.fixture(scope="module")
@@ -179,11 +157,6 @@ def test_blend_kernel_wide_rows_null_pairs_and_the_feature_grid_cap(L):
 
 
 # ------------------------------------------------------------------------------------------------ 3. the two-label loss
-def make_weights(g, C):
-    w = torch.rand(C, generator=g) * 2.8 + 0.2
-    return (w / w.mean()).float()
-
-
 def reference(lg, y, y_b, lam, w, eps):
     """float64 on the CPU: (lam CE(y) + (1 - lam) CE(y_b), its gradient), both terms over the one normaliser of y (the sum of
     w[y], or the row count)."""
@@ -275,21 +248,6 @@ def test_mix_ce_kernel(L, B, C, weighted):
         assert not bool(d[[3, 5, 7]].any())
         assert abs(float(loss) - float(ref)) < 2e-6 * max(1.0, abs(float(ref)))
         assert bool(((d.double().cpu() - x.grad).abs() <= 1e-7 + 1e-5 * x.grad.abs()).all())
-
-
-def tail_call(L, name, P, h_d, len_d, y_d, dims, eps, norm, mix=()):
-    B, T, D, MID, C = dims
-    f = lambda *s: torch.empty(*s, device="cuda")  # noqa: E731
-    out = dict(attn=f(B, T), xhat=f(B, D), rstd=f(B), ln=f(B, D), mid=f(B, MID), mid_d=f(B, MID), logits=f(B, C),
-               d_logits=torch.full((B, C), 3.0, device="cuda"), loss=torch.zeros(1, device="cuda"),
-               correct=torch.zeros(1, device="cuda", dtype=torch.int32))
-    L.call(name, h_d.data_ptr(), len_d.data_ptr(), P["pool.score.weight"].data_ptr(), P["pool.score.bias"].data_ptr(),
-           P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(), P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(),
-           P["head.4.weight"].data_ptr(), P["head.4.bias"].data_ptr(), y_d.data_ptr(), *mix, B, T, D, MID, C, 1e-5, 0.0, 0, 0, eps,
-           *norm, *(out[k].data_ptr() for k in ("attn", "xhat", "rstd", "ln", "mid", "mid_d", "logits", "d_logits", "loss", "correct")),
-           L.stream())
-    torch.cuda.synchronize()
-    return out
 
 
 @pytest.mark.parametrize("C", [2, 10, 64, 65, 100, 129])
@@ -438,27 +396,13 @@ def test_bf16_engine_step_with_mix(ss):
 
 
 # ------------------------------------------------------------------------------------------------ 5. the store and fit
-WORDS = ["aura", "no", "yes"]
 COUNTS = (8, 5, 2)
 
 
 @pytest.fixture(scope="module")
 def clip_dir(tmp_path_factory):
     """3 words x (8, 5, 2) clips, built the way the other fit tests build their directory."""
-    from silent_speech_amd import data as Dm
-
-    rng = np.random.default_rng(0)
-    d = tmp_path_factory.mktemp("mixup") / "clips_npz"
-    d.mkdir()
-    labels = sum(([c] * n for c, n in enumerate(COUNTS)), [])
-    rng.shuffle(labels)
-    for i, c in enumerate(labels):
-        T = int(rng.integers(14, 22))
-        X = (0.05 * rng.normal(size=(T, 20))).astype(np.float32)
-        X[:, c * 4:c * 4 + 4] += 0.5
-        roi = rng.integers(0, 256, (T, 32, 32), dtype=np.uint8)
-        Dm.save_clip(str(d / f"{i:03d}.npz"), X, np.arange(T), WORDS[c], "me", np.arange(4), roi)
-    return str(d)
+    return write_clips(str(tmp_path_factory.mktemp("mixup") / "clips_npz"), WORDS, counts=COUNTS)
 
 
 def test_store_batch_with_mixup(ss, L, clip_dir):

@@ -13,19 +13,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import weights as W  # noqa: E402
+from gpu_support import ss  # noqa: E402, F401
 from oracle import model_ref as MR  # noqa: E402
 
 LOGIT_TOL = 1e-3  # the contract
 TIGHT = 5e-5      # what we hold ourselves to
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
 
 
 def load_case(golden_dir, name):

@@ -10,21 +10,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import weights as W  # noqa: E402
+from gpu_support import ss  # noqa: E402, F401
 from oracle import model_ref as MR  # noqa: E402
 from oracle import model_ref_bf16 as MB  # noqa: E402
 
 C5 = dict(roi_emb=64, hidden=512, cnn_channels=(16, 32, 64, 96))
 LOGIT_TOL_BF16 = 2e-2   # vs the f32 model (tests/test_oracle_bf16.py measures 6e-3 for the bf16 arithmetic itself)
 EMU_TOL = 3e-3          # vs the bf16 restatement: summation order, v_exp / v_rcp gates, rare 1-ulp bf16 flips
-
-
-@pytest.fixture(scope="module")
-def ss():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import silent_speech_amd as ss_
-
-    return ss_
 
 
 def build(ss, sd, C=100):

@@ -19,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 import roi_cnn_ref as RR
+from gpu_support import L  # noqa: F401
 from roi_cnn_ref import CNN_KEYS
 
 pytestmark = pytest.mark.gpu
@@ -31,16 +32,6 @@ SENT = -3.0
 SLACK = 2048  # floats behind every gradient buffer that must stay zero
 GEOMS = RR.GEOMS
 ALL_E = (1, 7, 16, 17, 32, 48, 63, 64)
-
-
-@pytest.fixture(scope="module")
-def L():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from silent_speech_amd import _lib
-
-    _lib.load()
-    return _lib
 
 
 _KEEP = []

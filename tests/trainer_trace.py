@@ -17,9 +17,9 @@ import os
 import sys
 import tempfile
 
-import numpy as np
 import torch
 
+import gpu_support as GS
 import launch_trace as LT
 
 F32 = dict(x_dim=84, num_classes=5, use_roi=True)
@@ -136,7 +136,6 @@ def run_config(mp, name):
 
 
 # ------------------------------------------------------------------------------------------------ fit
-WORDS = ["aura", "no", "yes"]
 FIT = dict(epochs=1, batch_size=4, max_t=16, log=lambda *a: None)
 # name -> the fit calls of the case, in order: keywords on top of FIT.  "init": the checkpoint of a plain one-epoch run (made once,
 # untraced); "policy" / "teacher": made when the package is there
@@ -154,18 +153,9 @@ FIT_CASES = {
 
 def write_clips(work):
     """12 clips, 3 labels, 6 to 14 frames, 32 x 32 ROI frames -> the directory; and the checkpoint ``init`` of one plain epoch."""
-    from silent_speech_amd import data as Dm
     from silent_speech_amd import harness as Hn
 
-    rng = np.random.default_rng(0)
-    clip_dir = os.path.join(work, "clips_npz")
-    os.makedirs(clip_dir)
-    for k in range(12):
-        n = int(rng.integers(6, 15))
-        X = (0.05 * rng.normal(size=(n, 20))).astype(np.float32)
-        X[:, (k % 3) * 4:(k % 3) * 4 + 4] += 0.5
-        Dm.save_clip(os.path.join(clip_dir, f"{k:03d}.npz"), X, np.arange(n), WORDS[k % 3], "me", np.arange(4),
-                     rng.integers(0, 256, (n,) + ROI, dtype=np.uint8))
+    clip_dir = GS.write_clips(os.path.join(work, "clips_npz"), GS.WORDS, n=12, roi=ROI, frames=(6, 15))
     Hn.fit(clip_dir, os.path.join(work, "init.pt"), **dict(FIT, plan="device"))
     return clip_dir
 
