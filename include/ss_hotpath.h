@@ -646,7 +646,10 @@ int ss_dropout(const float* x, float* y, long n, float p, uint64_t seed, uint64_
  * CrossEntropyLoss(label_smoothing)/denom with d(loss)/d(logits) (train_model_official.py:231-248, 271-277, 405).
  * Stash outputs (attn (B,T), xhat (B,D), rstd (B), ln (B,D) = LayerNorm output, mid (B,MID) = post-ReLU,
  * mid_d (B,MID) = after dropout) may each be NULL for inference.  Dropout draws the ss_dropout stream (seed, offset)
- * at element index b*MID + o. */
+ * at element index b*MID + o.
+ * Supported: any T, D, MID, C >= 1 (tested: T 1..15 221, D 1..2 050, MID 1..1 025, C 1..1 025; 1 <= lengths[b] <= T) as long as
+ * the clip's rows fit the workgroup's 60 KiB of LDS: T + 2 D + MID + C <= 15 360 floats here, MID + D + 2 T + C <= 15 360 in
+ * ss_tail_bwd; beyond that SS_ERR_UNSUPPORTED.  h behind a clip's length is never read. */
 int ss_tail_fwd(const float* h, const int32_t* lengths, const float* w_score, const float* b_score, const float* gamma,
                 const float* beta, const float* w1, const float* b1, const float* w4, const float* b4, const int64_t* y,
                 int B, int T, int D, int MID, int C, float ln_eps, float drop_p, uint64_t seed, uint64_t offset,
@@ -702,7 +705,8 @@ int ss_tail_fwd_kd(const float* h, const int32_t* lengths, const float* w_score,
  * first Linear's weight-gradient GEMM); g_gamma, g_beta (D), g_wscore (D), g_bscore (1) are accumulated -- unless
  * col_part (B,3,D) is given: then every clip STORES its terms of g_gamma | g_beta | g_wscore there and the caller adds the
  * column sums (ss_colsum_f32, lda = 3 D) to the three gradients; 256 clips' float atomics on the same D addresses serialise.  The two
- * Linear weight/bias gradients are ss_gemm_f32 calls on (d_logits, mid_d) and (d_mid, ln). */
+ * Linear weight/bias gradients are ss_gemm_f32 calls on (d_logits, mid_d) and (d_mid, ln).  d_h behind a clip's length and
+ * d_mid where the unit is dead or dropped are +0.0.  LDS: MID + D + 2 T + C <= 15 360 floats, else SS_ERR_UNSUPPORTED. */
 int ss_tail_bwd(const float* h, const int32_t* lengths, const float* w_score, const float* gamma, const float* w1,
                 const float* w4, const float* attn, const float* xhat, const float* rstd, const float* mid,
                 const float* d_logits, int B, int T, int D, int MID, int C, float drop_p, uint64_t seed,

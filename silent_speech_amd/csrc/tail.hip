@@ -1,5 +1,5 @@
 // Fused classifier tail: AttnPool -> LayerNorm -> Linear -> ReLU -> Dropout -> Linear (-> label-smoothed CE),
-// one 256-thread workgroup per clip, and its backward down to the gradient of the GRU output.
+// one 1024-thread workgroup (16 waves) per clip, and its backward down to the gradient of the GRU output.
 //
 // Replaces /root/reference/train_model_official.py:231-248 (AttnPool), :271-277 (head) and :405 (loss) as one
 // launch each way: at B = 256 the seven separate forward ops and six backward ops are latency-bound launches
@@ -272,8 +272,9 @@ __global__ __launch_bounds__(TNT) void tail_bwd_kernel(TailBwdParams p) {
     float acc = 0.f;
 #pragma unroll 16
     for (int c = 0; c < C; ++c) acc += dl[c] * p.w4[(long)c * MID + o];
-    acc *= drop_scale((long)b * MID + o, p.drop_p, p.seed, p.offset);
-    if (p.mid[(long)b * MID + o] <= 0.f) acc = 0.f;
+    // (a dropped element is +0.0 like a dead one, as ss_dropout writes it: a negative sum times a keep-scale of 0 is -0.0)
+    const float ks = drop_scale((long)b * MID + o, p.drop_p, p.seed, p.offset);
+    acc = (ks == 0.f || p.mid[(long)b * MID + o] <= 0.f) ? 0.f : acc * ks;
     dmid[o] = acc;
     p.d_mid[(long)b * MID + o] = acc;
   }

@@ -73,17 +73,17 @@ def write_clips(clip_dir, words, n=45, D=20, roi=(32, 32), frames=(14, 22), seed
     return clip_dir
 
 
-def tail_call(L, name, P, h_d, len_d, y_d, dims, eps, norm, mix=(), soft=(), status=False, fill=3.0):
+def tail_call(L, name, P, h_d, len_d, y_d, dims, eps, norm, mix=(), soft=(), status=False, fill=3.0, drop=(0.0, 0, 0)):
     """ss_tail_fwd (``norm`` = (denom,)), ss_tail_fwd_w ((w, den)), ss_tail_fwd_mix ((denom, w, den), ``mix`` = (y_b, lam)) or
     ss_tail_fwd_kd (the same, and ``soft`` = (teacher, ld, alpha, tau)) on output buffers filled with ``fill``; loss and correct
-    start at zero.  ``status``: call without the check and return the status under "status"."""
+    start at zero.  ``status``: call without the check and return the status under "status".  ``drop``: (p, seed, offset) of the dropout."""
     B, T, Dm, MID, C = dims
     f = lambda *s: torch.full(s, fill, device="cuda")  # noqa: E731
     out = dict(attn=f(B, T), xhat=f(B, Dm), rstd=f(B), ln=f(B, Dm), mid=f(B, MID), mid_d=f(B, MID), logits=f(B, C),
                d_logits=f(B, C), loss=torch.zeros(1, device="cuda"), correct=torch.zeros(1, device="cuda", dtype=torch.int32))
     args = (h_d.data_ptr(), len_d.data_ptr(), P["pool.score.weight"].data_ptr(), P["pool.score.bias"].data_ptr(),
             P["head.0.weight"].data_ptr(), P["head.0.bias"].data_ptr(), P["head.1.weight"].data_ptr(), P["head.1.bias"].data_ptr(),
-            P["head.4.weight"].data_ptr(), P["head.4.bias"].data_ptr(), y_d.data_ptr(), *mix, B, T, Dm, MID, C, 1e-5, 0.0, 0, 0, eps,
+            P["head.4.weight"].data_ptr(), P["head.4.bias"].data_ptr(), y_d.data_ptr(), *mix, B, T, Dm, MID, C, 1e-5, *drop, eps,
             *norm, *(out[k].data_ptr() for k in STASH + ("logits", "d_logits", "loss", "correct")), *soft, L.stream())
     if status:
         out["status"] = getattr(L.load(), name)(*args)
