@@ -13,7 +13,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libss_hotpath.so")
-SOURCES = ["features.hip", "batch.hip", "stream.hip", "crop_resize.hip", "roi_cnn.hip", "roi_cnn_bwd.hip", "roi_cnn_generic.hip", "gemm.hip", "gru.hip", "pool_head.hip", "eval.hip", "tail.hip", "optim.hip", "gemm_bf16.hip", "gru_bf16.hip", "cnn_bf16.hip", "cnn_bf16_bwd.hip"]
+SOURCES = ["features.hip", "batch.hip", "stream.hip", "crop_resize.hip", "roi_cnn.hip", "roi_cnn_bwd.hip", "roi_cnn_generic.hip", "gemm.hip", "gru.hip", "pool_head.hip", "eval.hip", "tail.hip", "optim.hip", "step_helpers.hip", "abi.hip", "gemm_bf16.hip", "gru_bf16.hip", "cnn_bf16.hip", "cnn_bf16_bwd.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wall", "-Wno-unused-function"]
 
 
@@ -33,7 +33,7 @@ def _stale(target: str, deps) -> bool:
 
 # the streaming kernels of these files keep everything in registers: a by-value table indexed per lane, or a spill, would show as a
 # private segment in the code object's metadata (ss_adamw_clip_groups)
-NO_SCRATCH = ["optim.hip", "batch.hip"]
+NO_SCRATCH = ["optim.hip", "step_helpers.hip", "batch.hip"]
 
 
 def _llvm_tool(name: str):

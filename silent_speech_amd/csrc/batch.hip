@@ -687,9 +687,7 @@ int launch_gather_f32(const float* src, int D, const int32_t* frame_map, long ro
   SS_REQUIRE(src && frame_map && dst && D > 0 && rows > 0 && noise_std >= 0.f, SS_ERR_ARG);
   SS_REQUIRE((reinterpret_cast<uintptr_t>(dst) & 3) == 0, SS_ERR_ARG);
   const long chunks = (rows * D + 3) / 4;
-  long blocks = (chunks + 255) / 256;
-  blocks = blocks > 4096 ? 4096 : blocks;
-  hipLaunchKernelGGL((batch_gather_f32_kernel<HOST_NOISE, SCALE>), dim3((unsigned)blocks), dim3(256), 0,
+  hipLaunchKernelGGL((batch_gather_f32_kernel<HOST_NOISE, SCALE>), dim3(ss_flat_grid(chunks, 4096)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), src, D, frame_map, rows, noise, noise_map, noise_std, seed, noise_first,
                      row_scale, rows_per_clip, dst);
   return ss_launch_status();
@@ -829,14 +827,13 @@ extern "C" int ss_batch_gather_z(const float* feat, int D, const int32_t* xmap, 
   // 16 bytes per lane where every chunk of a row is one aligned float4 on both sides; else one element per lane
   const bool wide = ((D | E | ld_dst) & 3) == 0 && (bases & 15) == 0;
   const long lanes = rows * ((D + E) / (wide ? 4 : 1));
-  long blocks = (lanes + 255) / 256;
-  blocks = blocks > 4096 ? 4096 : blocks;
+  const int blocks = ss_flat_grid(lanes, 4096);
   if (wide)
-    hipLaunchKernelGGL(batch_gather_z_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), feat, D,
+    hipLaunchKernelGGL(batch_gather_z_kernel<4>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), feat, D,
                        xmap, emb, E, rmap, emb_fill, rows, noise_map, noise_std, seed, noise_first, row_scale,
                        row_scale ? rows_per_clip : 1, dst, ld_dst);
   else
-    hipLaunchKernelGGL(batch_gather_z_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), feat, D,
+    hipLaunchKernelGGL(batch_gather_z_kernel<1>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), feat, D,
                        xmap, emb, E, rmap, emb_fill, rows, noise_map, noise_std, seed, noise_first, row_scale,
                        row_scale ? rows_per_clip : 1, dst, ld_dst);
   return ss_launch_status();
@@ -898,17 +895,15 @@ extern "C" int ss_batch_mixup(const float* X, int ld_x, int D, float* Xm, const 
   SS_REQUIRE(!R || ((reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(Rm)) & 15) == 0, SS_ERR_ARG);
   const long rows = (long)B * T;
   // at most 2048 workgroups per stream: eight of 256 lanes on each of 256 CUs is all the chip holds at once
-  long r_blocks = !R ? 0 : (rows * (frame_bytes / 16) + 255) / 256;
-  r_blocks = r_blocks > 2048 ? 2048 : r_blocks;
+  const int r_blocks = !R ? 0 : ss_flat_grid(rows * (frame_bytes / 16), 2048);
   const bool wide = X && ((D | ld_x) & 3) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Xm)) & 15) == 0;
-  long x_blocks = !X ? 0 : (rows * (D / (wide ? 4 : 1)) + 255) / 256;
-  x_blocks = x_blocks > 2048 ? 2048 : x_blocks;
-  const dim3 grid((unsigned)(r_blocks + x_blocks));
+  const int x_blocks = !X ? 0 : ss_flat_grid(rows * (D / (wide ? 4 : 1)), 2048);
+  const dim3 grid(r_blocks + x_blocks);
   if (wide)
     hipLaunchKernelGGL(batch_mixup_kernel<4>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), X, ld_x, D, Xm, R, Rm,
-                       frame_bytes / 16, perm, k, B, T, (int)r_blocks);
+                       frame_bytes / 16, perm, k, B, T, r_blocks);
   else
     hipLaunchKernelGGL(batch_mixup_kernel<1>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), X, ld_x, D, Xm, R, Rm,
-                       frame_bytes / 16, perm, k, B, T, (int)r_blocks);
+                       frame_bytes / 16, perm, k, B, T, r_blocks);
   return ss_launch_status();
 }

@@ -335,11 +335,8 @@ extern "C" int ss_layernorm_bwd(const float* d_y, const float* xhat, const float
 extern "C" int ss_dropout(const float* x, float* y, long n, float p, uint64_t seed, uint64_t offset,
                           const float* relu_of, ss_stream_t stream) {
   SS_REQUIRE(x && y && n > 0 && p >= 0.f && p < 1.f, SS_ERR_ARG);
-  long quads = (n + 3) / 4;
-  int blocks = (int)((quads + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(dropout_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, n, p, seed,
-                     offset, relu_of);
+  hipLaunchKernelGGL(dropout_kernel, dim3(ss_flat_grid((n + 3) / 4, 2048)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, n, p,
+                     seed, offset, relu_of);
   return ss_launch_status();
 }
 

@@ -161,6 +161,19 @@ __device__ __forceinline__ float ss_sqrt_rn_f32(float x) { return (float)__dsqrt
 
 #include "launch.h"  // the host side: ss_device_cus(), ss_dynamic_lds(), ss_persistent_grid()
 
+// Workgroups of a flat grid-stride launch: `work` items (elements, quads, chunks: the caller's count) over workgroups of 256 lanes,
+// at least one, at most `cap`.
+static inline int ss_flat_grid(long work, long cap) {
+  const long blocks = (work + 255) / 256;
+  return (int)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
+
+// Every one of these pointers is 16-byte aligned; a null pointer (an optional buffer left out) counts as aligned.
+template <class... P>
+static inline bool ss_aligned16(const P*... p) {
+  return (al16(p) && ...);
+}
+
 // ---- diagnostic build only (-DSS_STAMP): per-stage cycle shares of the persistent kernels.
 // Thread 0 of every workgroup accumulates s_memtime deltas between barriers; the real build has no stamps.
 #ifdef SS_STAMP

@@ -1,5 +1,5 @@
-"""Host references of the flat streaming kernels (csrc/optim.hip, csrc/pool_head.hip) in NumPy, float64 or integers: the
-clip + Adam step (``ss_adam_clip``, ``ss_adam_clip_ema``), the dropout stream (``ss_dropout``), softmax + top-k
+"""Host references of the flat streaming kernels (csrc/optim.hip, csrc/step_helpers.hip, csrc/pool_head.hip) in NumPy, float64
+or integers: the clip + Adam step (``ss_adam_clip``, ``ss_adam_clip_ema``), the dropout stream (``ss_dropout``), softmax + top-k
 (``ss_softmax_topk``) and the list of frames that belong to a clip (``ss_train_prologue``, ``ss_roi_active_frames``).  Test
 infrastructure: ``tests/test_flat_ref_cpu.py`` checks it against torch and Random123's known answers without a GPU,
 ``tests/test_gpu_flat_kernels.py`` holds the kernels to it.

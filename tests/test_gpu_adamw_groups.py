@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 GUARD = 8  # words of NaN patterns in front of and behind every buffer (32 bytes: the buffer stays 16-byte aligned)
 LR = ADAM[2]
 SWEEP = 2048 * 256 * 4  # elements one sweep of the capped grid covers
-NS = [1, 3, 4, 5, 1027, SWEEP - 1, SWEEP, SWEEP + 7]
+NS = [1, 2, 3, 4, 5, 6, 1027, SWEEP - 1, SWEEP, SWEEP + 7, 4 * SWEEP + 5]
 
 
 # ---------------------------------------------------------------------------------------------------------------- the kernel
@@ -123,8 +123,8 @@ def case(n, seed):
 @pytest.mark.parametrize("n", NS)
 def test_one_plain_segment_writes_the_bits_of_the_existing_kernels(L, n, with_ema):
     """One segment of a group {scale 1, decay 0}: p * 1.0f is exact and lr_G is lr, so p, m, v (and the average) are the bits of
-    ``ss_adam_clip`` (``ss_adam_clip_ema``).  Steps 1 and 7 from nonzero moments, the second one clipped; sizes on both sides of
-    one sweep of the capped grid."""
+    ``ss_adam_clip`` (``ss_adam_clip_ema``).  Steps 1 and 7 from nonzero moments, the second one clipped; sizes without a
+    quad, with every ``n & 3``, on both sides of one sweep of the capped grid and just past four."""
     host, ema = case(n, 200 + n)
     ema = ema if with_ema else None
     d = 0.9 if with_ema else None
@@ -145,6 +145,7 @@ TABLES = {
     "b_inside_a_wave": (1031, [4, 8, 256, 260, 1024, 1028, 1031]),
     "c_around_the_sweep": (SWEEP + 7, [SWEEP - 4, SWEEP, SWEEP + 4, SWEEP + 7]),
     "d_quad_then_two_million": (4 + 2000000, [4, 4 + 2000000]),
+    "e_last_is_a_quad_and_a_tail": (1030, [4, 512, 1024, 1030]),
 }
 
 
@@ -154,7 +155,8 @@ def test_segment_edges_bit_for_bit(L, name, with_ema):
     """All decays 0, three groups with scales {1, 0.1, 0} dealt to the segments in turn: every segment gets the bits of one
     ``ss_adam_clip`` (``ss_adam_clip_ema``) launch on its sub-range.  (b) has a boundary inside one wave's span and a tail segment
     of ``n & 3 = 3`` elements of its own: that one is checked against ``ss_adam_clip`` for p, m, v and against
-    ``optim_ref.ema_expected`` for the average."""
+    ``optim_ref.ema_expected`` for the average.  (e) ends in a segment of one quad and
+    ``n & 3 = 2`` elements, in the group of scale 1."""
     n, ends = TABLES[name]
     ids = [k % 3 for k in range(len(ends))]
     host, ema = case(n, 300 + len(ends))

@@ -21,10 +21,11 @@ pytestmark = pytest.mark.gpu
 
 SPREAD = 9.781275e-08
 LOSS_BOUND = 10 * SPREAD
-NS = [1, 3, 4, 5, 1023, 1024, 1025, 256 * 4 * 3 + 2]  # tail alone, one vector, vector + tail, both sides of a workgroup's stride
+NS = [1, 2, 3, 4, 5, 1023, 1024, 1025, 256 * 4 * 3 + 2]  # tail alone, one vector, vector + tail, both sides of a workgroup's stride
 # one sweep of the capped grid of ss_adam_clip_ema and ss_swap_f32 is 2048 x 256 x 4 = 2 097 152 elements: both sides of it, a
 # second trip of one lane + a tail, a third trip
 NS_LARGE = [2097151, 2097152, 2097157, 4194311]
+N_FOUR_SWEEPS = 4 * 2097152 + 5  # four whole sweeps, then a fifth trip of one lane + one tail element
 NS_FLOAT64 = (2097157, 4194311)
 DECAYS = [0.0, 0.1, 0.999]
 ADAM = (1.0, 1.0, 3e-4, 0.9, 0.999, 1e-8)  # grad_scale, max_norm, lr, beta1, beta2, eps
@@ -99,9 +100,9 @@ def test_adam_clip_ema_against_adam_clip(L, n):
     check_adam_clip_ema(L, n, DECAYS)
 
 
-@pytest.mark.parametrize("n", NS_LARGE)
+@pytest.mark.parametrize("n", NS_LARGE + [N_FOUR_SWEEPS])
 def test_adam_clip_ema_past_one_sweep_of_the_capped_grid(L, n):
-    """The same checks where the 2048-workgroup grid strides a second and a third time (two decays; d = 0 still makes the
+    """The same checks where the 2048-workgroup grid strides a second, a third and a fifth time (two decays; d = 0 still makes the
     average p_new exactly), and at two of the sizes p, m, v against the float64 step as well, not only against ``ss_adam_clip``."""
     worst = check_adam_clip_ema(L, n, [0.0, 0.999], against_float64=n in NS_FLOAT64)
     if n in NS_FLOAT64:

@@ -1,5 +1,5 @@
-"""GPU: the flat streaming kernels past their grid caps -- ``ss_sumsq_f32``, ``ss_adam_clip``, ``ss_dropout``,
-``ss_zero_f32x2``, ``ss_copy_rows_f32``, ``ss_train_prologue`` (csrc/optim.hip) and ``ss_softmax_topk`` (csrc/pool_head.hip)
+"""GPU: the flat streaming kernels past their grid caps -- ``ss_sumsq_f32``, ``ss_adam_clip`` (csrc/optim.hip), ``ss_zero_f32x2``,
+``ss_copy_rows_f32``, ``ss_train_prologue`` (csrc/step_helpers.hip), ``ss_dropout`` and ``ss_softmax_topk`` (csrc/pool_head.hip)
 -- through the C ABI against the host references of tests/flat_ref.py (float64 or integers; tests/test_flat_ref_cpu.py pins
 those without a GPU).
 
