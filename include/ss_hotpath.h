@@ -774,6 +774,53 @@ int ss_eval_accum_w(const float* logits, const int64_t* y, int B, int C, float l
  * probs (B,k) f32, idx (B,k) int32 (class ids; -1 / 0 when k > C). */
 int ss_softmax_topk(const float* logits, int B, int C, int k, float* probs, int32_t* idx, ss_stream_t stream);
 
+/* ss_softmax_topk at a temperature: the softmax of inv_temp[0] * logits, inv_temp a DEVICE float (u = 1 / T > 0), read by the
+ * kernel -- a captured graph is replayed under a new temperature by rewriting the float, without re-capture.  Every exponent is
+ * u * (l - max); inv_temp == NULL means u = 1, and with NULL or a stored 1.0f the results are the bits of ss_softmax_topk
+ * (1.0f * x is exact).  The indices do not depend on u.  Everything else as ss_softmax_topk. */
+int ss_softmax_topk_t(const float* logits, int B, int C, int k, const float* inv_temp, float* probs, int32_t* idx,
+                      ss_stream_t stream);
+
+/* Post-hoc temperature scaling, fitted on the device ("Calibrated confidences").  Parametrised by u = 1 / T.  Row with
+ * logits z (C floats), label y, m = max z:   e_c = exp(u (z_c - m)), S0 = sum e_c, S1 = sum e_c (z_c - m),
+ *   nll = log S0 - u (z_y - m),   g = d nll / du = S1 / S0 - (z_y - m);   sum g is non-decreasing in u.
+ * A fit is SS_CALIB_FIT_ITERS (ss_calib_moments, ss_calib_bisect) pairs on one stream, enqueue-only; no float atomics: the same
+ * inputs give the same bits on every run.
+ * state (8 doubles, device): u, lo, hi, nll, g, nll_at_1, iteration, at_bound.  The caller starts it as
+ *   {1, SS_CALIB_U_MIN, SS_CALIB_U_MAX, 0, 0, 0, 0, 0}.
+ * ss_calib_moments: reads u = state[0]; logits (N, C) f32, y (N) int64; one wave per row, rows by grid stride over exactly
+ *   n_partials workgroups (1..SS_CALIB_MAX_PARTIALS; four rows per workgroup and pass); per-row arithmetic in f32, sums over rows in
+ *   f64 in a fixed order; workgroup i WRITES partials[2 i] = its sum of nll, partials[2 i + 1] = its sum of g (partials: 2 *
+ *   n_partials doubles).  A label outside [0, C) is never an index: the row counts nowhere and *err_flag (one device word the caller
+ *   owns and clears) is set to 1.  C >= 2.
+ * ss_calib_bisect: one wave sums the partials in slot order, stores the sums as state's nll and g and advances the schedule:
+ *   iteration 0 evaluated u = 1: nll_at_1 = nll, next u = U_MIN;
+ *   iteration 1 evaluated U_MIN: g >= 0 -> the answer is U_MIN, at_bound = -1; else next u = U_MAX;
+ *   iteration 2 evaluated U_MAX: g <= 0 -> the answer is U_MAX, at_bound = +1; else next u = sqrt(lo hi);
+ *   iterations 3 .. 34: g > 0 moves hi to u, otherwise lo; next u = sqrt(lo hi) -- except after the last one, where u stays the
+ *   point just evaluated (an end of the final bracket), so that nll and g are those of the u the fit returns.
+ *   32 halvings of ln(U_MAX / U_MIN) = ln 400 leave 1.4e-9 of ln u, below the resolution of a float32 temperature.
+ *   Once at_bound != 0, or after SS_CALIB_FIT_ITERS iterations, a call leaves the state alone. */
+#define SS_CALIB_U_MIN 0.05
+#define SS_CALIB_U_MAX 20.0
+#define SS_CALIB_FIT_ITERS 35
+#define SS_CALIB_MAX_PARTIALS 256
+int ss_calib_moments(const float* logits, const int64_t* y, int N, int C, const double* state, double* partials, int n_partials,
+                     int32_t* err_flag, ss_stream_t stream);
+int ss_calib_bisect(double* state, const double* partials, int n_partials, ss_stream_t stream);
+
+/* Reliability of the confidences at inverse temperature inv_temp[0] (a DEVICE float; NULL: 1).  Per row: the confidence 1 / S0
+ * (the probability of the arg-max), the prediction (lowest index among equal maxima) and the rank of the true class = #{c: z_c >
+ * z_y, or z_c == z_y and c < y}.  Accumulated with integer atomics only (sums that do not depend on the order and add over ranks):
+ *   bin_count (n_bins) i32   [min(n_bins - 1, floor(conf * n_bins))] += 1
+ *   bin_hits (n_bins) i32    the same bin += (prediction == y)
+ *   bin_conf_fx (n_bins) u64 the same bin += llrint((double)conf * 2^32)
+ *   rank_hist (k_max + 1) i32 [min(rank, k_max)] += 1
+ * The caller clears them.  Labels outside [0, C): as ss_calib_moments.  n_bins and k_max in 1..64. */
+int ss_calib_bins(const float* logits, const int64_t* y, int N, int C, const float* inv_temp, int n_bins, int k_max,
+                  int32_t* bin_count, int32_t* bin_hits, uint64_t* bin_conf_fx, int32_t* rank_hist, int32_t* err_flag,
+                  ss_stream_t stream);
+
 /* sumsq (1) += sum x^2 over the flat gradient bucket (clip_grad_norm_'s global L2 norm). */
 int ss_sumsq_f32(const float* x, long n, float* sumsq, ss_stream_t stream);
 

@@ -6,7 +6,8 @@ Drop-in surface of the reference's per-clip path:
 All arithmetic runs in ``libss_hotpath.so`` (hand-written HIP, C ABI in ``include/ss_hotpath.h``);
 there is no CPU or PyTorch-op fallback.
 """
-from . import checkpoint, data, features, harness, serving
+from . import calibrate, checkpoint, data, features, harness, serving
+from .calibrate import Calibration
 from .checkpoint import load_classifier, save_checkpoint, topk_from_logits
 from .device_data import AugmentPolicy, DeviceClipStore
 from .engine import Config

@@ -126,6 +126,10 @@ SIGNATURES = {
     "ss_class_weight_sum": [_vp, _l, _vp, _i, _vp, _vp],
     "ss_eval_accum_w": [_vp, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "ss_softmax_topk": [_vp, _i, _i, _i, _vp, _vp, _vp],
+    "ss_softmax_topk_t": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "ss_calib_moments": [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp],
+    "ss_calib_bisect": [_vp, _vp, _i, _vp],
+    "ss_calib_bins": [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "ss_sumsq_f32": [_vp, _l, _vp, _vp],
     "ss_adam_clip": [_vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _vp],
     "ss_adam_clip_ema": [_vp, _vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _vp],

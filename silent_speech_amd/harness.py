@@ -7,6 +7,7 @@ Counterparts, by reference line (/root/reference/train_model_official.py):
   evaluate          :449-475   loss / accuracy / predictions over a validation set, forward only
   top_confusions    :79-91     "actual→predicted(count)" strings of the most frequent errors
   fit               :417-506   epochs, save-best checkpoint (:486-500), early stopping (:501-505)
+  fit_calibrated    (none)     ``fit``, then a softmax temperature fitted on the validation clips and stored in the checkpoint
   balanced_class_weights :406-412   the weights of the commented-out class-weighted loss (``fit(class_weights="balanced")``)
 
 Data parallelism (the reference has none): ``fit(rank=, world_size=, process_group=)`` -- every rank holds
@@ -27,6 +28,7 @@ import copy
 import dataclasses
 import glob
 import hashlib
+import inspect
 import os
 import random
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
@@ -34,8 +36,8 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .checkpoint import (TRAIN_STATE_FORMAT, fingerprint_difference, load_classifier, load_train_state, save_checkpoint,
-                         save_train_state)
+from .checkpoint import (TRAIN_STATE_FORMAT, add_calibration, fingerprint_difference, load_classifier, load_train_state,
+                         save_checkpoint, save_train_state)
 from .device_data import MASK_FIELDS, MIXUP_FIELDS, AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier, ParamGroup
 from .train import (PlateauSchedule, Trainer, check_class_weights, check_distill, check_lr_schedule, check_weight_decay,
@@ -702,4 +704,45 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
             log(f"Early stopping. Best val acc: {best:.3f}")
             break
     _barrier(process_group)
+    return best
+
+
+def calibrate_checkpoint(out_path: str, val_store: DeviceClipStore, batch_size: int = BATCH_SIZE, device="cuda", log=print):
+    """The weights of the checkpoint at ``out_path`` -- of a ``fit`` run: the best epoch's, under ``ema_decay`` the averaged ones --
+    are loaded into a model (``load_classifier``), ``calibrate.calibrate`` runs over the whole of ``val_store``, and the file is
+    rewritten atomically with the keys ``"temperature"`` and ``"calibration"`` and its weights bit for bit.  One line is logged:
+    T, NLL and ECE before and after, top-3 accuracy.  -> the ``Calibration``, or None when there is no checkpoint."""
+    from .calibrate import calibrate as run_calibration
+
+    if not os.path.exists(out_path):
+        return None
+    model = load_classifier(out_path, device=device)[0]
+    cal = run_calibration(model, val_store, batch_size)
+    add_calibration(out_path, cal.temperature, cal.plain())
+    top3 = cal.topk_acc[min(3, len(cal.topk_acc)) - 1]
+    log(f"calibrated {out_path}: T {cal.temperature:.4f} | val NLL {cal.nll_before:.4f} -> {cal.nll_after:.4f} | "
+        f"ECE {cal.ece_before:.4f} -> {cal.ece_after:.4f} | top-3 acc {top3:.3f}")
+    return cal
+
+
+def fit_calibrated(clip_dir: str, out_path: str, **fit_args) -> float:
+    """``fit(clip_dir, out_path, **fit_args)``, then calibrated confidences for the checkpoint it left (the reference prints
+    uncalibrated probabilities): when training is over -- after the last epoch, an early stop, or for a resumed run that had already
+    finished -- rank 0, if ``out_path`` exists, fits a softmax temperature on the whole validation store of the run's split with the
+    checkpoint's weights and rewrites the checkpoint with the keys ``"temperature"`` and ``"calibration"`` (``calibrate_checkpoint``);
+    the other ranks wait at a barrier, and every rank returns ``fit``'s ``best``.  ``fit`` itself is called as it is: nothing about
+    training, the run fingerprint or the train-state file changes, and the weights in the checkpoint keep their bits.
+    ``fit_args`` are checked against ``fit``'s signature before any work (``TypeError`` for a name it does not have)."""
+    bound = inspect.signature(fit).bind(clip_dir, out_path, **fit_args)
+    bound.apply_defaults()
+    a = bound.arguments
+    best = fit(clip_dir, out_path, **fit_args)
+    if a["rank"] == 0 and os.path.exists(out_path):
+        # the validation clips of the run: the same scan and the same split by the same seed
+        info = scan_clips(clip_dir)
+        _, val_files = split_by_label(info["files"], info["labels"], VAL_FRAC, seed=a["seed"])
+        use_roi = a["use_roi_if_present"] and info["has_roi"] > 0
+        val_store = DeviceClipStore(val_files, info["label_to_id"], max_t=a["max_t"], use_roi=use_roi, device=a["device"])
+        calibrate_checkpoint(out_path, val_store, a["batch_size"], a["device"], a["log"])
+    _barrier(a["process_group"])
     return best

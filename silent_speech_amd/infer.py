@@ -22,7 +22,12 @@ class GraphedInference:
     Inputs are copied into static device buffers (or written there directly through ``g.X / g.lengths / g.R``) and
     the captured forward is replayed; ``logits`` is the static output buffer (clone it to keep it across calls)."""
 
-    def __init__(self, model: BiGRUClassifier, B: int, T: int, roi_hw=None, warmup: int = 2, topk: int = 0):
+    def __init__(self, model: BiGRUClassifier, B: int, T: int, roi_hw=None, warmup: int = 2, topk: int = 0,
+                 temperature=None):
+        if temperature is not None:
+            from .calibrate import check_temperature
+
+            temperature = check_temperature(temperature)  # (host code, before any device work)
         if model.flat_params is None or not model.flat_params.is_cuda:
             raise RuntimeError("GraphedInference needs the model on a HIP device")
         if model.use_roi and roi_hw is None:
@@ -39,6 +44,11 @@ class GraphedInference:
         self.topk = min(int(topk), cfg.num_classes)
         self.top_probs = torch.zeros(B, self.topk, device=dev) if self.topk else None
         self.top_idx = torch.zeros(B, self.topk, device=dev, dtype=torch.int32) if self.topk else None
+        # temperature (with topk > 0): the captured top-k is ss_softmax_topk_t reading 1 / T from a one-float device buffer, which
+        # ``set_temperature`` rewrites between replays -- no re-capture.  None: today's graph, ss_softmax_topk.
+        self.inv_temp = None
+        if temperature is not None and self.topk:
+            self.inv_temp = torch.full((1,), 1.0 / temperature, device=dev, dtype=torch.float32)
         self._P = model._param_dict()
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
@@ -54,10 +64,23 @@ class GraphedInference:
     def _run(self) -> torch.Tensor:
         self.ws.lengths.copy_(self.lengths)
         logits = E.forward(self._P, self.model.cfg, self.ws, self.X, self.R, train=False, stash=False)
-        if self.topk:
+        if self.topk and self.inv_temp is not None:
+            E.L.call("ss_softmax_topk_t", logits.data_ptr(), self.B, self.model.cfg.num_classes, self.topk, self.inv_temp.data_ptr(),
+                     self.top_probs.data_ptr(), self.top_idx.data_ptr(), E.L.stream())
+        elif self.topk:
             E.L.call("ss_softmax_topk", logits.data_ptr(), self.B, self.model.cfg.num_classes, self.topk,
                      self.top_probs.data_ptr(), self.top_idx.data_ptr(), E.L.stream())
         return logits
+
+    def set_temperature(self, temperature) -> None:
+        """The temperature of the following replays' ``top_probs`` (a positive finite number): rewrites the device float the
+        captured ``ss_softmax_topk_t`` reads.  Only for a graph captured with ``topk`` and a ``temperature``."""
+        from .calibrate import check_temperature
+
+        temperature = check_temperature(temperature)
+        if self.inv_temp is None:
+            raise RuntimeError("set_temperature needs a graph captured with topk > 0 and a temperature")
+        self.inv_temp.fill_(1.0 / temperature)
 
     def __call__(self, X: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
                  R: Optional[torch.Tensor] = None) -> torch.Tensor:
