@@ -859,6 +859,28 @@ int ss_adamw_clip_groups(float* p, const float* g, float* m, float* v, float* em
                          const long* seg_end, const int* seg_group, int n_seg, const float* group_lr_scale,
                          const float* group_weight_decay, int n_groups, ss_stream_t stream);
 
+/* Sharpness-aware minimisation (Foret et al. 2021; adaptive: ASAM, Kwon et al. 2021) on a flat bucket, as the widely used torch
+ * SAM optimiser computes it (adaptive=True, no eta): three streams around the second forward and backward of a step.
+ *
+ * sumsq (1) += sum (|w_i| g_i)^2: the square of ASAM's scale-invariant norm.  The walk, the workgroup count and the order of
+ * adds are ss_sumsq_f32's; each product |w| g is rounded to f32 before it is squared.  w, g 16-byte aligned. */
+int ss_sumsq_absw_f32(const float* w, const float* g, long n, float* sumsq, ss_stream_t stream);
+
+/* The ascent step, one pass over n elements:  backup_i = p_i;  p_i = p_i + e_i;  g_i = +0, with
+ *     scale = rho * grad_scale / (sqrt(sumsq[0]) * grad_scale + 1e-12)      (f32, from the device word: no host read)
+ *     e_i   = scale * g_i               (adaptive == 0;  sumsq = sum g^2,        ss_sumsq_f32)
+ *     e_i   = scale * g_i * p_i^2       (adaptive != 0;  sumsq = sum (|p| g)^2,  ss_sumsq_absw_f32)
+ * grad_scale as ss_adam_clip takes it.  The launch also stores +0 to zero_f[0, n_zero_f) and 0 to zero_i[0, n_zero_i) (at most
+ * 256 each; a pointer may be NULL with a count of 0): the loss sum and hit count the second pass adds onto.
+ * p, g, backup 16-byte aligned; backup must overlap neither p nor g; sumsq must not be one of the cleared floats; rho finite and
+ * > 0.  SS_ERR_ARG otherwise, before any launch: nothing is written. */
+int ss_sam_perturb(float* p, float* g, float* backup, long n, const float* sumsq, float grad_scale, float rho, int adaptive,
+                   float* zero_f, int n_zero_f, int32_t* zero_i, int n_zero_i, ss_stream_t stream);
+
+/* Behind the second backward: p_i = backup_i bit for bit, and sumsq (1) += sum g_i^2 with the walk and the adds of ss_sumsq_f32
+ * (the same bits as ss_sumsq_f32 on g).  Alignment and overlap rules of ss_sam_perturb; SS_ERR_ARG otherwise, nothing written. */
+int ss_sam_restore_sumsq(float* p, const float* backup, const float* g, long n, float* sumsq, ss_stream_t stream);
+
 /* exchanges the contents of two f32 buffers of n elements in place (the weights and their average, Trainer.ema_weights).
  * Both 16-byte aligned; ranges that overlap are SS_ERR_ARG. */
 int ss_swap_f32(float* a, float* b, long n, ss_stream_t stream);

@@ -135,6 +135,9 @@ SIGNATURES = {
     "ss_adam_clip_ema": [_vp, _vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _vp],
     # (seg_end, seg_group, group_lr_scale, group_weight_decay: HOST arrays -- ``SegmentTable.ptrs``)
     "ss_adamw_clip_groups": [_vp, _vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _i, _vp, _vp, _i, _vp],
+    "ss_sumsq_absw_f32": [_vp, _vp, _l, _vp, _vp],
+    "ss_sam_perturb": [_vp, _vp, _vp, _l, _vp, _f, _f, _i, _vp, _i, _vp, _i, _vp],
+    "ss_sam_restore_sumsq": [_vp, _vp, _vp, _l, _vp, _vp],
     "ss_swap_f32": [_vp, _vp, _l, _vp],
     "ss_copy_rows_f32": [_vp, _i, _vp, _i, _i, _i, _vp],
 }

@@ -1,38 +1,149 @@
 // Flat-bucket optimiser step: the gradient's sum of squares, the global-norm clip folded into Adam (plain, with the weight average,
-// and grouped AdamW), and the swap of two buckets.  Replaces clip_grad_norm_ + torch.optim.Adam.step of
-// train_model_official.py:403, 438-439.  All HBM-bound, grid-stride; every kernel but adam_clip_kernel in 16-byte lanes.
+// and grouped AdamW), the swap of two buckets, and the two streams of a sharpness-aware step (perturb; restore + sum of squares).
+// Replaces clip_grad_norm_ + torch.optim.Adam.step of train_model_official.py:403, 438-439.  All HBM-bound, grid-stride; every
+// kernel but adam_clip_kernel in 16-byte lanes.
 #include <math.h>
 
 #include "ss_common.h"
 
 namespace {
 
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
+// The terms whose squares the sums below take: the elements of x themselves, or |w| g (the scale-invariant norm of ASAM; the
+// product is rounded on its own, then squared).  In two halves, so that the walk can issue all loads of a trip before anything
+// else: load<T>(i) reads item i (T = f32x4: floats [4i, 4i + 4); T = float: element i), term(i, raw) makes the term of it.
+template <class T>
+__device__ __forceinline__ T abs_times(const T& w, const T& g);
+template <>
+__device__ __forceinline__ float abs_times(const float& w, const float& g) { return fabsf(w) * g; }
+template <>
+__device__ __forceinline__ f32x4 abs_times(const f32x4& w, const f32x4& g) {
+  return f32x4{fabsf(w[0]) * g[0], fabsf(w[1]) * g[1], fabsf(w[2]) * g[2], fabsf(w[3]) * g[3]};
+}
+template <class T>
+struct Two {
+  T a, b;
+};
+struct PlainTerms {
+  const float* x;
+  template <class T>
+  __device__ __forceinline__ T load(long i) const { return reinterpret_cast<const T*>(x)[i]; }
+  template <class T>
+  __device__ __forceinline__ T term(long, const T& raw) const { return raw; }
+};
+struct AbsWeightTerms {
+  const float *w, *g;
+  template <class T>
+  __device__ __forceinline__ Two<T> load(long i) const { return {reinterpret_cast<const T*>(w)[i], reinterpret_cast<const T*>(g)[i]}; }
+  template <class T>
+  __device__ __forceinline__ T term(long, const Two<T>& raw) const { return abs_times(raw.a, raw.b); }
+};
+// g, and on the way p = backup for the same elements (ss_sam_restore_sumsq: the weights come back while their gradient is read)
+struct RestoreTerms {
+  float* p;
+  const float *backup, *g;
+  template <class T>
+  __device__ __forceinline__ Two<T> load(long i) const { return {reinterpret_cast<const T*>(backup)[i], reinterpret_cast<const T*>(g)[i]}; }
+  template <class T>
+  __device__ __forceinline__ T term(long i, const Two<T>& raw) const {
+    reinterpret_cast<T*>(p)[i] = raw.a;
+    return raw.b;
+  }
+};
+
+// out += the sum of the squared terms of [0, n): written once for ss_sumsq_f32, ss_sumsq_absw_f32 and ss_sam_restore_sumsq -- the
+// same walk, the same expressions, hence the same order of adds and the same contractions in all three.
+template <class Terms>
+__global__ __launch_bounds__(256) void sumsq_kernel(Terms t, long n, float* __restrict__ out) {
   __shared__ float red[4];
   float acc = 0.f;
   const long n4 = n >> 2;
-  const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-  // four 16-byte loads in flight per thread (a dependent chain of single loads made the 28 MB bucket of config 5 a 28 us kernel:
+  // four trips' 16-byte loads in flight per thread (a dependent chain of single loads made the 28 MB bucket of config 5 a 28 us kernel:
   // 1 TB/s; one launch's atomics -- one per workgroup on one address, ~12 ns each -- bound the workgroup count from above)
   const long stride = (long)gridDim.x * 256;
   long q = (long)blockIdx.x * 256 + threadIdx.x;
   for (; q + 3 * stride < n4; q += 4 * stride) {
-    const f32x4 v0 = x4[q], v1 = x4[q + stride], v2 = x4[q + 2 * stride], v3 = x4[q + 3 * stride];
+    const auto r0 = t.template load<f32x4>(q), r1 = t.template load<f32x4>(q + stride), r2 = t.template load<f32x4>(q + 2 * stride),
+               r3 = t.template load<f32x4>(q + 3 * stride);
+    const f32x4 v0 = t.term(q, r0), v1 = t.term(q + stride, r1), v2 = t.term(q + 2 * stride, r2), v3 = t.term(q + 3 * stride, r3);
     acc += (v0[0] * v0[0] + v0[1] * v0[1] + v0[2] * v0[2] + v0[3] * v0[3]) + (v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2] + v1[3] * v1[3]) +
            (v2[0] * v2[0] + v2[1] * v2[1] + v2[2] * v2[2] + v2[3] * v2[3]) + (v3[0] * v3[0] + v3[1] * v3[1] + v3[2] * v3[2] + v3[3] * v3[3]);
   }
   for (; q < n4; q += stride) {
-    const f32x4 v = x4[q];
+    const f32x4 v = t.term(q, t.template load<f32x4>(q));
     acc += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    float v = x[(n4 << 2) + threadIdx.x];
+    const long i = (n4 << 2) + threadIdx.x;
+    float v = t.term(i, t.template load<float>(i));
     acc += v * v;
   }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
+}
+
+// The ascent step of sharpness-aware minimisation, one pass: backup = w, w += e, g = 0, with e = scale g (SAM) or scale w^2 g
+// (ADAPTIVE: ASAM) and scale = rho grad_scale / (sqrt(sumsq) grad_scale + 1e-12), taken once per thread from the device word.
+// Two quads per lane and trip: four 16-byte loads in flight, six stores behind them; the n & 3 last elements by block 0, which
+// also clears the few scalars the second pass adds onto (none of them is the sumsq word: the entry point refuses that).
+struct SamParams {
+  float *p, *g, *backup;
+  long n;
+  const float* sumsq;
+  float grad_scale, rho;
+  float* zero_f;
+  int* zero_i;
+  int n_zero_f, n_zero_i;
+};
+constexpr int SAM_MAX_SCALARS = 256;
+
+template <bool ADAPTIVE>
+__device__ __forceinline__ float sam_ascend(float scale, float w, float g) {
+  return ADAPTIVE ? w + (scale * g) * (w * w) : w + scale * g;
+}
+template <bool ADAPTIVE>
+__device__ __forceinline__ f32x4 sam_ascend(float scale, const f32x4& w, const f32x4& g) {
+  return f32x4{sam_ascend<ADAPTIVE>(scale, w[0], g[0]), sam_ascend<ADAPTIVE>(scale, w[1], g[1]),
+               sam_ascend<ADAPTIVE>(scale, w[2], g[2]), sam_ascend<ADAPTIVE>(scale, w[3], g[3])};
+}
+
+template <bool ADAPTIVE>
+__global__ __launch_bounds__(256) void sam_perturb_kernel(SamParams a) {
+  const float scale = a.rho * a.grad_scale / (sqrtf(a.sumsq[0]) * a.grad_scale + 1e-12f);
+  const long n4 = a.n >> 2;
+  f32x4* p4 = reinterpret_cast<f32x4*>(a.p);
+  f32x4* g4 = reinterpret_cast<f32x4*>(a.g);
+  f32x4* b4 = reinterpret_cast<f32x4*>(a.backup);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const long stride = (long)gridDim.x * 256;
+  long q = (long)blockIdx.x * 256 + threadIdx.x;
+  for (; q + stride < n4; q += 2 * stride) {
+    const f32x4 w0 = p4[q], w1 = p4[q + stride], g0 = g4[q], g1 = g4[q + stride];
+    b4[q] = w0;
+    b4[q + stride] = w1;
+    p4[q] = sam_ascend<ADAPTIVE>(scale, w0, g0);
+    p4[q + stride] = sam_ascend<ADAPTIVE>(scale, w1, g1);
+    g4[q] = zero;
+    g4[q + stride] = zero;
+  }
+  if (q < n4) {
+    const f32x4 w = p4[q], g = g4[q];
+    b4[q] = w;
+    p4[q] = sam_ascend<ADAPTIVE>(scale, w, g);
+    g4[q] = zero;
+  }
+  if (blockIdx.x == 0) {
+    if ((long)threadIdx.x < (a.n & 3)) {
+      const long i = (n4 << 2) + threadIdx.x;
+      const float w = a.p[i], g = a.g[i];
+      a.backup[i] = w;
+      a.p[i] = sam_ascend<ADAPTIVE>(scale, w, g);
+      a.g[i] = 0.f;
+    }
+    if ((int)threadIdx.x < a.n_zero_f) a.zero_f[threadIdx.x] = 0.f;
+    if ((int)threadIdx.x < a.n_zero_i) a.zero_i[threadIdx.x] = 0;
+  }
 }
 
 struct AdamParams {
@@ -184,12 +295,23 @@ __global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float*
 
 }  // namespace
 
+// every block ends in one float atomic on the same word (~11 ns each, serialised): 128 blocks, not 1024
+template <class Terms>
+static int sumsq_launch(Terms t, long n, float* sumsq, ss_stream_t stream) {
+  hipLaunchKernelGGL(sumsq_kernel<Terms>, dim3(ss_flat_grid(n >> 2, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), t, n, sumsq);
+  return ss_launch_status();
+}
+
 extern "C" int ss_sumsq_f32(const float* x, long n, float* sumsq, ss_stream_t stream) {
   SS_REQUIRE(x && sumsq && n > 0, SS_ERR_ARG);
   SS_REQUIRE(ss_aligned16(x), SS_ERR_ARG);
-  // every block ends in one float atomic on the same word (~11 ns each, serialised): 128 blocks, not 1024
-  hipLaunchKernelGGL(sumsq_kernel, dim3(ss_flat_grid(n >> 2, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, n, sumsq);
-  return ss_launch_status();
+  return sumsq_launch(PlainTerms{x}, n, sumsq, stream);
+}
+
+extern "C" int ss_sumsq_absw_f32(const float* w, const float* g, long n, float* sumsq, ss_stream_t stream) {
+  SS_REQUIRE(w && g && sumsq && n > 0, SS_ERR_ARG);
+  SS_REQUIRE(ss_aligned16(w, g), SS_ERR_ARG);
+  return sumsq_launch(AbsWeightTerms{w, g}, n, sumsq, stream);
 }
 
 static float adam_step_size(float lr, float beta1, int step) {
@@ -285,6 +407,36 @@ extern "C" int ss_adamw_clip_groups(float* p, const float* g, float* m, float* v
     hipLaunchKernelGGL(adamw_groups_kernel<false>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, t, ema,
                        0.0f, 1.0f);
   return ss_launch_status();
+}
+
+// What the two SAM entry points both refuse: backup is scratch of its own beside the weights and their gradient.
+static int sam_check(const float* p, const float* backup, const float* g, const float* sumsq, long n) {
+  SS_REQUIRE(p && backup && g && sumsq && n > 0, SS_ERR_ARG);
+  SS_REQUIRE(ss_aligned16(p, backup, g), SS_ERR_ARG);
+  SS_REQUIRE(disjoint_f32(backup, p, n) && disjoint_f32(backup, g, n), SS_ERR_ARG);
+  return SS_OK;
+}
+
+extern "C" int ss_sam_perturb(float* p, float* g, float* backup, long n, const float* sumsq, float grad_scale, float rho,
+                              int adaptive, float* zero_f, int n_zero_f, int* zero_i, int n_zero_i, ss_stream_t stream) {
+  if (const int bad = sam_check(p, backup, g, sumsq, n)) return bad;
+  SS_REQUIRE(rho > 0.0f && isfinite(rho), SS_ERR_ARG);  // (a NaN fails >)
+  SS_REQUIRE(n_zero_f >= 0 && n_zero_f <= SAM_MAX_SCALARS && n_zero_i >= 0 && n_zero_i <= SAM_MAX_SCALARS, SS_ERR_ARG);
+  SS_REQUIRE((zero_f || n_zero_f == 0) && (zero_i || n_zero_i == 0), SS_ERR_ARG);
+  // every workgroup reads the sumsq word while block 0 clears: it is none of the cleared ones
+  SS_REQUIRE(!(sumsq >= zero_f && sumsq < zero_f + n_zero_f), SS_ERR_ARG);
+  SamParams a{p, g, backup, n, sumsq, grad_scale, rho, zero_f, zero_i, n_zero_f, n_zero_i};
+  const dim3 grid(ss_flat_grid(n >> 2, 2048));
+  if (adaptive)
+    hipLaunchKernelGGL(sam_perturb_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  else
+    hipLaunchKernelGGL(sam_perturb_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return ss_launch_status();
+}
+
+extern "C" int ss_sam_restore_sumsq(float* p, const float* backup, const float* g, long n, float* sumsq, ss_stream_t stream) {
+  if (const int bad = sam_check(p, backup, g, sumsq, n)) return bad;
+  return sumsq_launch(RestoreTerms{p, backup, g}, n, sumsq, stream);
 }
 
 extern "C" int ss_swap_f32(float* a, float* b, long n, ss_stream_t stream) {

@@ -40,8 +40,8 @@ from .checkpoint import (TRAIN_STATE_FORMAT, add_calibration, fingerprint_differ
                          save_checkpoint, save_train_state)
 from .device_data import MASK_FIELDS, MIXUP_FIELDS, AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier, ParamGroup
-from .train import (PlateauSchedule, Trainer, check_class_weights, check_distill, check_lr_schedule, check_weight_decay,
-                    shard_range)
+from .train import (PlateauSchedule, Trainer, check_class_weights, check_distill, check_lr_schedule, check_sam_rho,
+                    check_weight_decay, shard_range)
 
 VAL_FRAC, SEED, PATIENCE, EPOCHS, BATCH_SIZE = 0.15, 42, 12, 80, 16
 I32_MAX = 2 ** 31 - 1  # "no clip yet" in a first_seen matrix
@@ -311,7 +311,7 @@ def run_fingerprint(seed, batch_size, world_size, max_t, lr, labels, x_dim, use_
     ``fit`` fills in from ``epochs`` stays None, since ``epochs`` is no part of the fingerprint) and ``lr_plateau`` (its settings; its
     state travels in the train-state file); and for ``distill_from`` (the sha256 of the teacher's checkpoint file, or ``"module"``
     for a teacher handed over as a module), ``distill_alpha`` and ``distill_temperature``, all three entries only when
-    ``distill_from`` is set."""
+    ``distill_from`` is set.  (A ``fit_sam`` run adds ``sam_rho`` and ``sam_adaptive`` to what this returns: ``sam_fingerprint``.)"""
     extra = {}
     if float(weight_decay) != 0.0:
         extra["weight_decay"] = float(weight_decay)
@@ -479,7 +479,47 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     the teacher).  Data parallel, every rank holds the teacher and runs it on its own shard: no collective is added.  Validation,
     the checkpoint, the weight average, the schedules and the logged train accuracy are as without; the logged train loss is the
     blended one.  ``state_path``: the fingerprint holds ``distill_from`` (the file's sha256, or ``"module"``), ``distill_alpha`` and
-    ``distill_temperature`` only when ``distill_from`` is set; a resumed run must be given the same teacher."""
+    ``distill_temperature`` only when ``distill_from`` is set; a resumed run must be given the same teacher.
+
+    ``fit_sam(clip_dir, out_path, sam_rho, sam_adaptive=False, **fit_args)`` is this function with sharpness-aware minimisation
+    (SAM, or its scale-invariant form ASAM) in every training step; this signature is what it always was."""
+    return _fit(None, False, **locals())
+
+
+def sam_fingerprint(fingerprint: dict, sam_rho, sam_adaptive=False) -> dict:
+    """``run_fingerprint``'s dict for a ``fit_sam`` run: with ``sam_rho`` and ``sam_adaptive``, both only when ``sam_rho`` is set,
+    so the fingerprints and state files of runs without SAM are what they always were, and a run with and one without (or with
+    another radius) cannot resume each other."""
+    if sam_rho is None:
+        return dict(fingerprint)
+    return dict(fingerprint, sam_rho=float(sam_rho), sam_adaptive=bool(sam_adaptive))
+
+
+def fit_sam(clip_dir: str, out_path: str, sam_rho: float, sam_adaptive: bool = False, **fit_args) -> float:
+    """``fit(clip_dir, out_path, **fit_args)`` with sharpness-aware minimisation in every training step
+    (``Trainer.enable_sam(sam_rho, sam_adaptive)``: SAM, or with ``sam_adaptive`` its scale-invariant form ASAM, whose radius is
+    relative to the weights): the gradient that Adam applies is taken at the worst nearby point ``w + e`` of the step's batch, for a
+    second forward and backward per step.  ``sam_rho`` must be finite and > 0 as float32 (``ValueError``, before anything touches a
+    device or the clips); ``fit_args`` are checked against ``fit``'s signature first (``TypeError`` for a name it does not have).
+    Works under both plans and with everything ``fit`` takes -- class weights, the policy and mixup, the weight average,
+    ``freeze_cnn``, AdamW groups and schedules, a teacher (whose logits serve both passes), data parallel (two all-reduces per step;
+    the perturbation is the global batch's).  The logged train loss and accuracy are the first pass's: those of the unperturbed
+    weights, as a run without SAM logs them.  ``state_path``: the fingerprint holds ``sam_rho`` and ``sam_adaptive``
+    (``sam_fingerprint``), so a resumed run must be a ``fit_sam`` run with the same two; the second pass reuses the step's dropout
+    seed, a function of the step count, so a resumed run is the uninterrupted one as closely as it is without SAM.
+    ``fit_calibrated(..., sam_rho=, sam_adaptive=)`` comes here."""
+    sam_rho = check_sam_rho(sam_rho)
+    if sam_rho is None:
+        raise ValueError("fit_sam needs sam_rho (fit is the run without)")
+    bound = inspect.signature(fit).bind(clip_dir, out_path, **fit_args)
+    bound.apply_defaults()
+    return _fit(sam_rho, bool(sam_adaptive), **bound.arguments)
+
+
+def _fit(sam_rho, sam_adaptive, clip_dir, out_path, epochs, batch_size, patience, max_t, lr, seed, use_roi_if_present, device, log, plan,
+         rank, world_size, process_group, history, class_weights, augment_policy, ema_decay, state_path, resume, init_from, freeze_cnn,
+         weight_decay, param_groups, lr_schedule, lr_plateau, distill_from, distill_alpha, distill_temperature) -> float:
+    """The body of ``fit`` (its docstring) and ``fit_sam``; ``sam_rho`` None: no SAM."""
     if distill_from is not None:  # (host code, before anything touches a device or the clips)
         distill_alpha, distill_temperature = check_distill(distill_alpha, distill_temperature)
         if not isinstance(distill_from, (str, os.PathLike, BiGRUClassifier)):
@@ -565,6 +605,7 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                                       distill_from=None if distill_from is None else
                                       ("module" if module_teacher else file_sha256(distill_from)),
                                       distill_alpha=distill_alpha, distill_temperature=distill_temperature)
+        fingerprint = sam_fingerprint(fingerprint, sam_rho, sam_adaptive)
         if resume and os.path.exists(state_path):
             saved = load_train_state(state_path)
             field = fingerprint_difference(saved["fingerprint"], fingerprint)
@@ -602,6 +643,8 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
                       freeze_cnn=freeze_cnn, weight_decay=weight_decay, param_groups=param_groups, lr_schedule=lr_schedule,
                       **({} if distill_from is None else dict(distill_alpha=distill_alpha, distill_temperature=distill_temperature)))
     trainer.rank = rank
+    if sam_rho is not None:
+        trainer.enable_sam(sam_rho, sam_adaptive)
     teacher = None
     if distill_from is not None:
         teacher = distill_from if module_teacher else load_classifier(distill_from, device=device)[0]
@@ -733,10 +776,11 @@ def fit_calibrated(clip_dir: str, out_path: str, **fit_args) -> float:
     the other ranks wait at a barrier, and every rank returns ``fit``'s ``best``.  ``fit`` itself is called as it is: nothing about
     training, the run fingerprint or the train-state file changes, and the weights in the checkpoint keep their bits.
     ``fit_args`` are checked against ``fit``'s signature before any work (``TypeError`` for a name it does not have)."""
+    sam = {k: fit_args.pop(k) for k in ("sam_rho", "sam_adaptive") if k in fit_args}  # (fit_sam's two: not names of fit)
     bound = inspect.signature(fit).bind(clip_dir, out_path, **fit_args)
     bound.apply_defaults()
     a = bound.arguments
-    best = fit(clip_dir, out_path, **fit_args)
+    best = fit_sam(clip_dir, out_path, **sam, **fit_args) if sam.get("sam_rho") is not None else fit(clip_dir, out_path, **fit_args)
     if a["rank"] == 0 and os.path.exists(out_path):
         # the validation clips of the run: the same scan and the same split by the same seed
         info = scan_clips(clip_dir)

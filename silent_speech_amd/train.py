@@ -83,6 +83,21 @@ def check_weight_decay(weight_decay) -> None:
         raise ValueError(f"weight_decay must be finite and >= 0, not {weight_decay!r}")
 
 
+def check_sam_rho(sam_rho):
+    """The neighbourhood radius of sharpness-aware minimisation as a float, or None (off).  ``ValueError`` unless it is finite and
+    > 0 as the float32 the kernel takes.  Host code, for ``Trainer`` and ``harness.fit`` alike: nothing here touches a device."""
+    if sam_rho is None:
+        return None
+    try:
+        with np.errstate(over="ignore"):
+            r = float(np.float32(sam_rho))
+    except (TypeError, ValueError):
+        raise ValueError(f"sam_rho must be a number or None, not {sam_rho!r}") from None
+    if not (math.isfinite(r) and r > 0.0):
+        raise ValueError(f"sam_rho must be finite and > 0 as float32, not {sam_rho!r}")
+    return float(sam_rho)
+
+
 def check_lr_schedule(lr_schedule) -> None:
     """``TypeError`` unless ``lr_schedule`` is None or an ``LrSchedule``.  Host code, for ``Trainer`` and ``harness.fit`` alike."""
     if lr_schedule is not None and not isinstance(lr_schedule, LrSchedule):
@@ -284,7 +299,32 @@ class Trainer:
     ``distill_alpha`` (0.5) and ``distill_temperature`` (2.0) are checked on the host (``ValueError``) and used only when
     teacher logits are given.  The teacher logits must be finite; with ``mix=`` the teacher is expected to have seen the blended
     batch.  Not with ``micro_batches`` > 1 (``ValueError``).  Without ``teacher_logits`` a step issues exactly the launches it
-    always has."""
+    always has.
+
+    ``enable_sam(sam_rho, sam_adaptive=False)`` (a method, called once behind the constructor, whose signature is what it always
+    was; ``sam_rho`` finite and > 0 as float32, checked on the host; ``harness.fit_sam`` calls it): sharpness-aware minimisation
+    (Foret et al. 2021; ``sam_adaptive``: its scale-invariant form ASAM, Kwon et al. 2021), with the formulas of the widely used torch
+    SAM optimiser (``adaptive=True``, no ``eta``).  On the trainable range ``[n_frozen, n)`` of the flat buckets a step then is:
+    prologue, forward and backward as always (gradient ``g`` at the weights ``w``); the all-reduce of ``g``, if the trainer has one,
+    so that the perturbation is that of the global batch and every rank holds the same weights in the second pass (per-rank
+    perturbations, "m-sharpness", are not built); the norm ``s = sqrt(sum g^2)`` (``ss_sumsq_f32``) or ``sqrt(sum (|w| g)^2)``
+    (``ss_sumsq_absw_f32``); ONE ``ss_sam_perturb`` launch: ``backup = w``, ``w += e``, ``g = 0`` with ``e = sam_rho * g / (s +
+    1e-12)`` or ``sam_rho * w^2 * g / (s + 1e-12)``, which also clears the second pass's loss sum and hit count (``sam_scal``,
+    ``sam_correct``: no zeroing launch between the passes); a second forward and backward at ``w + e`` on the same batch with the
+    same ``engine.Loss`` (labels, smoothing, class weights and their normaliser, ``mix=``, ``teacher_logits=``) and the same
+    dropout seed -- both gradients belong to the same sub-network, and the seed stays a pure function of the step count, so a
+    resumed run reproduces it; the all-reduce of the new gradient ``g'``; ONE ``ss_sam_restore_sumsq`` launch in the place of
+    ``ss_sumsq_f32``: ``w = backup`` bit for bit and ``sum g'^2`` for the clip; and the clip + Adam launch the trainer would use
+    anyway (``ss_adam_clip``, ``_ema``, ``ss_adamw_clip_groups``) on ``(w, g')``: the weight average, groups and schedules need
+    nothing new.  The step returns the loss and the hits of the FIRST pass -- the loss at the unperturbed weights, which a run
+    without SAM logs; ``grad_norm()`` reports the norm of ``g'``, the one that is clipped.  An empty shard skips both passes and
+    joins both all-reduces, the perturb, the restore and Adam.  Works through ``step`` and ``step_embedded`` (``freeze_cnn``: on
+    ``[n_cnn, n)``) and on both engines.  On the bf16 engine the weights reach the MFMAs rounded to bf16, so a perturbation below
+    bf16 resolution of a weight (``|e| < 2^-9 |w|``) vanishes in the operands: a property of the method at this precision, not a
+    defect; the f32 parts (biases, LayerNorm, the head) see all of it.  Costs one more bucket-sized f32 buffer (``backup``: scratch,
+    not saved) and about a second forward and backward per step.  With ``micro_batches`` > 1 ``enable_sam`` is a ``ValueError``.  ``state_dict()``
+    gains ``sam_rho`` and ``sam_adaptive`` only with SAM, and ``load_state_dict`` raises ``ValueError`` when the two sides
+    disagree.  Without ``enable_sam`` a step issues exactly the launches it always has."""
 
     # CUs left to the other micro-batch's recurrence while a persistent ROI-CNN kernel runs (2 directions x 8 slices)
     CNN_RESERVED_CUS = 32
@@ -332,6 +372,8 @@ class Trainer:
         # [loss_sum, sumsq] fp32 and [correct] int32 live on the device
         self.scal = torch.zeros(2, device=dev, dtype=torch.float32)
         self.correct = torch.zeros(1, device=dev, dtype=torch.int32)
+        # sharpness-aware minimisation: off until enable_sam(), which allocates what it needs
+        self.sam_rho, self.sam_adaptive, self.backup, self.sam_scal, self.sam_correct = None, False, None, None, None
         # class weights (uploaded once) and the step's normaliser, sum of w[y] over the global batch: both stay on the device
         self.cw = None if cw is None else torch.from_numpy(cw).to(dev)
         self.den = None if cw is None else torch.zeros(1, device=dev, dtype=torch.float32)
@@ -353,6 +395,24 @@ class Trainer:
         self.ev_start = torch.cuda.Event()
         self.ev_done = [torch.cuda.Event() for _ in self.streams]
 
+    def enable_sam(self, rho, adaptive: bool = False) -> None:
+        """Switch sharpness-aware minimisation on for every following step (class docstring): ``rho`` finite and > 0 as float32,
+        ``adaptive`` for ASAM.  The refusals -- a bad ``rho``, ``micro_batches`` > 1 -- are host code and come before anything
+        touches a device.  Allocates, once, the bucket-sized ``backup``, the second pass's loss sum and hit count, and a third
+        float behind ``[loss_sum, sumsq]`` for the first gradient's sum of squares; a second call only changes the two settings."""
+        rho = check_sam_rho(rho)
+        if rho is None:
+            raise ValueError("sam_rho must be a number: a Trainer without enable_sam() is the one without SAM")
+        if self.micro_batches > 1:
+            raise ValueError("sam_rho does not combine with micro_batches > 1")
+        if self.backup is None:
+            flat = self.model.flat_params
+            self.scal = torch.zeros(3, device=flat.device, dtype=torch.float32)
+            self.backup = torch.empty_like(flat)
+            self.sam_scal = torch.zeros(1, device=flat.device, dtype=torch.float32)
+            self.sam_correct = torch.zeros(1, device=flat.device, dtype=torch.int32)
+        self.sam_rho, self.sam_adaptive = rho, bool(adaptive)
+
     def _bind_bucket(self):
         """(Re)resolve everything that aliases the model's flat buckets.  ``model.to()/.cuda()/.float()`` keep the bucket
         when nothing moves; when they do re-allocate it (``model._bucket_version`` moves) the gradient views are taken
@@ -367,6 +427,9 @@ class Trainer:
             if self.ema is not None:
                 self.ema = self.ema.to(flat.device)
             self.scal, self.correct = self.scal.to(flat.device), self.correct.to(flat.device)
+            if self.backup is not None:
+                self.backup, self.sam_scal = self.backup.to(flat.device), self.sam_scal.to(flat.device)
+                self.sam_correct = self.sam_correct.to(flat.device)
             if self.cw is not None:
                 self.cw, self.den = self.cw.to(flat.device), self.den.to(flat.device)
         self.G = model._views_of(model.flat_grads)
@@ -432,7 +495,7 @@ class Trainer:
         lo, grads = self.n_frozen, model.flat_grads  # (the trainable range [n_frozen, n): all of the bucket unless the CNN is frozen)
         fused = may_fuse and B > 0 and lengths.dtype == torch.int64 and lengths.is_cuda and lengths.is_contiguous()
         if fused:
-            L.call("ss_train_prologue", grads.data_ptr() + 4 * lo, grads.numel() - lo, self.scal.data_ptr(), 2,
+            L.call("ss_train_prologue", grads.data_ptr() + 4 * lo, grads.numel() - lo, self.scal.data_ptr(), self.scal.numel(),
                    self.correct.data_ptr(), lengths.data_ptr(), *prologue_args(*batch), L.stream())
         else:
             (grads[lo:] if lo else grads).zero_()
@@ -442,6 +505,11 @@ class Trainer:
         self.loss = E.Loss(y, self.ls, denom, self.scal, self.correct, cw, den, *labels_soft)
         if B > 0:  # (an empty shard: this rank's gradient is the zero bucket)
             fwd_bwd(self.loss, train, seed, fused, lengths, *batch)
+        if self.sam_rho is not None:
+            self._sam_ascend()
+            if B > 0:  # the same batch, loss description and dropout seed at w + e; its loss and hits go to scalars of their own
+                fwd_bwd(dataclasses.replace(self.loss, loss_sum=self.sam_scal, correct=self.sam_correct), train, seed, fused, lengths,
+                        *batch)
         self._reduce_clip_adam()
         return self.scal[0], self.correct[0]
 
@@ -526,11 +594,24 @@ class Trainer:
             return self.cw, self.den
         return None, None
 
-    def _reduce_clip_adam(self):
-        """Behind backward: the gradient all-reduce, the global norm, clip + Adam (+ the weight average), each on elements
-        ``[n_frozen, n)`` of the flat buckets -- all of them unless the ROI CNN is frozen."""
+    def _sam_ascend(self):
+        """SAM, behind the first backward: the all-reduce of ``g``, its norm into ``scal[2]`` (zeroed with the other two), and the
+        launch that saves ``w``, moves it to ``w + e``, clears ``g`` and the second pass's scalars -- on ``[n_frozen, n)``."""
         model, s, lo = self.model, L.stream(), self.n_frozen
-        grads = model.flat_grads if lo == 0 else model.flat_grads[lo:]
+        self._allreduce_grads()
+        n_el, at = model.flat_grads.numel() - lo, 4 * lo
+        w, g, norm = model.flat_params.data_ptr() + at, model.flat_grads.data_ptr() + at, self.scal.data_ptr() + 8
+        if self.sam_adaptive:
+            L.call("ss_sumsq_absw_f32", w, g, n_el, norm, s)
+        else:
+            L.call("ss_sumsq_f32", g, n_el, norm, s)
+        L.call("ss_sam_perturb", w, g, self.backup.data_ptr() + at, n_el, norm, 1.0, self.sam_rho, int(self.sam_adaptive),
+               self.sam_scal.data_ptr(), 1, self.sam_correct.data_ptr(), 1, s)
+
+    def _allreduce_grads(self):
+        """The all-reduce of the trainable range of the gradient bucket, if this trainer has one."""
+        lo = self.n_frozen
+        grads = self.model.flat_grads if lo == 0 else self.model.flat_grads[lo:]
         if self.world > 1 or self.always_allreduce:
             if self.allreduce_events is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -539,9 +620,20 @@ class Trainer:
             if self.allreduce_events is not None:
                 e1.record()
                 self.allreduce_events.append((e0, e1))
+
+    def _reduce_clip_adam(self):
+        """Behind backward: the gradient all-reduce, the global norm, clip + Adam (+ the weight average), each on elements
+        ``[n_frozen, n)`` of the flat buckets -- all of them unless the ROI CNN is frozen.  SAM: the norm's launch also puts the
+        weights back."""
+        model, s, lo = self.model, L.stream(), self.n_frozen
+        self._allreduce_grads()
         n_el, at = model.flat_grads.numel() - lo, 4 * lo
         sumsq = self.scal.data_ptr() + 4
-        L.call("ss_sumsq_f32", model.flat_grads.data_ptr() + at, n_el, sumsq, s)
+        if self.sam_rho is None:
+            L.call("ss_sumsq_f32", model.flat_grads.data_ptr() + at, n_el, sumsq, s)
+        else:
+            L.call("ss_sam_restore_sumsq", model.flat_params.data_ptr() + at, self.backup.data_ptr() + at,
+                   model.flat_grads.data_ptr() + at, n_el, sumsq, s)
         # d_logits already carries 1/(B*world), so the summed bucket IS the global-mean gradient
         lr = self.lr if self.lr_schedule is None and self.lr_scale == 1.0 else self.current_lr()
         grouped, averaged = self.table is not None, self.ema is not None
@@ -634,6 +726,8 @@ class Trainer:
         if self.table is not None or self.lr_schedule is not None or self.lr_scale != 1.0:  # (keys of trainers that use them only)
             extra.update(weight_decay=float(self.weight_decay), param_groups=None if self.table is None else self.table.plain(),
                          lr_schedule=None if self.lr_schedule is None else self.lr_schedule.plain(), lr_scale=float(self.lr_scale))
+        if self.sam_rho is not None:  # (the backup is scratch: the weights are in the bucket whenever a state is taken)
+            extra.update(sam_rho=float(self.sam_rho), sam_adaptive=bool(self.sam_adaptive))
         return dict(m=self.m.detach().clone(), v=self.v.detach().clone(), ema=None if self.ema is None else self.ema.detach().clone(),
                     step_count=int(self.step_count), ema_decay=self.ema_decay, ema_warmup=bool(self.ema_warmup),
                     betas=[float(b) for b in self.betas], eps=float(self.eps), lr=float(self.lr), max_norm=float(self.max_norm),
@@ -642,8 +736,8 @@ class Trainer:
     def load_state_dict(self, state: dict) -> None:
         """Take over a ``state_dict()``: the tensors are copied into this trainer's device buffers (nothing is re-allocated), the
         step count and the hyperparameters are set.  ``ValueError`` when the bucket has another element count, when one side
-        keeps a weight average and the other does not, when one side freezes the ROI CNN and the other does not, or when the
-        segment tables (groups, scales, decays) differ."""
+        keeps a weight average and the other does not, when one side freezes the ROI CNN and the other does not, when the
+        segment tables (groups, scales, decays) differ, or when the two sides disagree about ``sam_rho`` / ``sam_adaptive``."""
         if self._ema_swapped:
             raise RuntimeError("Trainer.load_state_dict inside ema_weights()")
         if self.model._bucket_version != self._bucket_version:
@@ -658,6 +752,10 @@ class Trainer:
         if saved_table != table:
             raise ValueError("the saved trainer state and this Trainer disagree about weight_decay / param_groups: "
                              f"saved table {saved_table!r}, this one {table!r}")
+        saved_sam = (state.get("sam_rho"), bool(state.get("sam_adaptive", False)))
+        if saved_sam != (self.sam_rho, self.sam_adaptive):
+            raise ValueError("the saved trainer state and this Trainer disagree about sam_rho / sam_adaptive: "
+                             f"saved {saved_sam!r}, this one {(self.sam_rho, self.sam_adaptive)!r}")
         if (state["ema"] is None) != (self.ema is None):
             raise ValueError("the saved trainer state and this Trainer disagree about ema_decay: "
                              f"saved {state['ema_decay']!r}, this one {self.ema_decay!r}")
@@ -686,5 +784,6 @@ class Trainer:
             E.backward(P, self.G, cfg, ws, X, R, ws.d_logits, train=train, seed=seed)
 
     def grad_norm(self) -> torch.Tensor:
-        """Global L2 norm of the last step's (pre-clip) gradient (``freeze_cnn``: of the trainable parameters')."""
+        """Global L2 norm of the last step's (pre-clip) gradient (``freeze_cnn``: of the trainable parameters'; SAM: of the second
+        pass's gradient, the one that is clipped)."""
         return self.scal[1].sqrt()
