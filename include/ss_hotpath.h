@@ -859,6 +859,40 @@ int ss_adamw_clip_groups(float* p, const float* g, float* m, float* v, float* em
                          const long* seg_end, const int* seg_group, int n_seg, const float* group_lr_scale,
                          const float* group_weight_decay, int n_groups, ss_stream_t stream);
 
+/* LAMB (You et al., "Large Batch Optimization for Deep Learning", ICLR 2020) on a flat bucket: the Adam direction plus the weight
+ * decay, rescaled per segment -- one parameter tensor -- by |w| / |update|.  Bias correction on, the decay inside u (not decoupled
+ * as in ss_adamw_clip_groups), no clamp on |w|, no eta, no clipping of the ratio.  The segment arrays are ss_adamw_clip_groups'
+ * (HOST arrays, read during the call, handed to the kernels by value, nothing kept), with one more: seg_adapt[n_seg], nonzero where
+ * the segment takes its trust ratio, 0 where it takes r = 1 (biases, LayerNorm).  With coef, inv_sqrt_bc2 as ss_adam_clip takes
+ * them, bc1 = float(1 / (1 - double(beta1)^step)) and, for segment s of group G, wd_s = group_weight_decay[G] and
+ * lr_s = float(double(lr) * double(group_lr_scale[G])):
+ *     g'   = g * coef;   m = beta1 m + (1 - beta1) g';   v = beta2 v + (1 - beta2) g' g'       (ss_adam_clip's m and v, bit for bit)
+ *     quot = m / (sqrt(v) * inv_sqrt_bc2 + eps)
+ *     u    = fmaf(wd_s, p, bc1 * quot)                        (the product bc1 * quot rounded to f32 on its own)
+ *     P_s  = sum p^2,  U_s = sum u^2 over the segment         (f32 squares, each widened, summed in float64 in one fixed order)
+ *     r_s  = seg_adapt[s] && P_s > 0 && U_s > 0 ? float(sqrt(P_s / U_s)) : 1
+ *     p    = p - (lr_s * r_s) * u                              (lr_s * r_s: one f32 product per segment);  ema as ss_adam_clip_ema's
+ *
+ * ss_lamb_moments: two launches.  The first streams g, m, v, p once, writes m and v, and leaves the float64 sums of p^2 and u^2 of
+ * every (segment, workgroup) in scratch (ss_lamb_scratch_bytes(n, n_seg) bytes, 8-byte aligned; it need not be cleared and is
+ * scratch again when the call's work is done).  The second adds each segment's partials in workgroup order and writes
+ * norms[2 s] = float(sqrt(P_s)), norms[2 s + 1] = float(sqrt(U_s)) and ratio[s] (n_seg floats), all on the device.  No atomics: two
+ * calls on the same inputs write the same bits.  p is only read.
+ * ss_lamb_apply: one launch.  Recomputes u from the stored m, v and p -- the same expression, the same bits -- reads ratio[s] once
+ * per segment and writes p and, when ema != NULL, ema (0 <= ema_decay < 1; ema must not overlap p).  It needs beta2 for
+ * inv_sqrt_bc2.  seg_adapt is checked and otherwise unused here (the ratios already hold it): it is taken so that both entry points
+ * are handed one and the same table.
+ * p, g, m, v, ema 16-byte aligned; scales, decays and lr finite and >= 0; step >= 1; n_seg in 1..64, n_groups in 1..8; every
+ * segment end but the last a multiple of 4, the last n.  SS_ERR_ARG otherwise, before any launch: nothing is written. */
+int ss_lamb_scratch_bytes(long n, int n_seg, long* bytes);
+int ss_lamb_moments(const float* p, const float* g, float* m, float* v, long n, const float* sumsq, float grad_scale, float max_norm,
+                    float beta1, float beta2, float eps, int step, const long* seg_end, const int* seg_group, int n_seg,
+                    const float* group_lr_scale, const float* group_weight_decay, int n_groups, const int* seg_adapt, double* scratch,
+                    float* norms, float* ratio, ss_stream_t stream);
+int ss_lamb_apply(float* p, const float* m, const float* v, float* ema, long n, float beta1, float beta2, float eps, int step,
+                  float ema_decay, float lr, const long* seg_end, const int* seg_group, int n_seg, const float* group_lr_scale,
+                  const float* group_weight_decay, int n_groups, const int* seg_adapt, const float* ratio, ss_stream_t stream);
+
 /* Sharpness-aware minimisation (Foret et al. 2021; adaptive: ASAM, Kwon et al. 2021) on a flat bucket, as the widely used torch
  * SAM optimiser computes it (adaptive=True, no eta): three streams around the second forward and backward of a step.
  *

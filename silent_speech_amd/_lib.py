@@ -135,6 +135,10 @@ SIGNATURES = {
     "ss_adam_clip_ema": [_vp, _vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _vp],
     # (seg_end, seg_group, group_lr_scale, group_weight_decay: HOST arrays -- ``SegmentTable.ptrs``)
     "ss_adamw_clip_groups": [_vp, _vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _i, _vp, _vp, _i, _vp],
+    # (the four host arrays of ss_adamw_clip_groups and seg_adapt, a fifth -- ``LambTable.args``)
+    "ss_lamb_scratch_bytes": [_l, _i, _vp],
+    "ss_lamb_moments": [_vp, _vp, _vp, _vp, _l, _vp, _f, _f, _f, _f, _f, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "ss_lamb_apply": [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _i, _f, _f, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "ss_sumsq_absw_f32": [_vp, _vp, _l, _vp, _vp],
     "ss_sam_perturb": [_vp, _vp, _vp, _l, _vp, _f, _f, _i, _vp, _i, _vp, _i, _vp],
     "ss_sam_restore_sumsq": [_vp, _vp, _vp, _l, _vp, _vp],

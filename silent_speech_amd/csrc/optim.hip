@@ -1,5 +1,6 @@
 // Flat-bucket optimiser step: the gradient's sum of squares, the global-norm clip folded into Adam (plain, with the weight average,
-// and grouped AdamW), the swap of two buckets, and the two streams of a sharpness-aware step (perturb; restore + sum of squares).
+// and grouped AdamW), the swap of two buckets, the two streams of a sharpness-aware step (perturb; restore + sum of squares), and
+// the layer-wise adaptive step LAMB (moments + per-segment norms; apply).
 // Replaces clip_grad_norm_ + torch.optim.Adam.step of train_model_official.py:403, 438-439.  All HBM-bound, grid-stride; every
 // kernel but adam_clip_kernel in 16-byte lanes.
 #include <math.h>
@@ -275,6 +276,196 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(AdamParams a, AdamwSe
     adam_update_at<true, EMA, float>(b, coef, decay, ema, d, omd, (a.n & ~3L) + threadIdx.x);
 }
 
+// LAMB (You et al. 2020): the Adam direction plus the weight decay, rescaled per segment (one parameter tensor) by |w| / |u|.  Two
+// streams with a small reduction between them, on the walk of adamw_groups_kernel (by-value table, wave-uniform segment loop,
+// first_block dealing, the n & 3 last elements by block 0 in the last segment):
+//   lamb_moments_kernel  reads g, m, v, p; writes m, v (adam_clip_moments: the bits of adam_clip_kernel); forms u and leaves the
+//                        float64 sums of p^2 and u^2 of every (segment, workgroup) that holds quads of the segment in `scratch`
+//   lamb_norms_kernel    one workgroup per segment adds those partials up in a fixed order -> sqrt P, sqrt U and the trust ratio
+//   lamb_apply_kernel    recomputes u from the stored m, v, p (lamb_direction again: the same bits) and takes p -= (lr_s r_s) u
+// Nothing is added with atomics: every sum below has one order, whatever the schedule, so two runs give the same bits.
+struct LambSegments {
+  long end[ADAMW_MAX_SEGMENTS];  // as AdamwSegments
+  float wd[ADAMW_MAX_SEGMENTS], lr[ADAMW_MAX_SEGMENTS];
+  int first_block[ADAMW_MAX_SEGMENTS];
+  int n_seg;
+};
+
+// u = wd p + bc1 m / (sqrt(v) inv_sqrt_bc2 + eps): the quotient is adam_clip_moments' expression on the same operands, the product
+// bc1 * quot is rounded on its own and then fused into the sum
+__device__ __forceinline__ float lamb_direction(const AdamParams& a, float bc1, float wd, float p, float m, float v) {
+  const float denom = sqrtf(v) * a.inv_sqrt_bc2 + a.eps;
+  return fmaf(wd, p, __fmul_rn(bc1, m / denom));
+}
+
+// The workgroup's piece of segment s (the 256-quad pieces of a segment are dealt round the grid from first_block[s] on), and
+// whether the workgroup adds anything to the segment's sums: it holds quads of it, or it is block 0 with the n & 3 last elements
+__device__ __forceinline__ int lamb_piece(const LambSegments& t, int s, int block, int blocks) {
+  const int piece = block - t.first_block[s];
+  return piece < 0 ? piece + blocks : piece;
+}
+__device__ __forceinline__ bool lamb_contributes(const LambSegments& t, int s, int block, int blocks, long n) {
+  const long q0 = s ? t.end[s - 1] >> 2 : 0, q1 = t.end[s] >> 2;
+  return q0 + (long)lamb_piece(t, s, block, blocks) * 256 < q1 || (block == 0 && s == t.n_seg - 1 && (n & 3));
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {  // (a butterfly: every lane ends with the same bits)
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Moments and squares of item i: T = f32x4 (quad i) or float (element i).  The squares are f32 products, widened, added in f64.
+template <class T>
+__device__ __forceinline__ void lamb_moments_at(const AdamParams& a, float coef, float bc1, float wd, long i, double& sum_p, double& sum_u);
+template <>
+__device__ __forceinline__ void lamb_moments_at<float>(const AdamParams& a, float coef, float bc1, float wd, long i, double& sum_p,
+                                                       double& sum_u) {
+  float m = a.m[i], v = a.v[i];
+  const float p = a.p[i];
+  adam_clip_moments(a, coef, a.g[i], m, v);
+  a.m[i] = m;
+  a.v[i] = v;
+  const float u = lamb_direction(a, bc1, wd, p, m, v);
+  sum_p += (double)__fmul_rn(p, p);
+  sum_u += (double)__fmul_rn(u, u);
+}
+template <>
+__device__ __forceinline__ void lamb_moments_at<f32x4>(const AdamParams& a, float coef, float bc1, float wd, long i, double& sum_p,
+                                                       double& sum_u) {
+  f32x4* mp = reinterpret_cast<f32x4*>(a.m) + i;
+  f32x4* vp = reinterpret_cast<f32x4*>(a.v) + i;
+  f32x4 m = *mp, v = *vp;
+  const f32x4 g = reinterpret_cast<const f32x4*>(a.g)[i], p = reinterpret_cast<const f32x4*>(a.p)[i];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    float mk = m[k], vk = v[k];
+    adam_clip_moments(a, coef, g[k], mk, vk);
+    m[k] = mk; v[k] = vk;
+  }
+  *mp = m;
+  *vp = v;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float u = lamb_direction(a, bc1, wd, p[k], m[k], v[k]);
+    sum_p += (double)__fmul_rn(p[k], p[k]);
+    sum_u += (double)__fmul_rn(u, u);
+  }
+}
+
+// scratch[(s * gridDim.x + block) * 2 + {0, 1}] = the workgroup's sums of p^2 and u^2 over segment s, written only where
+// lamb_contributes (a condition on the block, the same in all its lanes): a thread's items in ascending order, the butterfly over
+// the wave, the four waves in order.  red is used in turns (`turn` counts this workgroup's reductions), so one barrier per
+// reduction separates thread 0's reads from the next writes to the same half.
+__global__ __launch_bounds__(256) void lamb_moments_kernel(AdamParams a, LambSegments t, float bc1, double* __restrict__ scratch) {
+  __shared__ double red[2][4][2];
+  const float coef = adam_clip_coef(a);
+  const bool tail = blockIdx.x == 0 && (a.n & 3);
+  int turn = 0;
+  long q0 = 0;
+  for (int s = 0; s < t.n_seg; ++s) {
+    const long q1 = t.end[s] >> 2;
+    const float wd = t.wd[s];
+    const long first = q0 + (long)lamb_piece(t, s, blockIdx.x, gridDim.x) * 256;
+    const bool last = s == t.n_seg - 1;
+    if (first < q1 || (last && tail)) {
+      double sum_p = 0.0, sum_u = 0.0;
+      for (long q = first + threadIdx.x; q < q1; q += (long)gridDim.x * 256) lamb_moments_at<f32x4>(a, coef, bc1, wd, q, sum_p, sum_u);
+      if (last && tail && (long)threadIdx.x < (a.n & 3)) lamb_moments_at<float>(a, coef, bc1, wd, (a.n & ~3L) + threadIdx.x, sum_p, sum_u);
+      sum_p = wave_sum_f64(sum_p);
+      sum_u = wave_sum_f64(sum_u);
+      if ((threadIdx.x & 63) == 0) {
+        red[turn][threadIdx.x >> 6][0] = sum_p;
+        red[turn][threadIdx.x >> 6][1] = sum_u;
+      }
+      __syncthreads();
+      if (threadIdx.x < 2)
+        scratch[((long)s * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
+            ((red[turn][0][threadIdx.x] + red[turn][1][threadIdx.x]) + red[turn][2][threadIdx.x]) + red[turn][3][threadIdx.x];
+      turn ^= 1;
+    }
+    q0 = q1;
+  }
+}
+
+// Workgroup s: the partials of segment s in workgroup order -- thread t takes the workgroups t, t + 256, ... in ascending order,
+// then the butterfly and the four waves as above -- and norms[2 s] = sqrt P, norms[2 s + 1] = sqrt U, ratio[s] = sqrt(P / U) where
+// the segment adapts (bit s of `adapt`) and both sums are positive, else 1.  `blocks`: the grid of lamb_moments_kernel.
+__global__ __launch_bounds__(256) void lamb_norms_kernel(LambSegments t, long n, int blocks, unsigned long long adapt,
+                                                         const double* __restrict__ scratch, float* __restrict__ norms,
+                                                         float* __restrict__ ratio) {
+  __shared__ double red[4][2];
+  const int s = blockIdx.x;
+  double sum_p = 0.0, sum_u = 0.0;
+  for (int b = threadIdx.x; b < blocks; b += 256)
+    if (lamb_contributes(t, s, b, blocks, n)) {
+      sum_p += scratch[((long)s * blocks + b) * 2];
+      sum_u += scratch[((long)s * blocks + b) * 2 + 1];
+    }
+  sum_p = wave_sum_f64(sum_p);
+  sum_u = wave_sum_f64(sum_u);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6][0] = sum_p;
+    red[threadIdx.x >> 6][1] = sum_u;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double P = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0], U = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+    norms[2 * s] = (float)sqrt(P);
+    norms[2 * s + 1] = (float)sqrt(U);
+    ratio[s] = ((adapt >> s) & 1) && P > 0.0 && U > 0.0 ? (float)sqrt(P / U) : 1.0f;
+  }
+}
+
+// Load p, m, v (and the average) of item i, take p -= step u with u = lamb_direction, store p (and the average: ema_elem).
+template <bool EMA, class T>
+__device__ __forceinline__ void lamb_apply_at(const AdamParams& a, float bc1, float wd, float step, float* ema, float d, float omd, long i);
+template <bool EMA>
+__device__ __forceinline__ float lamb_apply_elem(const AdamParams& a, float bc1, float wd, float step, float d, float omd, float p,
+                                                 float m, float v, float& e) {
+  p = p - step * lamb_direction(a, bc1, wd, p, m, v);
+  if (EMA) e = ema_elem(d, omd, e, p);
+  return p;
+}
+template <bool EMA, class T>
+__device__ __forceinline__ void lamb_apply_at(const AdamParams& a, float bc1, float wd, float step, float* ema, float d, float omd, long i) {
+  T* pp = reinterpret_cast<T*>(a.p) + i;
+  T* ep = reinterpret_cast<T*>(ema) + i;
+  T p = *pp, e = {};
+  const T m = reinterpret_cast<const T*>(a.m)[i], v = reinterpret_cast<const T*>(a.v)[i];
+  if (EMA) e = *ep;
+  if constexpr (sizeof(T) == sizeof(float)) {
+    p = lamb_apply_elem<EMA>(a, bc1, wd, step, d, omd, p, m, v, e);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float ek = e[k];
+      p[k] = lamb_apply_elem<EMA>(a, bc1, wd, step, d, omd, p[k], m[k], v[k], ek);
+      e[k] = ek;
+    }
+  }
+  *pp = p;
+  if (EMA) *ep = e;
+}
+
+// ratio[s] is read once per segment, with the loop counter: a scalar load, as the table's entries are
+template <bool EMA>
+__global__ __launch_bounds__(256) void lamb_apply_kernel(AdamParams a, LambSegments t, float bc1, const float* __restrict__ ratio,
+                                                         float* ema, float d, float omd) {
+  float wd = 0.0f, step = 0.0f;
+  long q0 = 0;
+  for (int s = 0; s < t.n_seg; ++s) {
+    const long q1 = t.end[s] >> 2;
+    wd = t.wd[s];
+    step = __fmul_rn(t.lr[s], ratio[s]);
+    for (long q = q0 + (long)lamb_piece(t, s, blockIdx.x, gridDim.x) * 256 + threadIdx.x; q < q1; q += (long)gridDim.x * 256)
+      lamb_apply_at<EMA, f32x4>(a, bc1, wd, step, ema, d, omd, q);
+    q0 = q1;
+  }
+  if (blockIdx.x == 0 && (long)threadIdx.x < (a.n & 3))  // (in the last segment: wd and step still are that segment's)
+    lamb_apply_at<EMA, float>(a, bc1, wd, step, ema, d, omd, (a.n & ~3L) + threadIdx.x);
+}
+
 // a <-> b, two disjoint 16-byte aligned buffers of n floats: 16-byte lanes, the n & 3 last elements by block 0
 __global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
   const long n4 = n >> 2;
@@ -406,6 +597,92 @@ extern "C" int ss_adamw_clip_groups(float* p, const float* g, float* m, float* v
   else
     hipLaunchKernelGGL(adamw_groups_kernel<false>, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, t, ema,
                        0.0f, 1.0f);
+  return ss_launch_status();
+}
+
+// The table of the two LAMB entry points from the host arrays, checked as ss_adamw_clip_groups checks its own.  blocks: the grid the
+// pieces are dealt round (both launches of ss_lamb_moments use one grid; ss_lamb_apply's is the same function of n).
+static int lamb_grid(long n) { return ss_flat_grid(n >> 2, 2048); }
+
+static int lamb_table(LambSegments& t, unsigned long long& adapt, long n, float lr, const long* seg_end, const int* seg_group, int n_seg,
+                      const float* group_lr_scale, const float* group_weight_decay, int n_groups, const int* seg_adapt) {
+  SS_REQUIRE(seg_end && seg_group && group_lr_scale && group_weight_decay && seg_adapt, SS_ERR_ARG);
+  SS_REQUIRE(n_seg >= 1 && n_seg <= ADAMW_MAX_SEGMENTS && n_groups >= 1 && n_groups <= ADAMW_MAX_GROUPS, SS_ERR_ARG);
+  SS_REQUIRE(lr >= 0.0f && isfinite(lr), SS_ERR_ARG);
+  for (int G = 0; G < n_groups; ++G)  // (a NaN fails >=, an infinity isfinite)
+    SS_REQUIRE(group_lr_scale[G] >= 0.0f && isfinite(group_lr_scale[G]) && group_weight_decay[G] >= 0.0f &&
+                   isfinite(group_weight_decay[G]), SS_ERR_ARG);
+  const int blocks = lamb_grid(n);
+  long lo = 0, pieces = 0;
+  adapt = 0;
+  for (int s = 0; s < ADAMW_MAX_SEGMENTS; ++s) {
+    if (s >= n_seg) {  // (unused entries: defined values, never read)
+      t.end[s] = n; t.wd[s] = 0.0f; t.lr[s] = 0.0f; t.first_block[s] = 0;
+      continue;
+    }
+    const long hi = seg_end[s];
+    const int G = seg_group[s];
+    SS_REQUIRE(hi > lo && hi <= n && (s == n_seg - 1 ? hi == n : (hi & 3) == 0) && G >= 0 && G < n_groups, SS_ERR_ARG);
+    t.end[s] = hi;
+    t.wd[s] = group_weight_decay[G];
+    t.lr[s] = (float)((double)lr * (double)group_lr_scale[G]);
+    t.first_block[s] = (int)(pieces % blocks);
+    if (seg_adapt[s]) adapt |= 1ull << s;
+    pieces += ((hi >> 2) - (lo >> 2) + 255) / 256;
+    lo = hi;
+  }
+  t.n_seg = n_seg;
+  return SS_OK;
+}
+
+static float lamb_bc1(float beta1, int step) { return (float)(1.0 / (1.0 - pow((double)beta1, step))); }
+
+extern "C" int ss_lamb_scratch_bytes(long n, int n_seg, long* bytes) {
+  SS_REQUIRE(bytes && n > 0 && n_seg >= 1 && n_seg <= ADAMW_MAX_SEGMENTS, SS_ERR_ARG);
+  *bytes = (long)n_seg * lamb_grid(n) * 2 * (long)sizeof(double);
+  return SS_OK;
+}
+
+extern "C" int ss_lamb_moments(const float* p, const float* g, float* m, float* v, long n, const float* sumsq, float grad_scale,
+                               float max_norm, float beta1, float beta2, float eps, int step, const long* seg_end,
+                               const int* seg_group, int n_seg, const float* group_lr_scale, const float* group_weight_decay,
+                               int n_groups, const int* seg_adapt, double* scratch, float* norms, float* ratio, ss_stream_t stream) {
+  if (const int bad = adam_check(p, g, m, v, sumsq, n, step, true, nullptr, 0.0f)) return bad;
+  SS_REQUIRE(scratch && norms && ratio && (reinterpret_cast<uintptr_t>(scratch) & 7) == 0, SS_ERR_ARG);
+  LambSegments t;
+  unsigned long long adapt;
+  if (const int bad = lamb_table(t, adapt, n, 0.0f, seg_end, seg_group, n_seg, group_lr_scale, group_weight_decay, n_groups, seg_adapt))
+    return bad;
+  AdamParams a;
+  adam_params(a, const_cast<float*>(p), g, m, v, n, sumsq, grad_scale, max_norm, 0.0f, beta1, beta2, eps, step);
+  const int blocks = lamb_grid(n);
+  hipLaunchKernelGGL(lamb_moments_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a, t, lamb_bc1(beta1, step),
+                     scratch);
+  hipLaunchKernelGGL(lamb_norms_kernel, dim3(n_seg), dim3(256), 0, static_cast<hipStream_t>(stream), t, n, blocks, adapt, scratch, norms,
+                     ratio);
+  return ss_launch_status();
+}
+
+extern "C" int ss_lamb_apply(float* p, const float* m, const float* v, float* ema, long n, float beta1, float beta2, float eps, int step,
+                             float ema_decay, float lr, const long* seg_end, const int* seg_group, int n_seg,
+                             const float* group_lr_scale, const float* group_weight_decay, int n_groups, const int* seg_adapt,
+                             const float* ratio, ss_stream_t stream) {
+  // (adam_check's rules, with the ratios in the place of the gradient and its sum of squares: pointers it only tests for NULL)
+  if (const int bad = adam_check(p, ratio, m, v, ratio, n, step, false, ema, ema_decay)) return bad;
+  SS_REQUIRE(ss_aligned16(p, m, v, ema), SS_ERR_ARG);
+  LambSegments t;
+  unsigned long long adapt;
+  if (const int bad = lamb_table(t, adapt, n, lr, seg_end, seg_group, n_seg, group_lr_scale, group_weight_decay, n_groups, seg_adapt))
+    return bad;
+  AdamParams a;
+  adam_params(a, p, nullptr, const_cast<float*>(m), const_cast<float*>(v), n, nullptr, 1.0f, 1.0f, 0.0f, beta1, beta2, eps, step);
+  const float bc1 = lamb_bc1(beta1, step);
+  const dim3 grid(lamb_grid(n));
+  if (ema)
+    hipLaunchKernelGGL(lamb_apply_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a, t, bc1, ratio, ema, ema_decay,
+                       1.0f - ema_decay);
+  else
+    hipLaunchKernelGGL(lamb_apply_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a, t, bc1, ratio, ema, 0.0f, 1.0f);
   return ss_launch_status();
 }
 

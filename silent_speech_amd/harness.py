@@ -40,7 +40,7 @@ from .checkpoint import (TRAIN_STATE_FORMAT, add_calibration, fingerprint_differ
                          save_checkpoint, save_train_state)
 from .device_data import MASK_FIELDS, MIXUP_FIELDS, AugmentPolicy, DeviceClipStore
 from .model import BiGRUClassifier, ParamGroup
-from .train import (PlateauSchedule, Trainer, check_class_weights, check_distill, check_lr_schedule, check_sam_rho,
+from .train import (PlateauSchedule, Trainer, check_class_weights, check_distill, check_lamb_exclude, check_lr_schedule, check_sam_rho,
                     check_weight_decay, shard_range)
 
 VAL_FRAC, SEED, PATIENCE, EPOCHS, BATCH_SIZE = 0.15, 42, 12, 80, 16
@@ -482,7 +482,10 @@ def fit(clip_dir: str, out_path: str, epochs: int = EPOCHS, batch_size: int = BA
     ``distill_temperature`` only when ``distill_from`` is set; a resumed run must be given the same teacher.
 
     ``fit_sam(clip_dir, out_path, sam_rho, sam_adaptive=False, **fit_args)`` is this function with sharpness-aware minimisation
-    (SAM, or its scale-invariant form ASAM) in every training step; this signature is what it always was."""
+    (SAM, or its scale-invariant form ASAM) in every training step; this signature is what it always was.
+
+    ``fit_lamb(clip_dir, out_path, lamb_exclude=None, **fit_args)`` is this function with the layer-wise adaptive optimiser LAMB in
+    every training step; this signature is what it always was."""
     return _fit(None, False, **locals())
 
 
@@ -516,10 +519,42 @@ def fit_sam(clip_dir: str, out_path: str, sam_rho: float, sam_adaptive: bool = F
     return _fit(sam_rho, bool(sam_adaptive), **bound.arguments)
 
 
+def lamb_fingerprint(fingerprint: dict, lamb_exclude) -> dict:
+    """A run fingerprint for a ``fit_lamb`` run: with ``lamb`` and ``lamb_exclude`` (the patterns as a list), both only when
+    ``lamb_exclude`` is not None -- ``fit_lamb`` hands over the checked patterns, ``fit`` None -- so the fingerprints and state files
+    of runs without LAMB are what they always were, and a run with and one without cannot resume each other."""
+    if lamb_exclude is None:
+        return dict(fingerprint)
+    return dict(fingerprint, lamb=True, lamb_exclude=[str(p) for p in lamb_exclude])
+
+
+def fit_lamb(clip_dir: str, out_path: str, lamb_exclude=None, **fit_args) -> float:
+    """``fit(clip_dir, out_path, **fit_args)`` with the layer-wise adaptive optimiser LAMB in every training step
+    (``Trainer.enable_lamb(lamb_exclude)``): the Adam direction plus the weight decay, rescaled per parameter tensor by ``|w| /
+    |update|`` -- the usual tool when the global batch grows (``batch_size``, ``world_size``) and the learning rate should not be
+    retuned per layer by hand.  ``lamb_exclude``: name patterns with ``ParamGroup.match``'s semantics whose tensors take the ratio 1;
+    None: what ``no_decay()`` matches, the biases and the LayerNorm.  Bad patterns are a ``ValueError`` before anything touches a
+    device or the clips; ``fit_args`` are checked against ``fit``'s signature first (``TypeError`` for a name it does not have),
+    except ``sam_rho`` / ``sam_adaptive``, which switch SAM on as ``fit_sam`` does (its streams run in front of the optimiser).
+    Works under both plans and with everything ``fit`` takes: ``lr``, the schedules, ``weight_decay`` (inside the update here),
+    ``param_groups``, the weight average, ``freeze_cnn``, data parallel (the gradient is all-reduced before the optimiser, so every
+    rank computes the same ratios).  The per-epoch log line gains the smallest, the median and the largest trust ratio of the
+    epoch's last step over the tensors that adapt -- one read per epoch, behind the validation -- and ``history`` gets them as
+    ``trust_ratio``.  ``state_path``: the fingerprint holds ``lamb`` and ``lamb_exclude`` (``lamb_fingerprint``), so a resumed run
+    must be a ``fit_lamb`` run with the same exclusion; LAMB keeps no state beyond Adam's moments."""
+    lamb_exclude = check_lamb_exclude(lamb_exclude)
+    sam_rho = check_sam_rho(fit_args.pop("sam_rho", None))
+    sam_adaptive = bool(fit_args.pop("sam_adaptive", False))
+    bound = inspect.signature(fit).bind(clip_dir, out_path, **fit_args)
+    bound.apply_defaults()
+    return _fit(sam_rho, sam_adaptive, **bound.arguments, lamb_exclude=lamb_exclude)
+
+
 def _fit(sam_rho, sam_adaptive, clip_dir, out_path, epochs, batch_size, patience, max_t, lr, seed, use_roi_if_present, device, log, plan,
          rank, world_size, process_group, history, class_weights, augment_policy, ema_decay, state_path, resume, init_from, freeze_cnn,
-         weight_decay, param_groups, lr_schedule, lr_plateau, distill_from, distill_alpha, distill_temperature) -> float:
-    """The body of ``fit`` (its docstring) and ``fit_sam``; ``sam_rho`` None: no SAM."""
+         weight_decay, param_groups, lr_schedule, lr_plateau, distill_from, distill_alpha, distill_temperature,
+         lamb_exclude=None) -> float:
+    """The body of ``fit`` (its docstring), ``fit_sam`` and ``fit_lamb``; ``sam_rho`` None: no SAM; ``lamb_exclude`` None: no LAMB."""
     if distill_from is not None:  # (host code, before anything touches a device or the clips)
         distill_alpha, distill_temperature = check_distill(distill_alpha, distill_temperature)
         if not isinstance(distill_from, (str, os.PathLike, BiGRUClassifier)):
@@ -605,7 +640,7 @@ def _fit(sam_rho, sam_adaptive, clip_dir, out_path, epochs, batch_size, patience
                                       distill_from=None if distill_from is None else
                                       ("module" if module_teacher else file_sha256(distill_from)),
                                       distill_alpha=distill_alpha, distill_temperature=distill_temperature)
-        fingerprint = sam_fingerprint(fingerprint, sam_rho, sam_adaptive)
+        fingerprint = lamb_fingerprint(sam_fingerprint(fingerprint, sam_rho, sam_adaptive), lamb_exclude)
         if resume and os.path.exists(state_path):
             saved = load_train_state(state_path)
             field = fingerprint_difference(saved["fingerprint"], fingerprint)
@@ -645,6 +680,8 @@ def _fit(sam_rho, sam_adaptive, clip_dir, out_path, epochs, batch_size, patience
     trainer.rank = rank
     if sam_rho is not None:
         trainer.enable_sam(sam_rho, sam_adaptive)
+    if lamb_exclude is not None:
+        trainer.enable_lamb(lamb_exclude)
     teacher = None
     if distill_from is not None:
         teacher = distill_from if module_teacher else load_classifier(distill_from, device=device)[0]
@@ -720,10 +757,16 @@ def _fit(sam_rho, sam_adaptive, clip_dir, out_path, epochs, batch_size, patience
                 va_loss, va_acc, y_true, y_pred = evaluate(model, val_store, batch_size, plan=plan, class_weights=class_weights)
             confs = top_confusions(y_true, y_pred, info["id_to_label"], k=6)
         n = max(1, len(order))
+        trust = None
+        if lamb_exclude is not None:  # (one read per epoch, behind the validation's: the last step's ratios of the tensors that adapt)
+            r = trainer.trust_ratios()[torch.tensor(trainer.lamb.adapt, dtype=torch.bool, device=trainer.lamb_ratio.device)]
+            trust = tuple(torch.stack([r.min(), r.median(), r.max()]).tolist()) if r.numel() else (1.0, 1.0, 1.0)
         if history is not None:
             history.append(dict(epoch=ep, train_loss=float(tr_loss) / n, train_acc=int(tr_ok) / n, val_loss=va_loss, val_acc=va_acc,
-                                **({} if lr_schedule is None and plateau is None else {"lr": trainer.current_lr()})))
+                                **({} if lr_schedule is None and plateau is None else {"lr": trainer.current_lr()}),
+                                **({} if trust is None else {"trust_ratio": trust})))
         log(f"ep {ep:02d} | train loss {float(tr_loss) / n:.4f} acc {int(tr_ok) / n:.3f} | val loss {va_loss:.4f} acc {va_acc:.3f}"
+            + ("" if trust is None else f" | trust ratio min {trust[0]:.3g} med {trust[1]:.3g} max {trust[2]:.3g}")
             + ((" | top confusions: " + ", ".join(confs)) if confs else ""))
         if plateau is not None:  # (every rank holds the same reduced metrics: the same decision everywhere)
             if plateau.step(va_acc if plateau.mode == "max" else va_loss):

@@ -279,6 +279,25 @@ class BiGRUClassifier(nn.Module):
             raise ValueError(f"these groups cut the bucket into {len(ends)} segments: at most {MAX_SEGMENTS} fit one launch")
         return ends, ids, members
 
+    def param_tensor_segments(self, groups: Sequence[ParamGroup] = (), lo: int = 0):
+        """``param_segments`` without the merging: one segment per parameter tensor of ``[lo, n)`` -> ``(ends, ids, names)``, the
+        table of ``ss_lamb_moments`` / ``ss_lamb_apply`` (``Trainer.enable_lamb``), whose norms are taken per tensor.  The same
+        ends' rule (the alignment gap stays with the tensor in front of it: zeros that add nothing to a norm), the same group ids
+        and the same refusals; ``ValueError`` beyond ``MAX_SEGMENTS`` tensors.  Host code."""
+        self.param_segments(groups, lo)  # (its refusals)
+        groups = tuple(groups)
+        lay, total = self._layout()
+        ends, ids, names = [], [], []
+        for k, (name, off, n, shape) in enumerate(lay):
+            if off < lo:
+                continue
+            ends.append((lay[k + 1][1] if k + 1 < len(lay) else total) - lo)
+            ids.append(next((i for i, g in enumerate(groups) if g.matches(name)), len(groups)))
+            names.append(name)
+        if len(ends) > MAX_SEGMENTS:
+            raise ValueError(f"{len(ends)} parameter tensors: at most {MAX_SEGMENTS} segments fit one launch")
+        return ends, ids, names
+
     def _views_of(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         return {name: flat[off:off + n].view(shape) for name, off, n, shape in self._layout()[0]}
 

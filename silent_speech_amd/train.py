@@ -23,7 +23,7 @@ import torch
 
 from . import _lib as L
 from . import engine as E
-from .model import BiGRUClassifier
+from .model import BiGRUClassifier, ParamGroup, no_decay
 
 
 def shard_range(n_items: int, rank: int, world: int):
@@ -241,6 +241,51 @@ class SegmentTable:
                     lr_scale=[float(np.float32(x)) for x in self.lr_scale], weight_decay=[float(np.float32(x)) for x in self.weight_decay])
 
 
+def check_lamb_exclude(exclude):
+    """``enable_lamb(exclude=)`` / ``fit_lamb(lamb_exclude=)`` as a tuple of name patterns with ``ParamGroup.match``'s semantics (a
+    prefix, or ``*`` + a suffix); None: what ``no_decay()`` matches, the biases and the LayerNorm.  An empty sequence excludes
+    nothing.  ``ValueError`` for anything else.  Host code: nothing here touches a device."""
+    if exclude is None:
+        return tuple(no_decay().match)
+    pats = (exclude,) if isinstance(exclude, str) else exclude
+    try:
+        pats = tuple(pats)
+    except TypeError:
+        raise ValueError(f"lamb exclude must be a name pattern or a sequence of them, not {exclude!r}") from None
+    if not all(isinstance(p, str) and p not in ("", "*") for p in pats):
+        raise ValueError(f"lamb exclude must hold non-empty name prefixes (or '*' + suffix), not {exclude!r}")
+    return pats
+
+
+class LambTable:
+    """The host arrays of the two LAMB launches (``ss_lamb_moments``, ``ss_lamb_apply``), built once by ``Trainer.enable_lamb``:
+    ``model.param_tensor_segments`` -- one segment per parameter tensor of ``[lo, n)``, since the norms are per tensor -- the
+    trainer's groups as ``SegmentTable`` holds them (one default group without any), and ``seg_adapt``: 0 for the tensors whose
+    name matches one of ``exclude`` (they take the trust ratio 1), 1 for the others."""
+
+    def __init__(self, model: BiGRUClassifier, param_groups, weight_decay: float, exclude, lo: int = 0):
+        groups = tuple(param_groups or ())
+        ends, ids, names = model.param_tensor_segments(groups, lo)
+        self.n = model._layout()[1] - lo
+        assert ends[-1] == self.n and all(e % 4 == 0 for e in ends)
+        self.exclude = tuple(exclude)
+        self.names, self.seg_end, self.seg_group = list(names), list(ends), list(ids)
+        self.adapt = [0 if any(ParamGroup.pattern_matches(p, name) for p in self.exclude) else 1 for name in names]
+        self.lr_scale = [g.lr_scale for g in groups] + [1.0]
+        self.weight_decay = [float(weight_decay) if g.weight_decay is None else g.weight_decay for g in groups] + [float(weight_decay)]
+        self._end = (C.c_long * len(ends))(*ends)
+        self._group = (C.c_int * len(ids))(*ids)
+        self._scale = (C.c_float * len(self.lr_scale))(*self.lr_scale)
+        self._decay = (C.c_float * len(self.weight_decay))(*self.weight_decay)
+        self._adapt = (C.c_int * len(self.adapt))(*self.adapt)
+
+    @property
+    def args(self):
+        """(seg_end, seg_group, n_seg, group_lr_scale, group_weight_decay, n_groups, seg_adapt) as the entry points take them."""
+        return (C.addressof(self._end), C.addressof(self._group), len(self.seg_end), C.addressof(self._scale),
+                C.addressof(self._decay), len(self.lr_scale), C.addressof(self._adapt))
+
+
 class Trainer:
     """``micro_batches`` > 1 splits this rank's clips into that many equal slices which travel through forward and
     backward on their own HIP streams.  The GRU recurrence is latency-bound and occupies only one CU per
@@ -324,7 +369,22 @@ class Trainer:
     defect; the f32 parts (biases, LayerNorm, the head) see all of it.  Costs one more bucket-sized f32 buffer (``backup``: scratch,
     not saved) and about a second forward and backward per step.  With ``micro_batches`` > 1 ``enable_sam`` is a ``ValueError``.  ``state_dict()``
     gains ``sam_rho`` and ``sam_adaptive`` only with SAM, and ``load_state_dict`` raises ``ValueError`` when the two sides
-    disagree.  Without ``enable_sam`` a step issues exactly the launches it always has."""
+    disagree.  Without ``enable_sam`` a step issues exactly the launches it always has.
+
+    ``enable_lamb(exclude=None)`` (a method, like ``enable_sam``; ``harness.fit_lamb`` calls it): the layer-wise adaptive optimiser
+    LAMB (You et al. 2020) for large and data-parallel batches.  The optimiser launch of every following step becomes
+    ``ss_lamb_moments`` + ``ss_lamb_apply`` (include/ss_hotpath.h states the formulas) on the range the Adam launch would take
+    (``[n_cnn, n)`` under ``freeze_cnn``), with the trainer's ``lr``, ``lr_scale``, ``lr_schedule``, ``weight_decay``,
+    ``param_groups`` and weight average: the Adam direction plus the weight decay -- inside the update here, not decoupled -- is
+    rescaled per PARAMETER TENSOR by ``|w| / |update|``, so the table of these launches has one segment per tensor
+    (``model.param_tensor_segments``; more than 64 tensors: ``ValueError``).  Tensors whose name matches one of ``exclude``
+    (``ParamGroup.match``'s patterns; default: what ``no_decay()`` matches, biases and LayerNorm) take the ratio 1.  The clip is
+    still the one global norm.  ``trust_ratios()`` is the last step's ratio per tensor, a device tensor in the order of
+    ``lamb_segments()``, the tensors' names; nothing is read back inside a step.  Combines with SAM (whose streams come first),
+    ``micro_batches`` > 1, data parallelism (the gradient is all-reduced before the optimiser, so every rank computes the same
+    ratios), ``step_embedded`` and both engines.  ``state_dict()`` gains ``lamb`` and ``lamb_exclude`` only with LAMB, and
+    ``load_state_dict`` raises ``ValueError`` when the two sides disagree.  Without ``enable_lamb`` a step issues exactly the
+    launches it always has."""
 
     # CUs left to the other micro-batch's recurrence while a persistent ROI-CNN kernel runs (2 directions x 8 slices)
     CNN_RESERVED_CUS = 32
@@ -374,6 +434,9 @@ class Trainer:
         self.correct = torch.zeros(1, device=dev, dtype=torch.int32)
         # sharpness-aware minimisation: off until enable_sam(), which allocates what it needs
         self.sam_rho, self.sam_adaptive, self.backup, self.sam_scal, self.sam_correct = None, False, None, None, None
+        # LAMB: off until enable_lamb(); then its table (host arrays), the partial sums, the norms and the ratios (device)
+        self.lamb, self.lamb_scratch, self.lamb_norms, self.lamb_ratio = None, None, None, None
+        self.param_groups = None if param_groups is None else tuple(param_groups)
         # class weights (uploaded once) and the step's normaliser, sum of w[y] over the global batch: both stay on the device
         self.cw = None if cw is None else torch.from_numpy(cw).to(dev)
         self.den = None if cw is None else torch.zeros(1, device=dev, dtype=torch.float32)
@@ -413,6 +476,35 @@ class Trainer:
             self.sam_correct = torch.zeros(1, device=flat.device, dtype=torch.int32)
         self.sam_rho, self.sam_adaptive = rho, bool(adaptive)
 
+    def enable_lamb(self, exclude=None) -> None:
+        """Switch the layer-wise adaptive optimiser LAMB on for every following step (class docstring).  ``exclude``: name patterns
+        with ``ParamGroup.match``'s semantics whose tensors take the trust ratio 1; None: what ``no_decay()`` matches.  The
+        refusals -- bad patterns, more than 64 parameter tensors in the optimiser's range -- are host code and come before anything
+        touches a device.  Allocates, once, the partial sums of the norms (``ss_lamb_scratch_bytes``), the norms and the ratios; a
+        second call only changes the exclusion."""
+        exclude = check_lamb_exclude(exclude)
+        table = LambTable(self.model, self.param_groups, self.weight_decay, exclude, self.n_frozen)
+        if self.lamb_ratio is None:
+            dev, n_seg = self.model.flat_params.device, len(table.seg_end)
+            size = C.c_long(0)
+            L.call("ss_lamb_scratch_bytes", table.n, n_seg, C.addressof(size))
+            self.lamb_scratch = torch.empty(size.value // 8, device=dev, dtype=torch.float64)
+            self.lamb_norms = torch.zeros(2 * n_seg, device=dev, dtype=torch.float32)
+            self.lamb_ratio = torch.ones(n_seg, device=dev, dtype=torch.float32)
+        self.lamb = table
+
+    def trust_ratios(self) -> torch.Tensor:
+        """The trust ratios of the last step, one per tensor of ``lamb_segments()``: a device tensor (ones before the first step)."""
+        if self.lamb is None:
+            raise RuntimeError("trust_ratios() needs enable_lamb()")
+        return self.lamb_ratio
+
+    def lamb_segments(self) -> list:
+        """The names of the parameter tensors LAMB rescales on their own, in the order of ``trust_ratios()``."""
+        if self.lamb is None:
+            raise RuntimeError("lamb_segments() needs enable_lamb()")
+        return list(self.lamb.names)
+
     def _bind_bucket(self):
         """(Re)resolve everything that aliases the model's flat buckets.  ``model.to()/.cuda()/.float()`` keep the bucket
         when nothing moves; when they do re-allocate it (``model._bucket_version`` moves) the gradient views are taken
@@ -430,6 +522,9 @@ class Trainer:
             if self.backup is not None:
                 self.backup, self.sam_scal = self.backup.to(flat.device), self.sam_scal.to(flat.device)
                 self.sam_correct = self.sam_correct.to(flat.device)
+            if self.lamb_ratio is not None:
+                self.lamb_scratch, self.lamb_norms = self.lamb_scratch.to(flat.device), self.lamb_norms.to(flat.device)
+                self.lamb_ratio = self.lamb_ratio.to(flat.device)
             if self.cw is not None:
                 self.cw, self.den = self.cw.to(flat.device), self.den.to(flat.device)
         self.G = model._views_of(model.flat_grads)
@@ -638,6 +733,8 @@ class Trainer:
         lr = self.lr if self.lr_schedule is None and self.lr_scale == 1.0 else self.current_lr()
         grouped, averaged = self.table is not None, self.ema is not None
         assert not grouped or self.table.n == n_el
+        if self.lamb is not None:
+            return self._lamb(n_el, at, sumsq, lr, s)
         # one pass over the range: Adam; Adam and the weight average; or AdamW with parameter groups, average or not
         entry = "ss_adamw_clip_groups" if grouped else "ss_adam_clip_ema" if averaged else "ss_adam_clip"
         ranges = [t.data_ptr() + at for t in (model.flat_params, model.flat_grads, self.m, self.v)]
@@ -646,6 +743,19 @@ class Trainer:
             ranges.append(self.ema.data_ptr() + at if averaged else None)
             scalars += (ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup) if averaged else 0.0,)
         L.call(entry, *ranges, *scalars, *(self.table.args if grouped else ()), s)
+
+    def _lamb(self, n_el, at, sumsq, lr, s):
+        """LAMB in the place of the Adam launch: the moments and the per-tensor norms and ratios, then the update (and the weight
+        average) -- three passes over ``[n_frozen, n)`` in two entry points, everything between them on the device."""
+        model, t = self.model, self.lamb
+        assert t.n == n_el
+        p, g, m, v = (x.data_ptr() + at for x in (model.flat_params, model.flat_grads, self.m, self.v))
+        averaged = self.ema is not None
+        L.call("ss_lamb_moments", p, g, m, v, n_el, sumsq, 1.0, self.max_norm, self.betas[0], self.betas[1], self.eps, self.step_count,
+               *t.args, self.lamb_scratch.data_ptr(), self.lamb_norms.data_ptr(), self.lamb_ratio.data_ptr(), s)
+        L.call("ss_lamb_apply", p, m, v, self.ema.data_ptr() + at if averaged else None, n_el, self.betas[0], self.betas[1], self.eps,
+               self.step_count, ema_decay_at(self.ema_decay, self.step_count, self.ema_warmup) if averaged else 0.0, lr, *t.args,
+               self.lamb_ratio.data_ptr(), s)
 
     def current_lr(self, step: Optional[int] = None) -> float:
         """The learning rate of step ``step`` (default: the last one taken, ``step_count``): ``lr * lr_scale *
@@ -728,6 +838,8 @@ class Trainer:
                          lr_schedule=None if self.lr_schedule is None else self.lr_schedule.plain(), lr_scale=float(self.lr_scale))
         if self.sam_rho is not None:  # (the backup is scratch: the weights are in the bucket whenever a state is taken)
             extra.update(sam_rho=float(self.sam_rho), sam_adaptive=bool(self.sam_adaptive))
+        if self.lamb is not None:  # (the norms and ratios are each step's own: nothing of them to save)
+            extra.update(lamb=True, lamb_exclude=list(self.lamb.exclude))
         return dict(m=self.m.detach().clone(), v=self.v.detach().clone(), ema=None if self.ema is None else self.ema.detach().clone(),
                     step_count=int(self.step_count), ema_decay=self.ema_decay, ema_warmup=bool(self.ema_warmup),
                     betas=[float(b) for b in self.betas], eps=float(self.eps), lr=float(self.lr), max_norm=float(self.max_norm),
@@ -737,7 +849,8 @@ class Trainer:
         """Take over a ``state_dict()``: the tensors are copied into this trainer's device buffers (nothing is re-allocated), the
         step count and the hyperparameters are set.  ``ValueError`` when the bucket has another element count, when one side
         keeps a weight average and the other does not, when one side freezes the ROI CNN and the other does not, when the
-        segment tables (groups, scales, decays) differ, or when the two sides disagree about ``sam_rho`` / ``sam_adaptive``."""
+        segment tables (groups, scales, decays) differ, or when the two sides disagree about ``sam_rho`` / ``sam_adaptive`` or
+        about ``lamb`` / ``lamb_exclude``."""
         if self._ema_swapped:
             raise RuntimeError("Trainer.load_state_dict inside ema_weights()")
         if self.model._bucket_version != self._bucket_version:
@@ -756,6 +869,11 @@ class Trainer:
         if saved_sam != (self.sam_rho, self.sam_adaptive):
             raise ValueError("the saved trainer state and this Trainer disagree about sam_rho / sam_adaptive: "
                              f"saved {saved_sam!r}, this one {(self.sam_rho, self.sam_adaptive)!r}")
+        saved_lamb = (bool(state.get("lamb", False)), None if state.get("lamb_exclude") is None else list(state["lamb_exclude"]))
+        this_lamb = (self.lamb is not None, None if self.lamb is None else list(self.lamb.exclude))
+        if saved_lamb != this_lamb:
+            raise ValueError("the saved trainer state and this Trainer disagree about lamb / lamb_exclude: "
+                             f"saved {saved_lamb!r}, this one {this_lamb!r}")
         if (state["ema"] is None) != (self.ema is None):
             raise ValueError("the saved trainer state and this Trainer disagree about ema_decay: "
                              f"saved {state['ema_decay']!r}, this one {self.ema_decay!r}")
